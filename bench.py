@@ -40,6 +40,7 @@ PEAK_F32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, de
 PEAK_I8_MFMA_TOPS = 5000.0     # i8 = 2x bf16 dense (~2.5 PF) per MI355X_MICROARCH.md
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # bf16 dense
 PEAK_HBM_GBS = 8000.0          # HBM3E spec
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this much in all
 
 WORKLOADS = {
     # name: space, method, dim, batch, k, description
@@ -57,6 +58,8 @@ WORKLOADS = {
                     desc="HNSW cosinesimil {n}x{dim} f32 sharded {world} ways, M=16 efS={ef} k=10 batch={batch} "
                          "(BASELINE configs[4] at {rpg} rows per GPU)"),
 }
+
+ALL_RUN = ("bruteforce", "hnsw", "sift", "cos768x")    # --workload all: the headline first, then workloads.{...}
 
 
 def note(msg):
@@ -89,7 +92,35 @@ def parse():
     ap.add_argument("--gt-sample", type=int, default=128, help="queries in the exact-ground-truth sample")
     ap.add_argument("--dump", default="", help="rank 0 saves the ids / distances of the last timed step here (.npz): "
                                                   "tests compare sharded and unsharded runs")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0 writes what the timed path returned in its last step as DIR/<workload>_<array>.npy "
+                         "(ids, distances, counts; float64 / float32): two builds compare output for output")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
+
+
+def dump_outputs(outdir, name, ids, dists, cnt, budget):
+    """--dump-outputs: the arrays a caller of the timed path received from its last step; ids and counts as float64
+    (exact), distances as float32.  Beyond `budget` bytes a fixed, seeded sample of query rows is written instead,
+    and <workload>_query_rows.npy names them."""
+    os.makedirs(outdir, exist_ok=True)
+    nq, k = ids.shape
+    per_row = k * (8 + 4) + (8 if cnt is not None else 0)
+    rows = None
+    if nq * per_row > budget:
+        m = max(1, (budget - 4096) // (per_row + 8))          # (npy headers)
+        rows = np.sort(np.random.default_rng(0).choice(nq, m, replace=False))
+        ids, dists = ids[rows], dists[rows]
+        cnt = cnt[rows] if cnt is not None else None
+    arrays = {"ids": ids.astype(np.float64), "distances": dists.astype(np.float32)}
+    if cnt is not None:
+        arrays["counts"] = cnt.astype(np.float64)
+    if rows is not None:
+        arrays["query_rows"] = rows.astype(np.float64)
+    for key, arr in arrays.items():
+        np.save(os.path.join(outdir, f"{name}_{key}.npy"), arr)
 
 
 def s_768(n, dim, seed, rank=64, chunk=1 << 18):
@@ -343,6 +374,10 @@ def run_workload(a, name, cx):
     res_ds = (m_ds if world > 1 else d_ds).cpu().numpy()
     if a.dump and rank == 0:
         np.savez(a.dump, ids=res_ids, dists=res_ds)
+    if a.dump_outputs and rank == 0:
+        # one merged list per query on N > 1 (the per-shard counts are not what the caller receives)
+        dump_outputs(a.dump_outputs, name, res_ids, res_ds, d_cnt.cpu().numpy() if world == 1 else None,
+                     DUMP_BYTES // (len(ALL_RUN) if a.workload == "all" else 1))
     counters = idx.read_counters(nq) if method == "hnsw" else None
     stats = idx.stats()
     last_path = int(stats.get("last_path", 0))
@@ -585,9 +620,9 @@ def main():
             dist.init_process_group(cx.backend)
 
     if a.workload == "all":
-        out = run_workload(a, "bruteforce", cx)
+        out = run_workload(a, ALL_RUN[0], cx)
         subs = {}
-        for name in ("hnsw", "sift", "cos768x"):
+        for name in ALL_RUN[1:]:
             r = run_workload(a, name, cx)
             if r is not None:
                 subs[name] = r
