@@ -24,6 +24,39 @@ ERRORS = {
 }
 DATATYPE = {"DenseVector": 0, "SparseVector": 1, "DenseUInt8Vector": 2, "ObjectAsString": 3}
 DISTTYPE = {"Float": 0, "Int": 1}
+# nmslib_sparse_elem_float_t (nmslib_c.h): {uint32 id, float value}
+SPARSE_ELEM = np.dtype([("id", "<u4"), ("value", "<f4")])
+
+
+def sparse_rows(rows):
+    """Pack sparse rows back to back, the reference's batch layout (nmslib_c.cpp:770-800).
+    rows: a list of (ids, values) pairs, a CSR triple (indptr, indices, data) of arrays, or an object with
+    .indptr / .indices / .data (scipy's csr_matrix).  -> (elements [total] SPARSE_ELEM, counts [n] uint64)"""
+    if hasattr(rows, "indptr"):
+        rows = (rows.indptr, rows.indices, rows.data)
+    if isinstance(rows, tuple) and len(rows) == 3 and all(isinstance(a, np.ndarray) for a in rows):
+        indptr = np.asarray(rows[0], np.int64)
+        el = np.empty(int(indptr[-1] - indptr[0]), SPARSE_ELEM)
+        el["id"] = np.asarray(rows[1])[indptr[0]:indptr[-1]]
+        el["value"] = np.asarray(rows[2])[indptr[0]:indptr[-1]]
+        return el, np.diff(indptr).astype(np.uint64)
+    counts = np.array([len(r[0]) for r in rows], np.uint64)
+    el = np.empty(int(counts.sum()), SPARSE_ELEM)
+    at = 0
+    for ids, vals in rows:
+        m = len(ids)
+        el["id"][at:at + m] = ids
+        el["value"][at:at + m] = vals
+        at += m
+    return el, counts
+
+
+def sparse_vector(ids, values):
+    """One sparse vector as nmslib_sparse_elem_float_t elements."""
+    el = np.empty(len(ids), SPARSE_ELEM)
+    el["id"] = ids
+    el["value"] = values
+    return el
 
 
 class NmslibError(RuntimeError):
@@ -281,6 +314,17 @@ class Index:
         _check(lib().nmslib_add_data_point_batch_uint8(self.h, data.ctypes.data, data.shape[0], data.shape[1],
                                                        None if idp is None else idp.ctypes.data), self.alloc)
 
+    def addSparseBatch(self, rows, ids=None):
+        """lib.zig:724-756: rows back to back, row i with num_elements[i] elements.  rows: see sparse_rows()."""
+        el, counts = sparse_rows(rows)
+        if len(counts) == 0:
+            return
+        el = np.ascontiguousarray(el)
+        idp = None if ids is None else np.ascontiguousarray(ids, np.int32)
+        _check(lib().nmslib_add_data_point_batch(self.h, el.ctypes.data, len(counts), max(int(counts.max()), 1),
+                                                 None if idp is None else idp.ctypes.data, counts.ctypes.data),
+               self.alloc)
+
     def buildIndex(self, **index_params):
         p = Params(self.alloc, **index_params) if index_params else None
         try:
@@ -298,49 +342,73 @@ class Index:
             p.free()
 
     # -- queries (host buffers: the reference's own entry points) -----------------------------
+    def _query(self, query):
+        """-> (buffer, query_size_or_elem_count, num_elements); a sparse query is (ids, values) or SPARSE_ELEM elements
+        (QueryPoint.SparseVector, lib.zig:414-424): its slot is 2 floats per element, num_elements its length."""
+        if self.data_type == "SparseVector":
+            q = query if isinstance(query, np.ndarray) and query.dtype == SPARSE_ELEM else sparse_vector(*query)
+            q = np.ascontiguousarray(q)
+            return q, max(2 * len(q), 1), len(q)
+        q = np.ascontiguousarray(query, np.uint8 if self.data_type == "DenseUInt8Vector" else np.float32)
+        return q, q.shape[0], 0
+
     def knnQuery(self, query, k):
         L = lib()
-        q = np.ascontiguousarray(query, np.uint8 if self.data_type == "DenseUInt8Vector" else np.float32)
+        q, qsz, ne = self._query(query)
         L.nmslib_initialize_pool(self.h)      # lib.zig:802
         cap = C.c_size_t()
-        _check(L.nmslib_knn_query_get_size(self.h, q.ctypes.data, q.shape[0], k, C.byref(cap), 0), self.alloc)
+        _check(L.nmslib_knn_query_get_size(self.h, q.ctypes.data, qsz, k, C.byref(cap), ne), self.alloc)
         ids = np.empty(cap.value, np.int32)
         ds = np.empty(cap.value, np.float32)
         r = Result(ids.ctypes.data_as(C.POINTER(C.c_int32)), ds.ctypes.data_as(C.POINTER(C.c_float)), 0, cap.value)
-        _check(L.nmslib_knn_query_fill(self.h, q.ctypes.data, q.shape[0], k, C.byref(r), 0), self.alloc)
+        _check(L.nmslib_knn_query_fill(self.h, q.ctypes.data, qsz, k, C.byref(r), ne), self.alloc)
         return ids[:r.size].copy(), ds[:r.size].copy()
 
     def rangeQuery(self, query, radius):
         """lib.zig:933-965: get_size (an estimate, 128) sizes the buffers, fill writes the first `capacity`
         objects within the radius, in insertion order.  HNSW -> NmslibError(SPACE_INCOMPATIBLE)."""
         L = lib()
-        q = np.ascontiguousarray(query, np.uint8 if self.data_type == "DenseUInt8Vector" else np.float32)
+        q, qsz, ne = self._query(query)
         L.nmslib_initialize_pool(self.h)
         cap = C.c_size_t()
-        _check(L.nmslib_range_query_get_size(self.h, q.ctypes.data, q.shape[0], float(radius), C.byref(cap), 0), self.alloc)
+        _check(L.nmslib_range_query_get_size(self.h, q.ctypes.data, qsz, float(radius), C.byref(cap), ne), self.alloc)
         return self.rangeQueryFill(q, radius, cap.value)
 
     def rangeQueryFill(self, query, radius, capacity):
         L = lib()
-        q = np.ascontiguousarray(query, np.uint8 if self.data_type == "DenseUInt8Vector" else np.float32)
+        q, qsz, ne = self._query(query)
         ids = np.empty(capacity, np.int32)
         ds = np.empty(capacity, np.float32)
         r = Result(ids.ctypes.data_as(C.POINTER(C.c_int32)), ds.ctypes.data_as(C.POINTER(C.c_float)), 0, capacity)
-        _check(L.nmslib_range_query_fill(self.h, q.ctypes.data, q.shape[0], float(radius), C.byref(r), 0), self.alloc)
+        _check(L.nmslib_range_query_fill(self.h, q.ctypes.data, qsz, float(radius), C.byref(r), ne), self.alloc)
         return ids[:r.size].copy(), ds[:r.size].copy()
 
     def knnQueryBatch(self, queries, k):
-        """One call of nmslib_knn_query_batch: a single GPU batch.  -> ids [Q,k], dists [Q,k], counts [Q]"""
+        """One call of nmslib_knn_query_batch: a single GPU batch.  -> ids [Q,k], dists [Q,k], counts [Q]
+        Sparse queries (see sparse_rows) are packed in the reference's slot layout (nmslib_c.cpp:1003-1031): query i
+        at byte i * query_size_or_elem_count * 4, one slot of the longest query's size each, num_elements[i] elements."""
         L = lib()
-        q = np.ascontiguousarray(queries, np.uint8 if self.data_type == "DenseUInt8Vector" else np.float32)
-        nq = q.shape[0]
+        num = None
+        if self.data_type == "SparseVector":
+            el, counts = sparse_rows(queries)
+            nq, width = len(counts), max(int(counts.max()) if len(counts) else 1, 1)
+            q = np.zeros((nq, width), SPARSE_ELEM)
+            starts = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+            for i in range(nq):
+                q[i, :counts[i]] = el[starts[i]:starts[i + 1]]
+            qsz = 2 * width
+            num = np.ascontiguousarray(counts, np.uint64)
+        else:
+            q = np.ascontiguousarray(queries, np.uint8 if self.data_type == "DenseUInt8Vector" else np.float32)
+            nq, qsz = q.shape[0], q.shape[1]
         ids = np.full((nq, k), -1, np.int32)
         ds = np.full((nq, k), np.inf, np.float32)
         res = (Result * nq)()
         for i in range(nq):
             res[i] = Result(ids[i].ctypes.data_as(C.POINTER(C.c_int32)),
                             ds[i].ctypes.data_as(C.POINTER(C.c_float)), 0, k)
-        _check(L.nmslib_knn_query_batch(self.h, q.ctypes.data, nq, q.shape[1], k, res, None, 0), self.alloc)
+        _check(L.nmslib_knn_query_batch(self.h, q.ctypes.data, nq, qsz, k, res,
+                                        None if num is None else num.ctypes.data, 0), self.alloc)
         cnt = np.array([res[i].size for i in range(nq)], np.int32)
         return ids, ds, cnt
 
@@ -417,6 +485,9 @@ class Index:
         _check(lib().nmslib_get_data_point_fill(self.h, pos, buf.ctypes.data, n.value), self.alloc)
         if self.data_type == "DenseUInt8Vector":
             return buf[:128].copy()
+        if self.data_type == "SparseVector":   # -> (ids, values)
+            el = buf.view(SPARSE_ELEM)
+            return el["id"].copy(), el["value"].copy()
         return buf.view(np.float32).copy()
 
     def save(self, path, save_data=True):

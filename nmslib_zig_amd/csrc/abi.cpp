@@ -94,6 +94,21 @@ nmslib_error_t guarded(nmslib_error_t generic, const char* what, Fn&& fn) {
 
 void borrowed_free(void* ptr);
 
+using gfxknn::SparseElem;
+static_assert(sizeof(SparseElem) == sizeof(nmslib_sparse_elem_float_t), "sparse element layout");
+
+bool is_sparse(nmslib_index_handle_t h) { return H(h)->header.data_type == NMSLIB_DATATYPE_SPARSE_VECTOR; }
+
+// validate_sparse_elements (nmslib_c.cpp:96-109, called with sorted = true): at least one element, ids strictly
+// increasing
+bool valid_sparse(const void* elems, size_t count) {
+    if (!elems || count == 0) return false;
+    const SparseElem* e = static_cast<const SparseElem*>(elems);
+    for (size_t i = 1; i < count; ++i)
+        if (e[i].id <= e[i - 1].id) return false;
+    return true;
+}
+
 }  // namespace
 
 extern "C" {
@@ -105,10 +120,10 @@ nmslib_error_t nmslib_index_create(const char* space, nmslib_params_handle_t spa
                                    const nmslib_allocator_t* allocator, nmslib_index_handle_t* out_handle) {
     if (!space || !method || !allocator || !allocator->alloc || !allocator->free || !out_handle)
         FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid arguments");
-    (void)space_params;  // dense space factories ignore their params, e.g. "dim" (factory/space/space_lp.h:37-40)
+    // dense space factories ignore their params, e.g. "dim" (factory/space/space_lp.h:37-40); lp_sparse reads "p"
     Engine* eng = nullptr;
     try {
-        eng = new Engine(space, method, (int)data_type, (int)dist_type);
+        eng = new Engine(space, method, (int)data_type, (int)dist_type, params_of(space_params));
     } catch (const std::bad_alloc&) {
         FAIL(NMSLIB_ERROR_OUT_OF_MEMORY, "Failed to allocate index");
     } catch (const std::exception& e) {
@@ -252,6 +267,14 @@ nmslib_error_t nmslib_get_last_error_detail(nmslib_error_detail_t* detail, const
 nmslib_error_t nmslib_add_data_point(nmslib_index_handle_t handle, const void* data, size_t element_count,
                                      int32_t id) {
     if (!handle || !data || element_count == 0) FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid inputs for adding data point");
+    if (is_sparse(handle)) {  // element_count = number of elements (nmslib_c.cpp:725-728)
+        if (!valid_sparse(data, element_count)) FAIL(NMSLIB_ERROR_INVALID_SPARSE_ELEMENT, "Invalid sparse elements");
+        return guarded(NMSLIB_ERROR_RUNTIME, "Failed to add data point", [&] {
+            Engine* e = H(handle)->engine;
+            std::lock_guard<std::mutex> lk(e->mu);
+            e->add_sparse_row(static_cast<const SparseElem*>(data), element_count, id);
+        });
+    }
     return guarded(NMSLIB_ERROR_RUNTIME, "Failed to add data point", [&] {
         Engine* e = H(handle)->engine;
         std::lock_guard<std::mutex> lk(e->mu);
@@ -261,8 +284,27 @@ nmslib_error_t nmslib_add_data_point(nmslib_index_handle_t handle, const void* d
 
 nmslib_error_t nmslib_add_data_point_batch(nmslib_index_handle_t handle, const void* data, size_t count,
                                            size_t element_count, const int32_t* ids, const size_t* num_elements) {
-    (void)num_elements;  // sparse only
     if (!handle || !data || count == 0 || element_count == 0) FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid batch inputs");
+    if (is_sparse(handle)) {
+        // rows back to back, row i has num_elements[i] elements (element_count without the array), nmslib_c.cpp:770-800;
+        // the whole batch is validated before any row is stored
+        const SparseElem* p = static_cast<const SparseElem*>(data);
+        for (size_t i = 0; i < count; ++i) {
+            const size_t m = num_elements ? num_elements[i] : element_count;
+            if (!valid_sparse(p, m)) FAIL(NMSLIB_ERROR_INVALID_SPARSE_ELEMENT, "Invalid sparse elements");
+            p += m;
+        }
+        return guarded(NMSLIB_ERROR_RUNTIME, "Failed to add batch", [&] {
+            Engine* e = H(handle)->engine;
+            std::lock_guard<std::mutex> lk(e->mu);
+            const SparseElem* q = static_cast<const SparseElem*>(data);
+            for (size_t i = 0; i < count; ++i) {
+                const size_t m = num_elements ? num_elements[i] : element_count;
+                e->add_sparse_row(q, m, ids ? ids[i] : (int32_t)i);
+                q += m;
+            }
+        });
+    }
     return guarded(NMSLIB_ERROR_RUNTIME, "Failed to add batch", [&] {
         Engine* e = H(handle)->engine;
         std::lock_guard<std::mutex> lk(e->mu);
@@ -297,12 +339,26 @@ nmslib_error_t nmslib_add_data_point_batch_pointers(nmslib_index_handle_t handle
                                                     const void* const* data_ptrs, size_t count,
                                                     size_t element_count, const int32_t* ids,
                                                     const size_t* num_elements) {
-    (void)num_elements;
     if (!handle || !data_ptrs || count == 0) FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid pointer batch inputs");
     for (size_t i = 0; i < count; ++i)
         if (!data_ptrs[i]) FAIL(NMSLIB_ERROR_NULL_POINTER, "Null pointer in batch");
     const nmslib_data_type_t dt = H(handle)->header.data_type;
-    if (data_mode == NMSLIB_DATA_MODE_SPARSE) FAIL(NMSLIB_ERROR_SPACE_INCOMPATIBLE, "Not sparse space");
+    if (data_mode == NMSLIB_DATA_MODE_SPARSE) {
+        if (dt != NMSLIB_DATATYPE_SPARSE_VECTOR) FAIL(NMSLIB_ERROR_SPACE_INCOMPATIBLE, "Not sparse space");
+        // one pointer per row plus num_elements[] (nmslib_c.cpp:1591-1620)
+        for (size_t i = 0; i < count; ++i) {
+            const size_t m = num_elements ? num_elements[i] : element_count;
+            if (!valid_sparse(data_ptrs[i], m)) FAIL(NMSLIB_ERROR_INVALID_SPARSE_ELEMENT, "Invalid sparse elements");
+        }
+        return guarded(NMSLIB_ERROR_RUNTIME, "Failed to add pointer batch", [&] {
+            Engine* e = H(handle)->engine;
+            std::lock_guard<std::mutex> lk(e->mu);
+            for (size_t i = 0; i < count; ++i)
+                e->add_sparse_row(static_cast<const SparseElem*>(data_ptrs[i]),
+                                  num_elements ? num_elements[i] : element_count, ids ? ids[i] : (int32_t)i);
+        });
+    }
+    if (dt == NMSLIB_DATATYPE_SPARSE_VECTOR) FAIL(NMSLIB_ERROR_SPACE_INCOMPATIBLE, "Not dense space");
     if (data_mode == NMSLIB_DATA_MODE_DENSE_FLOAT && dt != NMSLIB_DATATYPE_DENSE_VECTOR)
         FAIL(NMSLIB_ERROR_SPACE_INCOMPATIBLE, "Not dense float space");
     if (data_mode == NMSLIB_DATA_MODE_UINT8 && dt != NMSLIB_DATATYPE_DENSE_UINT8_VECTOR)
@@ -346,7 +402,6 @@ static void fill_result(nmslib_result_t* r, const int32_t* ids, const float* dis
 nmslib_error_t nmslib_knn_query_batch(nmslib_index_handle_t index, const void* queries, size_t query_count,
                                       size_t query_size_or_elem_count, size_t k, nmslib_result_t* results,
                                       const size_t* num_elements, size_t thread_pool_size) {
-    (void)num_elements;
     (void)thread_pool_size;
     if (!index || !queries || query_count == 0 || !results) FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid batch knn inputs");
     if (query_size_or_elem_count == 0 || k == 0) FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid KNN query inputs");
@@ -355,12 +410,30 @@ nmslib_error_t nmslib_knn_query_batch(nmslib_index_handle_t index, const void* q
             FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Result buffers invalid");
     Engine* e = H(index)->engine;
     if (!e->index_created()) FAIL(NMSLIB_ERROR_INDEX_BUILD_FAILED, "Index not built");  // nmslib_c.cpp:963-967
+    // sparse: query i starts at byte i * query_size_or_elem_count * 4 and has num_elements[i] elements
+    // (nmslib_c.cpp:1003-1031), i.e. a fixed-size slot per query
+    std::vector<const SparseElem*> sq;
+    std::vector<size_t> sn;
+    if (is_sparse(index)) {
+        sq.resize(query_count);
+        sn.resize(query_count);
+        for (size_t i = 0; i < query_count; ++i) {
+            sq[i] = reinterpret_cast<const SparseElem*>(static_cast<const char*>(queries) +
+                                                        i * query_size_or_elem_count * sizeof(float));
+            sn[i] = num_elements ? num_elements[i] : 0;
+            if (!valid_sparse(sq[i], sn[i])) {
+                for (size_t j = 0; j < query_count; ++j) results[j].size = 0;
+                FAIL(NMSLIB_ERROR_INVALID_SPARSE_ELEMENT, "Invalid sparse elements");
+            }
+        }
+    }
     bool too_small = false;
     nmslib_error_t rc = guarded(NMSLIB_ERROR_QUERY_EXECUTION_FAILED, "KNN query failed", [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         const int32_t *ids = nullptr, *cnt = nullptr;
         const float* dists = nullptr;
-        e->knn_host(queries, query_count, query_size_or_elem_count, k, &ids, &dists, &cnt);
+        if (!sq.empty()) e->knn_sparse_host(sq.data(), sn.data(), query_count, k, &ids, &dists, &cnt);
+        else e->knn_host(queries, query_count, query_size_or_elem_count, k, &ids, &dists, &cnt);
         for (size_t i = 0; i < query_count; ++i) {
             fill_result(&results[i], &ids[i * k], &dists[i * k], (size_t)cnt[i]);
             too_small |= ((size_t)cnt[i] > results[i].capacity);
@@ -377,13 +450,13 @@ nmslib_error_t nmslib_knn_query_batch(nmslib_index_handle_t index, const void* q
 nmslib_error_t nmslib_knn_query_fill(nmslib_index_handle_t index, const void* query,
                                      size_t query_size_or_elem_count, size_t k, nmslib_result_t* result,
                                      size_t num_elements) {
-    (void)num_elements;
     if (!index || !query || query_size_or_elem_count == 0 || !result)
         FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid KNN query inputs");
     if (!result->ids || !result->distances || result->capacity == 0)
         FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Result buffers invalid");
     if (k == 0) FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid KNN query inputs");
-    return nmslib_knn_query_batch(index, query, 1, query_size_or_elem_count, k, result, nullptr, 0);
+    // sparse: num_elements is the element count (nmslib_c.cpp:969-975)
+    return nmslib_knn_query_batch(index, query, 1, query_size_or_elem_count, k, result, &num_elements, 0);
 }
 
 // ---- range queries -----------------------------------------------------------------------------
@@ -402,17 +475,22 @@ nmslib_error_t nmslib_range_query_get_size(nmslib_index_handle_t index, const vo
 nmslib_error_t nmslib_range_query_fill(nmslib_index_handle_t index, const void* query,
                                        size_t query_size_or_elem_count, double radius, nmslib_result_t* result,
                                        size_t num_elements) {
-    (void)num_elements;
     if (!index || !query || !result || result->capacity == 0) FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid range fill inputs");
     Engine* e = H(index)->engine;
     if (!e->index_created()) FAIL(NMSLIB_ERROR_INDEX_BUILD_FAILED, "Index not built");
     result->size = 0;
     if (e->method_name() == "hnsw")  // Hnsw::Search(RangeQuery*) throws (hnsw.cc:710-715) -> nmslib_c.cpp:1131-1141
         FAIL(NMSLIB_ERROR_SPACE_INCOMPATIBLE, "Range query not supported by method: Range search is not supported!");
+    const bool sparse = is_sparse(index);
+    if (sparse && !valid_sparse(query, num_elements)) FAIL(NMSLIB_ERROR_INVALID_SPARSE_ELEMENT, "Invalid sparse elements");
     try {
         std::lock_guard<std::mutex> lk(e->mu);
-        result->size = e->range_host(query, query_size_or_elem_count, radius, result->capacity, result->ids,
-                                     result->distances);
+        if (sparse)
+            result->size = e->range_sparse_host(static_cast<const SparseElem*>(query), num_elements, radius,
+                                                result->capacity, result->ids, result->distances);
+        else
+            result->size = e->range_host(query, query_size_or_elem_count, radius, result->capacity, result->ids,
+                                         result->distances);
     } catch (const EngineError& ex) {
         FAIL(static_cast<nmslib_error_t>(ex.code), std::string("Range query exception: ") + ex.what());
     } catch (const std::bad_alloc& ex) {
@@ -438,7 +516,8 @@ nmslib_error_t nmslib_get_distance(nmslib_index_handle_t index, size_t pos1, siz
 
 nmslib_error_t nmslib_get_data_point_size(nmslib_index_handle_t index, size_t position, size_t* size) {
     if (!index || position >= nmslib_data_qty(index) || !size) FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid data point size inputs");
-    *size = H(index)->engine->stored_row_bytes();  // Object::datalength()
+    Engine* e = H(index)->engine;
+    *size = e->is_sparse() ? e->sparse_row_len(position) * sizeof(SparseElem) : e->stored_row_bytes();  // Object::datalength()
     SET_LAST(NMSLIB_SUCCESS, "Data point size retrieved");
     return NMSLIB_SUCCESS;
 }
@@ -447,6 +526,13 @@ nmslib_error_t nmslib_get_data_point_fill(nmslib_index_handle_t index, size_t po
     if (!index || !data || size == 0 || position >= nmslib_data_qty(index))
         FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid data point fill inputs");
     Engine* e = H(index)->engine;
+    if (e->is_sparse()) {
+        if (size < e->sparse_row_len(position) * sizeof(SparseElem))
+            FAIL(NMSLIB_ERROR_BUFFER_TOO_SMALL, "Buffer too small for data point");
+        e->sparse_row(position, static_cast<SparseElem*>(data));
+        SET_LAST(NMSLIB_SUCCESS, "Data point filled");
+        return NMSLIB_SUCCESS;
+    }
     if (size < e->stored_row_bytes()) FAIL(NMSLIB_ERROR_BUFFER_TOO_SMALL, "Buffer too small for data point");
     e->stored_row(position, data);
     SET_LAST(NMSLIB_SUCCESS, "Data point filled");
@@ -502,7 +588,22 @@ nmslib_error_t nmslib_borrow_data_sparse(nmslib_index_handle_t index, size_t pos
                                          void (**free_fn)(void*)) {
     if (!index || !data || !size || !free_fn || position >= nmslib_data_qty(index))
         FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid sparse borrow inputs");
-    FAIL(NMSLIB_ERROR_SPACE_INCOMPATIBLE, "Not sparse vector");
+    HandleBlock* hb = H(index);
+    if (hb->header.data_type != NMSLIB_DATATYPE_SPARSE_VECTOR) FAIL(NMSLIB_ERROR_SPACE_INCOMPATIBLE, "Not sparse vector");
+    Engine* e = hb->engine;
+    // *size = number of elements (nmslib_c.cpp:1339-1340); the copy is released by *free_fn, as the dense borrow's
+    const size_t count = e->sparse_row_len(position);
+    char* blk = static_cast<char*>(hb->allocator.alloc(sizeof(BorrowHeader) + count * sizeof(SparseElem), hb->allocator.ctx));
+    if (!blk) FAIL(NMSLIB_ERROR_OUT_OF_MEMORY, "Failed to allocate sparse copy");
+    BorrowHeader* bh = reinterpret_cast<BorrowHeader*>(blk);
+    bh->allocator = hb->allocator;
+    bh->magic = kBorrowMagic;
+    e->sparse_row(position, reinterpret_cast<SparseElem*>(blk + sizeof(BorrowHeader)));
+    *data = blk + sizeof(BorrowHeader);
+    *size = count;
+    *free_fn = borrowed_free;
+    SET_LAST(NMSLIB_SUCCESS, "Sparse data borrowed");
+    return NMSLIB_SUCCESS;
 }
 
 // ---- persistence -------------------------------------------------------------------------------

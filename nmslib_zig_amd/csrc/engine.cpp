@@ -115,9 +115,51 @@ static int space_from_name(const std::string& s) {
     return -1;
 }
 
-Engine::Engine(const std::string& space, const std::string& method, int data_type, int dist_type)
+// Sparse spaces whose objects the reference's C ABI can build (SpaceSparseVectorSimpleStorage, nmslib_c.cpp:245-265):
+// include/space/space_sparse_scalar.h:32-35, include/space/space_sparse_lp.h.  lp_sparse needs its parameter p.
+static int sparse_space_from_name(const std::string& s, const std::vector<std::string>& space_params) {
+    if (s == "cosinesimil_sparse") return SP_COSINE;
+    if (s == "angulardist_sparse") return SP_ANGULAR;
+    if (s == "negdotprod_sparse") return SP_NEGDOT;
+    if (s == "querynorm_negdotprod_sparse") return SP_QNORM_NEGDOT;
+    if (s == "l1_sparse") return SP_L1;
+    if (s == "l2_sparse") return SP_L2;
+    if (s == "linf_sparse") return SP_LINF;
+    if (s == "lp_sparse") {
+        ParamSet ps(space_params);
+        if (!ps.has("p")) throw EngineError(Err::SpaceIncompatible, "lp_sparse: parameter p is required");
+        double p = 0;
+        ps.get("p", p);
+        // SpaceLpDist (include/space/space_lp.h:43-66): p in {-1, 1, 2} selects LInf / L1 / L2NormSIMD
+        const float pf = (float)p;
+        if (pf == -1.f) return SP_LINF;
+        if (pf == 1.f) return SP_L1;
+        if (pf == 2.f) return SP_L2;
+        throw EngineError(Err::SpaceIncompatible, "lp_sparse: only p = 1, 2 and -1 are served by the GPU engine (p = " +
+                                                      std::to_string(p) + " uses the generic Lp formula)");
+    }
+    return -1;
+}
+
+Engine::Engine(const std::string& space, const std::string& method, int data_type, int dist_type,
+               const std::vector<std::string>& space_params)
     : space_name_(space), method_name_(method) {
     (void)dist_type;
+    if (data_type == 1) {
+        const int ssp = sparse_space_from_name(space, space_params);
+        if (ssp < 0)
+            throw EngineError(Err::SpaceIncompatible,
+                              "sparse space '" + space + "' is not served by the GPU engine (sparse spaces: "
+                              "cosinesimil_sparse, angulardist_sparse, negdotprod_sparse, querynorm_negdotprod_sparse, "
+                              "l1_sparse, l2_sparse, linf_sparse, lp_sparse with p = 1, 2, -1)");
+        if (method != "brute_force" && method != "seq_search")
+            throw EngineError(Err::SpaceIncompatible,
+                              "method '" + method + "' over sparse data is not served (sparse: brute_force, seq_search)");
+        space_ = ssp;
+        sparse_ = true;
+        thread_pool_size = std::thread::hardware_concurrency();
+        return;
+    }
     const int sp = space_from_name(space);
     if (sp < 0)
         throw EngineError(Err::SpaceIncompatible,
@@ -175,6 +217,7 @@ void Engine::collect_profile(double* total_ms, uint64_t* launches) {
 }
 
 void Engine::add_row(const void* data, size_t elem_count, int32_t id) {
+    if (sparse_) throw EngineError(Err::SpaceIncompatible, "Not dense space");
     if (is_u8()) {
         // CreateObjFromUint8Vect CHECKs size == SIFT_DIM (space_l2sqr_sift.cc:136-140)
         if (elem_count != 128) throw EngineError(Err::Runtime, "SIFT vectors must have 128 bytes");
@@ -213,6 +256,9 @@ void Engine::reset() {
     ids_.clear();
     rows_f32_.clear();
     rows_u8_.clear();
+    sp_ptr_.assign(1, 0);
+    sp_ids_.clear();
+    sp_vals_.clear();
     graph_ = HostGraph();
     graph_rows_.clear();
     loaded_graph_ = false;
@@ -234,6 +280,8 @@ void Engine::reset() {
 size_t Engine::memory_usage() const {
     // nmslib_index_memory_usage (nmslib_c.cpp:1546-1565): object buffers + n*dim*4
     if (!created_) return 0;
+    if (sparse_)  // objects (16-byte header + elements) and the CSR copy in HBM
+        return ids_.size() * 16 + sp_ids_.size() * sizeof(SparseElem) + hbm_bytes();
     size_t total = ids_.size() * (16 + stored_row_bytes());
     total += ids_.size() * dim_ * sizeof(float);
     return total;
@@ -243,7 +291,8 @@ size_t Engine::hbm_bytes() const {
     size_t sh = 0;
     for (const auto& c : shards_) sh += c->hbm_bytes();
     return sh + d_rows_.bytes() + d_rows_i8_.bytes() + d_aux_.bytes() + d_ids_.bytes() + d_links0_.bytes() + d_up_off_.bytes() +
-           d_up_links_.bytes() + d_rownorm_.bytes() + d_rows_sel_.bytes() + d_auxh_.bytes() + d_bf_hi_.bytes() + d_bf_lo_.bytes() + d_auxp_.bytes();
+           d_up_links_.bytes() + d_rownorm_.bytes() + d_rows_sel_.bytes() + d_auxh_.bytes() + d_bf_hi_.bytes() + d_bf_lo_.bytes() + d_auxp_.bytes() +
+           d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -291,6 +340,9 @@ void Engine::create_index(const std::vector<std::string>& params) {
         ps.get("gpu_defer", defer);
         ps.get("gpu_shards", gpu_shards_);
         ps.check_unused();
+        if (sparse_ && gpu_shards_ != -1 && gpu_shards_ != 1)
+            throw EngineError(Err::IndexBuildFailed, "a sparse index runs on one GPU: gpu_shards=" +
+                                                         std::to_string(gpu_shards_) + " is not supported");
     } else {
         throw EngineError(Err::IndexBuildFailed,
                           "method '" + method_name_ + "' is not served by the GPU engine (hnsw, brute_force, seq_search)");
@@ -687,6 +739,11 @@ void Engine::ensure_graph() {
 void Engine::finalize() {
     if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
     if (!dirty_) return;
+    if (sparse_) {
+        upload_sparse();
+        dirty_ = false;
+        return;
+    }
     if (!parent_) {
         const int nsh = resolve_shards();
         if (nsh > 1) {
@@ -1039,6 +1096,9 @@ void Engine::knn_device(const void* d_queries, size_t nq, size_t elem_count, siz
     check_device();
     if (nq == 0) return;
     if (k == 0) throw EngineError(Err::InvalidArgument, "k must be positive");
+    if (sparse_)
+        throw EngineError(Err::SpaceIncompatible, "the device-resident batch takes dense queries; sparse queries go "
+                                                  "through nmslib_knn_query_batch");
     last_stream_ = stream;
     if (!shards_.empty()) {
         if (size() > 0 && elem_count != dim_)
@@ -1493,6 +1553,7 @@ size_t Engine::range_host(const void* query, size_t elem_count, double radius, s
 
 float Engine::pair_distance(size_t p1, size_t p2) {
     // Space::IndexTimeDistance on the ORIGINAL rows (nmslib_c.cpp:1166), one wave on the GPU
+    if (sparse_) return pair_distance_sparse(p1, p2);
     check_device();
     const size_t rb = is_u8() ? 128 : (size_t)f32_row_stride((int)dim_) * 4;
     ws_pair_.ensure(2 * rb + 16);
@@ -1525,6 +1586,9 @@ static void rd(std::istream& i, T& v) {
 
 void Engine::save(const std::string& path, bool save_data) {
     if (!created_) throw EngineError(Err::InvalidArgument, "Index not built");
+    if (sparse_)  // SeqSearch has no SaveIndex (include/index.h:56-58); the object file is not written either
+        throw EngineError(Err::DataIO, "SaveIndex is not implemented for method: Sequential search (sparse index; "
+                                       "the data file is not written)");
     if (method_ == Method::Hnsw && !loaded_graph_ && (shards_.size() > 1 || (dirty_ && resolve_shards() > 1)))
         throw EngineError(Err::DataIO, "a sharded HNSW index holds one graph per GPU and has no single-file form; "
                                        "build with gpu_shards=1 to save it in the reference's format");

@@ -115,9 +115,17 @@ void hnsw_build_host(int space, const void* rows, size_t n, size_t dim, const Hn
 // ---- the index ---------------------------------------------------------------------------------
 enum class Method { Brute, Hnsw };
 
+// nmslib_sparse_elem_float_t (nmslib_c.h): the reference's SparseVectElem<float> layout
+struct SparseElem {
+    uint32_t id;
+    float value;
+};
+
 class Engine {
    public:
-    Engine(const std::string& space, const std::string& method, int data_type, int dist_type);
+    // space_params: the space factory's parameters ("p" of lp_sparse); the dense factories ignore theirs
+    Engine(const std::string& space, const std::string& method, int data_type, int dist_type,
+           const std::vector<std::string>& space_params = {});
     ~Engine();
 
     const std::string& space_name() const { return space_name_; }
@@ -134,6 +142,18 @@ class Engine {
     void stored_row(size_t pos, void* dst) const;  // payload as the reference stores it
     int32_t ext_id(size_t pos) const { return ids_[pos]; }
     void reset();
+
+    // ---- sparse vectors (data type 1; sparse.cpp) ----
+    bool is_sparse() const { return sparse_; }
+    // one row of strictly increasing ids (validated by the caller)
+    void add_sparse_row(const SparseElem* elems, size_t count, int32_t id);
+    size_t sparse_row_len(size_t pos) const { return (size_t)(sp_ptr_[pos + 1] - sp_ptr_[pos]); }
+    void sparse_row(size_t pos, SparseElem* dst) const;
+    // k-NN of nq sparse queries (query i: counts[i] elements at queries[i]); results in the pinned staging block
+    void knn_sparse_host(const SparseElem* const* queries, const size_t* counts, size_t nq, size_t k,
+                         const int32_t** ids, const float** dists, const int32_t** cnt);
+    size_t range_sparse_host(const SparseElem* query, size_t count, double radius, size_t capacity, int32_t* ids,
+                             float* dists);
 
     void create_index(const std::vector<std::string>& params);  // nmslib_create_index
     void set_query_params(const std::vector<std::string>& params);
@@ -204,6 +224,8 @@ class Engine {
     void* pinned_ = nullptr;
     size_t pinned_bytes_ = 0;
     void check_device();
+    void upload_sparse();
+    float pair_distance_sparse(size_t p1, size_t p2);
     void ensure_graph();
     void upload_rows();
     void build_graph();
@@ -225,6 +247,13 @@ class Engine {
     std::vector<int32_t> ids_;
     std::vector<float> rows_f32_;
     std::vector<uint8_t> rows_u8_;
+    // sparse rows: host CSR (get_data_point / borrow) and its copy in HBM after finalize
+    bool sparse_ = false;
+    std::vector<int64_t> sp_ptr_{0};
+    std::vector<uint32_t> sp_ids_;
+    std::vector<float> sp_vals_;
+    DevBuf d_sp_ptr_, d_sp_ids_, d_sp_vals_;
+    DevBuf ws_sp_q_, ws_sp_split_;  // batch queries (CSR), per-split lists
 
     // index-time state
     bool created_ = false;       // nmslib_create_index was called

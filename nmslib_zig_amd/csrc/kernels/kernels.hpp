@@ -20,6 +20,8 @@ enum SpaceCode : int {
     // cosine over pre-normalised rows
     SP_L2SQR = 7,
     SP_NORMCOS = 8,
+    // sparse only: -QueryNormScalarProduct over the union arrays (querynorm_negdotprod_sparse)
+    SP_QNORM_NEGDOT = 9,
 };
 
 // ---- geometry shared by host and device ------------------------------------------------
@@ -337,6 +339,39 @@ size_t bf_bigk_temp_bytes(int n);
 hipError_t launch_bf_bigk(int space, const void* rows, int ld, int n, const void* queries_padded, size_t query_stride_bytes,
                           int nq, int dim, int k, const int32_t* ext_ids, float* dist_ws, uint32_t* key_ws, void* temp,
                           size_t temp_bytes, int32_t* out_ids, float* out_dists, int32_t* out_cnt, hipStream_t s);
+
+// Range selection over a precomputed distance array: the matches of `filter` (distance <= radius), in position order,
+// the first `capacity` of them, each reported with report[position] (the dense path passes filter twice).
+hipError_t launch_range_select(const float* filter, const float* report, int n, float radius, const int32_t* ext_ids,
+                               int* count_ws, int capacity, int32_t* out_ids, float* out_dists, hipStream_t s);
+
+// ---- sparse vectors (sparse_kernels.hip) -----------------------------------------------------
+// Rows and queries are CSR: row_ptr int64 [n+1], ids uint32, vals f32.  Spaces: SP_L2, SP_L1, SP_LINF, SP_COSINE,
+// SP_ANGULAR, SP_NEGDOT, SP_QNORM_NEGDOT, each evaluated over the union of the two id lists.
+constexpr int kSparseQCap = 4096;   // query elements staged in LDS by the k-NN scan (longer: read from HBM)
+constexpr int kSparseMaxKl = 4096;  // for k above this a split holds at most this many rows (its list keeps them all)
+constexpr int kSparseTileQ = 8;     // queries per workgroup of the k-NN scan (k small enough for 8 key buffers in LDS)
+struct SparseScanPlan {
+    int n, nq, k;
+    int nsplit, rows_per_split;  // row ranges scanned by separate workgroups
+    int kl;                      // keys kept per (split, query) = min(k, rows_per_split)
+    int P;                       // LDS key buffer per query (power of two >= kl + 256)
+    int tq;                      // queries per workgroup (kSparseTileQ or 1)
+};
+SparseScanPlan sparse_make_plan(int n, int nq, int k);
+size_t sparse_knn_lds_bytes(const SparseScanPlan& p);
+// per-(split, query) lists, ascending (distance, position): split_d / split_pos [nsplit][nq][k]; merged by
+// launch_merge_topk_ex with shard_stride nq*k
+hipError_t launch_sparse_knn(int space, const SparseScanPlan& p, const int64_t* row_ptr, const uint32_t* ids,
+                             const float* vals, const int64_t* q_ptr, const uint32_t* q_ids, const float* q_vals,
+                             float* split_d, int32_t* split_pos, hipStream_t s);
+// d_row_q[r] = distance(row r, query), d_q_row[r] = distance(query, row r)
+hipError_t launch_sparse_dist(int space, const int64_t* row_ptr, const uint32_t* ids, const float* vals, int n,
+                              const uint32_t* q_ids, const float* q_vals, int qn, float* d_row_q, float* d_q_row,
+                              hipStream_t s);
+// *out = distance(row p1, row p2)
+hipError_t launch_sparse_pair(int space, const int64_t* row_ptr, const uint32_t* ids, const float* vals, int p1, int p2,
+                              float* out, hipStream_t s);
 
 // ---- shard merge ---------------------------------------------------------------------------
 // shard s's lists start at dists_in + s*shard_stride / ids_in + s*shard_stride (elements)

@@ -74,7 +74,7 @@ __global__ __launch_bounds__(256) void range_scan_kernel(int* block_counts, int 
     if (threadIdx.x == 0) block_counts[nb] = carry;
 }
 
-__global__ __launch_bounds__(256) void range_scatter_kernel(const float* dist, int n, float radius,
+__global__ __launch_bounds__(256) void range_scatter_kernel(const float* dist, const float* report, int n, float radius,
                                                             const int* block_offsets, const int32_t* ext_ids,
                                                             int capacity, int32_t* out_ids, float* out_dists) {
     const int row0 = blockIdx.x * kRangeBlockRows + threadIdx.x * 4;
@@ -92,7 +92,7 @@ __global__ __launch_bounds__(256) void range_scatter_kernel(const float* dist, i
         if (row0 + i < n && d[i] <= radius) {
             if (at < capacity) {
                 out_ids[at] = ext_ids[row0 + i];
-                out_dists[at] = d[i];
+                out_dists[at] = report[row0 + i];
             }
             ++at;
         }
@@ -106,10 +106,16 @@ hipError_t launch_range_search(int space, const void* rows, int ld, int n, const
     int grid = (n + 3) / 4;
     if (grid > 65536) grid = 65536;
     hipLaunchKernelGGL(range_dist_kernel, dim3(grid), dim3(256), 0, s, space, rows, ld, n, query_padded, dim, dist_ws);
+    return launch_range_select(dist_ws, dist_ws, n, radius, ext_ids, count_ws, capacity, out_ids, out_dists, s);
+}
+
+hipError_t launch_range_select(const float* filter, const float* report, int n, float radius, const int32_t* ext_ids,
+                               int* count_ws, int capacity, int32_t* out_ids, float* out_dists, hipStream_t s) {
+    if (n <= 0) return hipMemsetAsync(count_ws, 0, 4, s);
     const int nb = (n + kRangeBlockRows - 1) / kRangeBlockRows;
-    hipLaunchKernelGGL(range_count_kernel, dim3(nb), dim3(256), 0, s, dist_ws, n, radius, count_ws);
+    hipLaunchKernelGGL(range_count_kernel, dim3(nb), dim3(256), 0, s, filter, n, radius, count_ws);
     hipLaunchKernelGGL(range_scan_kernel, dim3(1), dim3(256), 0, s, count_ws, nb);
-    hipLaunchKernelGGL(range_scatter_kernel, dim3(nb), dim3(256), 0, s, dist_ws, n, radius, count_ws, ext_ids,
+    hipLaunchKernelGGL(range_scatter_kernel, dim3(nb), dim3(256), 0, s, filter, report, n, radius, count_ws, ext_ids,
                        capacity, out_ids, out_dists);
     return hipGetLastError();
 }
