@@ -30,7 +30,7 @@ typedef enum {
     NMSLIB_DATATYPE_DENSE_VECTOR,        /* float32 rows                      */
     NMSLIB_DATATYPE_SPARSE_VECTOR,       /* accepted by the ABI, not by the GPU engine */
     NMSLIB_DATATYPE_DENSE_UINT8_VECTOR,  /* 128-byte SIFT descriptors         */
-    NMSLIB_DATATYPE_OBJECT_AS_STRING     /* accepted by the ABI, not by the GPU engine */
+    NMSLIB_DATATYPE_OBJECT_AS_STRING     /* leven, bit_hamming (int distance)  */
 } nmslib_data_type_t;
 
 typedef enum { NMSLIB_DISTTYPE_FLOAT, NMSLIB_DISTTYPE_INT } nmslib_dist_type_t;

@@ -98,6 +98,12 @@ typedef struct {
 } nmslib_gpu_stats_t;
 nmslib_error_t nmslib_gpu_get_stats(nmslib_index_handle_t index, nmslib_gpu_stats_t* out);
 
+/* The HNSW graph of a string index (data type 3), for inspection: *enterpoint, *maxlevel and, for node `node` at
+ * `level`, its neighbour list (positions) in out[0 .. *count) when *count <= capacity.  level above the node's own
+ * level -> NMSLIB_ERROR_INVALID_ARGUMENT.  Other indexes -> NMSLIB_ERROR_SPACE_INCOMPATIBLE. */
+nmslib_error_t nmslib_gpu_string_hnsw_links(nmslib_index_handle_t index, size_t node, int level, int32_t* out,
+                                            size_t capacity, size_t* count, int* enterpoint, int* maxlevel);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,10 @@ def sparse_rows(rows):
     return el, counts
 
 
+def _as_bytes(s):
+    return s.encode() if isinstance(s, str) else bytes(s)
+
+
 def sparse_vector(ids, values):
     """One sparse vector as nmslib_sparse_elem_float_t elements."""
     el = np.empty(len(ids), SPARSE_ELEM)
@@ -138,6 +142,8 @@ def lib():
         "nmslib_add_data_point_batch": (C.c_int, [vp, vp, sz, sz, vp, vp]),
         "nmslib_add_data_point_batch_uint8": (C.c_int, [vp, vp, sz, sz, vp]),
         "nmslib_add_data_point_batch_string": (C.c_int, [vp, vp, sz, vp]),
+        "nmslib_gpu_string_hnsw_links": (C.c_int, [vp, sz, C.c_int, vp, sz, C.POINTER(sz), C.POINTER(C.c_int),
+                                                  C.POINTER(C.c_int)]),
         "nmslib_add_data_point_batch_pointers": (C.c_int, [vp, C.c_int, vp, sz, sz, vp, vp]),
         "nmslib_knn_query_get_size": (C.c_int, [vp, vp, sz, sz, C.POINTER(sz), sz]),
         "nmslib_knn_query_fill": (C.c_int, [vp, vp, sz, sz, C.POINTER(Result), sz]),
@@ -193,7 +199,8 @@ ABI_SYMBOLS_C = [  # the 37 symbols of the reference boundary
 ]
 ABI_SYMBOLS_GPU = ["nmslib_gpu_device_count", "nmslib_gpu_finalize",
                    "nmslib_gpu_knn_query_batch_device", "nmslib_gpu_last_batch_counters",
-                   "nmslib_gpu_merge_topk", "nmslib_gpu_merge_topk_strided", "nmslib_gpu_get_stats", "nmslib_gpu_kernel_timing"]
+                   "nmslib_gpu_merge_topk", "nmslib_gpu_merge_topk_strided", "nmslib_gpu_get_stats", "nmslib_gpu_kernel_timing",
+                   "nmslib_gpu_string_hnsw_links"]
 
 
 class TrackingAllocator:
@@ -325,6 +332,17 @@ class Index:
                                                  None if idp is None else idp.ctypes.data, counts.ctypes.data),
                self.alloc)
 
+    def addStringBatch(self, strings, ids=None):
+        """lib.zig addStringBatch: one NUL-terminated string per row (nmslib_add_data_point_batch_string).  leven rows
+        are the strings' bytes; bit_hamming rows are texts of 0/1 values ("0 1 1 0")."""
+        bs = [_as_bytes(x) for x in strings]
+        if not bs:
+            return
+        arr = (C.c_char_p * len(bs))(*bs)
+        idp = None if ids is None else np.ascontiguousarray(ids, np.int32)
+        _check(lib().nmslib_add_data_point_batch_string(self.h, C.cast(arr, C.c_void_p), len(bs),
+                                                        None if idp is None else idp.ctypes.data), self.alloc)
+
     def buildIndex(self, **index_params):
         p = Params(self.alloc, **index_params) if index_params else None
         try:
@@ -349,6 +367,9 @@ class Index:
             q = query if isinstance(query, np.ndarray) and query.dtype == SPARSE_ELEM else sparse_vector(*query)
             q = np.ascontiguousarray(q)
             return q, max(2 * len(q), 1), len(q)
+        if self.data_type == "ObjectAsString":   # create_object: elem_count - 1 bytes (nmslib_c.cpp:275-285)
+            b = _as_bytes(query)
+            return np.frombuffer(b + b"\0", np.uint8).copy(), len(b) + 1, 0
         q = np.ascontiguousarray(query, np.uint8 if self.data_type == "DenseUInt8Vector" else np.float32)
         return q, q.shape[0], 0
 
@@ -389,6 +410,8 @@ class Index:
         at byte i * query_size_or_elem_count * 4, one slot of the longest query's size each, num_elements[i] elements."""
         L = lib()
         num = None
+        if self.data_type == "ObjectAsString":
+            return self._knn_string_batch(queries, k)
         if self.data_type == "SparseVector":
             el, counts = sparse_rows(queries)
             nq, width = len(counts), max(int(counts.max()) if len(counts) else 1, 1)
@@ -411,6 +434,41 @@ class Index:
                                         None if num is None else num.ctypes.data, 0), self.alloc)
         cnt = np.array([res[i].size for i in range(nq)], np.int32)
         return ids, ds, cnt
+
+    def _knn_string_batch(self, queries, k):
+        """String queries in the reference's batch layout (nmslib_c.cpp:1003-1031): query i at byte
+        i * query_size_or_elem_count * 4, each query_size_or_elem_count - 1 bytes long.  One call per distinct length."""
+        L = lib()
+        bs = [_as_bytes(x) for x in queries]
+        nq = len(bs)
+        ids = np.full((nq, k), -1, np.int32)
+        ds = np.full((nq, k), np.inf, np.float32)
+        cnt = np.zeros(nq, np.int32)
+        for ln in sorted(set(len(b) for b in bs)):
+            sel = [i for i, b in enumerate(bs) if len(b) == ln]
+            qsz = ln + 1
+            buf = np.zeros((len(sel), 4 * qsz), np.uint8)
+            for j, i in enumerate(sel):
+                buf[j, :ln] = np.frombuffer(bs[i], np.uint8)
+            gi = np.full((len(sel), k), -1, np.int32)
+            gd = np.full((len(sel), k), np.inf, np.float32)
+            res = (Result * len(sel))()
+            for j in range(len(sel)):
+                res[j] = Result(gi[j].ctypes.data_as(C.POINTER(C.c_int32)), gd[j].ctypes.data_as(C.POINTER(C.c_float)),
+                                0, k)
+            _check(L.nmslib_knn_query_batch(self.h, buf.ctypes.data, len(sel), qsz, k, res, None, 0), self.alloc)
+            ids[sel], ds[sel] = gi, gd
+            cnt[sel] = [res[j].size for j in range(len(sel))]
+        return ids, ds, cnt
+
+    def getDataPointString(self, pos):
+        """nmslib_get_data_point_string: data_len bytes (the object's bytes as the reference's strncpy copy leaves
+        them, plus the terminating NUL)."""
+        p, n = C.c_void_p(), C.c_size_t()
+        _check(lib().nmslib_get_data_point_string(self.h, pos, C.byref(p), C.byref(n), self.alloc.ref()), self.alloc)
+        s = C.string_at(p, n.value)
+        lib().nmslib_free_string(p, self.alloc.ref())
+        return s
 
     # -- device-resident entry (include/nmslib_gpu.h) -------------------------------------------
     def finalize(self):
@@ -488,6 +546,8 @@ class Index:
         if self.data_type == "SparseVector":   # -> (ids, values)
             el = buf.view(SPARSE_ELEM)
             return el["id"].copy(), el["value"].copy()
+        if self.data_type == "ObjectAsString":  # -> the object's bytes (bit_hamming: packed words + bit count)
+            return buf.tobytes()
         return buf.view(np.float32).copy()
 
     def save(self, path, save_data=True):

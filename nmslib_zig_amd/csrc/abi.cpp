@@ -98,6 +98,12 @@ using gfxknn::SparseElem;
 static_assert(sizeof(SparseElem) == sizeof(nmslib_sparse_elem_float_t), "sparse element layout");
 
 bool is_sparse(nmslib_index_handle_t h) { return H(h)->header.data_type == NMSLIB_DATATYPE_SPARSE_VECTOR; }
+bool is_string(nmslib_index_handle_t h) { return H(h)->header.data_type == NMSLIB_DATATYPE_OBJECT_AS_STRING; }
+
+// create_object (nmslib_c.cpp:275-285): a string query or row is elem_count - 1 bytes, or strlen when elem_count = 0
+size_t string_len(const void* data, size_t elem_count) {
+    return elem_count > 0 ? elem_count - 1 : std::strlen(static_cast<const char*>(data));
+}
 
 // validate_sparse_elements (nmslib_c.cpp:96-109, called with sorted = true): at least one element, ids strictly
 // increasing
@@ -275,6 +281,15 @@ nmslib_error_t nmslib_add_data_point(nmslib_index_handle_t handle, const void* d
             e->add_sparse_row(static_cast<const SparseElem*>(data), element_count, id);
         });
     }
+    if (is_string(handle)) {
+        return guarded(NMSLIB_ERROR_RUNTIME, "Failed to add data point", [&] {
+            Engine* e = H(handle)->engine;
+            std::lock_guard<std::mutex> lk(e->mu);
+            const char* s = static_cast<const char*>(data);
+            const size_t len = string_len(data, element_count);
+            e->add_strings(&s, &len, 1, &id);
+        });
+    }
     return guarded(NMSLIB_ERROR_RUNTIME, "Failed to add data point", [&] {
         Engine* e = H(handle)->engine;
         std::lock_guard<std::mutex> lk(e->mu);
@@ -332,7 +347,19 @@ nmslib_error_t nmslib_add_data_point_batch_string(nmslib_index_handle_t handle, 
                                                   size_t count, const int32_t* ids) {
     (void)ids;
     if (!handle || !data || count == 0) FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid string batch inputs");
-    FAIL(NMSLIB_ERROR_SPACE_INCOMPATIBLE, "Not string space");  // nmslib_c.cpp:883-887
+    if (!is_string(handle)) FAIL(NMSLIB_ERROR_SPACE_INCOMPATIBLE, "Not string space");  // nmslib_c.cpp:883-887
+    // NUL-terminated strings (std::string(data[i]), nmslib_c.cpp:898); the whole batch is checked before any row is
+    // stored, so a refused batch leaves the index as it was
+    std::vector<size_t> lens(count);
+    for (size_t i = 0; i < count; ++i) {
+        if (!data[i]) FAIL(NMSLIB_ERROR_NULL_POINTER, "Null string in batch");
+        lens[i] = std::strlen(data[i]);
+    }
+    return guarded(NMSLIB_ERROR_RUNTIME, "Failed to add string batch", [&] {
+        Engine* e = H(handle)->engine;
+        std::lock_guard<std::mutex> lk(e->mu);
+        e->add_strings(data, lens.data(), count, ids);
+    });
 }
 
 nmslib_error_t nmslib_add_data_point_batch_pointers(nmslib_index_handle_t handle, nmslib_data_mode_t data_mode,
@@ -427,12 +454,22 @@ nmslib_error_t nmslib_knn_query_batch(nmslib_index_handle_t index, const void* q
             }
         }
     }
+    // strings: the same slots, each query query_size_or_elem_count - 1 bytes (create_object, nmslib_c.cpp:275-285)
+    std::vector<const char*> tq;
+    std::vector<size_t> tl;
+    if (is_string(index)) {
+        tq.resize(query_count);
+        tl.assign(query_count, query_size_or_elem_count - 1);
+        for (size_t i = 0; i < query_count; ++i)
+            tq[i] = static_cast<const char*>(queries) + i * query_size_or_elem_count * sizeof(float);
+    }
     bool too_small = false;
     nmslib_error_t rc = guarded(NMSLIB_ERROR_QUERY_EXECUTION_FAILED, "KNN query failed", [&] {
         std::lock_guard<std::mutex> lk(e->mu);
         const int32_t *ids = nullptr, *cnt = nullptr;
         const float* dists = nullptr;
         if (!sq.empty()) e->knn_sparse_host(sq.data(), sn.data(), query_count, k, &ids, &dists, &cnt);
+        else if (!tq.empty()) e->knn_string_host(tq.data(), tl.data(), query_count, k, &ids, &dists, &cnt);
         else e->knn_host(queries, query_count, query_size_or_elem_count, k, &ids, &dists, &cnt);
         for (size_t i = 0; i < query_count; ++i) {
             fill_result(&results[i], &ids[i * k], &dists[i * k], (size_t)cnt[i]);
@@ -488,6 +525,10 @@ nmslib_error_t nmslib_range_query_fill(nmslib_index_handle_t index, const void* 
         if (sparse)
             result->size = e->range_sparse_host(static_cast<const SparseElem*>(query), num_elements, radius,
                                                 result->capacity, result->ids, result->distances);
+        else if (is_string(index))
+            result->size = e->range_string_host(static_cast<const char*>(query),
+                                                string_len(query, query_size_or_elem_count), radius, result->capacity,
+                                                result->ids, result->distances);
         else
             result->size = e->range_host(query, query_size_or_elem_count, radius, result->capacity, result->ids,
                                          result->distances);
@@ -517,7 +558,9 @@ nmslib_error_t nmslib_get_distance(nmslib_index_handle_t index, size_t pos1, siz
 nmslib_error_t nmslib_get_data_point_size(nmslib_index_handle_t index, size_t position, size_t* size) {
     if (!index || position >= nmslib_data_qty(index) || !size) FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid data point size inputs");
     Engine* e = H(index)->engine;
-    *size = e->is_sparse() ? e->sparse_row_len(position) * sizeof(SparseElem) : e->stored_row_bytes();  // Object::datalength()
+    *size = e->is_sparse()   ? e->sparse_row_len(position) * sizeof(SparseElem)
+            : e->is_string() ? e->string_object_bytes(position)
+                             : e->stored_row_bytes();  // Object::datalength()
     SET_LAST(NMSLIB_SUCCESS, "Data point size retrieved");
     return NMSLIB_SUCCESS;
 }
@@ -533,6 +576,13 @@ nmslib_error_t nmslib_get_data_point_fill(nmslib_index_handle_t index, size_t po
         SET_LAST(NMSLIB_SUCCESS, "Data point filled");
         return NMSLIB_SUCCESS;
     }
+    if (e->is_string()) {
+        const std::string obj = e->string_object(position);
+        if (size < obj.size()) FAIL(NMSLIB_ERROR_BUFFER_TOO_SMALL, "Buffer too small for data point");
+        std::memcpy(data, obj.data(), obj.size());
+        SET_LAST(NMSLIB_SUCCESS, "Data point filled");
+        return NMSLIB_SUCCESS;
+    }
     if (size < e->stored_row_bytes()) FAIL(NMSLIB_ERROR_BUFFER_TOO_SMALL, "Buffer too small for data point");
     e->stored_row(position, data);
     SET_LAST(NMSLIB_SUCCESS, "Data point filled");
@@ -543,7 +593,17 @@ nmslib_error_t nmslib_get_data_point_string(nmslib_index_handle_t index, size_t 
                                             size_t* data_len, const nmslib_allocator_t* allocator) {
     if (!index || !data || !data_len || !allocator || position >= nmslib_data_qty(index))
         FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid string data point inputs");
-    FAIL(NMSLIB_ERROR_SPACE_INCOMPATIBLE, "Invalid data type for string");
+    if (!is_string(index)) FAIL(NMSLIB_ERROR_SPACE_INCOMPATIBLE, "Invalid data type for string");
+    // nmslib_c.cpp:1246-1251: *data_len = datalength() + 1 and the copy is made by strncpy, so it ends at the object's
+    // first NUL byte and is zero-filled from there (a bit_hamming object holds binary words)
+    const std::string obj = H(index)->engine->string_object(position);
+    char* out = static_cast<char*>(allocator->alloc(obj.size() + 1, allocator->ctx));
+    if (!out) FAIL(NMSLIB_ERROR_OUT_OF_MEMORY, "Failed to allocate string");
+    std::strncpy(out, obj.c_str(), obj.size() + 1);
+    *data = out;
+    *data_len = obj.size() + 1;
+    SET_LAST(NMSLIB_SUCCESS, "String data point retrieved");
+    return NMSLIB_SUCCESS;
 }
 
 namespace {
@@ -800,6 +860,26 @@ nmslib_error_t nmslib_gpu_get_stats(nmslib_index_handle_t handle, nmslib_gpu_sta
         out->last_path = (size_t)e->last_path;
         e->fast_tile_counts(&out->fast_tiles, &out->fast_tiles_precise, &out->fast_tiles_fallback);
         out->hnsw_redone = e->hnsw_redone();
+    });
+}
+
+nmslib_error_t nmslib_gpu_string_hnsw_links(nmslib_index_handle_t index, size_t node, int level, int32_t* out,
+                                            size_t capacity, size_t* count, int* enterpoint, int* maxlevel) {
+    if (!index || !count || !enterpoint || !maxlevel || node >= nmslib_data_qty(index) || level < 0)
+        FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid graph inputs");
+    Engine* e = H(index)->engine;
+    if (!e->is_string() || e->method_name() != "hnsw") FAIL(NMSLIB_ERROR_SPACE_INCOMPATIBLE, "Not a string HNSW index");
+    if (!e->index_created()) FAIL(NMSLIB_ERROR_INDEX_BUILD_FAILED, "Index not built");
+    return guarded(NMSLIB_ERROR_RUNTIME, "Graph inspection", [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        const gfxknn::HostGraph& g = e->string_graph();
+        if (level > g.levels[node]) throw EngineError(Err::InvalidArgument, "level above the node's level");
+        const int32_t* L = level == 0 ? &g.links0[node * (size_t)(g.maxM0 + 1)]
+                                      : &g.up_links[(size_t)g.up_off[node] + (size_t)(level - 1) * (g.maxM + 1)];
+        *count = (size_t)L[0];
+        *enterpoint = g.enterpoint;
+        *maxlevel = g.maxlevel;
+        if (out && *count <= capacity) std::memcpy(out, L + 1, *count * sizeof(int32_t));
     });
 }
 

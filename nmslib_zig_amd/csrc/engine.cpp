@@ -160,6 +160,25 @@ Engine::Engine(const std::string& space, const std::string& method, int data_typ
         thread_pool_size = std::thread::hardware_concurrency();
         return;
     }
+    if (data_type == 3) {
+        // the int-registry string spaces (include/factory/init_spaces.h:47-53) with the int distance; normleven and
+        // bit_jaccard are float spaces that the reference's data type 3 dispatch would treat as int indexes
+        // (nmslib_c.cpp:205-208)
+        if (space != "leven" && space != "bit_hamming")
+            throw EngineError(Err::SpaceIncompatible,
+                              "string space '" + space + "' is not served by the GPU engine (string spaces: leven, "
+                              "bit_hamming)");
+        if (dist_type != 1)
+            throw EngineError(Err::SpaceIncompatible, "string space '" + space + "' is served with the int distance type");
+        if (method != "brute_force" && method != "seq_search" && method != "hnsw")
+            throw EngineError(Err::SpaceIncompatible, "method '" + method +
+                                                          "' over string data is not served (strings: hnsw, brute_force, "
+                                                          "seq_search)");
+        space_ = space == "leven" ? SP_LEVEN : SP_BIT_HAMMING;
+        str_space_ = true;
+        thread_pool_size = std::thread::hardware_concurrency();
+        return;
+    }
     const int sp = space_from_name(space);
     if (sp < 0)
         throw EngineError(Err::SpaceIncompatible,
@@ -217,7 +236,7 @@ void Engine::collect_profile(double* total_ms, uint64_t* launches) {
 }
 
 void Engine::add_row(const void* data, size_t elem_count, int32_t id) {
-    if (sparse_) throw EngineError(Err::SpaceIncompatible, "Not dense space");
+    if (sparse_ || str_space_) throw EngineError(Err::SpaceIncompatible, "Not dense space");
     if (is_u8()) {
         // CreateObjFromUint8Vect CHECKs size == SIFT_DIM (space_l2sqr_sift.cc:136-140)
         if (elem_count != 128) throw EngineError(Err::Runtime, "SIFT vectors must have 128 bytes");
@@ -259,6 +278,10 @@ void Engine::reset() {
     sp_ptr_.assign(1, 0);
     sp_ids_.clear();
     sp_vals_.clear();
+    st_ptr_.assign(1, 0);
+    st_bytes_.clear();
+    st_words_.clear();
+    st_bits_ = -1;
     graph_ = HostGraph();
     graph_rows_.clear();
     loaded_graph_ = false;
@@ -282,6 +305,9 @@ size_t Engine::memory_usage() const {
     if (!created_) return 0;
     if (sparse_)  // objects (16-byte header + elements) and the CSR copy in HBM
         return ids_.size() * 16 + sp_ids_.size() * sizeof(SparseElem) + hbm_bytes();
+    if (str_space_)  // objects (16-byte header + datalength) and the store's copy in HBM
+        return ids_.size() * 16 + (space_ == SP_LEVEN ? st_bytes_.size() : ids_.size() * (ham_words() + 1) * 4) +
+               hbm_bytes();
     size_t total = ids_.size() * (16 + stored_row_bytes());
     total += ids_.size() * dim_ * sizeof(float);
     return total;
@@ -292,7 +318,7 @@ size_t Engine::hbm_bytes() const {
     for (const auto& c : shards_) sh += c->hbm_bytes();
     return sh + d_rows_.bytes() + d_rows_i8_.bytes() + d_aux_.bytes() + d_ids_.bytes() + d_links0_.bytes() + d_up_off_.bytes() +
            d_up_links_.bytes() + d_rownorm_.bytes() + d_rows_sel_.bytes() + d_auxh_.bytes() + d_bf_hi_.bytes() + d_bf_lo_.bytes() + d_auxp_.bytes() +
-           d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes();
+           d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes() + d_st_ptr_.bytes() + d_st_data_.bytes();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -340,8 +366,9 @@ void Engine::create_index(const std::vector<std::string>& params) {
         ps.get("gpu_defer", defer);
         ps.get("gpu_shards", gpu_shards_);
         ps.check_unused();
-        if (sparse_ && gpu_shards_ != -1 && gpu_shards_ != 1)
-            throw EngineError(Err::IndexBuildFailed, "a sparse index runs on one GPU: gpu_shards=" +
+        if ((sparse_ || str_space_) && gpu_shards_ != -1 && gpu_shards_ != 1)
+            throw EngineError(Err::IndexBuildFailed, std::string(sparse_ ? "a sparse" : "a string") +
+                                                         " index runs on one GPU: gpu_shards=" +
                                                          std::to_string(gpu_shards_) + " is not supported");
     } else {
         throw EngineError(Err::IndexBuildFailed,
@@ -728,6 +755,11 @@ void Engine::build_graph_gpu() {
 
 void Engine::ensure_graph() {
     if (method_ != Method::Hnsw || !graph_dirty_) return;
+    if (str_space_) {
+        build_string_graph();
+        graph_dirty_ = false;
+        return;
+    }
     if (use_gpu_build() || (!parent_ && (shards_.size() > 1 || (dirty_ && resolve_shards() > 1)))) {
         finalize();
         return;
@@ -741,6 +773,11 @@ void Engine::finalize() {
     if (!dirty_) return;
     if (sparse_) {
         upload_sparse();
+        dirty_ = false;
+        return;
+    }
+    if (str_space_) {
+        upload_strings();
         dirty_ = false;
         return;
     }
@@ -1096,9 +1133,9 @@ void Engine::knn_device(const void* d_queries, size_t nq, size_t elem_count, siz
     check_device();
     if (nq == 0) return;
     if (k == 0) throw EngineError(Err::InvalidArgument, "k must be positive");
-    if (sparse_)
-        throw EngineError(Err::SpaceIncompatible, "the device-resident batch takes dense queries; sparse queries go "
-                                                  "through nmslib_knn_query_batch");
+    if (sparse_ || str_space_)
+        throw EngineError(Err::SpaceIncompatible, "the device-resident batch takes dense queries; sparse and string "
+                                                  "queries go through nmslib_knn_query_batch");
     last_stream_ = stream;
     if (!shards_.empty()) {
         if (size() > 0 && elem_count != dim_)
@@ -1554,6 +1591,7 @@ size_t Engine::range_host(const void* query, size_t elem_count, double radius, s
 float Engine::pair_distance(size_t p1, size_t p2) {
     // Space::IndexTimeDistance on the ORIGINAL rows (nmslib_c.cpp:1166), one wave on the GPU
     if (sparse_) return pair_distance_sparse(p1, p2);
+    if (str_space_) return pair_distance_string(p1, p2);
     check_device();
     const size_t rb = is_u8() ? 128 : (size_t)f32_row_stride((int)dim_) * 4;
     ws_pair_.ensure(2 * rb + 16);
@@ -1586,6 +1624,9 @@ static void rd(std::istream& i, T& v) {
 
 void Engine::save(const std::string& path, bool save_data) {
     if (!created_) throw EngineError(Err::InvalidArgument, "Index not built");
+    if (str_space_)  // SeqSearch has no SaveIndex (include/index.h:56-58); the object file is not written either
+        throw EngineError(Err::DataIO, "SaveIndex is not implemented for method: Sequential search (string index; "
+                                       "the data file is not written)");
     if (sparse_)  // SeqSearch has no SaveIndex (include/index.h:56-58); the object file is not written either
         throw EngineError(Err::DataIO, "SaveIndex is not implemented for method: Sequential search (sparse index; "
                                        "the data file is not written)");

@@ -111,6 +111,9 @@ std::vector<int32_t> hnsw_random_levels(size_t n, const HnswBuildParams& bp);
 // or u8 [n][128].
 void hnsw_build_host(int space, const void* rows, size_t n, size_t dim, const HnswBuildParams& bp,
                      HostGraph& out);
+// ... over strings: leven rows as CSR bytes (row_ptr, bytes), bit_hamming rows as W words each
+void hnsw_build_strings(int space, const int64_t* row_ptr, const uint8_t* bytes, const uint32_t* words, size_t W,
+                        size_t n, const HnswBuildParams& bp, HostGraph& out);
 
 // ---- the index ---------------------------------------------------------------------------------
 enum class Method { Brute, Hnsw };
@@ -154,6 +157,22 @@ class Engine {
                          const int32_t** ids, const float** dists, const int32_t** cnt);
     size_t range_sparse_host(const SparseElem* query, size_t count, double radius, size_t capacity, int32_t* ids,
                              float* dists);
+
+    // ---- strings (data type 3; strings.cpp): leven and bit_hamming ----
+    bool is_string() const { return str_space_; }
+    // the HNSW graph of a string index (built by finalize / a deferred create_index), for inspection
+    const HostGraph& string_graph() {
+        ensure_graph();
+        return graph_;
+    }
+    // one row per string (strs[i]: lens[i] bytes); the whole batch is checked before any row is stored
+    void add_strings(const char* const* strs, const size_t* lens, size_t count, const int32_t* ids);
+    size_t string_object_bytes(size_t pos) const;  // Object::datalength()
+    std::string string_object(size_t pos) const;   // Object::data(), as the reference builds it
+    // k-NN of nq string queries (query i: lens[i] bytes); results in the pinned staging block
+    void knn_string_host(const char* const* queries, const size_t* lens, size_t nq, size_t k, const int32_t** ids,
+                         const float** dists, const int32_t** cnt);
+    size_t range_string_host(const char* query, size_t len, double radius, size_t capacity, int32_t* ids, float* dists);
 
     void create_index(const std::vector<std::string>& params);  // nmslib_create_index
     void set_query_params(const std::vector<std::string>& params);
@@ -226,6 +245,14 @@ class Engine {
     void check_device();
     void upload_sparse();
     float pair_distance_sparse(size_t p1, size_t p2);
+    void upload_strings();
+    void build_string_graph();
+    void knn_string_hnsw(const int64_t* d_qoff, const int32_t* d_qlen, const uint64_t* d_peq, const uint32_t* d_qw,
+                         int nw_max, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt);
+    float pair_distance_string(size_t p1, size_t p2);
+    static bool parse_bits(const char* s, size_t len, std::vector<uint32_t>& words, size_t& bits);
+    void string_query(const char* s, size_t len, Err parse_err, std::vector<uint32_t>& words) const;
+    size_t ham_words() const { return st_bits_ > 0 ? (size_t)(st_bits_ + 31) / 32 : 0; }
     void ensure_graph();
     void upload_rows();
     void build_graph();
@@ -254,6 +281,15 @@ class Engine {
     std::vector<float> sp_vals_;
     DevBuf d_sp_ptr_, d_sp_ids_, d_sp_vals_;
     DevBuf ws_sp_q_, ws_sp_split_;  // batch queries (CSR), per-split lists
+    // string rows: leven CSR bytes, or bit_hamming words (W = ham_words() per row, st_bits_ bits; -1: no row yet);
+    // the HBM copy after finalize
+    bool str_space_ = false;
+    std::vector<int64_t> st_ptr_{0};
+    std::vector<uint8_t> st_bytes_;
+    std::vector<uint32_t> st_words_;
+    int64_t st_bits_ = -1;
+    DevBuf d_st_ptr_, d_st_data_;
+    DevBuf ws_st_q_, ws_st_split_, ws_st_mw_;  // batch queries, per-split lists, multi-block leven state
 
     // index-time state
     bool created_ = false;       // nmslib_create_index was called

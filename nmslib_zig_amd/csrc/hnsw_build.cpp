@@ -110,13 +110,47 @@ inline float lane4_normdot(const float* a, const float* b, size_t n) {  // distc
     return v > -1.0f ? v : -1.0f;
 }
 
+// levenshtein (src/distcomp_edist.cc): unit-cost edit distance, the shorter string as the column
+int leven_host(const uint8_t* p1, size_t len1, const uint8_t* p2, size_t len2) {
+    if (len1 > len2) {
+        std::swap(p1, p2);
+        std::swap(len1, len2);
+    }
+    if (len1 == 0) return (int)len2;
+    thread_local std::vector<int> col;
+    col.resize(2 * (len1 + 1));
+    int* prev = col.data();
+    int* cur = prev + len1 + 1;
+    for (size_t k = 0; k <= len1; ++k) prev[k] = (int)k;
+    for (size_t i = 0; i < len2; ++i) {
+        cur[0] = (int)i + 1;
+        for (size_t k = 1; k <= len1; ++k)
+            cur[k] = std::min(1 + std::min(prev[k], cur[k - 1]), prev[k - 1] + (p1[k - 1] == p2[i] ? 0 : 1));
+        std::swap(prev, cur);
+    }
+    return prev[len1];
+}
+
 struct DistFn {
     int space;
     const float* f = nullptr;
     const uint8_t* u = nullptr;
     const int32_t* unorm = nullptr;
     size_t dim = 0;
+    // strings: leven CSR bytes, bit_hamming words (dim = words per row)
+    const int64_t* sptr = nullptr;
+    const uint8_t* sbytes = nullptr;
+    const uint32_t* words = nullptr;
     float operator()(int i, int j) const {
+        if (space == SP_LEVEN)  // exact integers in float
+            return (float)leven_host(sbytes + sptr[i], (size_t)(sptr[i + 1] - sptr[i]), sbytes + sptr[j],
+                                     (size_t)(sptr[j + 1] - sptr[j]));
+        if (space == SP_BIT_HAMMING) {  // BitHamming, include/distcomp.h:241-250
+            const uint32_t *a = words + (size_t)i * dim, *b = words + (size_t)j * dim;
+            int s = 0;
+            for (size_t t = 0; t < dim; ++t) s += __builtin_popcount(a[t] ^ b[t]);
+            return (float)s;
+        }
         if (u) {  // distcomp_l2sqr_sift.cc:41-50
             const uint8_t *a = u + (size_t)i * 128, *b = u + (size_t)j * 128;
             int32_t dot = 0;
@@ -596,6 +630,20 @@ std::vector<int32_t> hnsw_random_levels(size_t n, const HnswBuildParams& bp) {
     return levels;
 }
 
+static void build_with(const DistFn& dist, size_t n, const HnswBuildParams& bp, HostGraph& out);
+
+void hnsw_build_strings(int space, const int64_t* row_ptr, const uint8_t* bytes, const uint32_t* words, size_t W,
+                        size_t n, const HnswBuildParams& bp, HostGraph& out) {
+    hnsw_check_params(bp);
+    DistFn dist;
+    dist.space = space;
+    dist.dim = W;
+    dist.sptr = row_ptr;
+    dist.sbytes = bytes;
+    dist.words = words;
+    build_with(dist, n, bp, out);
+}
+
 void hnsw_build_host(int space, const void* rows, size_t n, size_t dim, const HnswBuildParams& bp,
                      HostGraph& out) {
     hnsw_check_params(bp);
@@ -615,6 +663,10 @@ void hnsw_build_host(int space, const void* rows, size_t n, size_t dim, const Hn
     } else {
         dist.f = static_cast<const float*>(rows);
     }
+    build_with(dist, n, bp, out);
+}
+
+static void build_with(const DistFn& dist, size_t n, const HnswBuildParams& bp, HostGraph& out) {
     const std::vector<int32_t> lv = hnsw_random_levels(n, bp);
     std::vector<int> levels(lv.begin(), lv.end());
     int threads = bp.threads > 0 ? bp.threads : (int)std::thread::hardware_concurrency();

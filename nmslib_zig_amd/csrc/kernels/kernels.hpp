@@ -22,6 +22,9 @@ enum SpaceCode : int {
     SP_NORMCOS = 8,
     // sparse only: -QueryNormScalarProduct over the union arrays (querynorm_negdotprod_sparse)
     SP_QNORM_NEGDOT = 9,
+    // strings (data type 3)
+    SP_LEVEN = 10,
+    SP_BIT_HAMMING = 11,
 };
 
 // ---- geometry shared by host and device ------------------------------------------------
@@ -372,6 +375,77 @@ hipError_t launch_sparse_dist(int space, const int64_t* row_ptr, const uint32_t*
 // *out = distance(row p1, row p2)
 hipError_t launch_sparse_pair(int space, const int64_t* row_ptr, const uint32_t* ids, const float* vals, int p1, int p2,
                               float* out, hipStream_t s);
+
+// ---- strings (string_kernels.hip) -----------------------------------------------------------
+// leven rows: CSR bytes (row_ptr int64 [n+1], data uint8).  Queries: Peq tables, [nw][256] uint64 per query at
+// q_off[q] (uint64 units, q_off [nq+1]), nw = ceil(len / 64), and their lengths q_len.
+// bit_hamming rows and queries: W uint32 words each (the reference's trailing count word is not stored).
+constexpr int kStrTileQ = 8;              // queries per workgroup of a k-NN scan (one-block leven queries, bit_hamming)
+constexpr int kStrMaxKl = 4096;           // for k above this a split holds at most this many rows
+constexpr size_t kStrPeqStage = 16384;    // bytes of Peq tables staged in LDS per workgroup (more: read from HBM)
+constexpr size_t kStrRowStage = 16384;    // bytes of a 256-row chunk staged in LDS (a longer chunk: read from HBM)
+constexpr int kStrMwLds = 4;              // multi-block leven: blocks whose state a lane keeps in LDS (more: HBM)
+constexpr size_t kStrHamQStage = 16384;   // bytes of bit_hamming queries staged in LDS per workgroup
+struct StringScanPlan {
+    int n, nq, k;
+    int nsplit, rows_per_split;  // row ranges scanned by separate workgroups
+    int kl;                      // keys kept per (split, query) = min(k, rows_per_split)
+    int P;                       // LDS key buffer per query (power of two >= kl + 256)
+    int tq;                      // queries per workgroup (the tq asked for, or 1 when k is large)
+};
+StringScanPlan string_make_plan(int n, int nq, int k, int tq);
+// HBM state of a multi-block leven scan (uint64 words; 0 when it fits LDS)
+size_t leven_mw_ws_words(const StringScanPlan& p, int nw);
+// per-(split, query) lists, ascending (distance, position): split_d / split_pos [nsplit][nq][k]; merged by
+// launch_merge_topk_ex with shard_stride nq*k.  nw = the batch's largest block count (nw > 1 needs p.tq == 1).
+hipError_t launch_leven_knn(const StringScanPlan& p, const int64_t* row_ptr, const uint8_t* data,
+                            const int64_t* q_off, const int32_t* q_len, const uint64_t* peq, int nw, uint64_t* mw_ws,
+                            float* split_d, int32_t* split_pos, hipStream_t s);
+hipError_t launch_ham_knn(const StringScanPlan& p, const uint32_t* rows, int W, const uint32_t* q, float* split_d,
+                          int32_t* split_pos, hipStream_t s);
+// d_out[r] = distance(row r, query); leven: mw_ws holds 2 * nw * 256 * leven_dist_grid(n) words when nw > 1
+int leven_dist_grid(int n);
+hipError_t launch_leven_dist(const int64_t* row_ptr, const uint8_t* data, int n, const uint64_t* peq, int m, int nw,
+                             uint64_t* mw_ws, float* d_out, hipStream_t s);
+hipError_t launch_ham_dist(const uint32_t* rows, int W, int n, const uint32_t* q, float* d_out, hipStream_t s);
+// *out = distance(pattern, row p2), the pattern given by its Peq table (mw_ws: 2 * nw words when nw > 1)
+hipError_t launch_leven_pair(const int64_t* row_ptr, const uint8_t* data, int p2, const uint64_t* peq, int m, int nw,
+                             uint64_t* mw_ws, float* out, hipStream_t s);
+hipError_t launch_ham_pair(const uint32_t* rows, int W, int p1, int p2, float* out, hipStream_t s);
+
+// HNSW search over strings (baseSearchAlgorithmV1Merge / baseSearchAlgorithmOld), one wave per query.  Queries as
+// for the scans (leven: Peq tables + lengths; bit_hamming: words).  Per query of a slice: vis_words of visited bits,
+// ws_per_query u64 words (string_hnsw_ws_words) and 64 * 2 * nw_max u64 of leven block state.
+struct StringHnswArgs {
+    int space;
+    const int64_t* row_ptr;
+    const uint8_t* data;
+    const uint32_t* words;
+    int W;
+    const int64_t* q_off;
+    const int32_t* q_len;
+    const unsigned long long* peq;
+    const uint32_t* q_words;
+    int nw_max;
+    const int32_t* links0;
+    const int64_t* up_off;
+    const int32_t* up_links;
+    const int32_t* ext_ids;
+    int n, maxM, maxM0, maxlevel, enterpoint;
+    int ef, k;
+    uint32_t* visited;
+    size_t vis_words;
+    unsigned long long* ws;
+    size_t ws_per_query;
+    unsigned long long* mw_ws;
+    int32_t* out_ids;
+    float* out_d;
+    int32_t* out_cnt;
+    int32_t *ndc, *hops, *hops_up;
+};
+size_t string_hnsw_ws_words(const StringHnswArgs& a, bool old);
+// queries [q0, q0 + nq) of the batch; workspaces hold nq queries
+hipError_t launch_string_hnsw(const StringHnswArgs& a, bool old, int q0, int nq, hipStream_t s);
 
 // ---- shard merge ---------------------------------------------------------------------------
 // shard s's lists start at dists_in + s*shard_stride / ids_in + s*shard_stride (elements)
