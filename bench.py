@@ -2,15 +2,18 @@
 """bench.py -- the reference's headline metric on MI355X.
 
 metric   : queries/sec @ recall@10, 1M x 128-D L2, batch=1024; HBM GB/s vs peak  (BASELINE.json)
-workloads: the default run measures three of BASELINE.json's configs in one go:
-             C2 "bruteforce"  brute-force L2, 1M x 128 f32, k=10, batch 1024   -> the headline line
+plain run: sets up C2 "bruteforce" (brute-force L2, 1M x 128 f32, k=10, batch 1024), warms up, times the steps
+           and prints the headline line (with the roofline of the timed launches).  With --dump-outputs the other
+           workloads of "all" below also go through their steps, to write their outputs; nothing of them is reported.
+--full   : also measures three more of BASELINE.json's configs in the same process, and checks every record:
              C3 "hnsw"        HNSW l2 1M x 128, M=16 efS=128, k=10, batch 1024 -> "workloads": {"hnsw": ...}
              C4 "sift"        l2sqr_sift 1M x 128 u8, k=100, batch 4096        -> "workloads": {"sift": ...}
-           every record carries its own roofline, cpu_baseline, host_entry and a recall against an
+             C5 shape "cos768x"                                                -> "workloads": {"cos768x": ...}
+           every record then carries its own cpu_baseline, host_entry and a recall against an
            INDEPENDENT exact ground truth (the reference's own sequential scan, oracle/_ref, on a query sample).
-           --workload X runs one of them alone (cos768 = one shard of C5).
+           --workload X runs one of them alone (cos768 = one shard of C5); --full adds the same legs to it.
 step     : one batch of queries, already resident in HBM, through the device-resident entry of the C ABI
-           (nmslib_gpu_knn_query_batch_device) on torch's current stream.  The reference-ABI entry
+           (nmslib_gpu_knn_query_batch_device) on torch's current stream.  Under --full the reference-ABI entry
            (nmslib_knn_query_batch: host pointers, PCIe inside the call) is timed beside it ("host_entry").
 N > 1    : the corpus is sharded by rows over the ranks (one process per GPU); every rank searches its shard
            for the same batch, per-shard top-k lists are all-gathered over RCCL and merged on the GPU
@@ -18,7 +21,7 @@ N > 1    : the corpus is sharded by rows over the ranks (one process per GPU); e
            environment launches the N ranks itself.
 
 One JSON line on stdout (rank 0).  torch is plumbing only: device buffers, streams, torch.distributed.
-The CPU baseline (rank 0, N == 1) times the real reference (oracle/_ref) on a bounded sample of the same
+The CPU baseline (--full, rank 0, N == 1) times the real reference (oracle/_ref) on a bounded sample of the same
 workload; the oracle is never part of the measured path.
 """
 import argparse
@@ -72,24 +75,30 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--workload", choices=["all"] + list(WORKLOADS), default="all")
+    ap.add_argument("--workload", choices=["all"] + list(WORKLOADS), default="all",
+                    help="all: the headline (bruteforce); with --full also hnsw, sift and cos768x (with "
+                         "--dump-outputs alone these run too, only to write their outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the other workloads of 'all', recall against the reference, "
+                         "the CPU baseline, the host-pointer entry, --ef-sweep")
     ap.add_argument("--rows-per-gpu", type=int, default=1_000_000, help="cos768x: rows indexed by every rank")
     ap.add_argument("--n", type=int, default=1_000_000)
     ap.add_argument("--dim", type=int, default=None)
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--k", type=int, default=None)
     ap.add_argument("--ef", type=int, default=128)
-    ap.add_argument("--ef-sweep", default="", help="hnsw / cos768: extra efSearch values measured on the same index, e.g. 256,512,1000")
+    ap.add_argument("--ef-sweep", default="", help="hnsw / cos768, --full: extra efSearch values measured on the same index, "
+                                                   "e.g. 256,512,1000")
     ap.add_argument("--rank", type=int, default=16, help="cos768 / cos768x: latent rank of the synthetic rows (16: the recall "
                                                          "set, recall@10 ~0.99 at efS=128; 64: the stress set, ~0.45 at 1M rows "
                                                          "for the reference's graph too -- tests/golden/c5_ref_1m768.json)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--index-cache", default="", help="hnsw, 1 GPU: save the built index here / load it if present")
     ap.add_argument("--gpu-build", type=int, default=-1, help="hnsw: 1 = batched GPU construction, 0 = host, -1 = library default")
     ap.add_argument("--space", default="", help="bruteforce workload: another dense space (l1, linf, cosinesimil, ...)")
     ap.add_argument("--index-extra", default="", help="hnsw: extra index parameters, k=v,k=v (experiments)")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="queries in the CPU baseline sample (0 = auto)")
-    ap.add_argument("--gt-sample", type=int, default=128, help="queries in the exact-ground-truth sample")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="--full: queries in the CPU baseline sample (0 = auto)")
+    ap.add_argument("--gt-sample", type=int, default=128, help="--full: queries in the exact-ground-truth sample")
     ap.add_argument("--dump", default="", help="rank 0 saves the ids / distances of the last timed step here (.npz): "
                                                   "tests compare sharded and unsharded runs")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
@@ -98,6 +107,8 @@ def parse():
     a = ap.parse_args()
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.ef_sweep and not a.full:
+        ap.error("--ef-sweep needs --full (its records carry a recall)")
     return a
 
 
@@ -382,7 +393,7 @@ def run_workload(a, name, cx):
     stats = idx.stats()
     last_path = int(stats.get("last_path", 0))
     gpu_gt = None
-    if sharded_gen or (name == "cos768" and n > 1_000_000):
+    if a.full and (sharded_gen or (name == "cos768" and n > 1_000_000)):
         # the reference's sequential scan of tens of GB is out of reach of a bench run: exact GPU scan instead
         note(f"[{name}] exact GPU scan for the ground truth")
         ngt = min(a.gt_sample, nq)
@@ -521,7 +532,7 @@ def run_workload(a, name, cx):
         idx.setQueryTimeParams(efSearch=a.ef)
 
     # ---- the reference-ABI entry: nmslib_knn_query_batch, host pointers, PCIe inside the call --------------
-    if world == 1:
+    if a.full and world == 1:
         h_ids = np.empty((nq, k), np.int32)
         h_ds = np.empty((nq, k), np.float32)
         res = (nz.Result * nq)()
@@ -540,6 +551,8 @@ def run_workload(a, name, cx):
         # what a caller of the reference's own ABI (lib.zig, C) gets, beside `value` (queries resident in HBM)
         out["value_host_entry"] = round(nq / th, 1)
     idx.close()
+    if not a.full:
+        return out
 
     # ---- recall against an independent exact ground truth + the CPU baseline ---------------------------------
     # (cos768 beyond 200k rows: the reference's 768-D build takes too long for a bench run; exact scan only)
@@ -621,13 +634,16 @@ def main():
 
     if a.workload == "all":
         out = run_workload(a, ALL_RUN[0], cx)
-        subs = {}
-        for name in ALL_RUN[1:]:
-            r = run_workload(a, name, cx)
-            if r is not None:
-                subs[name] = r
-        if out is not None:
-            out["workloads"] = subs
+        if a.full or a.dump_outputs:
+            # the other workloads: measured and reported under --full; a plain run goes through their timed steps
+            # only to write what --dump-outputs writes for them, and its line stays the headline alone
+            subs = {}
+            for name in ALL_RUN[1:]:
+                r = run_workload(a, name, cx)
+                if r is not None:
+                    subs[name] = r
+            if out is not None and a.full:
+                out["workloads"] = subs
     else:
         out = run_workload(a, a.workload, cx)
     if rank == 0:

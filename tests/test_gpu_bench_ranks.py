@@ -29,7 +29,7 @@ def _bench(args, tmp_path, gloo):
 
 
 def test_two_ranks_bruteforce_equals_one_rank(tmp_path):
-    common = ["--workload", "bruteforce", "--n", "200000", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"]
+    common = ["--workload", "bruteforce", "--n", "200000", "--steps", "3", "--warmup", "1", "--full", "--no-cpu-baseline"]
     one = _bench(["--gpus", "1", "--dump", str(tmp_path / "one.npz")] + common, tmp_path, False)
     two = _bench(["--gpus", "2", "--dump", str(tmp_path / "two.npz")] + common, tmp_path, True)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
@@ -45,7 +45,8 @@ def test_two_ranks_cos768x_weak_scaling_shape(tmp_path):
     """C5's shape at a small size: every rank generates and indexes only its own rows (HNSW, cosine, 768-D); the
     ground truth is the same protocol with the exact scan."""
     two = _bench(["--gpus", "2", "--workload", "cos768x", "--rows-per-gpu", "20000", "--batch", "512", "--rank", "16",
-                  "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--dump", str(tmp_path / "c.npz")], tmp_path, True)
+                  "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--dump", str(tmp_path / "c.npz")],
+                 tmp_path, True)
     assert two["n_gpus"] == 2 and two["scaling"] == "weak"
     assert two["config"]["rows"] == 40000 and two["config"]["rows_per_gpu"] == 20000
     assert two["recall_at_k"] is not None and two["recall_at_k"] >= 0.9, two["recall_at_k"]

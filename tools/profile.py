@@ -52,7 +52,8 @@ def main():
         i = args.index("--sets")
         only_sets = args[i + 1].split(",")
         del args[i:i + 2]
-    bench = ["python3", os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--no-cpu-baseline"] + args
+    bench = ["python3", os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "3", "--full",
+             "--no-cpu-baseline"] + args
     out = os.path.join(ROOT, "gpurun_out", "prof")
     os.makedirs(out, exist_ok=True)
     env = dict(os.environ, TMPDIR="/tmp")
