@@ -1515,28 +1515,100 @@ void* Engine::pinned(size_t bytes) {
     return pinned_;
 }
 
+// The result block of a host batch: ids | dists | counts in ONE device block (ws_ids_), so that one D2H brings it
+// into the pinned block.
+Engine::ResultBlock Engine::result_block(size_t nq, size_t k) {
+    ws_ids_.ensure(2 * nq * k * 4 + nq * 4);
+    int32_t* d_ids = ws_ids_.as<int32_t>();
+    return {d_ids, reinterpret_cast<float*>(d_ids + nq * k), d_ids + 2 * nq * k};
+}
+
+// ... copied into the pinned block (the caller sized it for the batch: its queries were staged there), after the
+// stream's work; the pointers stay valid until the next call
+void Engine::fetch_results(size_t nq, size_t k, const char* what, const int32_t** ids, const float** dists,
+                           const int32_t** cnt) {
+    const size_t rbytes = nq * k * 4;
+    char* hp = static_cast<char*>(pinned_);
+    hip_check(hipMemcpyAsync(hp, ws_ids_.ptr(), 2 * rbytes + nq * 4, hipMemcpyDeviceToHost, stream_), "results D2H");
+    hip_check(hipStreamSynchronize(stream_), what);
+    *ids = reinterpret_cast<const int32_t*>(hp);
+    *dists = reinterpret_cast<const float*>(hp + rbytes);
+    *cnt = reinterpret_cast<const int32_t*>(hp + 2 * rbytes);
+}
+
+// Exact scan of a batch over sparse or string rows.  Batches go through in slices of queries: the per-split lists
+// ([nsplit][queries][k] keys) stay bounded.  launch(plan, q0, split_d, split_pos) enqueues the scan of the slice that
+// starts at query q0; its lists are merged into `out`, positions mapped to external ids.
+void Engine::scan_slices(size_t nq, size_t k, int tq, const ResultBlock& out, const ScanLaunch& launch) {
+    const int n = (int)d_n_;
+    const size_t max_split_keys = (size_t)1 << 25;  // 256 MiB of per-split lists at most (one query always fits)
+    for (size_t q0 = 0; q0 < nq;) {
+        int m = (int)std::min<size_t>(32768, nq - q0);
+        ScanPlan p = scan_make_plan(n, m, (int)k, tq);
+        while (m > 1 && (size_t)p.nsplit * m * k > max_split_keys) {
+            m = std::max(1, m / 2);
+            p = scan_make_plan(n, m, (int)k, tq);
+        }
+        const size_t keys = (size_t)p.nsplit * m * k;
+        ws_split_.ensure(keys * 8);
+        float* split_d = ws_split_.as<float>();
+        int32_t* split_pos = reinterpret_cast<int32_t*>(split_d + keys);
+        prof_begin(stream_);
+        launch(p, q0, split_d, split_pos);
+        hip_check(launch_merge_topk_ex(split_d, split_pos, (size_t)m * k, p.nsplit, m, (int)k, out.dists + q0 * k,
+                                       out.ids + q0 * k, out.cnt + q0, d_ids_.as<int32_t>(), stream_),
+                  "scan merge");
+        prof_end(stream_);
+        q0 += (size_t)m;
+    }
+}
+
 void Engine::knn_host(const void* queries, size_t nq, size_t elem_count, size_t k, const int32_t** ids, const float** dists,
                       const int32_t** cnt) {
     if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
     if (dirty_) finalize();
     check_device();
     const size_t qbytes = nq * elem_count * elem_bytes();
-    const size_t rbytes = nq * k * 4;
     // device: queries | ids | dists | counts in ONE block each way; host: one pinned block
     ws_q_.ensure(qbytes);
-    ws_ids_.ensure(2 * rbytes + nq * 4);
-    int32_t* d_ids = ws_ids_.as<int32_t>();
-    float* d_dists = reinterpret_cast<float*>(d_ids + nq * k);
-    int32_t* d_cnt = d_ids + 2 * nq * k;
-    char* hp = static_cast<char*>(pinned(std::max(qbytes, 2 * rbytes + nq * 4)));
+    const ResultBlock out = result_block(nq, k);
+    char* hp = static_cast<char*>(pinned(std::max(qbytes, 2 * nq * k * 4 + nq * 4)));
     std::memcpy(hp, queries, qbytes);
     hip_check(hipMemcpyAsync(ws_q_.ptr(), hp, qbytes, hipMemcpyHostToDevice, stream_), "queries H2D");
-    knn_device(ws_q_.ptr(), nq, elem_count, k, d_ids, d_dists, d_cnt, stream_);
-    hip_check(hipMemcpyAsync(hp, d_ids, 2 * rbytes + nq * 4, hipMemcpyDeviceToHost, stream_), "results D2H");
-    hip_check(hipStreamSynchronize(stream_), "knn");
-    *ids = reinterpret_cast<const int32_t*>(hp);
-    *dists = reinterpret_cast<const float*>(hp + rbytes);
-    *cnt = reinterpret_cast<const int32_t*>(hp + 2 * rbytes);
+    knn_device(ws_q_.ptr(), nq, elem_count, k, out.ids, out.dists, out.cnt, stream_);
+    fetch_results(nq, k, "knn", ids, dists, cnt);
+}
+
+// Range search over all d_n_ rows (RangeQuery::CheckAndAddToResult, src/rangequery.cc:67-76).  launch(filter, report)
+// enqueues the distances of every row: the rows with filter[position] <= r are reported in insertion order, the first
+// `capacity` of them, each with report[position] (report = filter unless the space has two distances per row).  The
+// workspaces are sized before anything is enqueued: an allocation behind a kernel in flight waits for it.
+size_t Engine::range_select(bool two_dists, float r, size_t capacity, int32_t* ids, float* dists,
+                            const RangeLaunch& launch) {
+    const int n = (int)d_n_;
+    const size_t cnt_elems = range_count_elems(n);
+    ws_rdist_.ensure((two_dists ? 2 : 1) * d_n_ * 4);
+    ws_rcnt_.ensure(cnt_elems * 4);
+    ws_ids_.ensure(capacity * 4);
+    ws_dists_.ensure(capacity * 4);
+    float* filter = ws_rdist_.as<float>();
+    float* report = two_dists ? filter + d_n_ : filter;
+    launch(filter, report);
+    hip_check(launch_range_select(filter, report, n, r, d_ids_.as<int32_t>(), ws_rcnt_.as<int>(),
+                                  (int)std::min<size_t>(capacity, INT32_MAX), ws_ids_.as<int32_t>(),
+                                  ws_dists_.as<float>(), stream_),
+              "range select");
+    int total = 0;
+    hip_check(hipMemcpyAsync(&total, ws_rcnt_.as<int>() + (cnt_elems - 1), 4, hipMemcpyDeviceToHost, stream_),
+              "range count");
+    hip_check(hipStreamSynchronize(stream_), "range search");
+    const size_t m = std::min<size_t>((size_t)total, capacity);
+    if (m) {
+        hip_check(hipMemcpyAsync(ids, ws_ids_.ptr(), m * 4, hipMemcpyDeviceToHost, stream_), "range ids");
+        hip_check(hipMemcpyAsync(dists, ws_dists_.ptr(), m * 4, hipMemcpyDeviceToHost, stream_), "range dists");
+        hip_check(hipStreamSynchronize(stream_), "range search");
+    }
+    return m;
 }
 
 size_t Engine::range_host(const void* query, size_t elem_count, double radius, size_t capacity, int32_t* ids,
@@ -1565,27 +1637,20 @@ size_t Engine::range_host(const void* query, size_t elem_count, double radius, s
     const int elem = is_u8() ? 1 : 4;
     ws_qpad_.ensure((size_t)ld * elem);
     ws_q_.ensure(elem_count * elem);
-    ws_rdist_.ensure(n * 4);
-    ws_rcnt_.ensure(range_count_elems((int)n) * 4);
-    ws_ids_.ensure(capacity * 4);
-    ws_dists_.ensure(capacity * 4);
-    hip_check(hipMemcpyAsync(ws_q_.ptr(), query, elem_count * elem, hipMemcpyHostToDevice, stream_), "query H2D");
-    hip_check(launch_pad_rows(ws_q_.ptr(), 1, (int)dim_, ws_qpad_.ptr(), 1, ld, elem, stream_), "pad query");
-    hip_check(launch_range_search(space_, d_rows_.ptr(), ld, (int)n, ws_qpad_.ptr(), (int)dim_, r, d_ids_.as<int32_t>(),
-                                  ws_rdist_.as<float>(), ws_rcnt_.as<int>(), (int)std::min<size_t>(capacity, INT32_MAX),
-                                  ws_ids_.as<int32_t>(), ws_dists_.as<float>(), stream_),
-              "range search");
-    int total = 0;
-    hip_check(hipMemcpyAsync(&total, ws_rcnt_.as<int>() + (range_count_elems((int)n) - 1), 4, hipMemcpyDeviceToHost, stream_),
-              "range count");
-    hip_check(hipStreamSynchronize(stream_), "range search");
-    const size_t m = std::min<size_t>((size_t)total, capacity);
-    if (m) {
-        hip_check(hipMemcpyAsync(ids, ws_ids_.ptr(), m * 4, hipMemcpyDeviceToHost, stream_), "range ids");
-        hip_check(hipMemcpyAsync(dists, ws_dists_.ptr(), m * 4, hipMemcpyDeviceToHost, stream_), "range dists");
-        hip_check(hipStreamSynchronize(stream_), "range search");
-    }
-    return m;
+    return range_select(false, r, capacity, ids, dists, [&](float* d, float*) {
+        hip_check(hipMemcpyAsync(ws_q_.ptr(), query, elem_count * elem, hipMemcpyHostToDevice, stream_), "query H2D");
+        hip_check(launch_pad_rows(ws_q_.ptr(), 1, (int)dim_, ws_qpad_.ptr(), 1, ld, elem, stream_), "pad query");
+        hip_check(launch_range_dist(space_, d_rows_.ptr(), ld, (int)n, ws_qpad_.ptr(), (int)dim_, d, stream_),
+                  "range distances");
+    });
+}
+
+// *d_out, after the stream's work
+float Engine::read_float(const float* d_out, const char* what) {
+    float v = 0;
+    hip_check(hipMemcpyAsync(&v, d_out, 4, hipMemcpyDeviceToHost, stream_), "pair D2H");
+    hip_check(hipStreamSynchronize(stream_), what);
+    return v;
 }
 
 float Engine::pair_distance(size_t p1, size_t p2) {
@@ -1601,10 +1666,7 @@ float Engine::pair_distance(size_t p1, size_t p2) {
     hip_check(hipMemcpyAsync(base + rb, host_row(p2), row_bytes(), hipMemcpyHostToDevice, stream_), "pair H2D");
     float* out = reinterpret_cast<float*>(base + 2 * rb);
     hip_check(launch_pair_distance(space_, base, base + rb, (int)dim_, out, stream_), "pair_distance");
-    float v = 0;
-    hip_check(hipMemcpyAsync(&v, out, 4, hipMemcpyDeviceToHost, stream_), "pair D2H");
-    hip_check(hipStreamSynchronize(stream_), "pair_distance");
-    return v;
+    return read_float(out, "pair_distance");
 }
 
 // ---------------------------------------------------------------------------------------------

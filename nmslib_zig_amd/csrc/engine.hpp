@@ -8,6 +8,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <cstdint>
+#include <functional>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -37,6 +38,7 @@ struct EngineError : std::runtime_error {
 };
 
 void hip_check(hipError_t e, const char* what);  // throws EngineError(Runtime / OutOfMemory)
+inline size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
 
 // ---- "name=value" parameters (include/params.h:44-74,181-251) -------------------------------
 class ParamSet {
@@ -243,6 +245,20 @@ class Engine {
     void* pinned_ = nullptr;
     size_t pinned_bytes_ = 0;
     void check_device();
+    // ---- plumbing shared by the host entries of every data type (engine.cpp) ----
+    struct ResultBlock {  // device pointers into ws_ids_
+        int32_t* ids;
+        float* dists;
+        int32_t* cnt;
+    };
+    ResultBlock result_block(size_t nq, size_t k);
+    void fetch_results(size_t nq, size_t k, const char* what, const int32_t** ids, const float** dists,
+                       const int32_t** cnt);
+    using ScanLaunch = std::function<void(const ScanPlan& p, size_t q0, float* split_d, int32_t* split_pos)>;
+    void scan_slices(size_t nq, size_t k, int tq, const ResultBlock& out, const ScanLaunch& launch);
+    using RangeLaunch = std::function<void(float* filter, float* report)>;
+    size_t range_select(bool two_dists, float r, size_t capacity, int32_t* ids, float* dists, const RangeLaunch& launch);
+    float read_float(const float* d_out, const char* what);
     void upload_sparse();
     float pair_distance_sparse(size_t p1, size_t p2);
     void upload_strings();
@@ -280,7 +296,6 @@ class Engine {
     std::vector<uint32_t> sp_ids_;
     std::vector<float> sp_vals_;
     DevBuf d_sp_ptr_, d_sp_ids_, d_sp_vals_;
-    DevBuf ws_sp_q_, ws_sp_split_;  // batch queries (CSR), per-split lists
     // string rows: leven CSR bytes, or bit_hamming words (W = ham_words() per row, st_bits_ bits; -1: no row yet);
     // the HBM copy after finalize
     bool str_space_ = false;
@@ -289,7 +304,7 @@ class Engine {
     std::vector<uint32_t> st_words_;
     int64_t st_bits_ = -1;
     DevBuf d_st_ptr_, d_st_data_;
-    DevBuf ws_st_q_, ws_st_split_, ws_st_mw_;  // batch queries, per-split lists, multi-block leven state
+    DevBuf ws_st_mw_;  // multi-block leven state
 
     // index-time state
     bool created_ = false;       // nmslib_create_index was called
@@ -333,6 +348,7 @@ class Engine {
     DevBuf ws_ndc_, ws_hops_, ws_hops_up_, ws_pair_, ws_rdist_, ws_rcnt_, ws_old_a_, ws_old_r_, ws_old_heap_;
     DevBuf wb_pts_, wb_src_, wb_starts_, wb_cand_ids_, wb_cand_d_, wb_cand_n_, wb_status_, wb_req_key_, wb_req_dist_,
         wb_req_key2_, wb_req_dist2_, wb_sort_tmp_, wb_active_, wb_nactive_, wb_extra_ids_, wb_extra_d_, wb_extra_n_;  // construction workspaces (released after the build)
+    DevBuf ws_bq_, ws_split_;  // sparse / string batches: the packed queries; per-split lists (string HNSW: per-query state)
     DevBuf ws_fix_;       // visited-overflow list of the HNSW search (count + query ids), device only
     size_t ctr_off_ = 0;  // offset of the current slice inside the per-batch counter arrays
     bool have_counters_ = false;

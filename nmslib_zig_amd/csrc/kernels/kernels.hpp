@@ -329,12 +329,9 @@ hipError_t launch_hnsw_build_link(const HnswBuildGraph& bg, int level, const int
                                   const float* dist_sorted, int total, hipStream_t s);
 
 // ---- range search on the brute-force index (range_kernels.hip) ----------------------------------
-// dist_ws: [n] floats; count_ws: [ceil(n/1024) + 1] ints, the last one receives the number of matches.
-// Matches (distance <= radius) are written in position order, the first `capacity` of them.
-inline size_t range_count_elems(int n) { return (size_t)(n + 1023) / 1024 + 1; }
-hipError_t launch_range_search(int space, const void* rows, int ld, int n, const void* query_padded, int dim,
-                               float radius, const int32_t* ext_ids, float* dist_ws, int* count_ws, int capacity,
-                               int32_t* out_ids, float* out_dists, hipStream_t s);
+// dist_ws[r] = the reference's distance of row r to the query, r < n
+hipError_t launch_range_dist(int space, const void* rows, int ld, int n, const void* query_padded, int dim,
+                             float* dist_ws, hipStream_t s);
 
 // Exact scan for k > BF_MAX_K: per query one pass with the reference formula + one stable device radix sort of
 // (distance, position).  dist_ws [n] floats, key_ws [4][n] u32, temp from bf_bigk_temp_bytes(n).
@@ -343,29 +340,63 @@ hipError_t launch_bf_bigk(int space, const void* rows, int ld, int n, const void
                           int nq, int dim, int k, const int32_t* ext_ids, float* dist_ws, uint32_t* key_ws, void* temp,
                           size_t temp_bytes, int32_t* out_ids, float* out_dists, int32_t* out_cnt, hipStream_t s);
 
+// count_ws: [range_count_elems(n)] ints, the last one receives the number of matches.
+inline size_t range_count_elems(int n) { return (size_t)(n + 1023) / 1024 + 1; }
 // Range selection over a precomputed distance array: the matches of `filter` (distance <= radius), in position order,
-// the first `capacity` of them, each reported with report[position] (the dense path passes filter twice).
+// the first `capacity` of them, each reported with report[position] (a symmetric distance passes filter twice).
 hipError_t launch_range_select(const float* filter, const float* report, int n, float radius, const int32_t* ext_ids,
                                int* count_ws, int capacity, int32_t* out_ids, float* out_dists, hipStream_t s);
+
+// ---- exact scans over sparse and string rows: the plan they share ---------------------------------
+// A scan's grid is (row splits, query tiles); each workgroup keeps the best kl keys of its split per query of its tile
+// (kernels/split_topk_dev.hpp) and writes them as ascending lists that launch_merge_topk_ex merges.
+constexpr int kScanMaxKl = 4096;  // for k above this a split holds at most this many rows (its list keeps them all)
+struct ScanPlan {
+    int n, nq, k;
+    int nsplit, rows_per_split;  // row ranges scanned by separate workgroups
+    int kl;                      // keys kept per (split, query) = min(k, rows_per_split)
+    int P;                       // LDS key buffer per query (power of two >= kl + 256)
+    int tq;                      // queries per workgroup (the tq asked for, or 1 when k is large)
+};
+inline int pow2_at_least(int v) {
+    int p = 1;
+    while (p < v) p <<= 1;
+    return p;
+}
+inline ScanPlan scan_make_plan(int n, int nq, int k, int tq) {
+    ScanPlan p{};
+    p.n = n;
+    p.nq = nq;
+    p.k = k;
+    // enough workgroups to fill the chip (256 CUs, 8 per CU) without splitting rows finer than 1024 per workgroup;
+    // a workgroup takes a tile of tq queries when k is small
+    const long long tiles = ((long long)nq + tq - 1) / tq;
+    const long long want = (2048 + tiles - 1) / (tiles > 0 ? tiles : 1);
+    long long rps = ((long long)n + want - 1) / (want > 0 ? want : 1);
+    if (rps < 1024) rps = 1024;
+    // the split lists of a query merge in LDS while nsplit * k <= 8192 (launch_merge_topk_ex)
+    if (k <= 4096) {
+        const long long per = 8192 / k;
+        const long long rps_merge = ((long long)n + per - 1) / per;
+        if (rps < rps_merge) rps = rps_merge;
+    }
+    if (k > kScanMaxKl) rps = kScanMaxKl;  // then a split's list holds every row of the split
+    p.rows_per_split = (int)rps;
+    p.nsplit = n > 0 ? (int)(((long long)n + rps - 1) / rps) : 1;
+    p.kl = (int)(k < rps ? k : rps);
+    p.P = pow2_at_least(p.kl + 256);
+    p.tq = p.P <= 1024 ? tq : 1;  // the tile's key buffers: 8 x 8 KiB at most
+    return p;
+}
 
 // ---- sparse vectors (sparse_kernels.hip) -----------------------------------------------------
 // Rows and queries are CSR: row_ptr int64 [n+1], ids uint32, vals f32.  Spaces: SP_L2, SP_L1, SP_LINF, SP_COSINE,
 // SP_ANGULAR, SP_NEGDOT, SP_QNORM_NEGDOT, each evaluated over the union of the two id lists.
 constexpr int kSparseQCap = 4096;   // query elements staged in LDS by the k-NN scan (longer: read from HBM)
-constexpr int kSparseMaxKl = 4096;  // for k above this a split holds at most this many rows (its list keeps them all)
 constexpr int kSparseTileQ = 8;     // queries per workgroup of the k-NN scan (k small enough for 8 key buffers in LDS)
-struct SparseScanPlan {
-    int n, nq, k;
-    int nsplit, rows_per_split;  // row ranges scanned by separate workgroups
-    int kl;                      // keys kept per (split, query) = min(k, rows_per_split)
-    int P;                       // LDS key buffer per query (power of two >= kl + 256)
-    int tq;                      // queries per workgroup (kSparseTileQ or 1)
-};
-SparseScanPlan sparse_make_plan(int n, int nq, int k);
-size_t sparse_knn_lds_bytes(const SparseScanPlan& p);
 // per-(split, query) lists, ascending (distance, position): split_d / split_pos [nsplit][nq][k]; merged by
 // launch_merge_topk_ex with shard_stride nq*k
-hipError_t launch_sparse_knn(int space, const SparseScanPlan& p, const int64_t* row_ptr, const uint32_t* ids,
+hipError_t launch_sparse_knn(int space, const ScanPlan& p, const int64_t* row_ptr, const uint32_t* ids,
                              const float* vals, const int64_t* q_ptr, const uint32_t* q_ids, const float* q_vals,
                              float* split_d, int32_t* split_pos, hipStream_t s);
 // d_row_q[r] = distance(row r, query), d_q_row[r] = distance(query, row r)
@@ -381,27 +412,18 @@ hipError_t launch_sparse_pair(int space, const int64_t* row_ptr, const uint32_t*
 // q_off[q] (uint64 units, q_off [nq+1]), nw = ceil(len / 64), and their lengths q_len.
 // bit_hamming rows and queries: W uint32 words each (the reference's trailing count word is not stored).
 constexpr int kStrTileQ = 8;              // queries per workgroup of a k-NN scan (one-block leven queries, bit_hamming)
-constexpr int kStrMaxKl = 4096;           // for k above this a split holds at most this many rows
 constexpr size_t kStrPeqStage = 16384;    // bytes of Peq tables staged in LDS per workgroup (more: read from HBM)
 constexpr size_t kStrRowStage = 16384;    // bytes of a 256-row chunk staged in LDS (a longer chunk: read from HBM)
 constexpr int kStrMwLds = 4;              // multi-block leven: blocks whose state a lane keeps in LDS (more: HBM)
 constexpr size_t kStrHamQStage = 16384;   // bytes of bit_hamming queries staged in LDS per workgroup
-struct StringScanPlan {
-    int n, nq, k;
-    int nsplit, rows_per_split;  // row ranges scanned by separate workgroups
-    int kl;                      // keys kept per (split, query) = min(k, rows_per_split)
-    int P;                       // LDS key buffer per query (power of two >= kl + 256)
-    int tq;                      // queries per workgroup (the tq asked for, or 1 when k is large)
-};
-StringScanPlan string_make_plan(int n, int nq, int k, int tq);
 // HBM state of a multi-block leven scan (uint64 words; 0 when it fits LDS)
-size_t leven_mw_ws_words(const StringScanPlan& p, int nw);
+size_t leven_mw_ws_words(const ScanPlan& p, int nw);
 // per-(split, query) lists, ascending (distance, position): split_d / split_pos [nsplit][nq][k]; merged by
 // launch_merge_topk_ex with shard_stride nq*k.  nw = the batch's largest block count (nw > 1 needs p.tq == 1).
-hipError_t launch_leven_knn(const StringScanPlan& p, const int64_t* row_ptr, const uint8_t* data,
+hipError_t launch_leven_knn(const ScanPlan& p, const int64_t* row_ptr, const uint8_t* data,
                             const int64_t* q_off, const int32_t* q_len, const uint64_t* peq, int nw, uint64_t* mw_ws,
                             float* split_d, int32_t* split_pos, hipStream_t s);
-hipError_t launch_ham_knn(const StringScanPlan& p, const uint32_t* rows, int W, const uint32_t* q, float* split_d,
+hipError_t launch_ham_knn(const ScanPlan& p, const uint32_t* rows, int W, const uint32_t* q, float* split_d,
                           int32_t* split_pos, hipStream_t s);
 // d_out[r] = distance(row r, query); leven: mw_ws holds 2 * nw * 256 * leven_dist_grid(n) words when nw > 1
 int leven_dist_grid(int n);

@@ -99,14 +99,13 @@ __global__ __launch_bounds__(256) void range_scatter_kernel(const float* dist, c
     }
 }
 
-hipError_t launch_range_search(int space, const void* rows, int ld, int n, const void* query_padded, int dim,
-                               float radius, const int32_t* ext_ids, float* dist_ws, int* count_ws, int capacity,
-                               int32_t* out_ids, float* out_dists, hipStream_t s) {
-    if (n <= 0) return hipMemsetAsync(count_ws, 0, 4, s);
+hipError_t launch_range_dist(int space, const void* rows, int ld, int n, const void* query_padded, int dim,
+                             float* dist_ws, hipStream_t s) {
+    if (n <= 0) return hipSuccess;
     int grid = (n + 3) / 4;
     if (grid > 65536) grid = 65536;
     hipLaunchKernelGGL(range_dist_kernel, dim3(grid), dim3(256), 0, s, space, rows, ld, n, query_padded, dim, dist_ws);
-    return launch_range_select(dist_ws, dist_ws, n, radius, ext_ids, count_ws, capacity, out_ids, out_dists, s);
+    return hipGetLastError();
 }
 
 hipError_t launch_range_select(const float* filter, const float* report, int n, float radius, const int32_t* ext_ids,

@@ -16,17 +16,14 @@
 //                        (8 when k is small, else 1): a row is read once and merged against every query of the tile;
 //                        the tile's queries are staged in LDS when they fit (kSparseQCap elements together), otherwise
 //                        read from HBM (the long-list path: same code, slower, exact); the best kl keys
-//                        (distance, position) of the range are kept in LDS (append below the threshold, bitonic
-//                        compaction when the buffer could overflow).  The per-split lists are merged by
+//                        (distance, position) of the range are kept in LDS (SplitTopK, split_topk_dev.hpp).  The per-split lists are merged by
 //                        launch_merge_topk_ex (bf_kernels.hip), which also maps positions to external ids.
 //   sparse_dist_kernel : both argument orders of the distance for every row (range search: the filter uses
 //                        d(row, query), the reported distance is d(query, row), rangequery.cc:78-82 and
 //                        nmslib_c.cpp:1104-1113); the selection is range_kernels.hip's.
 //   sparse_pair_kernel : nmslib_get_distance.
-#include <algorithm>
-
-#include "common_dev.hpp"
 #include "kernels.hpp"
+#include "split_topk_dev.hpp"
 
 namespace gfxknn {
 
@@ -169,12 +166,12 @@ __global__ __launch_bounds__(256) void sparse_knn_kernel(const int64_t* __restri
                                                          const float* __restrict__ q_vals, int nq, int k, int kl, int P,
                                                          float* __restrict__ out_d, int32_t* __restrict__ out_pos) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    u64* keys = reinterpret_cast<u64*>(smem);                     // [TQ][P]
-    uint32_t* sq_ids = reinterpret_cast<uint32_t*>(keys + (size_t)TQ * P);  // [kSparseQCap]
-    float* sq_vals = reinterpret_cast<float*>(sq_ids + kSparseQCap);
     __shared__ int s_cnt[TQ];
     const int tid = threadIdx.x, split = blockIdx.x, q_first = blockIdx.y * TQ;
     const int tile_n = min(TQ, nq - q_first);
+    SplitTopK<TQ> sel{reinterpret_cast<u64*>(smem), s_cnt, P, kl, tile_n};
+    uint32_t* sq_ids = reinterpret_cast<uint32_t*>(sel.keys + (size_t)TQ * P);  // [kSparseQCap]
+    float* sq_vals = reinterpret_cast<float*>(sq_ids + kSparseQCap);
     const int64_t t0 = q_ptr[q_first], t1 = q_ptr[q_first + tile_n];
     const bool staged = t1 - t0 <= kSparseQCap;
     if (staged)
@@ -185,17 +182,14 @@ __global__ __launch_bounds__(256) void sparse_knn_kernel(const int64_t* __restri
     const uint32_t* qi[TQ];
     const float* qv[TQ];
     int qn[TQ];
-    u64 thr[TQ];
 #pragma unroll
     for (int t = 0; t < TQ; ++t) {
         const int64_t b = t < tile_n ? q_ptr[q_first + t] : t1;
         qn[t] = t < tile_n ? (int)(q_ptr[q_first + t + 1] - b) : 0;
         qi[t] = staged ? sq_ids + (b - t0) : q_ids + b;
         qv[t] = staged ? sq_vals + (b - t0) : q_vals + b;
-        thr[t] = ~0ull;
     }
-    for (int i = tid; i < TQ * P; i += 256) keys[i] = ~0ull;
-    if (tid < TQ) s_cnt[tid] = 0;
+    sel.init(tid);
     __syncthreads();
     const int r0 = (int)min((long long)split * rows_per_split, (long long)n);
     const int r1 = min(n, r0 + rows_per_split);
@@ -211,43 +205,13 @@ __global__ __launch_bounds__(256) void sparse_knn_kernel(const int64_t* __restri
                     // the scan calls IndexTimeDistance(row, query) (DistanceObjLeft, src/query.cc:60-62)
                     sparse_pair<SP>(ids + p0, vals + p0, rn, qi[t], qv[t], qn[t], d, unused);
                     // -0 and +0 are one distance (the reference's queue compares them equal): one key for both
-                    const u64 key = ((u64)f32_ord(d == 0.0f ? 0.0f : d) << 32) | (uint32_t)r;
-                    if (key < thr[t]) keys[(size_t)t * P + atomicAdd(&s_cnt[t], 1)] = key;
+                    sel.offer(t, f32_ord(d == 0.0f ? 0.0f : d), r);
                 }
             }
         }
-        __syncthreads();
-        const bool last = base + 256 >= r1;
-        // every thread takes the counts BEFORE any thread can change one (the next chunk's atomics, a compaction's
-        // reset): the compaction decisions below, and the barriers inside them, are then the same for the whole group
-        int cnts[TQ];
-#pragma unroll
-        for (int t = 0; t < TQ; ++t) cnts[t] = s_cnt[t];
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < TQ; ++t) {
-            const int cnt = cnts[t];
-            if (t < tile_n && (cnt + 256 > P || last)) {  // the next chunk could overflow, or the range is done
-                u64* kt = keys + (size_t)t * P;
-                block_bitonic_u64_asc(kt, P, tid, 256);
-                const int kept = cnt < kl ? cnt : kl;
-                if (kept == kl) thr[t] = kt[kl - 1];
-                __syncthreads();
-                for (int i = kl + tid; i < P; i += 256) kt[i] = ~0ull;
-                if (tid == 0) s_cnt[t] = kept;
-                __syncthreads();
-            }
-        }
+        sel.chunk_done(tid, base + 256 >= r1);
     }
-    for (int t = 0; t < tile_n; ++t) {
-        const size_t o = ((size_t)split * nq + q_first + t) * (size_t)k;
-        for (int i = tid; i < k; i += 256) {
-            const u64 key = i < kl ? keys[(size_t)t * P + i] : ~0ull;
-            const bool ok = key != ~0ull;
-            out_pos[o + i] = ok ? (int32_t)(uint32_t)key : -1;
-            out_d[o + i] = ok ? ord_f32((uint32_t)(key >> 32)) : INFINITY;
-        }
-    }
+    sel.write(tid, split, nq, q_first, k, out_d, out_pos, [](uint32_t hi) { return ord_f32(hi); });
 }
 
 template <int SP>
@@ -303,33 +267,18 @@ hipError_t dispatch_space(int space, Args... args) {
     }
 }
 
-int pow2_at_least(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
-template <int SP, int TQ>
-hipError_t knn_launch_tq(const SparseScanPlan& p, const int64_t* row_ptr, const uint32_t* ids, const float* vals,
-                         const int64_t* q_ptr, const uint32_t* q_ids, const float* q_vals, float* out_d,
-                         int32_t* out_pos, hipStream_t s) {
-    const size_t lds = sparse_knn_lds_bytes(p);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sparse_knn_kernel<SP, TQ>),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((sparse_knn_kernel<SP, TQ>), dim3(p.nsplit, (p.nq + TQ - 1) / TQ), dim3(256), lds, s, row_ptr,
-                       ids, vals, p.n, p.rows_per_split, q_ptr, q_ids, q_vals, p.nq, p.k, p.kl, p.P, out_d, out_pos);
-    return hipGetLastError();
-}
-
 template <int SP>
 struct KnnLaunch {
-    static hipError_t run(const SparseScanPlan& p, const int64_t* row_ptr, const uint32_t* ids, const float* vals,
+    static hipError_t run(const ScanPlan& p, const int64_t* row_ptr, const uint32_t* ids, const float* vals,
                           const int64_t* q_ptr, const uint32_t* q_ids, const float* q_vals, float* out_d,
                           int32_t* out_pos, hipStream_t s) {
+        const dim3 grid(p.nsplit, (p.nq + p.tq - 1) / p.tq);
+        const size_t lds = (size_t)p.tq * p.P * 8 + (size_t)kSparseQCap * 8;
         if (p.tq == kSparseTileQ)
-            return knn_launch_tq<SP, kSparseTileQ>(p, row_ptr, ids, vals, q_ptr, q_ids, q_vals, out_d, out_pos, s);
-        return knn_launch_tq<SP, 1>(p, row_ptr, ids, vals, q_ptr, q_ids, q_vals, out_d, out_pos, s);
+            return launch_with_lds(sparse_knn_kernel<SP, kSparseTileQ>, grid, lds, s, row_ptr, ids, vals, p.n,
+                                   p.rows_per_split, q_ptr, q_ids, q_vals, p.nq, p.k, p.kl, p.P, out_d, out_pos);
+        return launch_with_lds(sparse_knn_kernel<SP, 1>, grid, lds, s, row_ptr, ids, vals, p.n, p.rows_per_split, q_ptr,
+                               q_ids, q_vals, p.nq, p.k, p.kl, p.P, out_d, out_pos);
     }
 };
 
@@ -357,37 +306,7 @@ struct PairLaunch {
 
 }  // namespace
 
-SparseScanPlan sparse_make_plan(int n, int nq, int k) {
-    SparseScanPlan p{};
-    p.n = n;
-    p.nq = nq;
-    p.k = k;
-    // enough workgroups to fill the chip (256 CUs, 8 per CU) without splitting rows finer than 1024 per workgroup;
-    // a workgroup takes a tile of kSparseTileQ queries when k is small
-    const long long tiles = ((long long)nq + kSparseTileQ - 1) / kSparseTileQ;
-    const long long want = (2048 + tiles - 1) / (tiles > 0 ? tiles : 1);
-    long long rps = ((long long)n + want - 1) / (want > 0 ? want : 1);
-    if (rps < 1024) rps = 1024;
-    // the split lists of a query merge in LDS while nsplit * k <= 8192 (launch_merge_topk_ex)
-    if (k <= 4096) {
-        const long long per = 8192 / k;
-        const long long rps_merge = ((long long)n + per - 1) / per;
-        if (rps < rps_merge) rps = rps_merge;
-    }
-    if (k > kSparseMaxKl) rps = kSparseMaxKl;  // then a split's list holds every row of the split
-    p.rows_per_split = (int)rps;
-    p.nsplit = n > 0 ? (int)(((long long)n + rps - 1) / rps) : 1;
-    p.kl = (int)std::min<long long>((long long)k, rps);
-    p.P = pow2_at_least(p.kl + 256);
-    p.tq = p.P <= 1024 ? kSparseTileQ : 1;  // the tile's key buffers: 8 x 8 KiB at most
-    return p;
-}
-
-size_t sparse_knn_lds_bytes(const SparseScanPlan& p) {
-    return (size_t)p.tq * p.P * 8 + (size_t)kSparseQCap * 8;
-}
-
-hipError_t launch_sparse_knn(int space, const SparseScanPlan& p, const int64_t* row_ptr, const uint32_t* ids,
+hipError_t launch_sparse_knn(int space, const ScanPlan& p, const int64_t* row_ptr, const uint32_t* ids,
                              const float* vals, const int64_t* q_ptr, const uint32_t* q_ids, const float* q_vals,
                              float* split_d, int32_t* split_pos, hipStream_t s) {
     return dispatch_space<KnnLaunch>(space, p, row_ptr, ids, vals, q_ptr, q_ids, q_vals, split_d, split_pos, s);

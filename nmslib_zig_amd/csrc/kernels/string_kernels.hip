@@ -22,13 +22,13 @@
 //                              blocks' (Pv, Mv) live in LDS (nw <= kStrMwLds) or in a per-lane HBM workspace.
 //   ham_knn_kernel<TQ>       : grid (splits, query tiles); each lane streams one row (16-byte loads when W % 4 == 0)
 //                              and XORs it against the tile's queries, staged in LDS.
-//   Selection: the best kl keys (distance, position) of the range in LDS, as in sparse_kernels.hip; the per-split
-//   lists are merged by launch_merge_topk_ex.  Integer distances are exact in float.
+//   Selection: the best kl keys (distance, position) of the range in LDS (SplitTopK, split_topk_dev.hpp); the
+//   per-split lists are merged by launch_merge_topk_ex.  Integer distances are exact in float.
 //   *_dist_kernel: distance of every row to one query (range search); *_pair_kernel: nmslib_get_distance.
 #include <algorithm>
 
-#include "common_dev.hpp"
 #include "kernels.hpp"
+#include "split_topk_dev.hpp"
 
 namespace gfxknn {
 
@@ -93,60 +93,9 @@ __device__ __forceinline__ int ham_words(const uint32_t* a, const uint32_t* b, i
     return s;
 }
 
-// ---- per-split top-k of (distance, position) keys in LDS ----------------------------------------
-
-// Appends the candidates of one 256-row chunk (keys below the running threshold), then compacts a buffer that could
-// overflow with the next chunk, or every buffer after the last chunk.  Same protocol as sparse_knn_kernel.
-template <int TQ>
-struct SplitTopK {
-    u64* keys;  // [TQ][P]
-    int* cnt;   // [TQ]
-    int P, kl, tile_n;
-    u64 thr[TQ];
-
-    __device__ void init(int tid) {
-#pragma unroll
-        for (int t = 0; t < TQ; ++t) thr[t] = ~0ull;
-        for (int i = tid; i < TQ * P; i += 256) keys[i] = ~0ull;
-        if (tid < TQ) cnt[tid] = 0;
-    }
-    __device__ __forceinline__ void offer(int t, int d, int r) {
-        const u64 key = ((u64)(uint32_t)d << 32) | (uint32_t)r;  // d >= 0: the integer orders as its float does
-        if (key < thr[t]) keys[(size_t)t * P + atomicAdd(&cnt[t], 1)] = key;
-    }
-    // after a chunk's offers; every thread of the group calls it
-    __device__ void chunk_done(int tid, bool last) {
-        __syncthreads();
-        int cnts[TQ];
-#pragma unroll
-        for (int t = 0; t < TQ; ++t) cnts[t] = cnt[t];
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < TQ; ++t) {
-            const int c = cnts[t];
-            if (t < tile_n && (c + 256 > P || last)) {
-                u64* kt = keys + (size_t)t * P;
-                block_bitonic_u64_asc(kt, P, tid, 256);
-                const int kept = c < kl ? c : kl;
-                if (kept == kl) thr[t] = kt[kl - 1];
-                __syncthreads();
-                for (int i = kl + tid; i < P; i += 256) kt[i] = ~0ull;
-                if (tid == 0) cnt[t] = kept;
-                __syncthreads();
-            }
-        }
-    }
-    __device__ void write(int tid, int split, int nq, int q_first, int k, float* out_d, int32_t* out_pos) {
-        for (int t = 0; t < tile_n; ++t) {
-            const size_t o = ((size_t)split * nq + q_first + t) * (size_t)k;
-            for (int i = tid; i < k; i += 256) {
-                const u64 key = i < kl ? keys[(size_t)t * P + i] : ~0ull;
-                const bool ok = key != ~0ull;
-                out_pos[o + i] = ok ? (int32_t)(uint32_t)key : -1;
-                out_d[o + i] = ok ? (float)(uint32_t)(key >> 32) : INFINITY;
-            }
-        }
-    }
+// A distance d >= 0 is the upper half of its key as it is (the integer orders as its float does)
+struct KeyToDist {
+    __device__ float operator()(uint32_t hi) const { return (float)hi; }
 };
 
 // ---- k-NN scans ---------------------------------------------------------------------------------
@@ -201,7 +150,7 @@ __global__ __launch_bounds__(256) void leven_knn_kernel(const int64_t* __restric
             const uint8_t* text = rows_staged ? s_rows + (a - (w0 << 2)) : data + a;
             if constexpr (MW) {
                 const u64* pq = peq_staged ? s_peq : peq + p0;
-                sel.offer(0, leven_mw(pq, q_len[q_first], nw, text, len, st, 256), r);
+                sel.offer(0, (uint32_t)leven_mw(pq, q_len[q_first], nw, text, len, st, 256), r);
             } else {
                 // all TQ queries advance over the row together: one byte read per step for the whole tile
                 u64 pv[TQ], mv[TQ], high[TQ];
@@ -223,12 +172,12 @@ __global__ __launch_bounds__(256) void leven_knn_kernel(const int64_t* __restric
                 }
 #pragma unroll
                 for (int t = 0; t < TQ; ++t)
-                    if (t < tile_n) sel.offer(t, score[t], r);
+                    if (t < tile_n) sel.offer(t, (uint32_t)score[t], r);
             }
         }
         sel.chunk_done(tid, base + 256 >= r1);  // (its first barrier also keeps s_rows until every lane is done)
     }
-    sel.write(tid, split, nq, q_first, k, out_d, out_pos);
+    sel.write(tid, split, nq, q_first, k, out_d, out_pos, KeyToDist{});
 }
 
 template <int TQ>
@@ -279,11 +228,11 @@ __global__ __launch_bounds__(256) void ham_knn_kernel(const uint32_t* __restrict
             }
 #pragma unroll
             for (int t = 0; t < TQ; ++t)
-                if (t < tile_n) sel.offer(t, acc[t], r);
+                if (t < tile_n) sel.offer(t, (uint32_t)acc[t], r);
         }
         sel.chunk_done(tid, base + 256 >= r1);
     }
-    sel.write(tid, split, nq, q_first, k, out_d, out_pos);
+    sel.write(tid, split, nq, q_first, k, out_d, out_pos, KeyToDist{});
 }
 
 // ---- range / pair ---------------------------------------------------------------------------------
@@ -599,98 +548,41 @@ __global__ __launch_bounds__(64) void string_hnsw_kernel(StringHnswArgs a, int q
     }
 }
 
-int pow2_at_least(int v) {
-    int p = 1;
-    while (p < v) p <<= 1;
-    return p;
-}
-
 const u64* U(const uint64_t* p) { return reinterpret_cast<const u64*>(p); }
 u64* UW(uint64_t* p) { return reinterpret_cast<u64*>(p); }
 
-template <typename K>
-hipError_t set_lds(K kernel, size_t lds) {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds);
-}
-
 }  // namespace
 
-StringScanPlan string_make_plan(int n, int nq, int k, int tq) {
-    StringScanPlan p{};
-    p.n = n;
-    p.nq = nq;
-    p.k = k;
-    // enough workgroups to fill the chip without splitting rows finer than 1024 per workgroup; the split lists of a
-    // query merge in LDS while nsplit * k <= 8192 (launch_merge_topk_ex); k > kStrMaxKl caps a split at kStrMaxKl
-    // rows so its list keeps them all
-    const long long tiles = ((long long)nq + tq - 1) / tq;
-    const long long want = (2048 + tiles - 1) / (tiles > 0 ? tiles : 1);
-    long long rps = ((long long)n + want - 1) / (want > 0 ? want : 1);
-    if (rps < 1024) rps = 1024;
-    if (k <= 4096) {
-        const long long per = 8192 / k;
-        const long long rps_merge = ((long long)n + per - 1) / per;
-        if (rps < rps_merge) rps = rps_merge;
-    }
-    if (k > kStrMaxKl) rps = kStrMaxKl;
-    p.rows_per_split = (int)rps;
-    p.nsplit = n > 0 ? (int)(((long long)n + rps - 1) / rps) : 1;
-    p.kl = (int)std::min<long long>((long long)k, rps);
-    p.P = pow2_at_least(p.kl + 256);
-    p.tq = p.P <= 1024 ? tq : 1;  // the tile's key buffers: 8 x 8 KiB at most
-    return p;
-}
-
-size_t leven_mw_ws_words(const StringScanPlan& p, int nw) {
+size_t leven_mw_ws_words(const ScanPlan& p, int nw) {
     return nw > kStrMwLds ? (size_t)p.nsplit * ((p.nq + p.tq - 1) / p.tq) * 256 * 2 * nw : 0;
 }
 
-hipError_t launch_leven_knn(const StringScanPlan& p, const int64_t* row_ptr, const uint8_t* data,
+hipError_t launch_leven_knn(const ScanPlan& p, const int64_t* row_ptr, const uint8_t* data,
                             const int64_t* q_off, const int32_t* q_len, const uint64_t* peq, int nw, uint64_t* mw_ws,
                             float* split_d, int32_t* split_pos, hipStream_t s) {
     const dim3 grid(p.nsplit, (p.nq + p.tq - 1) / p.tq);
-    const size_t keys = (size_t)p.tq * p.P * 8;
-    if (nw == 1 && p.tq == kStrTileQ) {
-        const size_t lds = keys + kStrPeqStage + kStrRowStage;
-        hipError_t e = set_lds(leven_knn_kernel<kStrTileQ, false>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((leven_knn_kernel<kStrTileQ, false>), grid, dim3(256), lds, s, row_ptr, data, p.n,
-                           p.rows_per_split, q_off, q_len, U(peq), p.nq, p.k, p.kl, p.P, nw, UW(mw_ws), split_d, split_pos);
-    } else if (nw == 1) {
-        const size_t lds = keys + kStrPeqStage + kStrRowStage;
-        hipError_t e = set_lds(leven_knn_kernel<1, false>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((leven_knn_kernel<1, false>), grid, dim3(256), lds, s, row_ptr, data, p.n, p.rows_per_split,
-                           q_off, q_len, U(peq), p.nq, p.k, p.kl, p.P, nw, UW(mw_ws), split_d, split_pos);
-    } else {
-        if (p.tq != 1) return hipErrorInvalidValue;
-        const size_t lds = keys + kStrPeqStage + kStrRowStage + (nw <= kStrMwLds ? (size_t)256 * 2 * nw * 8 : 0);
-        hipError_t e = set_lds(leven_knn_kernel<1, true>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL((leven_knn_kernel<1, true>), grid, dim3(256), lds, s, row_ptr, data, p.n, p.rows_per_split,
-                           q_off, q_len, U(peq), p.nq, p.k, p.kl, p.P, nw, UW(mw_ws), split_d, split_pos);
-    }
-    return hipGetLastError();
+    size_t lds = (size_t)p.tq * p.P * 8 + kStrPeqStage + kStrRowStage;
+    if (nw == 1 && p.tq == kStrTileQ)
+        return launch_with_lds(leven_knn_kernel<kStrTileQ, false>, grid, lds, s, row_ptr, data, p.n, p.rows_per_split,
+                               q_off, q_len, U(peq), p.nq, p.k, p.kl, p.P, nw, UW(mw_ws), split_d, split_pos);
+    if (nw == 1)
+        return launch_with_lds(leven_knn_kernel<1, false>, grid, lds, s, row_ptr, data, p.n, p.rows_per_split, q_off,
+                               q_len, U(peq), p.nq, p.k, p.kl, p.P, nw, UW(mw_ws), split_d, split_pos);
+    if (p.tq != 1) return hipErrorInvalidValue;
+    if (nw <= kStrMwLds) lds += (size_t)256 * 2 * nw * 8;
+    return launch_with_lds(leven_knn_kernel<1, true>, grid, lds, s, row_ptr, data, p.n, p.rows_per_split, q_off, q_len,
+                           U(peq), p.nq, p.k, p.kl, p.P, nw, UW(mw_ws), split_d, split_pos);
 }
 
-hipError_t launch_ham_knn(const StringScanPlan& p, const uint32_t* rows, int W, const uint32_t* q, float* split_d,
+hipError_t launch_ham_knn(const ScanPlan& p, const uint32_t* rows, int W, const uint32_t* q, float* split_d,
                           int32_t* split_pos, hipStream_t s) {
     const dim3 grid(p.nsplit, (p.nq + p.tq - 1) / p.tq);
-    const size_t keys = (size_t)p.tq * p.P * 8;
-    const size_t lds = keys + kStrHamQStage;
-    if (p.tq == kStrTileQ) {
-        hipError_t e = set_lds(ham_knn_kernel<kStrTileQ>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(ham_knn_kernel<kStrTileQ>, grid, dim3(256), lds, s, rows, W, p.n, p.rows_per_split, q, p.nq,
-                           p.k, p.kl, p.P, split_d, split_pos);
-    } else {
-        hipError_t e = set_lds(ham_knn_kernel<1>, lds);
-        if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(ham_knn_kernel<1>, grid, dim3(256), lds, s, rows, W, p.n, p.rows_per_split, q, p.nq, p.k,
-                           p.kl, p.P, split_d, split_pos);
-    }
-    return hipGetLastError();
+    const size_t lds = (size_t)p.tq * p.P * 8 + kStrHamQStage;
+    if (p.tq == kStrTileQ)
+        return launch_with_lds(ham_knn_kernel<kStrTileQ>, grid, lds, s, rows, W, p.n, p.rows_per_split, q, p.nq, p.k,
+                               p.kl, p.P, split_d, split_pos);
+    return launch_with_lds(ham_knn_kernel<1>, grid, lds, s, rows, W, p.n, p.rows_per_split, q, p.nq, p.k, p.kl, p.P,
+                           split_d, split_pos);
 }
 
 int leven_dist_grid(int n) {

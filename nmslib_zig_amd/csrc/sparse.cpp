@@ -9,10 +9,6 @@
 
 namespace gfxknn {
 
-namespace {
-size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
-}  // namespace
-
 void Engine::add_sparse_row(const SparseElem* elems, size_t count, int32_t id) {
     if (!sparse_) throw EngineError(Err::SpaceIncompatible, "Not sparse space");
     if (count == 0 || count > (size_t)INT32_MAX)
@@ -53,7 +49,6 @@ void Engine::upload_sparse() {
     upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// Batches go through in slices of queries: the per-split lists ([nsplit][queries][k] keys) stay bounded.
 void Engine::knn_sparse_host(const SparseElem* const* queries, const size_t* counts, size_t nq, size_t k,
                              const int32_t** ids, const float** dists, const int32_t** cnt) {
     if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
@@ -65,8 +60,7 @@ void Engine::knn_sparse_host(const SparseElem* const* queries, const size_t* cou
     for (size_t i = 0; i < nq; ++i) total += counts[i];
     // device / pinned layout of the batch: q_ptr int64 [nq+1] | ids u32 [total] | vals f32 [total]
     const size_t ptr_b = (nq + 1) * 8, ids_b = align8(total * 4), qbytes = ptr_b + ids_b + total * 4;
-    const size_t rbytes = nq * k * 4;
-    char* hp = static_cast<char*>(pinned(std::max(qbytes, 2 * rbytes + nq * 4)));
+    char* hp = static_cast<char*>(pinned(std::max(qbytes, 2 * nq * k * 4 + nq * 4)));
     int64_t* hptr = reinterpret_cast<int64_t*>(hp);
     uint32_t* hids = reinterpret_cast<uint32_t*>(hp + ptr_b);
     float* hvals = reinterpret_cast<float*>(hp + ptr_b + ids_b);
@@ -80,45 +74,20 @@ void Engine::knn_sparse_host(const SparseElem* const* queries, const size_t* cou
         at += counts[i];
     }
     hptr[nq] = (int64_t)at;
-    ws_sp_q_.ensure(qbytes);
-    hip_check(hipMemcpyAsync(ws_sp_q_.ptr(), hp, qbytes, hipMemcpyHostToDevice, stream_), "sparse queries H2D");
-    const int64_t* d_qptr = ws_sp_q_.as<int64_t>();
-    const uint32_t* d_qids = reinterpret_cast<const uint32_t*>(ws_sp_q_.as<char>() + ptr_b);
-    const float* d_qvals = reinterpret_cast<const float*>(ws_sp_q_.as<char>() + ptr_b + ids_b);
+    ws_bq_.ensure(qbytes);
+    hip_check(hipMemcpyAsync(ws_bq_.ptr(), hp, qbytes, hipMemcpyHostToDevice, stream_), "sparse queries H2D");
+    const int64_t* d_qptr = ws_bq_.as<int64_t>();
+    const uint32_t* d_qids = reinterpret_cast<const uint32_t*>(ws_bq_.as<char>() + ptr_b);
+    const float* d_qvals = reinterpret_cast<const float*>(ws_bq_.as<char>() + ptr_b + ids_b);
 
-    ws_ids_.ensure(2 * rbytes + nq * 4);
-    int32_t* d_ids = ws_ids_.as<int32_t>();
-    float* d_dists = reinterpret_cast<float*>(d_ids + nq * k);
-    int32_t* d_cnt = d_ids + 2 * nq * k;
-    const int n = (int)d_n_;
-    const size_t max_split_keys = (size_t)1 << 25;  // 256 MiB of per-split lists at most (one query always fits)
-    for (size_t q0 = 0; q0 < nq;) {
-        int m = (int)std::min<size_t>(32768, nq - q0);
-        SparseScanPlan p = sparse_make_plan(n, m, (int)k);
-        while (m > 1 && (size_t)p.nsplit * m * k > max_split_keys) {
-            m = std::max(1, m / 2);
-            p = sparse_make_plan(n, m, (int)k);
-        }
-        const size_t keys = (size_t)p.nsplit * m * k;
-        ws_sp_split_.ensure(keys * 8);
-        float* split_d = ws_sp_split_.as<float>();
-        int32_t* split_pos = reinterpret_cast<int32_t*>(split_d + keys);
-        prof_begin(stream_);
+    const ResultBlock out = result_block(nq, k);
+    scan_slices(nq, k, kSparseTileQ, out, [&](const ScanPlan& p, size_t q0, float* split_d, int32_t* split_pos) {
         hip_check(launch_sparse_knn(space_, p, d_sp_ptr_.as<int64_t>(), d_sp_ids_.as<uint32_t>(), d_sp_vals_.as<float>(),
                                     d_qptr + q0, d_qids, d_qvals, split_d, split_pos, stream_),
                   "sparse scan");
-        hip_check(launch_merge_topk_ex(split_d, split_pos, (size_t)m * k, p.nsplit, m, (int)k, d_dists + q0 * k,
-                                       d_ids + q0 * k, d_cnt + q0, d_ids_.as<int32_t>(), stream_),
-                  "sparse merge");
-        prof_end(stream_);
-        q0 += (size_t)m;
-    }
-    hip_check(hipMemcpyAsync(hp, d_ids, 2 * rbytes + nq * 4, hipMemcpyDeviceToHost, stream_), "results D2H");
-    hip_check(hipStreamSynchronize(stream_), "sparse knn");
+    });
+    fetch_results(nq, k, "sparse knn", ids, dists, cnt);
     last_path = 0;
-    *ids = reinterpret_cast<const int32_t*>(hp);
-    *dists = reinterpret_cast<const float*>(hp + rbytes);
-    *cnt = reinterpret_cast<const int32_t*>(hp + 2 * rbytes);
 }
 
 size_t Engine::range_sparse_host(const SparseElem* query, size_t count, double radius, size_t capacity, int32_t* ids,
@@ -142,31 +111,12 @@ size_t Engine::range_sparse_host(const SparseElem* query, size_t count, double r
     float* d_qv = reinterpret_cast<float*>(ws_q_.as<char>() + ids_b);
     hip_check(hipMemcpyAsync(d_qi, qi.data(), count * 4, hipMemcpyHostToDevice, stream_), "query H2D");
     hip_check(hipMemcpyAsync(d_qv, qv.data(), count * 4, hipMemcpyHostToDevice, stream_), "query H2D");
-    ws_rdist_.ensure(2 * n * 4);
-    float* filter = ws_rdist_.as<float>();
-    float* report = filter + n;
-    ws_rcnt_.ensure(range_count_elems((int)n) * 4);
-    ws_ids_.ensure(capacity * 4);
-    ws_dists_.ensure(capacity * 4);
-    hip_check(launch_sparse_dist(space_, d_sp_ptr_.as<int64_t>(), d_sp_ids_.as<uint32_t>(), d_sp_vals_.as<float>(),
-                                 (int)n, d_qi, d_qv, (int)count, filter, report, stream_),
-              "sparse range distances");
-    const int cap = (int)std::min<size_t>(capacity, INT32_MAX);
-    hip_check(launch_range_select(filter, report, (int)n, r, d_ids_.as<int32_t>(), ws_rcnt_.as<int>(), cap,
-                                  ws_ids_.as<int32_t>(), ws_dists_.as<float>(), stream_),
-              "sparse range select");
-    int total = 0;
-    hip_check(hipMemcpyAsync(&total, ws_rcnt_.as<int>() + (range_count_elems((int)n) - 1), 4, hipMemcpyDeviceToHost,
-                             stream_),
-              "range count");
-    hip_check(hipStreamSynchronize(stream_), "sparse range");
-    const size_t m = std::min<size_t>((size_t)total, capacity);
-    if (m) {
-        hip_check(hipMemcpyAsync(ids, ws_ids_.ptr(), m * 4, hipMemcpyDeviceToHost, stream_), "range ids");
-        hip_check(hipMemcpyAsync(dists, ws_dists_.ptr(), m * 4, hipMemcpyDeviceToHost, stream_), "range dists");
-        hip_check(hipStreamSynchronize(stream_), "sparse range");
-    }
-    return m;
+    // the filter uses d(row, query), the reported distance is d(query, row)
+    return range_select(true, r, capacity, ids, dists, [&](float* filter, float* report) {
+        hip_check(launch_sparse_dist(space_, d_sp_ptr_.as<int64_t>(), d_sp_ids_.as<uint32_t>(), d_sp_vals_.as<float>(),
+                                     (int)n, d_qi, d_qv, (int)count, filter, report, stream_),
+                  "sparse range distances");
+    });
 }
 
 float Engine::pair_distance_sparse(size_t p1, size_t p2) {
@@ -192,10 +142,7 @@ float Engine::pair_distance_sparse(size_t p1, size_t p2) {
     hip_check(launch_sparse_pair(space_, reinterpret_cast<const int64_t*>(base), reinterpret_cast<const uint32_t*>(base + 32),
                                  reinterpret_cast<const float*>(base + 32 + ids_b), 0, 1, out, stream_),
               "sparse pair distance");
-    float v = 0;
-    hip_check(hipMemcpyAsync(&v, out, 4, hipMemcpyDeviceToHost, stream_), "pair D2H");
-    hip_check(hipStreamSynchronize(stream_), "sparse pair distance");
-    return v;
+    return read_float(out, "sparse pair distance");
 }
 
 }  // namespace gfxknn

@@ -18,8 +18,6 @@ namespace gfxknn {
 
 namespace {
 
-size_t align8(size_t b) { return (b + 7) & ~(size_t)7; }
-
 bool is_space(char c) { return std::isspace(static_cast<unsigned char>(c)) != 0; }
 
 // The reference parses a C string: a NUL ends the text.
@@ -219,9 +217,9 @@ void Engine::knn_string_hnsw(const int64_t* d_qoff, const int32_t* d_qlen, const
     a.ws_per_query = string_hnsw_ws_words(a, old);
     const size_t per_query = a.vis_words * 4 + a.ws_per_query * 8 + (size_t)64 * 2 * nw_max * 8;
     const size_t m = std::max<size_t>(1, std::min<size_t>(nq, ((size_t)256 << 20) / per_query));
-    ws_st_split_.ensure(m * per_query);
-    a.visited = ws_st_split_.as<uint32_t>();
-    a.ws = reinterpret_cast<unsigned long long*>(ws_st_split_.as<char>() + align8(m * a.vis_words * 4));
+    ws_split_.ensure(m * per_query);
+    a.visited = ws_split_.as<uint32_t>();
+    a.ws = reinterpret_cast<unsigned long long*>(ws_split_.as<char>() + align8(m * a.vis_words * 4));
     a.mw_ws = a.ws + m * a.ws_per_query;
     ws_ndc_.ensure(nq * 4);
     ws_hops_.ensure(nq * 4);
@@ -266,7 +264,6 @@ void Engine::string_query(const char* s, size_t len, Err parse_err, std::vector<
                                                     std::to_string(st_bits_));
 }
 
-// Batches go through in slices of queries: the per-split lists ([nsplit][queries][k] keys) stay bounded.
 void Engine::knn_string_host(const char* const* queries, const size_t* lens, size_t nq, size_t k, const int32_t** ids,
                              const float** dists, const int32_t** cnt) {
     if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
@@ -293,8 +290,7 @@ void Engine::knn_string_host(const char* const* queries, const size_t* lens, siz
     // device / pinned layout of the batch: leven q_off int64 [nq+1] | q_len int32 [nq] | Peq u64; bit_hamming words
     const size_t off_b = (nq + 1) * 8, len_b = align8(nq * 4);
     const size_t qbytes = lev ? off_b + len_b + peq_words * 8 : qwords.size() * 4;
-    const size_t rbytes = nq * k * 4;
-    char* hp = static_cast<char*>(pinned(std::max(std::max<size_t>(qbytes, 8), 2 * rbytes + nq * 4)));
+    char* hp = static_cast<char*>(pinned(std::max(std::max<size_t>(qbytes, 8), 2 * nq * k * 4 + nq * 4)));
     if (lev) {
         int64_t* hoff = reinterpret_cast<int64_t*>(hp);
         int32_t* hlen = reinterpret_cast<int32_t*>(hp + off_b);
@@ -310,43 +306,23 @@ void Engine::knn_string_host(const char* const* queries, const size_t* lens, siz
     } else if (!qwords.empty()) {
         std::memcpy(hp, qwords.data(), qbytes);
     }
-    ws_st_q_.ensure(std::max<size_t>(qbytes, 8));
-    hip_check(hipMemcpyAsync(ws_st_q_.ptr(), hp, qbytes, hipMemcpyHostToDevice, stream_), "string queries H2D");
-    const int64_t* d_qoff = ws_st_q_.as<int64_t>();
-    const int32_t* d_qlen = reinterpret_cast<const int32_t*>(ws_st_q_.as<char>() + off_b);
-    const uint64_t* d_peq = reinterpret_cast<const uint64_t*>(ws_st_q_.as<char>() + off_b + len_b);
-    const uint32_t* d_qw = ws_st_q_.as<uint32_t>();
+    ws_bq_.ensure(std::max<size_t>(qbytes, 8));
+    hip_check(hipMemcpyAsync(ws_bq_.ptr(), hp, qbytes, hipMemcpyHostToDevice, stream_), "string queries H2D");
+    const int64_t* d_qoff = ws_bq_.as<int64_t>();
+    const int32_t* d_qlen = reinterpret_cast<const int32_t*>(ws_bq_.as<char>() + off_b);
+    const uint64_t* d_peq = reinterpret_cast<const uint64_t*>(ws_bq_.as<char>() + off_b + len_b);
+    const uint32_t* d_qw = ws_bq_.as<uint32_t>();
 
-    ws_ids_.ensure(2 * rbytes + nq * 4);
-    int32_t* d_ids = ws_ids_.as<int32_t>();
-    float* d_dists = reinterpret_cast<float*>(d_ids + nq * k);
-    int32_t* d_cnt = d_ids + 2 * nq * k;
-    const int n = (int)d_n_;
-    if (method_ == Method::Hnsw && n > 0) {
-        knn_string_hnsw(d_qoff, d_qlen, d_peq, d_qw, nw_max, nq, k, d_ids, d_dists, d_cnt);
-        hip_check(hipMemcpyAsync(hp, d_ids, 2 * rbytes + nq * 4, hipMemcpyDeviceToHost, stream_), "results D2H");
-        hip_check(hipStreamSynchronize(stream_), "string hnsw");
+    const ResultBlock out = result_block(nq, k);
+    if (method_ == Method::Hnsw && d_n_ > 0) {
+        knn_string_hnsw(d_qoff, d_qlen, d_peq, d_qw, nw_max, nq, k, out.ids, out.dists, out.cnt);
+        fetch_results(nq, k, "string hnsw", ids, dists, cnt);
         last_path = 0;
-        *ids = reinterpret_cast<const int32_t*>(hp);
-        *dists = reinterpret_cast<const float*>(hp + rbytes);
-        *cnt = reinterpret_cast<const int32_t*>(hp + 2 * rbytes);
         return;
     }
     have_counters_ = false;
     const int tq = (lev && nw_max > 1) ? 1 : kStrTileQ;
-    const size_t max_split_keys = (size_t)1 << 25;  // 256 MiB of per-split lists at most (one query always fits)
-    for (size_t q0 = 0; q0 < nq;) {
-        int m = (int)std::min<size_t>(32768, nq - q0);
-        StringScanPlan p = string_make_plan(n, m, (int)k, tq);
-        while (m > 1 && (size_t)p.nsplit * m * k > max_split_keys) {
-            m = std::max(1, m / 2);
-            p = string_make_plan(n, m, (int)k, tq);
-        }
-        const size_t keys = (size_t)p.nsplit * m * k;
-        ws_st_split_.ensure(keys * 8);
-        float* split_d = ws_st_split_.as<float>();
-        int32_t* split_pos = reinterpret_cast<int32_t*>(split_d + keys);
-        prof_begin(stream_);
+    scan_slices(nq, k, tq, out, [&](const ScanPlan& p, size_t q0, float* split_d, int32_t* split_pos) {
         if (lev) {
             const size_t mw = leven_mw_ws_words(p, nw_max);
             if (mw) ws_st_mw_.ensure(mw * 8);
@@ -358,18 +334,9 @@ void Engine::knn_string_host(const char* const* queries, const size_t* lens, siz
             hip_check(launch_ham_knn(p, d_st_data_.as<uint32_t>(), (int)W, d_qw + q0 * W, split_d, split_pos, stream_),
                       "bit_hamming scan");
         }
-        hip_check(launch_merge_topk_ex(split_d, split_pos, (size_t)m * k, p.nsplit, m, (int)k, d_dists + q0 * k,
-                                       d_ids + q0 * k, d_cnt + q0, d_ids_.as<int32_t>(), stream_),
-                  "string merge");
-        prof_end(stream_);
-        q0 += (size_t)m;
-    }
-    hip_check(hipMemcpyAsync(hp, d_ids, 2 * rbytes + nq * 4, hipMemcpyDeviceToHost, stream_), "results D2H");
-    hip_check(hipStreamSynchronize(stream_), "string knn");
+    });
+    fetch_results(nq, k, "string knn", ids, dists, cnt);
     last_path = 0;
-    *ids = reinterpret_cast<const int32_t*>(hp);
-    *dists = reinterpret_cast<const float*>(hp + rbytes);
-    *cnt = reinterpret_cast<const int32_t*>(hp + 2 * rbytes);
 }
 
 size_t Engine::range_string_host(const char* query, size_t len, double radius, size_t capacity, int32_t* ids,
@@ -385,52 +352,32 @@ size_t Engine::range_string_host(const char* query, size_t len, double radius, s
     // RangeQuery<int>(space, obj, static_cast<int>(radius)), nmslib_c.cpp:1092-1093: the radius truncates to int
     const double rc = std::max(-1.0, std::min(radius, 2147483647.0));
     const float r = (float)(int)rc;
-    ws_rdist_.ensure(n * 4);
-    float* d = ws_rdist_.as<float>();
-    if (lev) {
-        const size_t nw = (len + 63) / 64;
-        std::vector<uint64_t> peq(nw * 256);
-        build_peq(reinterpret_cast<const uint8_t*>(query), len, peq.data());
-        ws_q_.ensure(peq.size() * 8);
-        hip_check(hipMemcpyAsync(ws_q_.ptr(), peq.data(), peq.size() * 8, hipMemcpyHostToDevice, stream_), "query H2D");
-        const size_t mw = nw > 1 ? (size_t)2 * nw * 256 * leven_dist_grid((int)n) : 0;
-        if (mw) ws_st_mw_.ensure(mw * 8);
-        hip_check(launch_leven_dist(d_st_ptr_.as<int64_t>(), d_st_data_.as<uint8_t>(), (int)n, ws_q_.as<uint64_t>(),
-                                    (int)len, (int)nw, mw ? ws_st_mw_.as<uint64_t>() : nullptr, d, stream_),
-                  "leven range distances");
-    } else {
-        ws_q_.ensure(std::max<size_t>(qw.size(), 1) * 4);
-        hip_check(hipMemcpyAsync(ws_q_.ptr(), qw.data(), qw.size() * 4, hipMemcpyHostToDevice, stream_), "query H2D");
-        hip_check(launch_ham_dist(d_st_data_.as<uint32_t>(), (int)ham_words(), (int)n, ws_q_.as<uint32_t>(), d, stream_),
-                  "bit_hamming range distances");
-    }
-    ws_rcnt_.ensure(range_count_elems((int)n) * 4);
-    ws_ids_.ensure(capacity * 4);
-    ws_dists_.ensure(capacity * 4);
-    const int cap = (int)std::min<size_t>(capacity, INT32_MAX);
     // both distances are symmetric: the filter d(row, query) is also the reported d(query, row)
-    hip_check(launch_range_select(d, d, (int)n, r, d_ids_.as<int32_t>(), ws_rcnt_.as<int>(), cap, ws_ids_.as<int32_t>(),
-                                  ws_dists_.as<float>(), stream_),
-              "string range select");
-    int total = 0;
-    hip_check(hipMemcpyAsync(&total, ws_rcnt_.as<int>() + (range_count_elems((int)n) - 1), 4, hipMemcpyDeviceToHost,
-                             stream_),
-              "range count");
-    hip_check(hipStreamSynchronize(stream_), "string range");
-    const size_t m = std::min<size_t>((size_t)total, capacity);
-    if (m) {
-        hip_check(hipMemcpyAsync(ids, ws_ids_.ptr(), m * 4, hipMemcpyDeviceToHost, stream_), "range ids");
-        hip_check(hipMemcpyAsync(dists, ws_dists_.ptr(), m * 4, hipMemcpyDeviceToHost, stream_), "range dists");
-        hip_check(hipStreamSynchronize(stream_), "string range");
-    }
-    return m;
+    return range_select(false, r, capacity, ids, dists, [&](float* d, float*) {
+        if (lev) {
+            const size_t nw = (len + 63) / 64;
+            std::vector<uint64_t> peq(nw * 256);
+            build_peq(reinterpret_cast<const uint8_t*>(query), len, peq.data());
+            ws_q_.ensure(peq.size() * 8);
+            hip_check(hipMemcpyAsync(ws_q_.ptr(), peq.data(), peq.size() * 8, hipMemcpyHostToDevice, stream_), "query H2D");
+            const size_t mw = nw > 1 ? (size_t)2 * nw * 256 * leven_dist_grid((int)n) : 0;
+            if (mw) ws_st_mw_.ensure(mw * 8);
+            hip_check(launch_leven_dist(d_st_ptr_.as<int64_t>(), d_st_data_.as<uint8_t>(), (int)n, ws_q_.as<uint64_t>(),
+                                        (int)len, (int)nw, mw ? ws_st_mw_.as<uint64_t>() : nullptr, d, stream_),
+                      "leven range distances");
+        } else {
+            ws_q_.ensure(std::max<size_t>(qw.size(), 1) * 4);
+            hip_check(hipMemcpyAsync(ws_q_.ptr(), qw.data(), qw.size() * 4, hipMemcpyHostToDevice, stream_), "query H2D");
+            hip_check(launch_ham_dist(d_st_data_.as<uint32_t>(), (int)ham_words(), (int)n, ws_q_.as<uint32_t>(), d, stream_),
+                      "bit_hamming range distances");
+        }
+    });
 }
 
 float Engine::pair_distance_string(size_t p1, size_t p2) {
     // IndexTimeDistance(data[p1], data[p2]) (nmslib_c.cpp:1166) on the device store
     if (dirty_) finalize();
     check_device();
-    float v = 0;
     ws_pair_.ensure(16);
     float* out = ws_pair_.as<float>();
     if (space_ == SP_LEVEN) {
@@ -447,9 +394,7 @@ float Engine::pair_distance_string(size_t p1, size_t p2) {
         hip_check(launch_ham_pair(d_st_data_.as<uint32_t>(), (int)ham_words(), (int)p1, (int)p2, out, stream_),
                   "bit_hamming pair distance");
     }
-    hip_check(hipMemcpyAsync(&v, out, 4, hipMemcpyDeviceToHost, stream_), "pair D2H");
-    hip_check(hipStreamSynchronize(stream_), "string pair distance");
-    return v;
+    return read_float(out, "string pair distance");
 }
 
 }  // namespace gfxknn

@@ -306,15 +306,18 @@ def test_python_binding_string_forms():
 
 @pytest.mark.skipif(not os.path.exists("/opt/rocm/bin/hipcc"), reason="hipcc not available")
 def test_string_kernels_use_no_scratch(tmp_path):
-    """Every kernel of string_kernels.hip keeps its state in registers and LDS: no private segment, no scratch_ ops."""
+    """Every kernel of string_kernels.hip and sparse_kernels.hip keeps its state in registers and LDS: no private
+    segment, no scratch_ ops.  (sparse_kernels.hip as the library builds it: -ffp-contract=off; its 7 spaces come as
+    two k-NN scans, one distance and one pair kernel each.)"""
     import re
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    src = os.path.join(root, "nmslib_zig_amd", "csrc", "kernels", "string_kernels.hip")
-    asm = str(tmp_path / "s.s")
-    subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-pass-failed", "-S",
-                           "--cuda-device-only", src, "-o", asm], stderr=subprocess.DEVNULL)
-    text = open(asm).read()
-    sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", text)
-    assert len(sizes) >= 9 and all(s == "0" for s in sizes), sizes
-    assert "scratch_" not in text
+    for name, flags, least in (("string_kernels.hip", [], 9), ("sparse_kernels.hip", ["-ffp-contract=off"], 28)):
+        src = os.path.join(root, "nmslib_zig_amd", "csrc", "kernels", name)
+        asm = str(tmp_path / (name + ".s"))
+        subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-Wno-pass-failed",
+                               *flags, "-S", "--cuda-device-only", src, "-o", asm], stderr=subprocess.DEVNULL)
+        text = open(asm).read()
+        sizes = re.findall(r"\.private_segment_fixed_size:\s*(\d+)", text)
+        assert len(sizes) >= least and all(s == "0" for s in sizes), (name, sizes)
+        assert "scratch_" not in text, name
