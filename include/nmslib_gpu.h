@@ -98,6 +98,11 @@ typedef struct {
 } nmslib_gpu_stats_t;
 nmslib_error_t nmslib_gpu_get_stats(nmslib_index_handle_t index, nmslib_gpu_stats_t* out);
 
+/* Which builder made the HNSW graph this index searches: *builder = 0 no graph (not built yet, not an HNSW index)
+ * or a graph loaded from a file, 1 the host builder (the reference's graph at indexThreadQty=1), 2 the batched GPU
+ * builder (index parameter gpu_build). */
+nmslib_error_t nmslib_gpu_graph_builder(nmslib_index_handle_t index, int* builder);
+
 /* The HNSW graph of a string index (data type 3), for inspection: *enterpoint, *maxlevel and, for node `node` at
  * `level`, its neighbour list (positions) in out[0 .. *count) when *count <= capacity.  level above the node's own
  * level -> NMSLIB_ERROR_INVALID_ARGUMENT.  Other indexes -> NMSLIB_ERROR_SPACE_INCOMPATIBLE. */

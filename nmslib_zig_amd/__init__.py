@@ -174,6 +174,7 @@ def lib():
         "nmslib_gpu_merge_topk_strided": (C.c_int, [vp, vp, sz, sz, sz, sz, vp, vp, vp]),
         "nmslib_gpu_get_stats": (C.c_int, [vp, C.POINTER(GpuStats)]),
         "nmslib_gpu_kernel_timing": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
+        "nmslib_gpu_graph_builder": (C.c_int, [vp, C.POINTER(C.c_int)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)   # AttributeError here = a declared symbol is not exported
@@ -200,7 +201,7 @@ ABI_SYMBOLS_C = [  # the 37 symbols of the reference boundary
 ABI_SYMBOLS_GPU = ["nmslib_gpu_device_count", "nmslib_gpu_finalize",
                    "nmslib_gpu_knn_query_batch_device", "nmslib_gpu_last_batch_counters",
                    "nmslib_gpu_merge_topk", "nmslib_gpu_merge_topk_strided", "nmslib_gpu_get_stats", "nmslib_gpu_kernel_timing",
-                   "nmslib_gpu_string_hnsw_links"]
+                   "nmslib_gpu_string_hnsw_links", "nmslib_gpu_graph_builder"]
 
 
 class TrackingAllocator:
@@ -512,6 +513,12 @@ class Index:
         s = GpuStats()
         _check(lib().nmslib_gpu_get_stats(self.h, C.byref(s)), self.alloc)
         return {f[0]: getattr(s, f[0]) for f in GpuStats._fields_}
+
+    def graphBuilder(self):
+        """Who built the HNSW graph: 0 = no graph or one loaded from a file, 1 = host builder, 2 = GPU builder."""
+        b = C.c_int()
+        _check(lib().nmslib_gpu_graph_builder(self.h, C.byref(b)), self.alloc)
+        return b.value
 
     # -- metadata / stored data -------------------------------------------------------------------
     def getDistance(self, a, b):

@@ -863,6 +863,15 @@ nmslib_error_t nmslib_gpu_get_stats(nmslib_index_handle_t handle, nmslib_gpu_sta
     });
 }
 
+nmslib_error_t nmslib_gpu_graph_builder(nmslib_index_handle_t handle, int* builder) {
+    if (!handle || !builder) FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid arguments");
+    Engine* e = H(handle)->engine;
+    return guarded(NMSLIB_ERROR_RUNTIME, "Failed to read the graph builder", [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        *builder = e->graph_builder();
+    });
+}
+
 nmslib_error_t nmslib_gpu_string_hnsw_links(nmslib_index_handle_t index, size_t node, int level, int32_t* out,
                                             size_t capacity, size_t* count, int* enterpoint, int* maxlevel) {
     if (!index || !count || !enterpoint || !maxlevel || node >= nmslib_data_qty(index) || level < 0)

@@ -94,6 +94,11 @@ void* DevBuf::ensure(size_t bytes) {
     if (poison) hip_check(hipMemset(p_, atoi(poison) & 0xFF, bytes), "poison");
     return p_;
 }
+void DevBuf::swap(DevBuf& o) {
+    std::swap(p_, o.p_);
+    std::swap(n_, o.n_);
+}
+
 void DevBuf::release() {
     if (p_) (void)hipFree(p_);
     p_ = nullptr;
@@ -285,6 +290,7 @@ void Engine::reset() {
     graph_ = HostGraph();
     graph_rows_.clear();
     loaded_graph_ = false;
+    graph_builder_ = 0;
     created_ = false;
     dirty_ = true;
     graph_dirty_ = true;
@@ -378,6 +384,7 @@ void Engine::create_index(const std::vector<std::string>& params) {
     dirty_ = true;
     graph_dirty_ = true;
     loaded_graph_ = false;
+    graph_builder_ = 0;
     if (!ids_.empty()) {
         if (defer) ensure_graph();
         else finalize();
@@ -471,6 +478,7 @@ void Engine::build_graph() {
     if (!loaded_graph_) {
         const void* rows = is_u8() ? static_cast<const void*>(rows_u8()) : static_cast<const void*>(rows_f32());
         hnsw_build_host(space_, rows, size(), dim_, bp_, graph_);
+        graph_builder_ = 1;
     }
     build_seconds = std::chrono::duration<double>(clk::now() - t0).count();
 }
@@ -538,14 +546,16 @@ void Engine::upload_graph() {
 
 bool Engine::use_gpu_build() const {
     if (loaded_graph_ || method_ != Method::Hnsw) return false;
-    // what only the host builder does (the reference's "no limits"): lists beyond two words per lane, selection
-    // heuristics 1 and 3, post-processing -- also when gpu_build=1 asks for the GPU
-    if (bp_.maxM > 62 || bp_.maxM0 > 126 || bp_.M > 62 || bp_.delaunay == 1 || bp_.delaunay == 3 || bp_.post != 0) return false;
+    // what only the host builder does (the reference's "no limits"): lists beyond four words per lane and selection
+    // heuristic 3 (its candidate pool is an unordered set of node addresses) -- also when gpu_build=1 asks for the
+    // GPU.  A new node's M links must fit its own lists (the select kernel writes them without a shrink step).
+    if (bp_.M > 127 || bp_.maxM > 127 || bp_.maxM0 > 254 || bp_.M > bp_.maxM || bp_.M > bp_.maxM0 || bp_.delaunay == 3)
+        return false;
     if (bp_.gpu_build >= 0) return bp_.gpu_build != 0;
     // auto: indexThreadQty=1 asks for the reference's sequential insertion order (bit-identical graph,
     // host builder); anything else is the concurrent build, whose schedule is free -> the GPU, unless the
     // parameters exceed what its kernels hold in LDS (the host builder has the reference's "no limits")
-    if (bp_.efConstruction > 1024 || bp_.maxM > 62 || bp_.maxM0 > 126) return false;
+    if (bp_.efConstruction > 1024) return false;
     return bp_.threads != 1;
 }
 
@@ -554,13 +564,80 @@ bool Engine::use_gpu_build() const {
 // the nodes of one batch are searched against the graph as it was before the batch, then linked.
 // Batches grow with the graph (size/16, at most gpu_build_batch), a node that raises the top level
 // closes its batch.  All searches of a batch (every level, top down) precede all link updates.
+//
+// post = 1, 2 (hnsw.cc:251-330): a second pass inserts the rows in reverse order (node 0, then n-1 .. 1, levels drawn
+// on from the same stream, as hnsw_build.cpp does); the result is the second graph with level-0 lists made from both
+// (hnsw_build_post_kernel).
 void Engine::build_graph_gpu() {
     auto t0 = clk::now();
     const size_t n = size();
     hnsw_check_params(bp_);
-    const int M = bp_.M, maxM = bp_.maxM, maxM0 = bp_.maxM0, efC = bp_.efConstruction;
+    const int maxM0 = bp_.maxM0, efC = bp_.efConstruction;
     if (efC < 1 || efC > 1024)
         throw EngineError(Err::IndexBuildFailed, "HNSW: efConstruction must be in [1, 1024] for the GPU builder");
+    graph_builder_ = 2;
+    const bool post = bp_.post != 0 && n > 1;
+    const std::vector<int32_t> draws = hnsw_random_levels(post ? 2 * n : n, bp_);
+    build_graph_gpu_pass(std::vector<int32_t>(draws.begin(), draws.begin() + (ptrdiff_t)n), false);
+    HostGraph& g = graph_;
+    hipStream_t s = stream_;
+    if (post) {
+        DevBuf first;
+        first.swap(d_links0_);
+        std::vector<int32_t> levels2(n);
+        levels2[0] = draws[n];
+        for (size_t pos = 1; pos < n; ++pos) levels2[n - pos] = draws[n + pos];
+        build_graph_gpu_pass(levels2, true);
+        // post = 1 keeps whole unions (up to 2 * maxM0) and then widens maxM0 to the longest list
+        const int wide = (bp_.post == 1 ? 2 * maxM0 : maxM0) + 1;
+        DevBuf out;
+        out.ensure(n * (size_t)wide * 4);
+        wb_nactive_.ensure(64);
+        hip_check(hipMemsetAsync(out.ptr(), 0, n * (size_t)wide * 4, s), "clear post lists");
+        hip_check(hipMemsetAsync(wb_nactive_.ptr(), 0, 4, s), "clear post length");
+        HnswDeviceGraph pg = dg_;
+        pg.ext_ids = nullptr;
+        hip_check(launch_hnsw_build_post(pg, d_links0_.as<int32_t>(), first.as<int32_t>(), maxM0, bp_.post, bp_.delaunay,
+                                         out.as<int32_t>(), wide, wb_nactive_.as<int32_t>(), s),
+                  "build post");
+        if (bp_.post == 1) {
+            int32_t longest = 0;
+            hip_check(hipMemcpyAsync(&longest, wb_nactive_.ptr(), 4, hipMemcpyDeviceToHost, s), "post length");
+            hip_check(hipStreamSynchronize(s), "build post");
+            g.maxM0 = std::max(longest, 1);
+            d_links0_.release();
+            d_links0_.ensure(n * (size_t)(g.maxM0 + 1) * 4);
+            hip_check(launch_hnsw_build_repack(out.as<int32_t>(), wide, d_links0_.as<int32_t>(), g.maxM0 + 1, (int)n, s),
+                      "build post repack");
+            hip_check(hipStreamSynchronize(s), "build post repack");  // `out` is freed below
+        } else {
+            d_links0_.swap(out);
+        }
+        dg_.links0 = d_links0_.as<int32_t>();
+        dg_.maxM0 = g.maxM0;
+    }
+    if (n) {
+        const size_t l0_ints = n * (size_t)(g.maxM0 + 1);
+        g.links0.resize(l0_ints);
+        g.up_links.resize(graph_up_ints_);
+        hip_check(hipMemcpyAsync(g.links0.data(), d_links0_.ptr(), l0_ints * 4, hipMemcpyDeviceToHost, s), "links0 D2H");
+        if (graph_up_ints_)
+            hip_check(hipMemcpyAsync(g.up_links.data(), d_up_links_.ptr(), graph_up_ints_ * 4, hipMemcpyDeviceToHost, s),
+                      "up_links D2H");
+        hip_check(hipStreamSynchronize(s), "graph download");
+    }
+    for (DevBuf* b : {&wb_pts_, &wb_src_, &wb_starts_, &wb_cand_ids_, &wb_cand_d_, &wb_cand_n_, &wb_status_,
+                      &wb_req_key_, &wb_req_dist_, &wb_req_key2_, &wb_req_dist2_, &wb_sort_tmp_, &wb_active_, &wb_nactive_, &wb_extra_ids_, &wb_extra_d_, &wb_extra_n_})
+        b->release();
+    build_seconds = n ? std::chrono::duration<double>(clk::now() - t0).count() : 0;
+}
+
+// One insertion pass over all rows: position 0 is node 0, position i > 0 is node i, or node n - i in reverse order.
+// Leaves the graph in d_links0_ / d_up_off_ / d_up_links_ (dg_) and its levels, offsets and entry point in graph_.
+void Engine::build_graph_gpu_pass(const std::vector<int32_t>& levels, bool reverse) {
+    const size_t n = size();
+    const int M = bp_.M, maxM = bp_.maxM, maxM0 = bp_.maxM0, efC = bp_.efConstruction;
+    auto node_at = [&](size_t pos) { return reverse && pos ? n - pos : pos; };
     HostGraph& g = graph_;
     g = HostGraph{};
     g.n = (int)n;
@@ -569,7 +646,7 @@ void Engine::build_graph_gpu() {
     g.maxM0 = maxM0;
     g.efConstruction = efC;
     g.delaunay = bp_.delaunay;
-    g.levels = hnsw_random_levels(n, bp_);
+    g.levels = levels;
     g.up_off.assign(n, -1);
     size_t up_ints = 0;
     for (size_t i = 0; i < n; ++i)
@@ -581,16 +658,14 @@ void Engine::build_graph_gpu() {
     d_links0_.ensure(std::max<size_t>(l0_ints, 1) * 4);
     d_up_off_.ensure(std::max<size_t>(n, 1) * 8);
     d_up_links_.ensure(std::max<size_t>(up_ints, 1) * 4);
-    prepare_graph_rows();
+    if (!reverse) prepare_graph_rows();  // (once: it normalises the cosine rows in place)
     dg_.links0 = d_links0_.as<int32_t>();
     dg_.up_off = d_up_off_.as<int64_t>();
     dg_.up_links = d_up_links_.as<int32_t>();
     dg_.maxM = maxM;
     dg_.maxM0 = maxM0;
-    if (n == 0) {
-        build_seconds = 0;
-        return;
-    }
+    graph_up_ints_ = up_ints;
+    if (n == 0) return;
     hipStream_t s = stream_;
     hip_check(hipMemsetAsync(d_links0_.ptr(), 0, l0_ints * 4, s), "clear links0");
     hip_check(hipMemsetAsync(d_up_links_.ptr(), 0, std::max<size_t>(up_ints, 1) * 4, s), "clear up_links");
@@ -623,7 +698,7 @@ void Engine::build_graph_gpu() {
         size_t bsz = std::min<size_t>(std::max<size_t>(sz / (size_t)batch_div, 1), (size_t)max_batch);
         size_t end = std::min(n, next + bsz);
         for (size_t i = next; i < end; ++i)
-            if (g.levels[i] > maxlevel) {
+            if (g.levels[node_at(i)] > maxlevel) {
                 end = i + 1;
                 break;
             }
@@ -636,9 +711,9 @@ void Engine::build_graph_gpu() {
         for (int l = top; l >= 0; --l) {
             base[l] = pts.size();
             for (size_t i = next; i < end; ++i) {
-                if (std::min(g.levels[i], top) < l) continue;
+                if (std::min(g.levels[node_at(i)], top) < l) continue;
                 cur_slot[i - next] = (int32_t)pts.size();
-                pts.push_back((int32_t)i);
+                pts.push_back((int32_t)node_at(i));
                 src.push_back(prev_slot[i - next]);
             }
             prev_slot = cur_slot;
@@ -722,15 +797,17 @@ void Engine::build_graph_gpu() {
                                                       wb_sort_tmp_.ptr(), sort_tmp, wb_active_.as<int32_t>(),
                                                       wb_nactive_.as<int32_t>(), s),
                       "build sort");
-            const size_t max_active = std::min<size_t>(sz, (size_t)total);
+            // distinct targets: the sz nodes linked before the batch and the slice's own nodes (batch-mates select each
+            // other); a smaller grid would drop whichever targets the head scan numbered last
+            const size_t max_active = std::min<size_t>(sz + m, (size_t)total);
             hip_check(launch_hnsw_build_link(bg, l, wb_active_.as<int32_t>(), wb_nactive_.as<int32_t>(), (int)max_active,
                                              wb_req_key2_.as<unsigned long long>(), wb_req_dist2_.as<float>(), total, s),
                       "build link");
         }
         for (size_t i = next; i < end; ++i)
-            if (g.levels[i] > maxlevel) {
-                maxlevel = g.levels[i];
-                enterpoint = (int)i;
+            if (g.levels[node_at(i)] > maxlevel) {
+                maxlevel = g.levels[node_at(i)];
+                enterpoint = (int)node_at(i);
             }
         // pts/src are reused by the next batch: the copies above must have been consumed
         hip_check(hipStreamSynchronize(s), "build batch");
@@ -738,19 +815,8 @@ void Engine::build_graph_gpu() {
     }
     g.maxlevel = maxlevel;
     g.enterpoint = enterpoint;
-    g.links0.resize(l0_ints);
-    g.up_links.resize(up_ints);
-    hip_check(hipMemcpyAsync(g.links0.data(), d_links0_.ptr(), l0_ints * 4, hipMemcpyDeviceToHost, s), "links0 D2H");
-    if (up_ints)
-        hip_check(hipMemcpyAsync(g.up_links.data(), d_up_links_.ptr(), up_ints * 4, hipMemcpyDeviceToHost, s),
-                  "up_links D2H");
-    hip_check(hipStreamSynchronize(s), "graph download");
     dg_.maxlevel = maxlevel;
     dg_.enterpoint = enterpoint;
-    for (DevBuf* b : {&wb_pts_, &wb_src_, &wb_starts_, &wb_cand_ids_, &wb_cand_d_, &wb_cand_n_, &wb_status_,
-                      &wb_req_key_, &wb_req_dist_, &wb_req_key2_, &wb_req_dist2_, &wb_sort_tmp_, &wb_active_, &wb_nactive_, &wb_extra_ids_, &wb_extra_d_, &wb_extra_n_})
-        b->release();
-    build_seconds = std::chrono::duration<double>(clk::now() - t0).count();
 }
 
 void Engine::ensure_graph() {

@@ -70,6 +70,7 @@ class DevBuf {
     DevBuf& operator=(const DevBuf&) = delete;
     void* ensure(size_t bytes);  // grow-only
     void release();
+    void swap(DevBuf& o);
     void* ptr() const { return p_; }
     template <typename T>
     T* as() const {
@@ -224,6 +225,8 @@ class Engine {
 
     // ---- row shards behind one handle (index parameter gpu_shards) ----
     size_t shard_count() const { return shards_.size(); }
+    // nmslib_gpu_graph_builder: 0 no graph or a loaded one, 1 host, 2 GPU (shards: all children take the same route)
+    int graph_builder() const { return shards_.empty() ? graph_builder_ : shards_[0]->graph_builder_; }
 
    private:
     // host rows / ids of this engine: its own, or (shard child) a window of the parent's
@@ -274,6 +277,7 @@ class Engine {
     void build_graph();
     bool use_gpu_build() const;
     void build_graph_gpu();
+    void build_graph_gpu_pass(const std::vector<int32_t>& levels, bool reverse);
     void prepare_graph_rows();
     void upload_graph();
     void knn_brute(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
@@ -311,6 +315,8 @@ class Engine {
     bool dirty_ = true;          // rows added since the last finalize (device copy stale)
     bool graph_dirty_ = true;    // rows added since the graph was last built
     bool loaded_graph_ = false;  // graph came from a file: never rebuild it
+    int graph_builder_ = 0;      // who built graph_: 0 nobody (no graph yet, or loaded), 1 the host builder, 2 the GPU builder
+    size_t graph_up_ints_ = 0;   // ints of the upper-level lists of the graph on the device (GPU builder)
     HnswBuildParams bp_;
     HostGraph graph_;
     std::vector<float> graph_rows_;  // rows as stored inside a loaded index (cosine: normalised)

@@ -15,6 +15,11 @@
 // sorted by (target, new node) with one device radix sort, and applied per target in that order: any
 // number of requests per target, no atomics, no dependence on scheduling -> the construction is
 // deterministic.  One wavefront per node/target; no workgroup ever waits for another inside a launch.
+//
+// List width: the select and link kernels are instantiated for W = 128 (M, maxM <= 62, maxM0 <= 126: a list and the
+// node that joins it are two items per lane) and W = 256 (M, maxM <= 127, maxM0 <= 254: four items per lane).  The
+// W = 256 form also carries getNeighborsByHeuristic1 (delaunay_type = 1), so the narrow kernels stay as they were.
+// Post-processing (hnsw.cc:251-330): hnsw_build_post_kernel, one wave per node, over the level-0 lists of two graphs.
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
@@ -109,17 +114,90 @@ __device__ __forceinline__ int heuristic2(const HnswDeviceGraph& g, const int* c
     return nk;
 }
 
+// getNeighborsByHeuristic1 (hnsw.h:82-127): heuristic 2, then the list is topped up to NN with the closest rejected
+// candidates.  Candidates ascending by (distance, position); kept ones are marked in place (cid[i] = ~id), so the
+// result comes out in candidate order again: ascending by (distance, position), like heuristic2's.
 template <int SPACE>
+__device__ __forceinline__ int heuristic1(const HnswDeviceGraph& g, int* cid, const float* cd, int nc, int NN, float* qv,
+                                          float* nd, int* kept_id, float* kept_d, int lane) {
+    if (nc < NN) {
+        for (int i = lane; i < nc; i += 64) {
+            kept_id[i] = cid[i];
+            kept_d[i] = cd[i];
+        }
+        __builtin_amdgcn_wave_barrier();
+        return nc;
+    }
+    int nk = 0;
+    for (int i = 0; i < nc && nk < NN; ++i) {
+        const int c = cid[i];
+        const float dc = cd[i];
+        bool good = true;
+        if (nk > 0) {
+            int qnorm;
+            stage_row<SPACE>(g, c, qv, qnorm, lane);
+            frontier_distances<SPACE>(g, qv, reinterpret_cast<const uint8_t*>(qv), qnorm, kept_id, nd, nk, lane);
+            bool bad = false;
+            for (int j = lane; j < nk; j += 64) bad |= nd[j] < dc;
+            good = !__any(bad);
+        }
+        if (good) {
+            if (lane == 0) {
+                kept_id[nk] = c;
+                kept_d[nk] = dc;
+                cid[i] = ~c;
+            }
+            nk++;
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (nk == NN) return nk;   // (the loop stopped at NN kept: nothing is topped up)
+    // every candidate was examined: the kept ones and the first NN - nk rejected ones, in candidate order
+    const int need = NN - nk;
+    const u64 below = (1ull << lane) - 1ull;
+    int out = 0, rej = 0;
+    for (int base = 0; base < nc; base += 64) {
+        const int i = base + lane;
+        const int c = i < nc ? cid[i] : 0;
+        const bool isk = i < nc && c < 0, isr = i < nc && c >= 0;
+        const u64 rm = __ballot(isr);
+        const bool take = isk || (isr && rej + __popcll(rm & below) < need);
+        const u64 tm = __ballot(take);
+        if (take) {
+            const int slot = out + __popcll(tm & below);
+            kept_id[slot] = isk ? ~c : c;
+            kept_d[slot] = cd[i];
+        }
+        out += __popcll(tm);
+        rej += __popcll(rm);
+    }
+    __builtin_amdgcn_wave_barrier();
+    return out;
+}
+
+// the selection of Hnsw::add (hnsw.cc:582-597) and of addFriendlevel's shrink (hnsw.h:283-289) by delaunay_type
+template <int SPACE, int W>
+__device__ __forceinline__ int select_neighbours(const HnswDeviceGraph& g, int* cid, const float* cd, int nc, int NN,
+                                                 int delaunay, float* qv, float* nd, int* kept_id, float* kept_d,
+                                                 int lane) {
+    if constexpr (W > 128) {
+        if (delaunay == 1) return heuristic1<SPACE>(g, cid, cd, nc, NN, qv, nd, kept_id, kept_d, lane);
+    }
+    return heuristic2<SPACE>(g, cid, cd, nc, NN, delaunay, qv, nd, kept_id, kept_d, lane);
+}
+
+template <int SPACE, int W>
 __global__ __launch_bounds__(64) void hnsw_build_select_kernel(BuildArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const HnswDeviceGraph& g = a.g;
     const int q = blockIdx.x, lane = threadIdx.x;
     const int qfloats = DistTraits<SPACE>::kU8 ? 32 : g.ldv;
     float* qv = reinterpret_cast<float*>(smem);                 // [ldv]
-    float* nd = qv + qfloats;                                   // [64]
-    int* kept_id = reinterpret_cast<int*>(nd + 64);             // [64]
-    float* kept_d = reinterpret_cast<float*>(kept_id + 64);     // [64]
-    int* lc_id = reinterpret_cast<int*>(kept_d + 64);           // [stride]
+    constexpr int KW = W / 2;                                   // the new node's list: M <= 62 (W = 128) or <= 127
+    float* nd = qv + qfloats;                                   // [KW]
+    int* kept_id = reinterpret_cast<int*>(nd + KW);             // [KW]
+    float* kept_d = reinterpret_cast<float*>(kept_id + KW);     // [KW]
+    int* lc_id = reinterpret_cast<int*>(kept_d + KW);           // [stride]
     float* lc_d = reinterpret_cast<float*>(lc_id + a.stride);   // [stride]
 
     const int p = a.pts[q];
@@ -164,16 +242,16 @@ __global__ __launch_bounds__(64) void hnsw_build_select_kernel(BuildArgs a) {
         nc = nc + nx < a.stride ? nc + nx : a.stride;
     }
     __builtin_amdgcn_wave_barrier();
-    const int nk = heuristic2<SPACE>(g, lc_id, lc_d, nc, a.M, a.delaunay, qv, nd, kept_id, kept_d, lane);
+    const int nk = select_neighbours<SPACE, W>(g, lc_id, lc_d, nc, a.M, a.delaunay, qv, nd, kept_id, kept_d, lane);
 
     // forward list of the new node: link() is called farthest first (hnsw.cc:597-601)
     int32_t* L = adj_list(a, p);
     if (lane == 0) L[0] = nk;
-    if (lane < nk) L[1 + lane] = kept_id[nk - 1 - lane];
-    // one reverse-link request per selected neighbour, in this node's own slots
-    if (lane < nk) {
-        a.req_key[(size_t)q * a.M + lane] = ((u64)(uint32_t)kept_id[lane] << 32) | (uint32_t)p;
-        a.req_dist[(size_t)q * a.M + lane] = kept_d[lane];
+    // + one reverse-link request per selected neighbour, in this node's own slots
+    for (int i = lane; i < nk; i += 64) {
+        L[1 + i] = kept_id[nk - 1 - i];
+        a.req_key[(size_t)q * a.M + i] = ((u64)(uint32_t)kept_id[i] << 32) | (uint32_t)p;
+        a.req_dist[(size_t)q * a.M + i] = kept_d[i];
     }
 }
 
@@ -260,13 +338,12 @@ __global__ void hnsw_build_heads_kernel(const u64* keys, int total, int32_t* act
     if (i == 0 || (uint32_t)(keys[i - 1] >> 32) != (uint32_t)(k >> 32)) active[atomicAdd(nactive, 1)] = i;
 }
 
-template <int SPACE>
+template <int SPACE, int W>   // W: list width = maxM0 friends + the new node (128: maxM0 <= 126; 256: maxM0 <= 254)
 __global__ __launch_bounds__(64) void hnsw_build_link_kernel(BuildArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const HnswDeviceGraph& g = a.g;
     const int lane = threadIdx.x;
     if ((int)blockIdx.x >= *a.nactive) return;
-    constexpr int W = 128;  // list width: maxM0 <= 126 friends + the new node
     const int qfloats = DistTraits<SPACE>::kU8 ? 32 : g.ldv;
     float* qv = reinterpret_cast<float*>(smem);                 // [ldv]
     float* nd = qv + qfloats;                                   // [W]
@@ -305,27 +382,31 @@ __global__ __launch_bounds__(64) void hnsw_build_link_kernel(BuildArgs a) {
         for (int i = lane; i < cnt; i += 64) td[i] = nd[i];
         if (lane == 0) {
             td[cnt] = dp;
-            fl[cnt] = p;   // (slot cnt <= 126 is free: the list is rebuilt below)
+            fl[cnt] = p;   // (slot cnt <= W - 2 is free: the list is rebuilt below)
         }
         __builtin_amdgcn_wave_barrier();
-        // rank sort by (distance, list position), up to two items per lane
-        const float da = lane < n1 ? td[lane] : INFINITY, db = lane + 64 < n1 ? td[lane + 64] : INFINITY;
-        int ra = 0, rb = 0;
+        // rank sort by (distance, list position), up to W / 64 items per lane
+        constexpr int E = W / 64;
+        float dv[E];
+        int rank[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+            dv[e] = lane + 64 * e < n1 ? td[lane + 64 * e] : INFINITY;
+            rank[e] = 0;
+        }
         for (int j = 0; j < n1; ++j) {
             const float dj = td[j];
-            ra += (dj < da || (dj == da && j < lane)) ? 1 : 0;
-            rb += (dj < db || (dj == db && j < lane + 64)) ? 1 : 0;
+#pragma unroll
+            for (int e = 0; e < E; ++e) rank[e] += (dj < dv[e] || (dj == dv[e] && j < lane + 64 * e)) ? 1 : 0;
         }
-        if (lane < n1) {
-            sc_id[ra] = fl[lane];
-            sc_d[ra] = da;
-        }
-        if (lane + 64 < n1) {
-            sc_id[rb] = fl[lane + 64];
-            sc_d[rb] = db;
-        }
+#pragma unroll
+        for (int e = 0; e < E; ++e)
+            if (lane + 64 * e < n1) {
+                sc_id[rank[e]] = fl[lane + 64 * e];
+                sc_d[rank[e]] = dv[e];
+            }
         __builtin_amdgcn_wave_barrier();
-        const int nk = heuristic2<SPACE>(g, sc_id, sc_d, n1, n1 - 1, a.delaunay, qv, nd, kept_id, kept_d, lane);
+        const int nk = select_neighbours<SPACE, W>(g, sc_id, sc_d, n1, n1 - 1, a.delaunay, qv, nd, kept_id, kept_d, lane);
         // refilled farthest first (hnsw.h:295-300)
         for (int i = lane; i < nk; i += 64) fl[i] = kept_id[nk - 1 - i];
         cnt = nk;
@@ -333,6 +414,113 @@ __global__ __launch_bounds__(64) void hnsw_build_link_kernel(BuildArgs a) {
     }
     if (lane == 0) L[0] = cnt;
     for (int i = lane; i < maxsz; i += 64) L[1 + i] = i < cnt ? fl[i] : 0;
+}
+
+// ---- post-processing (hnsw.cc:251-330) ------------------------------------------------------------------------------
+// Two graphs over the same rows: `first` built in insertion order, `second` in reverse order.  Every node but node 0
+// gets new level-0 friends from the union of its two lists (the second graph's entries, then the first graph's that
+// are not among them): post = 1 keeps the union whole, post = 2 ranks it again by (distance, position) and selects
+// maxM0 of it (delaunay_type 0: the closest; 1 and 2: heuristic 1), farthest first in the list.  One wave per node.
+struct PostArgs {
+    HnswDeviceGraph g;        // rows and distance
+    const int32_t* second;    // [n][maxM0 + 1]
+    const int32_t* first;     // [n][maxM0 + 1]
+    int32_t* out;             // [n][out_stride], cleared by the caller
+    int out_stride, maxM0, mode, delaunay;
+    int32_t* max_len;         // longest list written (post = 1 widens maxM0 to it), or NULL
+};
+
+constexpr int PW = 512;       // union of two lists of up to 254
+
+template <int SPACE>
+__global__ __launch_bounds__(64) void hnsw_build_post_kernel(PostArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const HnswDeviceGraph& g = a.g;
+    const int id = blockIdx.x, lane = threadIdx.x;
+    const int qfloats = DistTraits<SPACE>::kU8 ? 32 : g.ldv;
+    float* qv = reinterpret_cast<float*>(smem);                 // [ldv]
+    float* nd = qv + qfloats;                                   // [PW]
+    int* u_id = reinterpret_cast<int*>(nd + PW);                // [PW] the union
+    int* s_id = u_id + PW;                                      // [PW] the union, sorted
+    float* s_d = reinterpret_cast<float*>(s_id + PW);           // [PW]
+    int* kept_id = reinterpret_cast<int*>(s_d + PW);            // [PW / 2]
+    float* kept_d = reinterpret_cast<float*>(kept_id + PW / 2); // [PW / 2]
+
+    const int32_t* A = a.second + (size_t)id * (a.maxM0 + 1);
+    const int32_t* B = a.first + (size_t)id * (a.maxM0 + 1);
+    int32_t* O = a.out + (size_t)id * a.out_stride;
+    const u64 below = (1ull << lane) - 1ull;
+    const int na = A[0];
+    for (int i = lane; i < na; i += 64) u_id[i] = A[1 + i];
+    __builtin_amdgcn_wave_barrier();
+    int nu = na;
+    if (id != 0) {   // (node 0 keeps the second graph's list, hnsw.cc:281)
+        const int nb = B[0];
+        for (int base = 0; base < nb; base += 64) {
+            const int i = base + lane;
+            const int v = i < nb ? B[1 + i] : -1;
+            bool fresh = i < nb;
+            for (int j = 0; j < na; ++j) fresh &= u_id[j] != v;
+            const u64 fm = __ballot(fresh);
+            if (fresh) u_id[nu + __popcll(fm & below)] = v;
+            nu += __popcll(fm);
+        }
+        __builtin_amdgcn_wave_barrier();
+    }
+    if (a.mode == 1 || id == 0 || nu == 0) {
+        if (lane == 0) {
+            O[0] = nu;
+            if (a.max_len) atomicMax(a.max_len, nu);
+        }
+        for (int i = lane; i < nu; i += 64) O[1 + i] = u_id[i];
+        return;
+    }
+    int qnorm;
+    stage_row<SPACE>(g, id, qv, qnorm, lane);
+    frontier_distances<SPACE>(g, qv, reinterpret_cast<const uint8_t*>(qv), qnorm, u_id, nd, nu, lane);
+    __builtin_amdgcn_wave_barrier();
+    // rank sort by (distance, position in the union), up to PW / 64 items per lane
+    constexpr int E = PW / 64;
+    float dv[E];
+    int rk[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+        dv[e] = lane + 64 * e < nu ? nd[lane + 64 * e] : INFINITY;
+        rk[e] = 0;
+    }
+    for (int j = 0; j < nu; ++j) {
+        const float dj = nd[j];
+#pragma unroll
+        for (int e = 0; e < E; ++e) rk[e] += (dj < dv[e] || (dj == dv[e] && j < lane + 64 * e)) ? 1 : 0;
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e)
+        if (lane + 64 * e < nu) {
+            s_id[rk[e]] = u_id[lane + 64 * e];
+            s_d[rk[e]] = dv[e];
+        }
+    __builtin_amdgcn_wave_barrier();
+    const int NN = a.maxM0;
+    int nk;
+    const int* res = s_id;
+    if (a.delaunay == 0 || nu < NN) {
+        nk = nu < NN ? nu : NN;
+    } else {
+        nk = heuristic1<SPACE>(g, s_id, s_d, nu, NN, qv, nd, kept_id, kept_d, lane);
+        res = kept_id;
+    }
+    if (lane == 0) O[0] = nk;
+    for (int i = lane; i < nk; i += 64) O[1 + i] = res[nk - 1 - i];
+}
+
+// lists of stride sstride -> lists of stride dstride (post = 1: maxM0 becomes the longest union)
+__global__ void hnsw_build_repack_kernel(const int32_t* src, int sstride, int32_t* dst, int dstride, size_t total) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const size_t node = i / (size_t)dstride;
+    const int j = (int)(i - node * (size_t)dstride);
+    const int32_t* S = src + node * (size_t)sstride;
+    dst[i] = (j < sstride && j <= S[0]) ? S[j] : 0;
 }
 
 // start node of each (node, level) search = closest result of the same node's search one level up
@@ -353,8 +541,8 @@ hipError_t launch_hnsw_build_starts(const int32_t* src, const int32_t* cand_ids,
 }
 
 // ---------------------------------------------------------------------------------------
-template <typename Kern>
-static hipError_t launch_build(Kern kern, const BuildArgs& a, int grid, size_t lds, hipStream_t s) {
+template <typename Kern, typename Args>
+static hipError_t launch_build(Kern kern, const Args& a, int grid, size_t lds, hipStream_t s) {
     if (grid <= 0) return hipSuccess;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -363,19 +551,25 @@ static hipError_t launch_build(Kern kern, const BuildArgs& a, int grid, size_t l
     return hipGetLastError();
 }
 
-#define BUILD_DISPATCH(KERNEL, SPACEVAR, ARGS, GRID, LDS, STREAM)                                  \
-    switch (SPACEVAR) {                                                                            \
-        case SP_L2SQR: return launch_build(KERNEL<SP_L2SQR>, ARGS, GRID, LDS, STREAM);             \
-        case SP_L2: return launch_build(KERNEL<SP_L2>, ARGS, GRID, LDS, STREAM);                   \
-        case SP_L1: return launch_build(KERNEL<SP_L1>, ARGS, GRID, LDS, STREAM);                   \
-        case SP_LINF: return launch_build(KERNEL<SP_LINF>, ARGS, GRID, LDS, STREAM);               \
-        case SP_NORMCOS: return launch_build(KERNEL<SP_NORMCOS>, ARGS, GRID, LDS, STREAM);         \
-        case SP_COSINE: return launch_build(KERNEL<SP_COSINE>, ARGS, GRID, LDS, STREAM);           \
-        case SP_ANGULAR: return launch_build(KERNEL<SP_ANGULAR>, ARGS, GRID, LDS, STREAM);         \
-        case SP_NEGDOT: return launch_build(KERNEL<SP_NEGDOT>, ARGS, GRID, LDS, STREAM);           \
-        case SP_L2SQR_SIFT: return launch_build(KERNEL<SP_L2SQR_SIFT>, ARGS, GRID, LDS, STREAM);   \
-        default: return hipErrorInvalidValue;                                                      \
+#define BUILD_DISPATCH(KERNEL, SPACEVAR, ARGS, GRID, LDS, STREAM, ...)                                          \
+    switch (SPACEVAR) {                                                                                         \
+        case SP_L2SQR: return launch_build(KERNEL<SP_L2SQR __VA_ARGS__>, ARGS, GRID, LDS, STREAM);              \
+        case SP_L2: return launch_build(KERNEL<SP_L2 __VA_ARGS__>, ARGS, GRID, LDS, STREAM);                    \
+        case SP_L1: return launch_build(KERNEL<SP_L1 __VA_ARGS__>, ARGS, GRID, LDS, STREAM);                    \
+        case SP_LINF: return launch_build(KERNEL<SP_LINF __VA_ARGS__>, ARGS, GRID, LDS, STREAM);                \
+        case SP_NORMCOS: return launch_build(KERNEL<SP_NORMCOS __VA_ARGS__>, ARGS, GRID, LDS, STREAM);          \
+        case SP_COSINE: return launch_build(KERNEL<SP_COSINE __VA_ARGS__>, ARGS, GRID, LDS, STREAM);            \
+        case SP_ANGULAR: return launch_build(KERNEL<SP_ANGULAR __VA_ARGS__>, ARGS, GRID, LDS, STREAM);          \
+        case SP_NEGDOT: return launch_build(KERNEL<SP_NEGDOT __VA_ARGS__>, ARGS, GRID, LDS, STREAM);            \
+        case SP_L2SQR_SIFT: return launch_build(KERNEL<SP_L2SQR_SIFT __VA_ARGS__>, ARGS, GRID, LDS, STREAM);    \
+        default: return hipErrorInvalidValue;                                                                   \
     }
+#define COMMA ,
+
+// the W = 256 kernels: lists beyond two items per lane, and heuristic 1
+static bool wide_lists(const HnswBuildGraph& bg) {
+    return bg.M > 62 || bg.g.maxM > 62 || bg.g.maxM0 > 126 || bg.delaunay == 1;
+}
 
 static BuildArgs base_args(const HnswBuildGraph& bg, int level) {
     BuildArgs a{};
@@ -410,8 +604,13 @@ hipError_t launch_hnsw_build_select(const HnswBuildGraph& bg, int level, const i
     a.extra_d = const_cast<float*>(extra_d);
     a.extra_n = const_cast<int32_t*>(extra_n);
     const size_t qbytes = bg.g.space == SP_L2SQR_SIFT ? 128 : (size_t)bg.g.ldv * 4;
+    if (bg.M > 127) return hipErrorInvalidValue;
+    if (wide_lists(bg)) {
+        const size_t lds = qbytes + 3 * 128 * 4 + (size_t)stride * 8 + 16;
+        BUILD_DISPATCH(hnsw_build_select_kernel, bg.g.space, a, npts, lds, s, COMMA 256)
+    }
     const size_t lds = qbytes + 3 * 64 * 4 + (size_t)stride * 8 + 16;
-    BUILD_DISPATCH(hnsw_build_select_kernel, bg.g.space, a, npts, lds, s)
+    BUILD_DISPATCH(hnsw_build_select_kernel, bg.g.space, a, npts, lds, s, COMMA 128)
 }
 
 hipError_t launch_hnsw_build_mates(const HnswBuildGraph& bg, int level, const int32_t* pts, int npts,
@@ -467,8 +666,41 @@ hipError_t launch_hnsw_build_link(const HnswBuildGraph& bg, int level, const int
     a.req_dist = const_cast<float*>(dist_sorted);
     a.req_total = total;
     const size_t qbytes = bg.g.space == SP_L2SQR_SIFT ? 128 : (size_t)bg.g.ldv * 4;
+    if (bg.g.maxM > 254 || bg.g.maxM0 > 254) return hipErrorInvalidValue;
+    if (wide_lists(bg)) {
+        const size_t lds = qbytes + 7 * 256 * 4 + 16;
+        BUILD_DISPATCH(hnsw_build_link_kernel, bg.g.space, a, max_active, lds, s, COMMA 256)
+    }
     const size_t lds = qbytes + 7 * 128 * 4 + 16;
-    BUILD_DISPATCH(hnsw_build_link_kernel, bg.g.space, a, max_active, lds, s)
+    BUILD_DISPATCH(hnsw_build_link_kernel, bg.g.space, a, max_active, lds, s, COMMA 128)
+}
+
+hipError_t launch_hnsw_build_post(const HnswDeviceGraph& g, const int32_t* second, const int32_t* first, int maxM0,
+                                  int mode, int delaunay, int32_t* out, int out_stride, int32_t* max_len,
+                                  hipStream_t s) {
+    if (g.n <= 0) return hipSuccess;
+    if (maxM0 > 254 || out_stride < (mode == 1 ? 2 * maxM0 : maxM0) + 1) return hipErrorInvalidValue;
+    PostArgs a{};
+    a.g = g;
+    a.second = second;
+    a.first = first;
+    a.out = out;
+    a.out_stride = out_stride;
+    a.maxM0 = maxM0;
+    a.mode = mode;
+    a.delaunay = delaunay;
+    a.max_len = max_len;
+    const size_t qbytes = g.space == SP_L2SQR_SIFT ? 128 : (size_t)g.ldv * 4;
+    const size_t lds = qbytes + 5 * (size_t)PW * 4 + 16;
+    BUILD_DISPATCH(hnsw_build_post_kernel, g.space, a, g.n, lds, s)
+}
+
+hipError_t launch_hnsw_build_repack(const int32_t* src, int sstride, int32_t* dst, int dstride, int n, hipStream_t s) {
+    const size_t total = (size_t)n * (size_t)dstride;
+    if (total == 0) return hipSuccess;
+    hipLaunchKernelGGL(hnsw_build_repack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, sstride, dst,
+                       dstride, total);
+    return hipGetLastError();
 }
 
 }  // namespace gfxknn

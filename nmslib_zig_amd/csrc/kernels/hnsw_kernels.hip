@@ -307,9 +307,13 @@ __device__ __forceinline__ void hnsw_search_body(const HnswArgs& a, char* smem, 
             if (WIDE) {
                 // wide level-0 lists (maxM0 > 62, i.e. M >= 32): neighbours 63.. are list words 64.., read on demand in chunks
                 // of 64 (round 3: any number of chunks the frontier arrays hold -- a.nbcap)
+                // (construction mode above level 0, maxM > 62: the same walk over the node's list on that level)
+                const int32_t* Lc = a.level == 0 ? g.links0 + (size_t)c * (g.maxM0 + 1)
+                                                 : g.up_links + g.up_off[c] + (int64_t)(a.level - 1) * (g.maxM + 1);
+                const int Lmax = a.level == 0 ? g.maxM0 : g.maxM;
                 for (int c0 = 63; c0 < cntn; c0 += 64) {
                     int nb2 = 0;
-                    if (c0 + 1 + lane <= g.maxM0) nb2 = g.links0[(size_t)c * (g.maxM0 + 1) + c0 + 1 + lane];
+                    if (c0 + 1 + lane <= Lmax) nb2 = Lc[c0 + 1 + lane];
                     bool isn2 = false;
                     if (c0 + lane < cntn) isn2 = visit((uint32_t)nb2);
                     const u64 nmask2 = __ballot(isn2);

@@ -305,7 +305,8 @@ struct HnswBuildGraph {          // mutable twin of HnswDeviceGraph
 // starts[i] = first (closest) candidate of pair src[i] (src[i] < 0 or empty -> -1 = descend from the entry point)
 hipError_t launch_hnsw_build_starts(const int32_t* src, const int32_t* cand_ids, const int32_t* cand_n, int stride,
                                     int32_t* starts, int m, hipStream_t s);
-// Heuristic neighbour selection for the `npts` new nodes listed in pts at `level`: reads the sorted candidates
+// Heuristic neighbour selection (delaunay 2: heuristic 2, 1: heuristic 1, 0: the M closest; M <= 127, maxM0 <= 254)
+// for the `npts` new nodes listed in pts at `level`: reads the sorted candidates
 // (cand_ids/cand_d/cand_n, stride `stride`), writes each new node's forward list, and one reverse-link request per
 // selected neighbour into the node's own M slots: req_key [npts][M] = target << 32 | new node (unused: ~0), req_dist.
 hipError_t launch_hnsw_build_select(const HnswBuildGraph& bg, int level, const int32_t* pts, int npts,
@@ -327,6 +328,16 @@ hipError_t launch_hnsw_build_sort_requests(const unsigned long long* req_key, co
 hipError_t launch_hnsw_build_link(const HnswBuildGraph& bg, int level, const int32_t* active,
                                   const int32_t* nactive, int max_active, const unsigned long long* key_sorted,
                                   const float* dist_sorted, int total, hipStream_t s);
+// Post-processing (hnsw.cc:251-330) over the level-0 lists ([n][maxM0 + 1]) of the graph built in reverse order
+// (`second`) and the one built in insertion order (`first`), one wave per node: mode 1 writes the union (second's
+// entries, then first's new ones; out_stride >= 2 * maxM0 + 1), mode 2 the union ranked again and cut to maxM0
+// (delaunay 0: the closest, else heuristic 1), farthest first.  `out` must be cleared; max_len (or NULL) receives the
+// longest list by atomicMax.  maxM0 <= 254.
+hipError_t launch_hnsw_build_post(const HnswDeviceGraph& g, const int32_t* second, const int32_t* first, int maxM0,
+                                  int mode, int delaunay, int32_t* out, int out_stride, int32_t* max_len,
+                                  hipStream_t s);
+// lists of stride sstride copied into lists of stride dstride (unused slots 0)
+hipError_t launch_hnsw_build_repack(const int32_t* src, int sstride, int32_t* dst, int dstride, int n, hipStream_t s);
 
 // ---- range search on the brute-force index (range_kernels.hip) ----------------------------------
 // dist_ws[r] = the reference's distance of row r to the query, r < n

@@ -181,6 +181,7 @@ void Engine::upload_strings() {
 void Engine::build_string_graph() {
     const auto t0 = std::chrono::steady_clock::now();
     hnsw_build_strings(space_, st_ptr_.data(), st_bytes_.data(), st_words_.data(), ham_words(), ids_.size(), bp_, graph_);
+    graph_builder_ = 1;
     build_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
