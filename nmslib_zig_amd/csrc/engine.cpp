@@ -120,6 +120,21 @@ static int space_from_name(const std::string& s) {
     return -1;
 }
 
+// The divergences over dense float rows (include/factory/init_spaces.h:57-71): the Bregman family and Jensen-Shannon.
+static int diverg_space_from_name(const std::string& s) {
+    if (s == "kldivfast") return SP_KLDIV;
+    if (s == "kldivfastrq") return SP_KLDIV_RQ;
+    if (s == "kldivgenfast") return SP_KLDIVGEN;
+    if (s == "kldivgenfastrq") return SP_KLDIVGEN_RQ;
+    if (s == "kldivgenslow") return SP_KLDIVGEN_SLOW;
+    if (s == "itakurasaitofast") return SP_ITAKURASAITO;
+    if (s == "jsdivfast") return SP_JSDIV;
+    if (s == "jsdivslow") return SP_JSDIV_SLOW;
+    if (s == "jsmetrfast") return SP_JSMETR;
+    if (s == "jsmetrslow") return SP_JSMETR_SLOW;
+    return -1;
+}
+
 // Sparse spaces whose objects the reference's C ABI can build (SpaceSparseVectorSimpleStorage, nmslib_c.cpp:245-265):
 // include/space/space_sparse_scalar.h:32-35, include/space/space_sparse_lp.h.  lp_sparse needs its parameter p.
 static int sparse_space_from_name(const std::string& s, const std::vector<std::string>& space_params) {
@@ -149,7 +164,26 @@ static int sparse_space_from_name(const std::string& s, const std::vector<std::s
 Engine::Engine(const std::string& space, const std::string& method, int data_type, int dist_type,
                const std::vector<std::string>& space_params)
     : space_name_(space), method_name_(method) {
-    (void)dist_type;
+    if (space == "jsdivfastapprox" || space == "jsmetrfastapprox")
+        throw EngineError(Err::SpaceIncompatible,
+                          "space '" + space + "' is not served by the GPU engine: its table-lookup logarithm is not "
+                          "restated (Jensen-Shannon spaces: jsdivslow, jsdivfast, jsmetrslow, jsmetrfast)");
+    if (const int dsp = diverg_space_from_name(space); dsp >= 0) {
+        if (data_type != 0)
+            throw EngineError(Err::SpaceIncompatible, "divergence space '" + space + "' is served over dense float "
+                                                      "vectors only (data type 0)");
+        if (dist_type != 0)
+            throw EngineError(Err::SpaceIncompatible, "divergence space '" + space + "' is served with the float "
+                                                      "distance type");
+        if (method != "brute_force" && method != "seq_search")
+            throw EngineError(Err::SpaceIncompatible,
+                              "method '" + method + "' over divergence space '" + space + "' is not served: a graph over "
+                              "a non-symmetric divergence is not built (divergences: brute_force, seq_search)");
+        space_ = dsp;
+        diverg_ = true;
+        thread_pool_size = std::thread::hardware_concurrency();
+        return;
+    }
     if (data_type == 1) {
         const int ssp = sparse_space_from_name(space, space_params);
         if (ssp < 0)
@@ -188,7 +222,9 @@ Engine::Engine(const std::string& space, const std::string& method, int data_typ
     if (sp < 0)
         throw EngineError(Err::SpaceIncompatible,
                           "space '" + space + "' is not served by the GPU engine (dense spaces: l2, l1, linf, "
-                          "cosinesimil, angulardist, negdotprod, l2sqr_sift)");
+                          "cosinesimil, angulardist, negdotprod, l2sqr_sift; divergences: kldivfast, kldivfastrq, "
+                          "kldivgenfast, kldivgenfastrq, kldivgenslow, itakurasaitofast, jsdivslow, jsdivfast, "
+                          "jsmetrslow, jsmetrfast)");
     space_ = sp;
     // data_type: 0 dense float, 2 dense uint8 (nmslib_c.h:12-17)
     if (data_type != 0 && data_type != 2)
@@ -273,6 +309,8 @@ void Engine::stored_row(size_t pos, void* dst) const {
         std::memcpy(static_cast<char*>(dst) + 128, &s, 4);
     } else {
         std::memcpy(dst, &rows_f32_[pos * dim_], dim_ * 4);
+        // the "fast" divergence objects: the values, then their logarithms (CreateObjFromVect, space_bregman.cc:144-152)
+        if (diverg_stores_logs()) diverg_logs(&rows_f32_[pos * dim_], dim_, static_cast<float*>(dst) + dim_);
     }
 }
 
@@ -372,8 +410,8 @@ void Engine::create_index(const std::vector<std::string>& params) {
         ps.get("gpu_defer", defer);
         ps.get("gpu_shards", gpu_shards_);
         ps.check_unused();
-        if ((sparse_ || str_space_) && gpu_shards_ != -1 && gpu_shards_ != 1)
-            throw EngineError(Err::IndexBuildFailed, std::string(sparse_ ? "a sparse" : "a string") +
+        if ((sparse_ || str_space_ || diverg_) && gpu_shards_ != -1 && gpu_shards_ != 1)
+            throw EngineError(Err::IndexBuildFailed, std::string(sparse_ ? "a sparse" : str_space_ ? "a string" : "a divergence") +
                                                          " index runs on one GPU: gpu_shards=" +
                                                          std::to_string(gpu_shards_) + " is not supported");
     } else {
@@ -847,6 +885,11 @@ void Engine::finalize() {
         dirty_ = false;
         return;
     }
+    if (diverg_) {
+        upload_diverg();
+        dirty_ = false;
+        return;
+    }
     if (!parent_) {
         const int nsh = resolve_shards();
         if (nsh > 1) {
@@ -1195,6 +1238,10 @@ void Engine::knn_sharded(const void* d_queries, size_t nq, size_t elem_count, si
 void Engine::knn_device(const void* d_queries, size_t nq, size_t elem_count, size_t k, int32_t* d_ids,
                         float* d_dists, int32_t* d_cnt, hipStream_t stream) {
     if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
+    if (diverg_)
+        throw EngineError(Err::SpaceIncompatible, "the device-resident batch is not served over a divergence space: a "
+                                                  "query's logarithms are taken on the host, so divergence queries "
+                                                  "go through nmslib_knn_query_batch");
     if (dirty_) finalize();
     check_device();
     if (nq == 0) return;
@@ -1629,11 +1676,20 @@ void Engine::scan_slices(size_t nq, size_t k, int tq, const ResultBlock& out, co
     }
 }
 
+// the one place a divergence query's length is checked: the objects of a pair must be equally long
+static void check_diverg_query_length(size_t elem_count, size_t dim) {
+    if (elem_count != dim)
+        throw EngineError(Err::InvalidArgument, "query length " + std::to_string(elem_count) +
+                                                    " does not match the rows' length " + std::to_string(dim));
+}
+
 void Engine::knn_host(const void* queries, size_t nq, size_t elem_count, size_t k, const int32_t** ids, const float** dists,
                       const int32_t** cnt) {
     if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
+    if (diverg_ && !ids_.empty()) check_diverg_query_length(elem_count, dim_);  // refused before any device work
     if (dirty_) finalize();
     check_device();
+    if (diverg_) return knn_diverg_host(static_cast<const float*>(queries), nq, elem_count, k, ids, dists, cnt);
     const size_t qbytes = nq * elem_count * elem_bytes();
     // device: queries | ids | dists | counts in ONE block each way; host: one pinned block
     ws_q_.ensure(qbytes);
@@ -1680,9 +1736,11 @@ size_t Engine::range_select(bool two_dists, float r, size_t capacity, int32_t* i
 size_t Engine::range_host(const void* query, size_t elem_count, double radius, size_t capacity, int32_t* ids,
                           float* dists) {
     if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
+    if (diverg_ && !ids_.empty()) check_diverg_query_length(elem_count, dim_);  // refused before any device work
     if (dirty_) finalize();
     check_device();
     const size_t n = d_n_;
+    if (diverg_) return range_diverg_host(static_cast<const float*>(query), elem_count, radius, capacity, ids, dists);
     if (n == 0 || capacity == 0) return 0;
     if (elem_count != dim_) throw EngineError(Err::QueryExecutionFailed, "query dimension does not match the index");
     if (!shards_.empty()) {
@@ -1723,6 +1781,7 @@ float Engine::pair_distance(size_t p1, size_t p2) {
     // Space::IndexTimeDistance on the ORIGINAL rows (nmslib_c.cpp:1166), one wave on the GPU
     if (sparse_) return pair_distance_sparse(p1, p2);
     if (str_space_) return pair_distance_string(p1, p2);
+    if (diverg_) return pair_distance_diverg(p1, p2);
     check_device();
     const size_t rb = is_u8() ? 128 : (size_t)f32_row_stride((int)dim_) * 4;
     ws_pair_.ensure(2 * rb + 16);
@@ -1754,6 +1813,9 @@ void Engine::save(const std::string& path, bool save_data) {
     if (!created_) throw EngineError(Err::InvalidArgument, "Index not built");
     if (str_space_)  // SeqSearch has no SaveIndex (include/index.h:56-58); the object file is not written either
         throw EngineError(Err::DataIO, "SaveIndex is not implemented for method: Sequential search (string index; "
+                                       "the data file is not written)");
+    if (diverg_)  // SeqSearch has no SaveIndex (include/index.h:56-58); the object file is not written either
+        throw EngineError(Err::DataIO, "SaveIndex is not implemented for method: Sequential search (divergence index; "
                                        "the data file is not written)");
     if (sparse_)  // SeqSearch has no SaveIndex (include/index.h:56-58); the object file is not written either
         throw EngineError(Err::DataIO, "SaveIndex is not implemented for method: Sequential search (sparse index; "

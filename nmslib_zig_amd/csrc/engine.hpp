@@ -141,7 +141,8 @@ class Engine {
     size_t dim() const { return dim_; }
     size_t elem_bytes() const { return is_u8() ? 1 : 4; }
     size_t row_bytes() const { return dim_ * elem_bytes(); }
-    size_t stored_row_bytes() const { return is_u8() ? dim_ + 4 : dim_ * 4; }  // u8 rows carry their norm
+    // Object::datalength(): u8 rows carry their norm, the "fast" divergence objects their logarithms
+    size_t stored_row_bytes() const { return is_u8() ? dim_ + 4 : diverg_stores_logs() ? dim_ * 8 : dim_ * 4; }
 
     void add_row(const void* data, size_t elem_count, int32_t id);
     const void* host_row(size_t pos) const;
@@ -160,6 +161,12 @@ class Engine {
                          const int32_t** ids, const float** dists, const int32_t** cnt);
     size_t range_sparse_host(const SparseElem* query, size_t count, double radius, size_t capacity, int32_t* ids,
                              float* dists);
+
+    // ---- divergences over dense float rows (diverg.cpp): the KL family, Itakura-Saito, Jensen-Shannon ----
+    // rows enter through add_row; queries, range queries and pairs are routed here by knn_host / range_host /
+    // pair_distance
+    bool diverg_stores_logs() const;  // the reference's object is values + logarithms (2 * dim floats)
+    void diverg_logs(const float* x, size_t count, float* out) const;
 
     // ---- strings (data type 3; strings.cpp): leven and bit_hamming ----
     bool is_string() const { return str_space_; }
@@ -264,6 +271,13 @@ class Engine {
     float read_float(const float* d_out, const char* what);
     void upload_sparse();
     float pair_distance_sparse(size_t p1, size_t p2);
+    void upload_diverg();
+    DivergRows diverg_rows() const;
+    void knn_diverg_host(const float* queries, size_t nq, size_t elem_count, size_t k, const int32_t** ids,
+                         const float** dists, const int32_t** cnt);
+    size_t range_diverg_host(const float* query, size_t elem_count, double radius, size_t capacity, int32_t* ids,
+                             float* dists);
+    float pair_distance_diverg(size_t p1, size_t p2);
     void upload_strings();
     void build_string_graph();
     void knn_string_hnsw(const int64_t* d_qoff, const int32_t* d_qlen, const uint64_t* d_peq, const uint32_t* d_qw,
@@ -294,6 +308,7 @@ class Engine {
     std::vector<int32_t> ids_;
     std::vector<float> rows_f32_;
     std::vector<uint8_t> rows_u8_;
+    bool diverg_ = false;  // a divergence space: rows_f32_ on the host, values + logarithms in d_rows_
     // sparse rows: host CSR (get_data_point / borrow) and its copy in HBM after finalize
     bool sparse_ = false;
     std::vector<int64_t> sp_ptr_{0};

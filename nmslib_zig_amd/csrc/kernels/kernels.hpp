@@ -25,6 +25,18 @@ enum SpaceCode : int {
     // strings (data type 3)
     SP_LEVEN = 10,
     SP_BIT_HAMMING = 11,
+    // divergences over dense float rows (include/factory/init_spaces.h:57-71); SP_JSDIV / SP_JSMETR are the "fast"
+    // spaces, whose objects carry their logarithms
+    SP_KLDIV = 12,
+    SP_KLDIV_RQ = 13,
+    SP_KLDIVGEN = 14,
+    SP_KLDIVGEN_RQ = 15,
+    SP_KLDIVGEN_SLOW = 16,
+    SP_ITAKURASAITO = 17,
+    SP_JSDIV = 18,
+    SP_JSDIV_SLOW = 19,
+    SP_JSMETR = 20,
+    SP_JSMETR_SLOW = 21,
 };
 
 // ---- geometry shared by host and device ------------------------------------------------
@@ -479,6 +491,32 @@ struct StringHnswArgs {
 size_t string_hnsw_ws_words(const StringHnswArgs& a, bool old);
 // queries [q0, q0 + nq) of the batch; workspaces hold nq queries
 hipError_t launch_string_hnsw(const StringHnswArgs& a, bool old, int q0, int nq, hipStream_t s);
+
+// ---- divergences over dense float rows (diverg_kernels.hip) ------------------------------------
+// An object is its values and their logarithms (taken on the host), in groups of four elements, G = ceil(D / 4).
+// Rows: two planes of [ceil(n / 64)][G][64][4] floats (diverg_row_plane_floats): group g of row r at float
+// ((r / 64 * G + g) * 64 + r % 64) * 4.  Queries: planes of [G][stride][4] floats, group g of query q at
+// (g * stride + q) * 4; inv = 1 / value, read by the k-NN scan of SP_ITAKURASAITO only.
+constexpr int kDivergTileQ = 16;  // queries per workgroup of the k-NN scan (k small enough for 16 key buffers in LDS)
+inline int diverg_groups(int D) { return (D + 3) / 4; }
+inline size_t diverg_row_plane_floats(size_t n, int D) { return (n + 63) / 64 * (size_t)diverg_groups(D) * 256; }
+struct DivergRows {
+    const float *vals, *logs;
+    int n, D, G;
+};
+struct DivergQueries {
+    const float *vals, *logs, *inv;
+    int stride;  // queries per group
+};
+// queries [q0, q0 + p.nq) of the pack, which holds kDivergTileQ more queries than the batch (a tile reads past its
+// last query); per-(split, query) lists as for the sparse scan
+hipError_t launch_diverg_knn(int space, const ScanPlan& p, const DivergRows& rows, const DivergQueries& q, int q0,
+                             float* split_d, int32_t* split_pos, hipStream_t s);
+// query 0 of the pack: d_row_q[r] = distance(row r, query), d_q_row[r] = distance(query, row r)
+hipError_t launch_diverg_dist(int space, const DivergRows& rows, const DivergQueries& q, float* d_row_q, float* d_q_row,
+                              hipStream_t s);
+// *out = distance(object 0, object 1) of a pack with stride 2
+hipError_t launch_diverg_pair(int space, const DivergQueries& objs, int D, float* out, hipStream_t s);
 
 // ---- shard merge ---------------------------------------------------------------------------
 // shard s's lists start at dists_in + s*shard_stride / ids_in + s*shard_stride (elements)
