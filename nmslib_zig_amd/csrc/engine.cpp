@@ -775,6 +775,8 @@ void Engine::build_graph_gpu_pass(const std::vector<int32_t>& levels, bool rever
         bgraph.maxlevel = maxlevel;
         bgraph.enterpoint = enterpoint;
 
+        const HnswOut out{wb_cand_ids_.as<int32_t>(), wb_cand_d_.as<float>(), wb_cand_n_.as<int32_t>(), ws_ndc_.as<int32_t>(),
+                          ws_hops_.as<int32_t>(), ws_hops_up_.as<int32_t>(), wb_status_.as<int32_t>()};
         for (int attempt = 0; attempt < 2; ++attempt) {
             const bool force_bitset = attempt == 1;
             bool used_table = false;
@@ -786,19 +788,11 @@ void Engine::build_graph_gpu_pass(const std::vector<int32_t>& levels, bool rever
                           "build starts");
                 HnswSearchPlan p = hnsw_make_plan(bgraph, (int)m, efC, efC, force_bitset);
                 uint32_t* bitset = nullptr;
-                if (p.table_size == 0) {
-                    ws_bitset_.ensure(m * p.bitset_words * 4);
-                    hip_check(hipMemsetAsync(ws_bitset_.ptr(), 0, m * p.bitset_words * 4, s), "clear visited bitset");
-                    bitset = ws_bitset_.as<uint32_t>();
-                } else {
-                    used_table = true;
-                }
-                hip_check(launch_hnsw_search_ex(bgraph, p, nullptr, wb_pts_.as<int32_t>() + b0,
-                                                wb_starts_.as<int32_t>() + b0, l, bitset,
-                                                wb_cand_ids_.as<int32_t>() + b0 * efC, wb_cand_d_.as<float>() + b0 * efC,
-                                                wb_cand_n_.as<int32_t>() + b0, ws_ndc_.as<int32_t>() + b0,
-                                                ws_hops_.as<int32_t>() + b0, ws_hops_up_.as<int32_t>() + b0,
-                                                wb_status_.as<int32_t>() + b0, s),
+                if (p.table_size == 0) bitset = cleared_bitset(m, p.bitset_words, s);
+                else used_table = true;
+                hip_check(launch_hnsw_search(bgraph, p,
+                                             HnswQueries::stored(wb_pts_.as<int32_t>() + b0, wb_starts_.as<int32_t>() + b0, l),
+                                             bitset, HnswOverflow{}, out.at(b0, efC), s),
                           "build search");
             }
             if (!used_table) break;
@@ -1477,24 +1471,37 @@ void Engine::knn_brute(const void* d_queries, size_t nq, size_t k, int32_t* d_id
               "bf_rerank");
 }
 
+// The results and work counters of the current slice of a batch (knn_device sets ctr_off_): nq queries from d_ids /
+// d_dists / d_cnt on; the counts go to a workspace when the caller asks for none.
+HnswOut Engine::hnsw_out(int32_t* d_ids, float* d_dists, int32_t* d_cnt, size_t nq) {
+    if (!d_cnt) {
+        ws_outcnt_.ensure(nq * 4);
+        d_cnt = ws_outcnt_.as<int32_t>();
+    }
+    return {d_ids, d_dists, d_cnt, ws_ndc_.as<int32_t>() + ctr_off_, ws_hops_.as<int32_t>() + ctr_off_,
+            ws_hops_up_.as<int32_t>() + ctr_off_, ws_status_.as<int32_t>() + ctr_off_};
+}
+
+// m visited bitsets of `words` words each in ws_bitset_, cleared on the stream
+uint32_t* Engine::cleared_bitset(size_t m, size_t words, hipStream_t stream) {
+    ws_bitset_.ensure(m * words * 4);
+    hip_check(hipMemsetAsync(ws_bitset_.ptr(), 0, m * words * 4, stream), "clear visited bitset");
+    return ws_bitset_.as<uint32_t>();
+}
+
 void Engine::knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
                       hipStream_t stream) {
     const int ef = ef_;
     last_path = 4;
     hnsw_fix_valid_ = false;
-    // Hnsw::Search, hnsw.cc:724: algoType=old, or hybrid with ef >= 1000, runs SearchOld
-    if (algo_ == "old" || (algo_ == "hybrid" && ef >= 1000)) {
+    if (search_old()) {
         knn_hnsw_old(d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
         return;
     }
+    const HnswOut out = hnsw_out(d_ids, d_dists, d_cnt, nq);
     if (std::max<size_t>(ef, k) > 1024 || hnsw_nbcap(dg_) > HNSW_NBCAP_LDS) {
         // beyond the LDS kernels' sorted array, or adjacency lists longer than their frontier arrays (maxM0 > 254): the
         // same algorithm with the array in HBM and lists walked in chunks (slices of bounded workspace)
-        int32_t* cnt2 = d_cnt;
-        if (!cnt2) {
-            ws_outcnt_.ensure(nq * 4);
-            cnt2 = ws_outcnt_.as<int32_t>();
-        }
         const size_t cap = std::max<size_t>(ef, k), words = (d_n_ + 31) / 32;
         const size_t per_q = cap * 8 + words * 4;
         const size_t slice = std::max<size_t>(1, std::min<size_t>(nq, ((size_t)4 << 30) / per_q));
@@ -1504,37 +1511,22 @@ void Engine::knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids
             const size_t m = std::min(slice, nq - q0);
             ws_old_a_.ensure(m * cap * 4);
             ws_old_r_.ensure(m * cap * 4);
-            ws_bitset_.ensure(m * words * 4);
-            hip_check(hipMemsetAsync(ws_bitset_.ptr(), 0, m * words * 4, stream), "clear visited bitset");
+            uint32_t* bitset = cleared_bitset(m, words, stream);
             if (q0 == 0) prof_begin(stream);
             hip_check(launch_hnsw_search_big(dg_, (int)m, (int)k, ef, static_cast<const char*>(d_queries) + q0 * qbytes,
-                                             ws_bitset_.as<uint32_t>(), ws_old_a_.as<float>(), ws_old_r_.as<int32_t>(),
-                                             d_ids + q0 * k, d_dists + q0 * k, cnt2 + q0, ws_ndc_.as<int32_t>() + ctr_off_ + q0,
-                                             ws_hops_.as<int32_t>() + ctr_off_ + q0, ws_hops_up_.as<int32_t>() + ctr_off_ + q0,
-                                             ws_status_.as<int32_t>() + ctr_off_ + q0, stream),
+                                             bitset, ws_old_a_.as<float>(), ws_old_r_.as<int32_t>(), out.at(q0, k), stream),
                       "hnsw_search(big)");
             if (q0 + slice >= nq) prof_end(stream);
         }
         return;
     }
-    int32_t* cnt = d_cnt;
-    if (!cnt) {
-        ws_outcnt_.ensure(nq * 4);
-        cnt = ws_outcnt_.as<int32_t>();
-    }
-    int32_t* ndc = ws_ndc_.as<int32_t>() + ctr_off_;
-    int32_t* hops = ws_hops_.as<int32_t>() + ctr_off_;
-    int32_t* hops_up = ws_hops_up_.as<int32_t>() + ctr_off_;
-    int32_t* status = ws_status_.as<int32_t>() + ctr_off_;
+    const HnswQueries queries = HnswQueries::external(d_queries);
     HnswSearchPlan p = hnsw_make_plan(dg_, (int)nq, (int)k, ef, false);
     have_counters_ = true;
     if (p.table_size == 0) {
-        ws_bitset_.ensure(nq * p.bitset_words * 4);
-        hip_check(hipMemsetAsync(ws_bitset_.ptr(), 0, nq * p.bitset_words * 4, stream), "clear visited bitset");
+        uint32_t* bitset = cleared_bitset(nq, p.bitset_words, stream);
         prof_begin(stream);
-        hip_check(launch_hnsw_search(dg_, p, d_queries, ws_bitset_.as<uint32_t>(), d_ids, d_dists, cnt, ndc, hops, hops_up,
-                                     status, stream),
-                  "hnsw_search");
+        hip_check(launch_hnsw_search(dg_, p, queries, bitset, HnswOverflow{}, out, stream), "hnsw_search");
         prof_end(stream);
         return;
     }
@@ -1544,18 +1536,17 @@ void Engine::knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids
     const int fix_slots = (int)std::min<size_t>(nq, 128);
     HnswSearchPlan pb = hnsw_make_plan(dg_, (int)nq, (int)k, ef, true);
     ws_fix_.ensure((nq + 16) * 4);
+    // (not cleared_bitset: the workgroups that walk the list clear their own slot on the device)
     ws_bitset_.ensure((size_t)fix_slots * pb.bitset_words * 4);
     int32_t* fix_count = ws_fix_.as<int32_t>();
     int32_t* fix_list = fix_count + 16;
     hip_check(hipMemsetAsync(fix_count, 0, 4, stream), "clear overflow count");
     hnsw_fix_valid_ = true;
     prof_begin(stream);
-    hip_check(launch_hnsw_search_fix(dg_, p, d_queries, nullptr, 0, fix_list, fix_count, d_ids, d_dists, cnt, ndc, hops,
-                                     hops_up, status, stream),
-              "hnsw_search");
+    hip_check(launch_hnsw_search(dg_, p, queries, nullptr, HnswOverflow{0, fix_list, fix_count}, out, stream), "hnsw_search");
     prof_end(stream);
-    hip_check(launch_hnsw_search_fix(dg_, pb, d_queries, ws_bitset_.as<uint32_t>(), fix_slots, fix_list, fix_count, d_ids,
-                                     d_dists, cnt, ndc, hops, hops_up, status, stream),
+    hip_check(launch_hnsw_search(dg_, pb, queries, ws_bitset_.as<uint32_t>(), HnswOverflow{fix_slots, fix_list, fix_count},
+                                 out, stream),
               "hnsw_search(bitset)");
 }
 
@@ -1564,13 +1555,8 @@ void Engine::knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids
 void Engine::knn_hnsw_old(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
                           hipStream_t stream) {
     const int ef = ef_;
-    int32_t* cnt = d_cnt;
-    if (!cnt) {
-        ws_outcnt_.ensure(nq * 4);
-        cnt = ws_outcnt_.as<int32_t>();
-    }
+    const HnswOut out = hnsw_out(d_ids, d_dists, d_cnt, nq);
     const size_t qbytes = dim_ * elem_bytes();
-    const size_t co = ctr_off_;
     bool force_bitset = false;
     int heap_cap = 0;
     std::vector<int32_t> status(nq);
@@ -1582,27 +1568,19 @@ void Engine::knn_hnsw_old(const void* d_queries, size_t nq, size_t k, int32_t* d
         for (size_t q0 = 0; q0 < nq; q0 += slice) {
             const size_t m = std::min(slice, nq - q0);
             HnswSearchPlan p = hnsw_make_plan_old(dg_, (int)m, (int)k, ef, force_bitset, heap_cap);
-            uint32_t* bitset = nullptr;
-            if (p.table_size == 0) {
-                ws_bitset_.ensure(m * p.bitset_words * 4);
-                hip_check(hipMemsetAsync(ws_bitset_.ptr(), 0, m * p.bitset_words * 4, stream), "clear visited bitset");
-                bitset = ws_bitset_.as<uint32_t>();
-            }
+            uint32_t* bitset = p.table_size == 0 ? cleared_bitset(m, p.bitset_words, stream) : nullptr;
             ws_old_a_.ensure(std::max<size_t>(16, m * hnsw_old_ws_a(p)));
             ws_old_r_.ensure(std::max<size_t>(16, m * hnsw_old_ws_r(p)));
             ws_old_heap_.ensure(std::max<size_t>(16, m * hnsw_old_ws_heap(p)));
             if (q0 == 0) prof_begin(stream);  // all slices of one attempt are one timed interval
             hip_check(launch_hnsw_search_old(dg_, p, static_cast<const char*>(d_queries) + q0 * qbytes, bitset,
-                                             ws_old_a_.ptr(), ws_old_r_.ptr(), ws_old_heap_.ptr(), d_ids + q0 * k,
-                                             d_dists + q0 * k, cnt + q0, ws_ndc_.as<int32_t>() + co + q0,
-                                             ws_hops_.as<int32_t>() + co + q0, ws_hops_up_.as<int32_t>() + co + q0,
-                                             ws_status_.as<int32_t>() + co + q0, stream),
+                                             ws_old_a_.ptr(), ws_old_r_.ptr(), ws_old_heap_.ptr(), out.at(q0, k), stream),
                       "hnsw_search_old");
             if (q0 + slice >= nq) prof_end(stream);
         }
         have_counters_ = true;
         // status 1: the LDS visited table filled up -> HBM bitsets; status 2: the candidate heap outgrew its bound
-        hip_check(hipMemcpyAsync(status.data(), ws_status_.as<int32_t>() + co, nq * 4, hipMemcpyDeviceToHost, stream), "status");
+        hip_check(hipMemcpyAsync(status.data(), out.status, nq * 4, hipMemcpyDeviceToHost, stream), "status");
         hip_check(hipStreamSynchronize(stream), "hnsw_search_old");
         bool any1 = false, any2 = false;
         for (int32_t v : status) {

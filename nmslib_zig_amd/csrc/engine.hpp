@@ -300,6 +300,10 @@ class Engine {
                   int32_t* d_cnt, hipStream_t stream);
     void knn_hnsw_old(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
                       int32_t* d_cnt, hipStream_t stream);
+    // Hnsw::Search, hnsw.cc:724: algoType=old, or hybrid with ef >= 1000, runs SearchOld
+    bool search_old() const { return algo_ == "old" || (algo_ == "hybrid" && ef_ >= 1000); }
+    HnswOut hnsw_out(int32_t* d_ids, float* d_dists, int32_t* d_cnt, size_t nq);
+    uint32_t* cleared_bitset(size_t m, size_t words, hipStream_t stream);
 
     std::string space_name_, method_name_;
     int space_ = SP_L2;

@@ -551,21 +551,6 @@ static hipError_t launch_build(Kern kern, const Args& a, int grid, size_t lds, h
     return hipGetLastError();
 }
 
-#define BUILD_DISPATCH(KERNEL, SPACEVAR, ARGS, GRID, LDS, STREAM, ...)                                          \
-    switch (SPACEVAR) {                                                                                         \
-        case SP_L2SQR: return launch_build(KERNEL<SP_L2SQR __VA_ARGS__>, ARGS, GRID, LDS, STREAM);              \
-        case SP_L2: return launch_build(KERNEL<SP_L2 __VA_ARGS__>, ARGS, GRID, LDS, STREAM);                    \
-        case SP_L1: return launch_build(KERNEL<SP_L1 __VA_ARGS__>, ARGS, GRID, LDS, STREAM);                    \
-        case SP_LINF: return launch_build(KERNEL<SP_LINF __VA_ARGS__>, ARGS, GRID, LDS, STREAM);                \
-        case SP_NORMCOS: return launch_build(KERNEL<SP_NORMCOS __VA_ARGS__>, ARGS, GRID, LDS, STREAM);          \
-        case SP_COSINE: return launch_build(KERNEL<SP_COSINE __VA_ARGS__>, ARGS, GRID, LDS, STREAM);            \
-        case SP_ANGULAR: return launch_build(KERNEL<SP_ANGULAR __VA_ARGS__>, ARGS, GRID, LDS, STREAM);          \
-        case SP_NEGDOT: return launch_build(KERNEL<SP_NEGDOT __VA_ARGS__>, ARGS, GRID, LDS, STREAM);            \
-        case SP_L2SQR_SIFT: return launch_build(KERNEL<SP_L2SQR_SIFT __VA_ARGS__>, ARGS, GRID, LDS, STREAM);    \
-        default: return hipErrorInvalidValue;                                                                   \
-    }
-#define COMMA ,
-
 // the W = 256 kernels: lists beyond two items per lane, and heuristic 1
 static bool wide_lists(const HnswBuildGraph& bg) {
     return bg.M > 62 || bg.g.maxM > 62 || bg.g.maxM0 > 126 || bg.delaunay == 1;
@@ -607,10 +592,14 @@ hipError_t launch_hnsw_build_select(const HnswBuildGraph& bg, int level, const i
     if (bg.M > 127) return hipErrorInvalidValue;
     if (wide_lists(bg)) {
         const size_t lds = qbytes + 3 * 128 * 4 + (size_t)stride * 8 + 16;
-        BUILD_DISPATCH(hnsw_build_select_kernel, bg.g.space, a, npts, lds, s, COMMA 256)
+        return hnsw_dispatch_space(bg.g.space, [&](auto sp) {
+            return launch_build(hnsw_build_select_kernel<sp.value, 256>, a, npts, lds, s);
+        });
     }
     const size_t lds = qbytes + 3 * 64 * 4 + (size_t)stride * 8 + 16;
-    BUILD_DISPATCH(hnsw_build_select_kernel, bg.g.space, a, npts, lds, s, COMMA 128)
+    return hnsw_dispatch_space(bg.g.space, [&](auto sp) {
+        return launch_build(hnsw_build_select_kernel<sp.value, 128>, a, npts, lds, s);
+    });
 }
 
 hipError_t launch_hnsw_build_mates(const HnswBuildGraph& bg, int level, const int32_t* pts, int npts,
@@ -628,7 +617,9 @@ hipError_t launch_hnsw_build_mates(const HnswBuildGraph& bg, int level, const in
     a.extra_n = extra_n;
     const size_t qbytes = bg.g.space == SP_L2SQR_SIFT ? 128 : (size_t)bg.g.ldv * 4;
     const size_t lds = qbytes + 2 * 32 * 4 + 4 * (size_t)(XCAP + 32) * 4 + 16;
-    BUILD_DISPATCH(hnsw_build_mates_kernel, bg.g.space, a, npts, lds, s)
+    return hnsw_dispatch_space(bg.g.space, [&](auto sp) {
+        return launch_build(hnsw_build_mates_kernel<sp.value>, a, npts, lds, s);
+    });
 }
 
 size_t hnsw_build_sort_temp_bytes(int max_requests, int n) {
@@ -669,10 +660,14 @@ hipError_t launch_hnsw_build_link(const HnswBuildGraph& bg, int level, const int
     if (bg.g.maxM > 254 || bg.g.maxM0 > 254) return hipErrorInvalidValue;
     if (wide_lists(bg)) {
         const size_t lds = qbytes + 7 * 256 * 4 + 16;
-        BUILD_DISPATCH(hnsw_build_link_kernel, bg.g.space, a, max_active, lds, s, COMMA 256)
+        return hnsw_dispatch_space(bg.g.space, [&](auto sp) {
+            return launch_build(hnsw_build_link_kernel<sp.value, 256>, a, max_active, lds, s);
+        });
     }
     const size_t lds = qbytes + 7 * 128 * 4 + 16;
-    BUILD_DISPATCH(hnsw_build_link_kernel, bg.g.space, a, max_active, lds, s, COMMA 128)
+    return hnsw_dispatch_space(bg.g.space, [&](auto sp) {
+        return launch_build(hnsw_build_link_kernel<sp.value, 128>, a, max_active, lds, s);
+    });
 }
 
 hipError_t launch_hnsw_build_post(const HnswDeviceGraph& g, const int32_t* second, const int32_t* first, int maxM0,
@@ -692,7 +687,9 @@ hipError_t launch_hnsw_build_post(const HnswDeviceGraph& g, const int32_t* secon
     a.max_len = max_len;
     const size_t qbytes = g.space == SP_L2SQR_SIFT ? 128 : (size_t)g.ldv * 4;
     const size_t lds = qbytes + 5 * (size_t)PW * 4 + 16;
-    BUILD_DISPATCH(hnsw_build_post_kernel, g.space, a, g.n, lds, s)
+    return hnsw_dispatch_space(g.space, [&](auto sp) {
+        return launch_build(hnsw_build_post_kernel<sp.value>, a, g.n, lds, s);
+    });
 }
 
 hipError_t launch_hnsw_build_repack(const int32_t* src, int sstride, int32_t* dst, int dstride, int n, hipStream_t s) {

@@ -1,8 +1,28 @@
 // Device helpers shared by the HNSW search and construction kernels (wave64).
 #pragma once
+#include <type_traits>
+
 #include "common_dev.hpp"
 
 namespace gfxknn {
+
+// Host side: the space code of a graph as a compile-time constant.  f takes std::integral_constant<int, SP_...> and is
+// instantiated for each of the nine spaces an HNSW graph can have; any other code is an invalid value.
+template <class F>
+static hipError_t hnsw_dispatch_space(int space, F&& f) {
+    switch (space) {
+        case SP_L2SQR: return f(std::integral_constant<int, SP_L2SQR>{});
+        case SP_L2: return f(std::integral_constant<int, SP_L2>{});
+        case SP_L1: return f(std::integral_constant<int, SP_L1>{});
+        case SP_LINF: return f(std::integral_constant<int, SP_LINF>{});
+        case SP_NORMCOS: return f(std::integral_constant<int, SP_NORMCOS>{});
+        case SP_COSINE: return f(std::integral_constant<int, SP_COSINE>{});
+        case SP_ANGULAR: return f(std::integral_constant<int, SP_ANGULAR>{});
+        case SP_NEGDOT: return f(std::integral_constant<int, SP_NEGDOT>{});
+        case SP_L2SQR_SIFT: return f(std::integral_constant<int, SP_L2SQR_SIFT>{});
+        default: return hipErrorInvalidValue;
+    }
+}
 
 template <int SPACE>
 struct DistTraits {

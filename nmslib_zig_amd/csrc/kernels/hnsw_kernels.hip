@@ -1316,38 +1316,31 @@ __global__ __launch_bounds__(64) void hnsw_search_big_kernel(HnswArgs a, float* 
 // ---------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------
-static int ilog2(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return l;
-}
-
-HnswSearchPlan hnsw_make_plan(const HnswDeviceGraph& g, int nq, int k, int ef, bool force_bitset) {
-    HnswSearchPlan p{};
-    p.nq = nq;
-    p.k = k;
-    p.ef = ef;
-    p.cap = ef > k ? ef : k;
-    const bool u8 = g.space == SP_L2SQR_SIFT;
-    const size_t fixed = (size_t)((p.cap + 3) & ~3) * 8 + (u8 ? 128 : (size_t)g.ldv * 4) + (size_t)(2 * hnsw_nbcap(g) + 2 * 64) * 4;
-    // expected visited nodes ~ (maxM0 * expansions); expansions ~ ef.  Size the table for 2x that
-    // and never let LDS push residency below 4 waves per CU (160 KB / 4).
-    int want = 1 << ilog2((g.maxM0 > 0 ? g.maxM0 : 32) * p.cap * 2);
-    if (want < 2048) want = 2048;
-    const size_t budget = 40 * 1024 - 64;
-    while ((size_t)want * 4 + fixed > budget && want > 2048) want >>= 1;
-    // ~18 distance evaluations per unit of ef on 1M-row graphs: beyond half load
-    // the exact hash set is replaced by a per-query bitset in HBM
-    if (force_bitset || 18 * p.cap > want / 2 || (size_t)want * 4 + fixed > 64 * 1024) {
-        p.table_size = 0;
-        p.bitset_words = ((size_t)g.n + 31) / 32;
-        p.lds_bytes = fixed + 16;
-    } else {
-        p.table_size = want;
-        p.bitset_words = 0;
-        p.lds_bytes = fixed + (size_t)want * 4;
-    }
-    return p;
+// What every search kernel reads: the graph, the queries, the visited bitset and where the results go.  Each launch entry
+// adds what is its own (LDS carve-up, visited table, overflow list, diagnostics).
+static HnswArgs hnsw_args(const HnswDeviceGraph& g, int nq, int k, int ef, int cap, const HnswQueries& q, uint32_t* bitset,
+                          size_t bitset_words, const HnswOut& out) {
+    HnswArgs a{};
+    a.g = g;
+    a.nbcap = hnsw_nbcap(g);
+    a.queries = q.queries;
+    a.query_rows = q.query_rows;
+    a.start_nodes = q.start_nodes;
+    a.level = q.level;
+    a.bitset = bitset;
+    a.bitset_words = bitset_words;
+    a.out_ids = out.ids;
+    a.out_dists = out.dists;
+    a.out_cnt = out.cnt;
+    a.out_ndc = out.ndc;
+    a.out_hops = out.hops;
+    a.out_hops_up = out.hops_up;
+    a.status = out.status;
+    a.nq = nq;
+    a.k = k;
+    a.ef = ef;
+    a.cap = cap;
+    return a;
 }
 
 template <int SPACE, int EMAX, bool WIDE>
@@ -1398,141 +1391,50 @@ static hipError_t launch_space(const HnswArgs& a, const HnswSearchPlan& p, hipSt
     return launch_space_e<SPACE, SA_EMAX_MAX>(a, p, s);
 }
 
-// overflow-list arguments of the launch in progress on this thread (launch_hnsw_search_fix)
-static thread_local int32_t* t_fix_list = nullptr;
-static thread_local int32_t* t_fix_count = nullptr;
-static thread_local int t_fix_mode = 0;
-
-hipError_t launch_hnsw_search_ex(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries,
-                                 const int32_t* query_rows, const int32_t* start_nodes, int level,
-                              uint32_t* bitset, int32_t* out_ids, float* out_dists, int32_t* out_cnt,
-                              int32_t* out_ndc, int32_t* out_hops, int32_t* out_hops_up,
-                              int32_t* status, hipStream_t s) {
-    if (p.nq == 0) return hipSuccess;
-    if (p.cap > 64 * SA_EMAX_MAX || hnsw_nbcap(g) > HNSW_NBCAP_LDS) return hipErrorInvalidValue;
-    HnswArgs a{};
-    a.g = g;
-    a.nbcap = hnsw_nbcap(g);
-    a.queries = queries;
-    a.query_rows = query_rows;
-    a.start_nodes = start_nodes;
-    a.level = level;
-    a.bitset = bitset;
-    a.bitset_words = p.bitset_words;
-    a.out_ids = out_ids;
-    a.out_dists = out_dists;
-    a.out_cnt = out_cnt;
-    a.out_ndc = out_ndc;
-    a.out_hops = out_hops;
-    a.out_hops_up = out_hops_up;
-    a.status = status;
-    a.fix_list = t_fix_list;
-    a.fix_count = t_fix_count;
-    a.fix_mode = (p.table_size == 0) ? t_fix_mode : 0;
-    a.no_pipe = getenv("NMSLIB_HNSW_PIPE") ? atoi(getenv("NMSLIB_HNSW_PIPE")) == 0 : 0;
-    static const int prof = getenv("NMSLIB_HNSW_PROF") ? atoi(getenv("NMSLIB_HNSW_PROF")) : 0;
-    a.prof = (prof && !query_rows) ? 1 : 0;
-    a.nq = p.nq;
-    a.k = p.k;
-    a.ef = p.ef;
-    a.cap = p.cap;
-    a.capa = (p.cap + 3) & ~3;
-    a.table_size = p.table_size;
-    a.table_shift = p.table_size ? 32 - ilog2(p.table_size) : 0;
-    if (a.prof) {
-        hipError_t pe = hipErrorInvalidValue;
-        if (g.space == SP_L2SQR) pe = launch_space<SP_L2SQR>(a, p, s);
-        else if (g.space == SP_NORMCOS) pe = launch_space<SP_NORMCOS>(a, p, s);
-        unsigned long long h[8] = {0};
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_hnsw_prof), sizeof(h));
-        unsigned long long z[8] = {0};
-        (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hnsw_prof), z, sizeof(z));
-        const double w = h[6] ? (double)h[6] : 1.0;
-        if (h[6])
-            fprintf(stderr, "[hnsw_search] cycles/query: descent %.0f pick+adj %.0f visited %.0f gather %.0f accept %.0f insert %.0f\n",
-                    h[0] / w, h[1] / w, h[2] / w, h[3] / w, h[4] / w, h[5] / w);
-        unsigned long long hm[12] = {0};
-        hnsw_mw_read_prof(hm);
-        if (hm[6]) {
-            const double wq = (double)hm[6];
-            fprintf(stderr, "[hnsw_search_mw] control-wave cycles/query: descent %.0f pick %.0f slow-pick %.0f wait %.0f accept %.0f name-next %.0f probe %.0f list+barrierA %.0f merge %.0f  (mispredicted %llu of %llu)\n",
-                    hm[0] / wq, hm[1] / wq, hm[2] / wq, hm[3] / wq, hm[8] / wq, hm[9] / wq, hm[10] / wq, hm[11] / wq, hm[5] / wq,
-                    hm[7], hm[6]);
-        }
-        return pe;
-    }
-    switch (g.space) {
-        case SP_L2SQR: return launch_space<SP_L2SQR>(a, p, s);
-        case SP_L2: return launch_space<SP_L2>(a, p, s);
-        case SP_L1: return launch_space<SP_L1>(a, p, s);
-        case SP_LINF: return launch_space<SP_LINF>(a, p, s);
-        case SP_NORMCOS: return launch_space<SP_NORMCOS>(a, p, s);
-        case SP_COSINE: return launch_space<SP_COSINE>(a, p, s);
-        case SP_ANGULAR: return launch_space<SP_ANGULAR>(a, p, s);
-        case SP_NEGDOT: return launch_space<SP_NEGDOT>(a, p, s);
-        case SP_L2SQR_SIFT: return launch_space<SP_L2SQR_SIFT>(a, p, s);
-        default: return hipErrorInvalidValue;
+// NMSLIB_HNSW_PROF: waits for the launch, prints the cycles per query of each phase of both kernels and clears them
+static void hnsw_print_prof(hipStream_t s) {
+    unsigned long long h[8] = {0};
+    (void)hipStreamSynchronize(s);
+    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_hnsw_prof), sizeof(h));
+    unsigned long long z[8] = {0};
+    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_hnsw_prof), z, sizeof(z));
+    const double w = h[6] ? (double)h[6] : 1.0;
+    if (h[6])
+        fprintf(stderr, "[hnsw_search] cycles/query: descent %.0f pick+adj %.0f visited %.0f gather %.0f accept %.0f insert %.0f\n",
+                h[0] / w, h[1] / w, h[2] / w, h[3] / w, h[4] / w, h[5] / w);
+    unsigned long long hm[12] = {0};
+    hnsw_mw_read_prof(hm);
+    if (hm[6]) {
+        const double wq = (double)hm[6];
+        fprintf(stderr, "[hnsw_search_mw] control-wave cycles/query: descent %.0f pick %.0f slow-pick %.0f wait %.0f accept %.0f name-next %.0f probe %.0f list+barrierA %.0f merge %.0f  (mispredicted %llu of %llu)\n",
+                hm[0] / wq, hm[1] / wq, hm[2] / wq, hm[3] / wq, hm[8] / wq, hm[9] / wq, hm[10] / wq, hm[11] / wq, hm[5] / wq,
+                hm[7], hm[6]);
     }
 }
 
-hipError_t launch_hnsw_search_fix(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries,
-                                  uint32_t* bitset, int fix_slots, int32_t* fix_list, int32_t* fix_count,
-                                  int32_t* out_ids, float* out_dists, int32_t* out_cnt, int32_t* out_ndc,
-                                  int32_t* out_hops, int32_t* out_hops_up, int32_t* status, hipStream_t s) {
-    t_fix_list = fix_list;
-    t_fix_count = fix_count;
-    t_fix_mode = fix_slots;
-    const hipError_t e = launch_hnsw_search_ex(g, p, queries, nullptr, nullptr, 0, bitset, out_ids, out_dists, out_cnt,
-                                               out_ndc, out_hops, out_hops_up, status, s);
-    t_fix_list = nullptr;
-    t_fix_count = nullptr;
-    t_fix_mode = 0;
+hipError_t launch_hnsw_search(const HnswDeviceGraph& g, const HnswSearchPlan& p, const HnswQueries& q, uint32_t* bitset,
+                              const HnswOverflow& fix, const HnswOut& out, hipStream_t s) {
+    if (p.nq == 0) return hipSuccess;
+    if (p.cap > 64 * SA_EMAX_MAX || hnsw_nbcap(g) > HNSW_NBCAP_LDS) return hipErrorInvalidValue;
+    HnswArgs a = hnsw_args(g, p.nq, p.k, p.ef, p.cap, q, bitset, p.bitset_words, out);
+    a.capa = (p.cap + 3) & ~3;
+    a.table_size = p.table_size;
+    a.table_shift = p.table_shift;
+    a.fix_list = fix.fix_list;
+    a.fix_count = fix.fix_count;
+    a.fix_mode = (p.table_size == 0) ? fix.fix_slots : 0;
+    a.no_pipe = getenv("NMSLIB_HNSW_PIPE") ? atoi(getenv("NMSLIB_HNSW_PIPE")) == 0 : 0;
+    static const int prof = getenv("NMSLIB_HNSW_PROF") ? atoi(getenv("NMSLIB_HNSW_PROF")) : 0;
+    a.prof = (prof && !q.query_rows) ? 1 : 0;
+    const bool clocked = g.space == SP_L2SQR || g.space == SP_NORMCOS;  // the spaces whose kernels carry the phase clocks
+    const hipError_t e = (a.prof && !clocked)
+                             ? hipErrorInvalidValue
+                             : hnsw_dispatch_space(g.space, [&](auto sp) { return launch_space<sp.value>(a, p, s); });
+    if (a.prof) hnsw_print_prof(s);
     return e;
 }
 
-hipError_t launch_hnsw_search(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries,
-                              uint32_t* bitset, int32_t* out_ids, float* out_dists, int32_t* out_cnt,
-                              int32_t* out_ndc, int32_t* out_hops, int32_t* out_hops_up, int32_t* status,
-                              hipStream_t s) {
-    return launch_hnsw_search_ex(g, p, queries, nullptr, nullptr, 0, bitset, out_ids, out_dists, out_cnt, out_ndc,
-                                 out_hops, out_hops_up, status, s);
-}
-
 // ---- SearchOld ---------------------------------------------------------------------------------------------------
-HnswSearchPlan hnsw_make_plan_old(const HnswDeviceGraph& g, int nq, int k, int ef, bool force_bitset, int heap_cap) {
-    HnswSearchPlan p{};
-    p.nq = nq;
-    p.k = k;
-    p.ef = ef;
-    p.cap = ef > k ? ef : k;
-    const bool u8 = g.space == SP_L2SQR_SIFT;
-    p.a_in_lds = ef <= 8192;
-    p.r_in_lds = k <= 2048;
-    // accepted items are a fraction of the evaluated ones (~18 per unit of ef on 1M-row graphs)
-    long long hc = heap_cap > 0 ? heap_cap : 32ll * p.cap + 4096;
-    if (hc > (long long)g.n + 1) hc = (long long)g.n + 1;
-    p.heap_cap = (int)hc;
-    p.heap_lds = p.heap_cap < 2048 ? p.heap_cap : 2048;
-    const int nbcap = hnsw_nbcap(g);
-    const size_t fixed = (u8 ? 128 : (size_t)g.ldv * 4) + (size_t)(2 * nbcap + 64) * 4 + (size_t)p.heap_lds * 8 +
-                         (p.a_in_lds ? (size_t)((ef + 1) & ~1) * 4 : 0) + (p.r_in_lds ? (size_t)k * 8 : 0);
-    int want = 1 << ilog2((g.maxM0 > 0 ? g.maxM0 : 32) * p.cap * 2);
-    if (want < 2048) want = 2048;
-    const size_t budget = 64 * 1024;
-    while ((size_t)want * 4 + fixed > budget && want > 2048) want >>= 1;
-    if (force_bitset || 18 * p.cap > want / 2 || (size_t)want * 4 + fixed > budget) {
-        p.table_size = 0;
-        p.bitset_words = ((size_t)g.n + 31) / 32;
-        p.lds_bytes = fixed + 16;
-    } else {
-        p.table_size = want;
-        p.bitset_words = 0;
-        p.lds_bytes = fixed + (size_t)want * 4;
-    }
-    return p;
-}
-
 template <int SPACE>
 static hipError_t launch_old_space(const HnswArgs& a, const OldWs& w, const HnswSearchPlan& p, hipStream_t s) {
     auto go = [&](auto kern) -> hipError_t {
@@ -1547,31 +1449,12 @@ static hipError_t launch_old_space(const HnswArgs& a, const OldWs& w, const Hnsw
     return wide ? go(hnsw_search_old_kernel<SPACE, false, true>) : go(hnsw_search_old_kernel<SPACE, false, false>);
 }
 
-hipError_t launch_hnsw_search_old(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries,
-                                  uint32_t* bitset, void* ws_a, void* ws_r, void* ws_heap, int32_t* out_ids,
-                                  float* out_dists, int32_t* out_cnt, int32_t* out_ndc, int32_t* out_hops,
-                                  int32_t* out_hops_up, int32_t* status, hipStream_t s) {
+hipError_t launch_hnsw_search_old(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries, uint32_t* bitset,
+                                  void* ws_a, void* ws_r, void* ws_heap, const HnswOut& out, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
-    HnswArgs a{};
-    a.g = g;
-    a.nbcap = hnsw_nbcap(g);
-    a.queries = queries;
-    a.level = 0;
-    a.bitset = bitset;
-    a.bitset_words = p.bitset_words;
-    a.out_ids = out_ids;
-    a.out_dists = out_dists;
-    a.out_cnt = out_cnt;
-    a.out_ndc = out_ndc;
-    a.out_hops = out_hops;
-    a.out_hops_up = out_hops_up;
-    a.status = status;
-    a.nq = p.nq;
-    a.k = p.k;
-    a.ef = p.ef;
-    a.cap = p.cap;
+    HnswArgs a = hnsw_args(g, p.nq, p.k, p.ef, p.cap, HnswQueries::external(queries), bitset, p.bitset_words, out);
     a.table_size = p.table_size;
-    a.table_shift = p.table_size ? 32 - ilog2(p.table_size) : 0;
+    a.table_shift = p.table_shift;
     OldWs w{};
     w.capA = p.ef;
     w.capR = p.k;
@@ -1582,20 +1465,8 @@ hipError_t launch_hnsw_search_old(const HnswDeviceGraph& g, const HnswSearchPlan
     w.a_hbm = static_cast<float*>(ws_a);
     w.r_hbm = static_cast<u64*>(ws_r);
     w.heap_hbm = static_cast<u64*>(ws_heap);
-    switch (g.space) {
-        case SP_L2SQR: return launch_old_space<SP_L2SQR>(a, w, p, s);
-        case SP_L2: return launch_old_space<SP_L2>(a, w, p, s);
-        case SP_L1: return launch_old_space<SP_L1>(a, w, p, s);
-        case SP_LINF: return launch_old_space<SP_LINF>(a, w, p, s);
-        case SP_NORMCOS: return launch_old_space<SP_NORMCOS>(a, w, p, s);
-        case SP_COSINE: return launch_old_space<SP_COSINE>(a, w, p, s);
-        case SP_ANGULAR: return launch_old_space<SP_ANGULAR>(a, w, p, s);
-        case SP_NEGDOT: return launch_old_space<SP_NEGDOT>(a, w, p, s);
-        case SP_L2SQR_SIFT: return launch_old_space<SP_L2SQR_SIFT>(a, w, p, s);
-        default: return hipErrorInvalidValue;
-    }
+    return hnsw_dispatch_space(g.space, [&](auto sp) { return launch_old_space<sp.value>(a, w, p, s); });
 }
-
 
 // ---- SearchV1Merge beyond 1024 items (hnsw_search_big_kernel) ---------------------------------------------------
 template <int SPACE>
@@ -1606,40 +1477,13 @@ static hipError_t launch_big_space(const HnswArgs& a, float* ws_keys, int32_t* w
 }
 
 hipError_t launch_hnsw_search_big(const HnswDeviceGraph& g, int nq, int k, int ef, const void* queries, uint32_t* bitset,
-                                  float* ws_keys, int32_t* ws_idu, int32_t* out_ids, float* out_dists, int32_t* out_cnt,
-                                  int32_t* out_ndc, int32_t* out_hops, int32_t* out_hops_up, int32_t* status, hipStream_t s) {
+                                  float* ws_keys, int32_t* ws_idu, const HnswOut& out, hipStream_t s) {
     if (nq == 0) return hipSuccess;
-    HnswArgs a{};
-    a.g = g;
-    a.nbcap = hnsw_nbcap(g);
-    a.queries = queries;
-    a.bitset = bitset;
-    a.bitset_words = ((size_t)g.n + 31) / 32;
-    a.out_ids = out_ids;
-    a.out_dists = out_dists;
-    a.out_cnt = out_cnt;
-    a.out_ndc = out_ndc;
-    a.out_hops = out_hops;
-    a.out_hops_up = out_hops_up;
-    a.status = status;
-    a.nq = nq;
-    a.k = k;
-    a.ef = ef;
-    a.cap = ef > k ? ef : k;
+    const HnswArgs a = hnsw_args(g, nq, k, ef, ef > k ? ef : k, HnswQueries::external(queries), bitset,
+                                 ((size_t)g.n + 31) / 32, out);
     const bool u8 = g.space == SP_L2SQR_SIFT;
     const size_t lds = (u8 ? 128 : (size_t)g.ldv * 4) + (size_t)(2 * hnsw_nbcap(g) + 2 * 64) * 4 + 16;
-    switch (g.space) {
-        case SP_L2SQR: return launch_big_space<SP_L2SQR>(a, ws_keys, ws_idu, lds, s);
-        case SP_L2: return launch_big_space<SP_L2>(a, ws_keys, ws_idu, lds, s);
-        case SP_L1: return launch_big_space<SP_L1>(a, ws_keys, ws_idu, lds, s);
-        case SP_LINF: return launch_big_space<SP_LINF>(a, ws_keys, ws_idu, lds, s);
-        case SP_NORMCOS: return launch_big_space<SP_NORMCOS>(a, ws_keys, ws_idu, lds, s);
-        case SP_COSINE: return launch_big_space<SP_COSINE>(a, ws_keys, ws_idu, lds, s);
-        case SP_ANGULAR: return launch_big_space<SP_ANGULAR>(a, ws_keys, ws_idu, lds, s);
-        case SP_NEGDOT: return launch_big_space<SP_NEGDOT>(a, ws_keys, ws_idu, lds, s);
-        case SP_L2SQR_SIFT: return launch_big_space<SP_L2SQR_SIFT>(a, ws_keys, ws_idu, lds, s);
-        default: return hipErrorInvalidValue;
-    }
+    return hnsw_dispatch_space(g.space, [&](auto sp) { return launch_big_space<sp.value>(a, ws_keys, ws_idu, lds, s); });
 }
 
 }  // namespace gfxknn

@@ -640,17 +640,10 @@ static hipError_t launch_mw_space(const HnswArgs& a, size_t lds, int sa_emax, hi
 
 hipError_t launch_hnsw_search_mw(const HnswArgs& a, size_t lds_bytes, int sa_emax, hipStream_t s) {
     if (sa_emax > MW_MAX_EMAX || a.g.maxM0 > 62 || a.g.maxM > 62) return hipErrorInvalidValue;
-    switch (a.g.space) {
-        case SP_L2SQR: return launch_mw_space<SP_L2SQR>(a, lds_bytes, sa_emax, s);
-        case SP_L2: return launch_mw_space<SP_L2>(a, lds_bytes, sa_emax, s);
-        case SP_L1: return launch_mw_space<SP_L1>(a, lds_bytes, sa_emax, s);
-        case SP_LINF: return launch_mw_space<SP_LINF>(a, lds_bytes, sa_emax, s);
-        case SP_NORMCOS: return launch_mw_space<SP_NORMCOS>(a, lds_bytes, sa_emax, s);
-        case SP_COSINE: return launch_mw_space<SP_COSINE>(a, lds_bytes, sa_emax, s);
-        case SP_ANGULAR: return launch_mw_space<SP_ANGULAR>(a, lds_bytes, sa_emax, s);
-        case SP_NEGDOT: return launch_mw_space<SP_NEGDOT>(a, lds_bytes, sa_emax, s);
-        default: return hipErrorInvalidValue;
-    }
+    return hnsw_dispatch_space(a.g.space, [&](auto sp) {
+        if constexpr (sp.value == SP_L2SQR_SIFT) return hipErrorInvalidValue;  // (no multi-wave kernel over u8 rows)
+        else return launch_mw_space<sp.value>(a, lds_bytes, sa_emax, s);
+    });
 }
 
 void hnsw_mw_read_prof(unsigned long long out[12]) {

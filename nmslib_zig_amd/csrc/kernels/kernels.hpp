@@ -250,6 +250,7 @@ struct HnswSearchPlan {
     int table_size;            // LDS visited hash entries (power of two); 0 -> global bitset
     size_t lds_bytes;
     size_t bitset_words;       // per query, when table_size == 0
+    int table_shift;           // hash -> slot of the LDS table: 32 - log2(table_size); 0 without a table
     // SearchOld kernel only (hnsw_make_plan_old): candidate heap and queue placement
     int heap_lds, heap_cap;    // heap entries in LDS / in total per query (the rest lives in the HBM workspace)
     int a_in_lds, r_in_lds;    // closest-queue values (ef floats) / result queue (k pairs) in LDS?
@@ -272,40 +273,54 @@ HnswSearchPlan hnsw_make_plan_old(const HnswDeviceGraph& g, int nq, int k, int e
 inline size_t hnsw_old_ws_a(const HnswSearchPlan& p) { return p.a_in_lds ? 0 : (size_t)p.ef * 4; }
 inline size_t hnsw_old_ws_r(const HnswSearchPlan& p) { return p.r_in_lds ? 0 : (size_t)p.k * 8; }
 inline size_t hnsw_old_ws_heap(const HnswSearchPlan& p) { return (size_t)(p.heap_cap - p.heap_lds) * 8; }
-hipError_t launch_hnsw_search_old(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries,
-                                  uint32_t* bitset, void* ws_a, void* ws_r, void* ws_heap, int32_t* out_ids,
-                                  float* out_dists, int32_t* out_cnt, int32_t* out_ndc, int32_t* out_hops,
-                                  int32_t* out_hops_up, int32_t* status, hipStream_t s);
-// queries: [nq][dim] f32 (row stride dim) or u8 [nq][128].  status[q] != 0 -> visited table
-// overflowed (caller re-runs those with the bitset variant).
-hipError_t launch_hnsw_search(const HnswDeviceGraph& g, const HnswSearchPlan& p,
-                              const void* queries, uint32_t* bitset, int32_t* out_ids,
-                              float* out_dists, int32_t* out_cnt, int32_t* out_ndc,
-                              int32_t* out_hops, int32_t* out_hops_up, int32_t* status,
-                              hipStream_t s);
 
+// ---- the named parts of a search launch (host side) ----
+// Where a launch writes: k results per query, then one entry per query of the result count, the work counters (ndc, hops
+// on the search level, hops above it; each optional) and the status (optional).
+struct HnswOut {
+    int32_t* ids;
+    float* dists;
+    int32_t *cnt, *ndc, *hops, *hops_up, *status;
+    // the block of the queries from q0 on, k results each
+    HnswOut at(size_t q0, size_t k) const {
+        auto from = [q0](int32_t* p) { return p ? p + q0 : p; };
+        return {ids + q0 * k, dists + q0 * k, from(cnt), from(ndc), from(hops), from(hops_up), from(status)};
+    }
+};
+// Where the queries come from.  External: [nq][dim] f32 (row stride dim) or u8 [nq][128].  Construction mode
+// (hnsw_build): the queries are stored rows (query_rows), the best-first phase runs on `level`, start_nodes[q] >= 0 gives
+// the start node (else descend from the entry point to level + 1).
+struct HnswQueries {
+    const void* queries;
+    const int32_t* query_rows;
+    const int32_t* start_nodes;
+    int level;
+    static HnswQueries external(const void* queries) { return {queries, nullptr, nullptr, 0}; }
+    static HnswQueries stored(const int32_t* query_rows, const int32_t* start_nodes, int level) {
+        return {nullptr, query_rows, start_nodes, level};
+    }
+};
+// Visited-table overflow handled on the device (no host round trip); null / zero = not in use:
+//   1. LDS-table plan:  fix_slots = 0, fix_list / fix_count given -> overflowed queries are appended to fix_list;
+//   2. bitset plan:     fix_slots = S > 0 -> S workgroups walk fix_list (count read on the device), each clearing and
+//      using its own bitset slot (bitset must hold S * bitset_words words) and overwriting those queries' outputs.
+struct HnswOverflow {
+    int fix_slots;
+    int32_t* fix_list;
+    int32_t* fix_count;
+};
+
+// SearchV1Merge with max(ef, k) <= 1024 (the sorted array in LDS).  status[q] != 0 -> the visited table overflowed (a
+// caller without an overflow list re-runs those with a bitset plan).
+hipError_t launch_hnsw_search(const HnswDeviceGraph& g, const HnswSearchPlan& p, const HnswQueries& q, uint32_t* bitset,
+                              const HnswOverflow& fix, const HnswOut& out, hipStream_t s);
+// SearchOld; ws_a / ws_r / ws_heap: the per-query HBM workspaces above (may be unused)
+hipError_t launch_hnsw_search_old(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries, uint32_t* bitset,
+                                  void* ws_a, void* ws_r, void* ws_heap, const HnswOut& out, hipStream_t s);
 // SearchV1Merge with max(ef, k) beyond the LDS kernels' 1024 items: the sorted array in a per-query HBM workspace
 // (ws_keys / ws_idu: [nq][max(ef, k)]), visited set = HBM bitset [nq][ceil(n / 32)] (cleared by the caller).
 hipError_t launch_hnsw_search_big(const HnswDeviceGraph& g, int nq, int k, int ef, const void* queries, uint32_t* bitset,
-                                  float* ws_keys, int32_t* ws_idu, int32_t* out_ids, float* out_dists, int32_t* out_cnt,
-                                  int32_t* out_ndc, int32_t* out_hops, int32_t* out_hops_up, int32_t* status, hipStream_t s);
-
-// Visited-table overflow handled on the device (no host round trip):
-//   1. LDS-table plan:  fix_slots = 0, fix_list/fix_count given -> overflowed queries are appended to fix_list;
-//   2. bitset plan:     fix_slots = S > 0 -> S workgroups walk fix_list (count read on the device), each clearing and
-//      using its own bitset slot (bitset must hold S * bitset_words words) and overwriting those queries' outputs.
-hipError_t launch_hnsw_search_fix(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries,
-                                  uint32_t* bitset, int fix_slots, int32_t* fix_list, int32_t* fix_count,
-                                  int32_t* out_ids, float* out_dists, int32_t* out_cnt, int32_t* out_ndc,
-                                  int32_t* out_hops, int32_t* out_hops_up, int32_t* status, hipStream_t s);
-
-// Construction-mode search (hnsw_build): queries are stored rows (query_rows), the best-first phase runs on
-// `level`, start_nodes[q] >= 0 gives the start node (else descend from the entry point to level+1).
-hipError_t launch_hnsw_search_ex(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries,
-                                 const int32_t* query_rows, const int32_t* start_nodes, int level,
-                                 uint32_t* bitset, int32_t* out_ids, float* out_dists, int32_t* out_cnt,
-                                 int32_t* out_ndc, int32_t* out_hops, int32_t* out_hops_up, int32_t* status,
-                                 hipStream_t s);
+                                  float* ws_keys, int32_t* ws_idu, const HnswOut& out, hipStream_t s);
 
 // ---- HNSW construction on the GPU (hnsw_build_kernels.hip) ------------------------------------
 struct HnswBuildGraph {          // mutable twin of HnswDeviceGraph

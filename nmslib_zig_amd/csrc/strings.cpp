@@ -191,7 +191,7 @@ void Engine::build_string_graph() {
 void Engine::knn_string_hnsw(const int64_t* d_qoff, const int32_t* d_qlen, const uint64_t* d_peq, const uint32_t* d_qw,
                              int nw_max, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt) {
     const HostGraph& g = graph_;
-    const bool old = algo_ == "old" || (algo_ == "hybrid" && ef_ >= 1000);
+    const bool old = search_old();
     StringHnswArgs a{};
     a.space = space_;
     a.row_ptr = d_st_ptr_.as<int64_t>();
