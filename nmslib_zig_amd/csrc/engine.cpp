@@ -247,13 +247,16 @@ Engine::~Engine() {
     if (stream_) (void)hipStreamDestroy(stream_);
 }
 
-void Engine::prof_begin(hipStream_t s) {
-    if (!prof_ || prof_events_.size() >= 65536) return;
+std::pair<hipEvent_t, hipEvent_t> Engine::prof_pair() {
+    if (!prof_ || prof_events_.size() >= 65536) return {nullptr, nullptr};
     hipEvent_t a, b;
     hip_check(hipEventCreate(&a), "hipEventCreate");
     hip_check(hipEventCreate(&b), "hipEventCreate");
     prof_events_.emplace_back(a, b);
-    hip_check(hipEventRecord(a, s), "hipEventRecord");
+    return prof_events_.back();
+}
+void Engine::prof_begin(hipStream_t s) {
+    if (hipEvent_t a = prof_pair().first) hip_check(hipEventRecord(a, s), "hipEventRecord");
 }
 void Engine::prof_end(hipStream_t s) {
     if (!prof_ || prof_events_.empty()) return;
@@ -335,8 +338,7 @@ void Engine::reset() {
     d_n_ = 0;
     shards_.clear();
     dim_ = 0;  // a reset index accepts rows of another dimension
-    centred_ = false;
-    have_bf16_ = false;
+    brute_ = BruteDense();
     last_path = 0;
     fast_flags_ = nullptr;
     fast_nqt_ = 0;
@@ -360,9 +362,8 @@ size_t Engine::memory_usage() const {
 size_t Engine::hbm_bytes() const {
     size_t sh = 0;
     for (const auto& c : shards_) sh += c->hbm_bytes();
-    return sh + d_rows_.bytes() + d_rows_i8_.bytes() + d_aux_.bytes() + d_ids_.bytes() + d_links0_.bytes() + d_up_off_.bytes() +
-           d_up_links_.bytes() + d_rownorm_.bytes() + d_rows_sel_.bytes() + d_auxh_.bytes() + d_bf_hi_.bytes() + d_bf_lo_.bytes() + d_auxp_.bytes() +
-           d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes() + d_st_ptr_.bytes() + d_st_data_.bytes();
+    return sh + d_rows_.bytes() + d_aux_.bytes() + d_ids_.bytes() + d_links0_.bytes() + d_up_off_.bytes() + d_up_links_.bytes() +
+           d_rownorm_.bytes() + brute_.bytes() + d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes() + d_st_ptr_.bytes() + d_st_data_.bytes();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -905,189 +906,9 @@ void Engine::finalize() {
     ensure_graph();  // host-side construction first: it needs no device
     check_device();
     upload_rows();
-    if (method_ == Method::Brute) {
-        const size_t n = size();
-        if (is_u8()) {
-            const size_t n_pad = (size_t)bf_u8_rows_padded((int)n);
-            d_aux_.ensure(n_pad * 4);
-            d_rows_i8_.ensure(n_pad * 128);
-            d_auxh_.ensure(n_pad * 4);
-            hip_check(launch_prepare_u8(d_rows_.as<uint8_t>(), (int)n, d_rows_i8_.as<uint8_t>(), d_aux_.as<int32_t>(),
-                                        d_auxh_.as<int32_t>(), stream_),
-                      "prepare u8 rows");
-        } else {
-            d_aux_.ensure(std::max<size_t>(n, 1) * 4);
-            const float* sel_rows = d_rows_.as<float>();
-            centred_ = false;
-            d_rows_sel_.release();
-            if ((space_ == SP_L2 || space_ == SP_COSINE || space_ == SP_ANGULAR) && n > 0) {
-                // L2 is translation invariant, the Q.B^T score q.b - |b|^2/2 is not: its f32 rounding error grows with
-                // |q||b|, i.e. with a common offset of the data, and can exceed the gaps between neighbours (the
-                // reference's direct sum (a-b)^2, distcomp_lp.cc:304-365, has no such term).  When the column mean
-                // is not small against the spread, SELECTION runs on rows - mean and queries - mean; the exact
-                // re-rank keeps using the original rows.  Cosine / angular: same centred copy, and the score is
-                // rebuilt as 1 - cos = (|q'-b'|^2 - (|q|-|b|)^2) / (2|q||b|) (bf_kernels.hip, BF_COSC).
-                std::vector<double> st((size_t)ldb_ + 1);
-                DevBuf d_stats;
-                d_stats.ensure(st.size() * 8);
-                hip_check(launch_col_stats(d_rows_.as<float>(), (int)n, ldb_, (int)dim_, d_stats.as<double>(), stream_),
-                          "column stats");
-                hip_check(hipMemcpyAsync(st.data(), d_stats.ptr(), st.size() * 8, hipMemcpyDeviceToHost, stream_), "stats D2H");
-                hip_check(hipStreamSynchronize(stream_), "column stats");
-                double mu2 = 0;
-                std::vector<float> mean((size_t)ldb_, 0.f);
-                for (size_t c = 0; c < dim_; ++c) {
-                    const double m = st[c] / (double)n;
-                    mean[c] = (float)m;
-                    mu2 += m * m;
-                }
-                const double spread2 = std::max(0.0, st[(size_t)ldb_] / (double)n - mu2);
-                cosc_spread2_ = spread2;
-                bool centre = mu2 > 0.0625 * spread2;
-                if (const char* env = getenv("NMSLIB_GPU_CENTER")) centre = atoi(env) != 0;
-                if (centre) {
-                    d_mean_.ensure((size_t)ldb_ * 4);
-                    d_rows_sel_.ensure(n * (size_t)ldb_ * 4);
-                    hip_check(hipMemcpyAsync(d_mean_.ptr(), mean.data(), (size_t)ldb_ * 4, hipMemcpyHostToDevice, stream_), "mean");
-                    hip_check(launch_center_rows(d_rows_.as<float>(), d_mean_.as<float>(), (int)n, (int)n, ldb_, (int)dim_,
-                                                 d_rows_sel_.as<float>(), stream_),
-                              "centre rows");
-                    hip_check(hipStreamSynchronize(stream_), "centre rows");  // `mean` is read by the copy above
-                    sel_rows = d_rows_sel_.as<float>();
-                    centred_ = true;
-                    mu_norm_ = 0;
-                    for (size_t c = 0; c < dim_; ++c) mu_norm_ += (double)mean[c] * (double)mean[c];
-                    mu_norm_ = std::sqrt(mu_norm_);
-                }
-            }
-            if (centred_ && space_ != SP_L2) {
-                d_aux_.ensure(std::max<size_t>(n, 1) * 12);
-                hip_check(launch_row_aux_cosc(d_rows_.as<float>(), sel_rows, (int)n, ldb_, (int)dim_, mu_norm_,
-                                              d_aux_.as<float>(), stream_),
-                          "row aux");
-            } else {
-                hip_check(launch_row_aux_f32(sel_rows, (int)n, ldb_, (int)dim_, space_, d_aux_.as<float>(), stream_),
-                          "row aux");
-            }
-            // largest norm (and bf16 rounding residual) of the selection rows: the error bounds of the selection scores
-            // (proofs in bf_rerank_kernel and bf_rerank_f32_list_kernel)
-            {
-                const bool cosine = space_ == SP_COSINE || space_ == SP_ANGULAR;
-                float bm[4] = {0.f, 0.f, 0.f, 0.f};
-                measure_rows_f16(sel_rows, n, ldb_, (int)dim_, cosine, bm);
-                bmax_ = bm[0];
-                bres_ = bm[1];
-            }
-            // fast path (large batches, D <= 128): bf16 hi / lo tiles of the selection rows + padded aux
-            have_bf16_ = false;
-            d_bf_hi_.release();
-            d_bf_lo_.release();
-            d_f16_hi_.release();
-            d_auxp_.release();
-            d_auxp16_.release();
-            const bool cosine_space = space_ == SP_COSINE || space_ == SP_ANGULAR;
-            const bool fast_space = space_ == SP_L2 || space_ == SP_NEGDOT || (cosine_space && !centred_);
-            if (cosine_space && centred_ && dim_ + 3 <= 1024 && n >= 65536) {
-                // centred cosine / angular (round 3): the score -(1 - cos)|q| as an inner product of rows and queries with
-                // three more columns (bf_kernels.hip, row_aug_cosc_kernel); bf16 tiles of those rows, scanned in the
-                // inner-product mode.  A zero-norm row has no score of this form: the index then stays on the adaptive kernel.
-                const BfF32Fast f0 = bf_f32_fast_plan((int)n, (int)dim_, 1024, 10, space_, true);
-                if (f0.use) {
-                    const size_t dp = (size_t)f0.dp;
-                    const size_t n_pad = (size_t)bf_f32_rows_padded((int)n);
-                    DevBuf d_aug, d_flag;
-                    d_aug.ensure(n * dp * 4);
-                    d_flag.ensure(16);
-                    hip_check(hipMemsetAsync(d_flag.ptr(), 0, 16, stream_), "clear");
-                    // (the two constant columns balanced at the typical (|b'|^2 - db^2) / 2 <= spread^2 / 2)
-                    cosc_lambda_ = (float)std::sqrt(std::max(0.5 * cosc_spread2_, 1e-30));
-                    hip_check(launch_row_aug_cosc(d_rows_.as<float>(), sel_rows, (int)n, ldb_, (int)dim_, mu_norm_, cosc_lambda_,
-                                                  d_aug.as<float>(), (int)dp, d_flag.as<int>(), stream_),
-                              "augmented rows");
-                    int fl[1] = {0};
-                    hip_check(hipMemcpyAsync(fl, d_flag.ptr(), 4, hipMemcpyDeviceToHost, stream_), "flags");
-                    hip_check(hipStreamSynchronize(stream_), "augmented rows");
-                    if (fl[0] == 0) {
-                        float bm[4] = {0.f, 0.f, 0.f, 0.f};
-                        measure_rows_f16(d_aug.as<float>(), n, (int)dp, (int)dim_ + 3, false, bm);   // (sets f16_scale_, bres16_)
-                        // (the augmented rows are divided by their norm ~ |mean|, the augmented queries are not)
-                        if (mu_norm_ > 0) {
-                            const int eq = std::max(-40, std::min(40, (int)std::lround(std::log2((double)f16_scale_) - std::log2(mu_norm_))));
-                            f16_scale_q_ = std::ldexp(1.f, eq);
-                        }
-                        bmax_c_ = bm[0];
-                        bres_c_ = bm[1];
-                        if (dp == 128) {
-                            d_bf_hi_.ensure(n_pad * dp * 2);
-                            d_bf_lo_.ensure(n_pad * 128 * 2);
-                        }
-                        d_f16_hi_.ensure(n_pad * dp * 2);
-                        d_auxp_.ensure(n_pad * 4);
-                        d_auxp16_.ensure(n_pad * 4);
-                        hip_check(launch_split_bf16(d_aug.as<float>(), (int)n, (int)n_pad, (int)dp, (int)dim_ + 3,
-                                                    dp == 128 ? d_bf_hi_.ptr() : nullptr, dp == 128 ? d_bf_lo_.ptr() : nullptr,
-                                                    nullptr, 0.f, d_auxp_.as<float>(), stream_, (int)dp, d_f16_hi_.ptr(), f16_scale_,
-                                                    d_auxp16_.as<float>(), 1.f),
-                                  "split rows");
-                        hip_check(hipStreamSynchronize(stream_), "split rows");   // (d_aug goes out of scope)
-                        have_bf16_ = true;
-                    }
-                }
-            }
-            if (fast_space && dim_ <= 1024 && n >= 65536) {
-                // (rows up to 128 dimensions: hi and lo tiles; longer rows, round 3: hi tiles of 128 * kch columns
-                //  for the K-chunked one-product scan -- the plan's kch, which depends on the dimension only)
-                const BfF32Fast f0 = bf_f32_fast_plan((int)n, (int)dim_, 1024, 10, space_, centred_);
-                const size_t dp = f0.use ? (size_t)f0.dp : 128;
-                const size_t n_pad = (size_t)bf_f32_rows_padded((int)n);
-                // (bf16 hi / lo tiles: the split-product scan, rows of up to 128 dimensions only; fp16 tiles of the rows times
-                //  f16_scale_: the one-product scan -- its start values in units of scale^2 for l2, the plain 1/|b| for cosine)
-                if (dp == 128) {
-                    d_bf_hi_.ensure(n_pad * dp * 2);
-                    d_bf_lo_.ensure(n_pad * 128 * 2);
-                }
-                d_f16_hi_.ensure(n_pad * dp * 2);
-                d_auxp_.ensure(n_pad * 4);
-                d_auxp16_.ensure(n_pad * 4);
-                const float pad = space_ == SP_L2 ? -INFINITY : 0.f;
-                hip_check(launch_split_bf16(sel_rows, (int)n, (int)n_pad, ldb_, (int)dim_, dp == 128 ? d_bf_hi_.ptr() : nullptr,
-                                            dp == 128 ? d_bf_lo_.ptr() : nullptr,
-                                            space_ == SP_NEGDOT ? nullptr : d_aux_.as<float>(), pad, d_auxp_.as<float>(),
-                                            stream_, (int)dp, d_f16_hi_.ptr(), f16_scale_, d_auxp16_.as<float>(),
-                                            space_ == SP_L2 ? f16_scale_ * f16_scale_ : 1.f),
-                          "split rows");
-                have_bf16_ = true;
-            }
-        }
-        hip_check(hipStreamSynchronize(stream_), "finalize");
-    } else {
-        upload_graph();
-    }
+    if (method_ == Method::Brute) prepare_brute();
+    else upload_graph();
     dirty_ = false;
-}
-
-// bm[0] largest row norm, bm[1] largest bf16 residual; chooses the fp16 scale of the one-product scan from the largest
-// |element| (a power of two that puts it into [2^13, 2^14): a factor 4 of headroom below fp16's 65504 for the queries) and
-// measures the rows' largest fp16 residual at that scale (f16_scale_, bres16_)
-void Engine::measure_rows_f16(const float* rows, size_t n, int ld, int dim, bool relative, float* bm) {
-    DevBuf d_bm;
-    d_bm.ensure(16);
-    hip_check(launch_row_maxnorm(rows, (int)n, ld, dim, relative, d_bm.as<float>(), stream_), "row norms");
-    hip_check(hipMemcpyAsync(bm, d_bm.ptr(), 16, hipMemcpyDeviceToHost, stream_), "bmax");
-    hip_check(hipStreamSynchronize(stream_), "row norms");
-    f16_scale_ = 1.f;
-    if (bm[2] > 0.f && std::isfinite(bm[2])) {
-        // (|exponent| <= 40: scale^2, the unit of the scan's scores, must stay a float; rows smaller than 2^-27 simply lose
-        //  fp16 precision, which the measured residual reports)
-        const int e = std::max(-40, std::min(40, 13 - (int)std::floor(std::log2(bm[2]))));
-        f16_scale_ = std::ldexp(1.f, e);
-    }
-    float bm2[4] = {0.f, 0.f, 0.f, 0.f};
-    hip_check(launch_row_maxnorm(rows, (int)n, ld, dim, relative, d_bm.as<float>(), stream_, f16_scale_), "row residuals");
-    hip_check(hipMemcpyAsync(bm2, d_bm.ptr(), 16, hipMemcpyDeviceToHost, stream_), "bres16");
-    hip_check(hipStreamSynchronize(stream_), "row residuals");
-    bres16_ = bm2[3];
-    f16_scale_q_ = f16_scale_;
 }
 
 // restores the calling thread's current device on every way out of a scope that visits other devices
@@ -1300,175 +1121,6 @@ size_t Engine::hnsw_redone() {
     hip_check(hipStreamSynchronize(last_stream_ ? last_stream_ : stream_), "stats");
     hip_check(hipMemcpy(&v, ws_fix_.ptr(), 4, hipMemcpyDeviceToHost), "stats redo count");
     return (size_t)v;
-}
-
-void Engine::knn_brute(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
-                       hipStream_t stream) {
-    have_counters_ = false;
-    const int dim_eff = d_n_ ? (int)dim_ : 1;
-    if (k > (size_t)BF_MAX_K) {
-        // beyond the selection kernels' capacity: per query one pass with the reference formula + one stable radix sort
-        const int ld = is_u8() ? 128 : ldb_;
-        const int elem = is_u8() ? 1 : 4;
-        const size_t n = d_n_;
-        ws_qpad_.ensure(std::max<size_t>(nq, 1) * ld * elem);
-        hip_check(launch_pad_rows(d_queries, (int)nq, dim_eff, ws_qpad_.ptr(), (int)nq, ld, elem, stream), "pad queries");
-        ws_rdist_.ensure(std::max<size_t>(n, 1) * 4);
-        ws_bigk_.ensure(std::max<size_t>(n, 1) * 16);
-        const size_t tb = bf_bigk_temp_bytes((int)n);
-        ws_bigk_tmp_.ensure(tb);
-        hip_check(launch_bf_bigk(space_, d_rows_.ptr(), ld, (int)n, ws_qpad_.ptr(), (size_t)ld * elem, (int)nq, dim_eff, (int)k,
-                                 d_ids_.as<int32_t>(), ws_rdist_.as<float>(), ws_bigk_.as<uint32_t>(), ws_bigk_tmp_.ptr(), tb,
-                                 d_ids, d_dists, d_cnt, stream),
-                  "bf_bigk");
-        last_path = 5;
-        return;
-    }
-    if (is_u8()) {
-        // large batches: thresholds fixed by a sample pass, then one streaming scan (bf_kernels.hip, bf_scan_u8_kernel)
-        const BfU8Fast f = bf_u8_fast_plan((int)d_n_, (int)nq, (int)k);
-        if (f.use) {
-            ws_qpad_.ensure((size_t)f.qpad * 128);
-            ws_cand_.ensure(bf_cand_elems(f.fallback) * 8);
-            ws_cnt_.ensure(bf_cnt_elems(f.fallback) * 4);
-            ws_u8_cand_.ensure(bf_u8_top8_elems(f) * 4);
-            ws_u8_thr_.ensure((size_t)f.qpad * 4 + (size_t)f.nqt * 4 + 64);
-            ws_u8_list_.ensure(bf_u8_list_elems(f) * 4);
-            ws_u8_listcnt_.ensure(bf_u8_listcnt_elems(f) * 4);
-            int* thr = ws_u8_thr_.as<int>();
-            int* tile_fail = thr + f.qpad;
-            // (padding happens inside the fast path's one preparation kernel)
-            hipEvent_t eb = nullptr, ee = nullptr;
-            if (prof_ && prof_events_.size() < 65536) {
-                hip_check(hipEventCreate(&eb), "hipEventCreate");
-                hip_check(hipEventCreate(&ee), "hipEventCreate");
-                prof_events_.emplace_back(eb, ee);
-            }
-            hip_check(launch_bf_u8_fast(f, (int)d_n_, (int)nq, (int)k, d_rows_.as<uint8_t>(), d_rows_i8_.as<uint8_t>(),
-                                        d_aux_.as<int32_t>(), d_auxh_.as<int32_t>(), ws_qpad_.as<uint8_t>(),
-                                        ws_u8_cand_.as<int>(),
-                                        ws_cand_.as<unsigned long long>(), ws_cnt_.as<int>(), thr,
-                                        ws_u8_list_.as<uint32_t>(), ws_u8_listcnt_.as<int>(), tile_fail,
-                                        d_ids_.as<int32_t>(), d_ids, d_dists, d_cnt, eb, ee, stream,
-                                        static_cast<const uint8_t*>(d_queries)),
-                      "bf_u8_fast");
-            last_path = 3;
-            fast_flags_ = tile_fail;
-            fast_nqt_ = f.nqt;
-            fast_has_precise_ = false;
-            return;
-        }
-    }
-    if (!is_u8() && have_bf16_) {
-        // large batches at D <= 128: split-bf16 MFMA selection with sample-fixed thresholds (bf_scan_f32_kernel)
-        const BfF32Fast f = bf_f32_fast_plan((int)d_n_, dim_eff, (int)nq, (int)k, space_, centred_);
-        if (f.use) {
-            const int ldb = ldb_;
-            ws_qpad_.ensure((size_t)f.qpad * ldb * 4);
-            // (uncentred rows: padding happens inside the fast path's one preparation kernel)
-            if (centred_) hip_check(launch_pad_rows(d_queries, (int)nq, dim_eff, ws_qpad_.ptr(), f.qpad, ldb, 4, stream), "pad queries");
-            const float* qsel = ws_qpad_.as<float>();
-            if (centred_) {
-                ws_qsel_.ensure((size_t)f.qpad * ldb * 4);
-                hip_check(launch_center_rows(ws_qpad_.as<float>(), d_mean_.as<float>(), f.qpad, (int)nq, ldb, dim_eff,
-                                             ws_qsel_.as<float>(), stream),
-                          "centre queries");
-                qsel = ws_qsel_.as<float>();
-            }
-            if (f.cosc) {   // centred cosine / angular: the augmented queries (query_aug_cosc_kernel) are what the scans see
-                ws_qaux_.ensure((size_t)f.qpad * 16);
-                ws_qaug_.ensure((size_t)f.qpad * f.dp * 4);
-                hip_check(launch_query_aux_cosc(ws_qpad_.as<float>(), ws_qsel_.as<float>(), f.qpad, ldb, dim_eff, mu_norm_,
-                                                ws_qaux_.as<float>(), stream),
-                          "query aux");
-                hip_check(launch_query_aug_cosc(ws_qsel_.as<float>(), ws_qaux_.as<float>(), (int)nq, f.qpad, ldb, dim_eff,
-                                                cosc_lambda_, ws_qaug_.as<float>(), f.dp, stream),
-                          "augmented queries");
-                qsel = ws_qaug_.as<float>();
-            }
-            ws_cand_.ensure(bf_cand_elems(f.fallback) * 8);
-            ws_cnt_.ensure(bf_cnt_elems(f.fallback) * 4);
-            ws_f32_q_.ensure((size_t)f.qpad * f.dp * 2 * 3);   // bf16 hi, bf16 lo, fp16
-            ws_u8_cand_.ensure(bf_f32_top8_elems(f) * 4);
-            ws_u8_thr_.ensure(bf_f32_thr_bytes(f));
-            ws_flags_.ensure((size_t)f.fallback.nqt * 4 + 64);
-            ws_u8_list_.ensure(bf_f32_list_elems(f) * 4);
-            ws_u8_listcnt_.ensure(bf_f32_listcnt_elems(f) * 4);
-            float* thr = ws_u8_thr_.as<float>();
-            int* tile_fail = reinterpret_cast<int*>(thr + 2 * (size_t)f.qpad);
-            char* qh = ws_f32_q_.as<char>();
-            char* ql = qh + (size_t)f.qpad * f.dp * 2;
-            BfF16Side h16{d_f16_hi_.ptr(), d_auxp16_.as<float>(), ql + (size_t)f.qpad * f.dp * 2, f16_scale_, bres16_, f16_scale_q_};
-            hipEvent_t eb = nullptr, ee = nullptr;
-            if (prof_ && prof_events_.size() < 65536) {
-                hip_check(hipEventCreate(&eb), "hipEventCreate");
-                hip_check(hipEventCreate(&ee), "hipEventCreate");
-                prof_events_.emplace_back(eb, ee);
-            }
-            hip_check(launch_bf_f32_fast(f, space_, (int)d_n_, dim_eff, ldb, (int)nq, (int)k, d_rows_.as<float>(),
-                                         centred_ ? d_rows_sel_.as<float>() : d_rows_.as<float>(), d_aux_.as<float>(),
-                                         d_bf_hi_.ptr(), d_bf_lo_.ptr(), d_auxp_.as<float>(), f.cosc ? bmax_c_ : bmax_,
-                                         f.cosc ? bres_c_ : bres_, ws_qpad_.as<float>(), qsel, qh, ql,
-                                         ws_u8_cand_.as<float>(), ws_cand_.as<unsigned long long>(), ws_cnt_.as<int>(), thr,
-                                         ws_u8_list_.as<uint32_t>(), ws_u8_listcnt_.as<int>(), tile_fail, ws_flags_.as<int>(),
-                                         d_ids_.as<int32_t>(), d_ids, d_dists, d_cnt, eb, ee, stream,
-                                         centred_ ? nullptr : static_cast<const float*>(d_queries), centred_ ? nullptr : ws_qpad_.as<float>(),
-                                         f.cosc ? ws_qaux_.as<float>() : nullptr, f.cosc ? ws_qsel_.as<float>() : nullptr, f.dp, h16),
-                      "bf_f32_fast");
-            last_path = 1;
-            fast_flags_ = tile_fail;
-            fast_nqt_ = f.nqt;
-            fast_has_precise_ = true;
-            return;
-        }
-    }
-    last_path = is_u8() ? 2 : 0;
-    BfPlan p = bf_make_plan((int)d_n_, dim_eff, (int)nq, (int)k, is_u8());
-    if (d_n_ == 0) p.ldb = is_u8() ? 128 : f32_row_stride(dim_eff);
-    const int elem = is_u8() ? 1 : 4;
-    ws_qpad_.ensure((size_t)p.qpad * p.ldb * elem);
-    ws_cand_.ensure(bf_cand_elems(p) * 8);
-    ws_cnt_.ensure(bf_cnt_elems(p) * 4);
-    hip_check(launch_pad_rows(d_queries, (int)nq, dim_eff, ws_qpad_.ptr(), p.qpad, p.ldb, elem, stream), "pad queries");
-    if (centred_) {
-        ws_qsel_.ensure((size_t)p.qpad * p.ldb * 4);
-        hip_check(launch_center_rows(ws_qpad_.as<float>(), d_mean_.as<float>(), p.qpad, (int)nq, p.ldb, dim_eff,
-                                     ws_qsel_.as<float>(), stream),
-                  "centre queries");
-        if (space_ != SP_L2) {
-            ws_qaux_.ensure((size_t)p.qpad * 16);
-            hip_check(launch_query_aux_cosc(ws_qpad_.as<float>(), ws_qsel_.as<float>(), p.qpad, p.ldb, dim_eff, mu_norm_,
-                                            ws_qaux_.as<float>(), stream),
-                      "query aux");
-        }
-    }
-    prof_begin(stream);
-    if (is_u8()) {
-        hip_check(launch_bf_select_u8(p, d_rows_i8_.as<uint8_t>(), d_aux_.as<int32_t>(), ws_qpad_.as<uint8_t>(),
-                                      ws_cand_.as<unsigned long long>(), ws_cnt_.as<int>(), stream),
-                  "bf_select_u8");
-    } else if (space_ == SP_L1 || space_ == SP_LINF) {
-        hip_check(launch_bf_select_direct_f32(p, space_, d_rows_.as<float>(), ws_qpad_.as<float>(),
-                                              ws_cand_.as<unsigned long long>(), ws_cnt_.as<int>(), stream),
-                  "bf_select_direct");
-    } else {
-        // selection + re-rank in one chain (l2: verified, with the exact tail for tiles of near-duplicates)
-        ws_flags_.ensure((size_t)p.nqt * 4 + 64);
-        hip_check(launch_bf_adaptive_f32(p, space_, dim_eff, (int)k, d_rows_.as<float>(),
-                                         centred_ ? d_rows_sel_.as<float>() : d_rows_.as<float>(), d_aux_.as<float>(),
-                                         ws_qpad_.as<float>(), centred_ ? ws_qsel_.as<float>() : ws_qpad_.as<float>(),
-                                         (centred_ && space_ != SP_L2) ? ws_qaux_.as<float>() : nullptr, bmax_,
-                                         ws_cand_.as<unsigned long long>(), ws_cnt_.as<int>(), ws_flags_.as<int>(),
-                                         d_ids_.as<int32_t>(), d_ids, d_dists, d_cnt, nullptr, 1, stream),
-                  "bf_adaptive_f32");
-        prof_end(stream);
-        return;
-    }
-    prof_end(stream);
-    hip_check(launch_bf_rerank(p, space_, dim_eff, (int)k, d_rows_.ptr(), ws_qpad_.ptr(),
-                               ws_cand_.as<unsigned long long>(), ws_cnt_.as<int>(), d_ids_.as<int32_t>(), d_ids,
-                               d_dists, d_cnt, stream),
-              "bf_rerank");
 }
 
 // The results and work counters of the current slice of a batch (knn_device sets ctr_off_): nq queries from d_ids /

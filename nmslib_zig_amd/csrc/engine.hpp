@@ -68,6 +68,12 @@ class DevBuf {
     ~DevBuf() { release(); }
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept { swap(o); }
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        release();
+        swap(o);
+        return *this;
+    }
     void* ensure(size_t bytes);  // grow-only
     void release();
     void swap(DevBuf& o);
@@ -117,6 +123,35 @@ void hnsw_build_host(int space, const void* rows, size_t n, size_t dim, const Hn
 // ... over strings: leven rows as CSR bytes (row_ptr, bytes), bit_hamming rows as W words each
 void hnsw_build_strings(int space, const int64_t* row_ptr, const uint8_t* bytes, const uint32_t* words, size_t W,
                         size_t n, const HnswBuildParams& bp, HostGraph& out);
+
+// ---- dense brute force (brute.cpp): what prepare_brute leaves for knn_brute, next to the engine's rows, ids and aux ----
+struct BruteDense {
+    // uint8: the re-centred rows (x ^ 0x80) and aux >> 1 of the fast-path scan
+    DevBuf rows_i8, auxh;
+    // float rows on un-centred data (l2, cosine, angular): selection copy (rows - column mean) and the mean
+    DevBuf rows_sel, mean;
+    bool centred = false;
+    double mu_norm = 0;       // |column mean| (centred cosine scoring)
+    double cosc_spread2 = 0;  // E|b - mean|^2 measured at finalize
+    float bmax = 0;           // largest norm of the selection rows
+    float bres = 0;           // their largest bf16 rounding residual (relative to the norm for the cosine spaces)
+    // f32 fast path: bf16 hi / lo tiles of the selection rows and their start values (split-product scan); fp16 tiles of
+    // the rows times f16_scale and their start values (one-product scan)
+    DevBuf bf_hi, bf_lo, auxp, f16_hi, auxp16;
+    bool have_bf16 = false;
+    float f16_scale = 1.f, bres16 = 0;   // power-of-two scale of the fp16 tiles, the rows' largest fp16 residual
+    float f16_scale_q = 1.f;             // scale of a batch's fp16 queries (the rows' scale, except centred cosine)
+    float cosc_lambda = 1.f;             // centred cosine on the fast path: scale of the two constant columns (row_aug_cosc_kernel)
+    float bmax_c = 0, bres_c = 0;        // largest norm / bf16 rounding residual of the augmented rows
+    // per-batch workspaces (grow-only, not resident data): the blocks of BfFastWs; the augmented queries of centred
+    // cosine on the fast path; verified l2 path: query tiles whose proof failed (exact tail)
+    DevBuf ws_top8, ws_thr, ws_list, ws_listcnt, ws_f32_q, ws_qaug, ws_flags;
+
+    void release();        // drops the fast-path tiles
+    size_t bytes() const;  // every resident buffer (no workspace)
+    // the tiles as a launch part; dp: the plan's row length; augmented: they were cut from the augmented rows
+    BfF32Tiles tiles(int dp, bool augmented) const;
+};
 
 // ---- the index ---------------------------------------------------------------------------------
 enum class Method { Brute, Hnsw };
@@ -294,6 +329,10 @@ class Engine {
     void build_graph_gpu_pass(const std::vector<int32_t>& levels, bool reverse);
     void prepare_graph_rows();
     void upload_graph();
+    // dense brute force (brute.cpp)
+    void prepare_brute();
+    void measure_rows_f16(const float* rows, size_t n, int ld, int dim, bool relative, float* bm);
+    void make_fast_tiles(const BfSplitSrc& src, int dp, const float* aux, float aux_pad, float aux16_mul);
     void knn_brute(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
                    int32_t* d_cnt, hipStream_t stream);
     void knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
@@ -345,25 +384,8 @@ class Engine {
     // device state
     int device_ = -1;
     hipStream_t stream_ = nullptr;
-    DevBuf d_rows_, d_rows_i8_, d_aux_, d_ids_, d_links0_, d_up_off_, d_up_links_, d_rownorm_;
-    DevBuf d_auxh_;  // uint8 brute force: aux >> 1 (fast-path scan)
-    DevBuf d_f16_hi_, d_auxp16_;   // fp16 tiles of the selection rows times f16_scale_ and their start values (one-product scan)
-    DevBuf d_bf_hi_, d_bf_lo_, d_auxp_, ws_f32_q_;  // f32 fast path: bf16 hi / lo tiles of the selection rows, padded aux, split queries
-    bool have_bf16_ = false;
-    float f16_scale_q_ = 1.f;              // ... and of the batch's fp16 queries (the rows' scale, except centred cosine)
-    float f16_scale_ = 1.f, bres16_ = 0;   // one-product scan: power-of-two scale of its fp16 tiles, the rows' largest fp16 residual
-    void measure_rows_f16(const float* rows, size_t n, int ld, int dim, bool relative, float* bm);
-    float bmax_ = 0;  // largest norm of the selection rows
-    float bres_ = 0;  // their largest bf16 rounding residual (relative to the norm for the cosine spaces)
-    DevBuf ws_u8_cand_, ws_u8_cnt_, ws_u8_thr_, ws_u8_list_, ws_u8_listcnt_;
-    DevBuf ws_flags_;   // verified l2 path: query tiles whose proof failed (exact tail)
-    DevBuf d_rows_sel_, d_mean_;  // brute-force L2 on un-centred data: selection copy (rows - column mean) and the mean
-    bool centred_ = false;
-    double mu_norm_ = 0;  // |column mean| (centred cosine scoring)
-    double cosc_spread2_ = 0;          // E|b - mean|^2 measured at finalize
-    float cosc_lambda_ = 1.f;          // centred cosine on the fast path: scale of the two constant columns (row_aug_cosc_kernel)
-    float bmax_c_ = 0, bres_c_ = 0;    // largest norm / bf16 rounding residual of the augmented rows
-    DevBuf ws_qaug_;                   // augmented queries of a batch
+    DevBuf d_rows_, d_aux_, d_ids_, d_links0_, d_up_off_, d_up_links_, d_rownorm_;
+    BruteDense brute_;
     size_t d_n_ = 0;
     int ldb_ = 0;
     HnswDeviceGraph dg_{};
@@ -379,6 +401,7 @@ class Engine {
     bool have_counters_ = false;
     bool prof_ = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events_;
+    std::pair<hipEvent_t, hipEvent_t> prof_pair();  // a new pair of prof_events_ (nulls: not profiling)
     void prof_begin(hipStream_t s);
     void prof_end(hipStream_t s);
 };

@@ -3369,14 +3369,16 @@ static hipError_t launch_select_mode(const BfPlan& p, const BfArgs& a, hipStream
 #endif
 }
 
-static BfArgs make_args(const BfPlan& p, const float* base, const float* aux, const float* q, u64* cand,
-                        int* cnt, uint32_t* gthr) {
+static BfArgs make_args(const BfPlan& p, const float* base, const float* aux, const float* q, const BfCand& c,
+                        const BfGate& gate, uint32_t* gthr) {
     BfArgs a{};
     a.base = base;
     a.aux = aux;
     a.queries = q;
-    a.cand = cand;
-    a.cand_cnt = cnt;
+    a.cand = c.cand;
+    a.cand_cnt = c.cnt;
+    a.tile_fail = gate.flags;
+    a.fail_group = gate.tiles;
     a.gthr = gthr;
     a.gq = gthr + p.qpad;
     a.xj = p.xj;
@@ -3395,31 +3397,24 @@ static BfArgs make_args(const BfPlan& p, const float* base, const float* aux, co
     return a;
 }
 
-hipError_t launch_bf_select_f32(const BfPlan& p, int space, const float* base, const float* aux,
-                                const float* queries_padded, const float* qaux_cosc, unsigned long long* cand,
-                                int* cand_cnt, hipStream_t s) {
-    return launch_bf_select_f32_ex(p, space, base, aux, queries_padded, qaux_cosc, cand, cand_cnt, nullptr, 1, s);
-}
-
-hipError_t launch_bf_select_f32_ex(const BfPlan& p, int space, const float* base, const float* aux,
-                                   const float* queries_padded, const float* qaux_cosc, unsigned long long* cand,
-                                   int* cand_cnt, const int* tile_fail, int fail_group, hipStream_t s, bool cleared) {
+// MFMA selection of the adaptive path.  qaux_cosc != null (cosine / angular only): base and queries are CENTRED copies,
+// aux holds three planes (launch_row_aux_cosc) and qaux_cosc the per-query constants (launch_query_aux_cosc).
+static hipError_t select_f32(const BfPlan& p, int space, const float* base, const float* aux, const float* queries_padded,
+                             const float* qaux_cosc, const BfCand& c, const BfGate& gate, hipStream_t s, bool cleared) {
     // per-query shared thresholds live behind the survivor counts; cleared for every batch (by the caller's prep
     // kernel when `cleared`)
-    uint32_t* gthr = reinterpret_cast<uint32_t*>(cand_cnt + (size_t)p.qpad * p.nsplit);
+    uint32_t* gthr = reinterpret_cast<uint32_t*>(c.cnt + (size_t)p.qpad * p.nsplit);
     if (!cleared) {
         hipError_t me = hipMemsetAsync(gthr, 0, ((size_t)p.qpad + (size_t)p.qpad * p.nsplit) * 4, s);
         if (me != hipSuccess) return me;
     }
-    BfArgs a = make_args(p, base, aux, queries_padded, cand, cand_cnt, gthr);
-    a.tile_fail = tile_fail;
-    a.fail_group = fail_group;
+    BfArgs a = make_args(p, base, aux, queries_padded, c, gate, gthr);
     switch (space) {
         case SP_L2: return launch_select_mode<BF_L2>(p, a, s);
         case SP_NEGDOT: return launch_select_mode<BF_DOT>(p, a, s);
         case SP_COSINE:
         case SP_ANGULAR:
-            if (qaux_cosc) {  // centred rows + three aux planes (engine: centred_)
+            if (qaux_cosc) {  // centred rows + three aux planes (engine: centred)
                 a.qaux = qaux_cosc;
                 a.aux_stride = p.n;
                 return launch_select_mode<BF_COSC>(p, a, s);
@@ -3429,58 +3424,41 @@ hipError_t launch_bf_select_f32_ex(const BfPlan& p, int space, const float* base
     }
 }
 
-hipError_t launch_bf_select_direct_f32(const BfPlan& p, int space, const float* base,
-                                       const float* queries_padded, unsigned long long* cand,
-                                       int* cand_cnt, hipStream_t s) {
-    return launch_bf_select_direct_f32_ex(p, space, base, queries_padded, cand, cand_cnt, nullptr, 1, s);
-}
-
-// SP_L2 here = squared differences summed by the VALU on the ORIGINAL rows (the exact tail of the verified l2 path)
-hipError_t launch_bf_select_direct_f32_ex(const BfPlan& p, int space, const float* base, const float* queries_padded,
-                                          unsigned long long* cand, int* cand_cnt, const int* tile_fail, int fail_group,
-                                          hipStream_t s, bool cleared_second_region) {
+hipError_t launch_bf_select_direct_f32(const BfPlan& p, int space, const float* base, const float* queries_padded,
+                                       const BfCand& c, const BfGate& gate, hipStream_t s, bool cleared_second_region) {
     const size_t gwords = (size_t)p.qpad + (size_t)p.qpad * p.nsplit;
-    uint32_t* gthr = reinterpret_cast<uint32_t*>(cand_cnt + (size_t)p.qpad * p.nsplit);
+    uint32_t* gthr = reinterpret_cast<uint32_t*>(c.cnt + (size_t)p.qpad * p.nsplit);
     if (cleared_second_region) {
         gthr += gwords;   // its own region, cleared at the start of the batch together with the first (bf_f32_prep_kernel)
     } else {
         hipError_t me = hipMemsetAsync(gthr, 0, gwords * 4, s);
         if (me != hipSuccess) return me;
     }
-    BfArgs a = make_args(p, base, nullptr, queries_padded, cand, cand_cnt, gthr);
-    a.tile_fail = tile_fail;
-    a.fail_group = fail_group;
+    BfArgs a = make_args(p, base, nullptr, queries_padded, c, gate, gthr);
     if (space == SP_L1) return launch_select_mode<BF_L1>(p, a, s);
     if (space == SP_LINF) return launch_select_mode<BF_LINF>(p, a, s);
     if (space == SP_L2) return launch_select_mode<BF_L2D>(p, a, s);
     return hipErrorInvalidValue;
 }
 
-hipError_t launch_bf_select_u8(const BfPlan& p, const uint8_t* base_i8, const int32_t* aux,
-                               const uint8_t* queries_padded, unsigned long long* cand, int* cand_cnt,
-                               hipStream_t s) {
-    return launch_bf_select_u8_ex(p, base_i8, aux, queries_padded, cand, cand_cnt, 1, nullptr, 1, s, false);
-}
-
-hipError_t launch_bf_select_u8_ex(const BfPlan& p, const uint8_t* base_i8, const int32_t* aux,
-                                  const uint8_t* queries_padded, unsigned long long* cand, int* cand_cnt,
-                                  int tile_stride, const int* tile_fail, int fail_group, hipStream_t s, bool cleared) {
+hipError_t launch_bf_select_u8(const BfPlan& p, const uint8_t* base_i8, const int32_t* aux, const uint8_t* queries_padded,
+                               const BfCand& c, const BfGate& gate, hipStream_t s, bool cleared) {
     BfArgsU8 a{};
-    a.tile_stride = tile_stride;
-    a.tile_fail = tile_fail;
-    a.fail_group = fail_group;
+    a.tile_stride = 1;
+    a.tile_fail = gate.flags;
+    a.fail_group = gate.tiles;
     a.base_i8 = base_i8;
     a.aux = aux;
     a.queries = queries_padded;
-    a.cand = cand;
-    a.cand_cnt = cand_cnt;
+    a.cand = c.cand;
+    a.cand_cnt = c.cnt;
     a.n = p.n;
     a.nqt = p.nqt;
     a.nsplit = p.nsplit;
     a.rows_per_split = p.rows_per_split;
     a.kprime = p.kprime;
     a.cap = p.cap;
-    uint32_t* gthr = reinterpret_cast<uint32_t*>(cand_cnt + (size_t)p.qpad * p.nsplit);
+    uint32_t* gthr = reinterpret_cast<uint32_t*>(c.cnt + (size_t)p.qpad * p.nsplit);
     a.gq = gthr + p.qpad;
     a.xj = p.xj;
     a.xm = p.xm;
@@ -3498,44 +3476,24 @@ hipError_t launch_bf_select_u8_ex(const BfPlan& p, const uint8_t* base_i8, const
     return hipGetLastError();
 }
 
-hipError_t launch_bf_rerank(const BfPlan& p, int space, int dim, int k, const void* base,
-                            const void* queries_padded, const unsigned long long* cand,
-                            const int* cand_cnt, const int32_t* ext_ids, int32_t* out_ids,
-                            float* out_dists, int32_t* out_cnt, hipStream_t s) {
-    return launch_bf_rerank_ex(p, space, dim, k, base, queries_padded, cand, cand_cnt, ext_ids, out_ids, out_dists,
-                               out_cnt, nullptr, 1, s);
-}
-
-hipError_t launch_bf_rerank_ex(const BfPlan& p, int space, int dim, int k, const void* base,
-                               const void* queries_padded, const unsigned long long* cand,
-                               const int* cand_cnt, const int32_t* ext_ids, int32_t* out_ids,
-                               float* out_dists, int32_t* out_cnt, const int* tile_fail, int fail_queries,
-                               hipStream_t s) {
-    return launch_bf_rerank_verify(p, space, dim, k, base, queries_padded, cand, cand_cnt, ext_ids, out_ids, out_dists,
-                                   out_cnt, tile_fail, fail_queries, nullptr, nullptr, 0.f, s);
-}
-
-hipError_t launch_bf_rerank_verify(const BfPlan& p, int space, int dim, int k, const void* base,
-                                   const void* queries_padded, const unsigned long long* cand,
-                                   const int* cand_cnt, const int32_t* ext_ids, int32_t* out_ids,
-                                   float* out_dists, int32_t* out_cnt, const int* tile_fail, int fail_queries,
-                                   int* verify_flags, const float* queries_sel, float bmax, hipStream_t s) {
+hipError_t launch_bf_rerank(const BfPlan& p, int space, int dim, int k, const void* base, const void* queries_padded,
+                            const BfCand& c, const BfGate& gate, const BfVerify& verify, const BfOut& out, hipStream_t s) {
     RerankArgs a{};
-    a.verify_flags = verify_flags;
+    a.verify_flags = verify.flags;
     a.verify_queries = BF_TQ;
-    a.queries_sel = queries_sel;
-    a.bmax = bmax;
+    a.queries_sel = verify.queries_sel;
+    a.bmax = verify.bmax;
     a.eps_rel = 1.5f * (float)(dim + 2) * 5.9604645e-8f;   // (D + 2) roundings of 2^-24, half again for the aux term
-    a.tile_fail = tile_fail;
-    a.fail_queries = fail_queries;
+    a.tile_fail = gate.flags;
+    a.fail_queries = gate.tiles * BF_TQ;
     a.base = base;
     a.queries = queries_padded;
-    a.cand = cand;
-    a.cand_cnt = cand_cnt;
-    a.ext_ids = ext_ids;
-    a.out_ids = out_ids;
-    a.out_dists = out_dists;
-    a.out_cnt = out_cnt;
+    a.cand = c.cand;
+    a.cand_cnt = c.cnt;
+    a.ext_ids = out.ext_ids;
+    a.out_ids = out.ids;
+    a.out_dists = out.dists;
+    a.out_cnt = out.cnt;
     a.space = space;
     a.dim = dim;
     a.ldb = p.ldb;
@@ -3552,32 +3510,26 @@ hipError_t launch_bf_rerank_verify(const BfPlan& p, int space, int dim, int k, c
 }
 
 // The adaptive f32 selection + re-rank, verified for l2 (see bf_rerank_kernel), with the exact tail: tiles whose proof
-// fails are selected again by BF_L2D on the original rows.  `gate` / gate_tiles: run only the query-tile groups flagged
-// by an earlier stage (the fast paths' fallback), or null.  flags: [p.nqt] ints of workspace.
-hipError_t launch_bf_adaptive_f32(const BfPlan& p, int space, int dim, int k, const float* base_orig, const float* sel_rows,
-                                  const float* aux, const float* queries_orig, const float* queries_sel,
-                                  const float* qaux_cosc, float bmax, unsigned long long* cand, int* cand_cnt, int* flags,
-                                  const int32_t* ext_ids, int32_t* out_ids, float* out_dists, int32_t* out_cnt,
-                                  const int* gate, int gate_tiles, hipStream_t s, bool cleared) {
+// fails are selected again by BF_L2D on the original rows.  `gate`: run only the query-tile groups flagged by an earlier
+// stage (the fast paths' fallback).  flags: [p.nqt] ints of workspace.
+hipError_t launch_bf_adaptive_f32(const BfPlan& p, int space, int k, const BfF32Rows& rows, const BfF32Queries& q,
+                                  const BfCand& c, int* flags, const BfGate& gate, const BfOut& out, hipStream_t s,
+                                  bool cleared) {
     // cleared: the caller's prep kernel zeroed `flags` and both shared-threshold regions at the start of the batch
-    hipError_t e = launch_bf_select_f32_ex(p, space, sel_rows, aux, queries_sel, qaux_cosc, cand, cand_cnt, gate, gate_tiles, s,
-                                           cleared);
+    hipError_t e = select_f32(p, space, rows.sel, rows.aux, q.sel, q.qaux_cosc, c, gate, s, cleared);
     if (e != hipSuccess) return e;
-    const bool verify = space == SP_L2 && flags != nullptr && bmax > 0.f;
-    if (!verify)
-        return launch_bf_rerank_ex(p, space, dim, k, base_orig, queries_orig, cand, cand_cnt, ext_ids, out_ids, out_dists,
-                                   out_cnt, gate, gate_tiles * BF_TQ, s);
+    const bool verify = space == SP_L2 && flags != nullptr && rows.bmax > 0.f;
+    if (!verify) return launch_bf_rerank(p, space, rows.dim, k, rows.orig, q.padded, c, gate, BfVerify{}, out, s);
     if (!cleared) {
         e = hipMemsetAsync(flags, 0, (size_t)p.nqt * 4, s);
         if (e != hipSuccess) return e;
     }
-    e = launch_bf_rerank_verify(p, space, dim, k, base_orig, queries_orig, cand, cand_cnt, ext_ids, out_ids, out_dists,
-                                out_cnt, gate, gate_tiles * BF_TQ, flags, queries_sel, bmax, s);
+    e = launch_bf_rerank(p, space, rows.dim, k, rows.orig, q.padded, c, gate, BfVerify{flags, q.sel, rows.bmax}, out, s);
     if (e != hipSuccess) return e;
-    e = launch_bf_select_direct_f32_ex(p, SP_L2, base_orig, queries_orig, cand, cand_cnt, flags, 1, s, cleared);
+    const BfGate failed{flags, 1};
+    e = launch_bf_select_direct_f32(p, SP_L2, rows.orig, q.padded, c, failed, s, cleared);
     if (e != hipSuccess) return e;
-    return launch_bf_rerank_ex(p, space, dim, k, base_orig, queries_orig, cand, cand_cnt, ext_ids, out_ids, out_dists,
-                               out_cnt, flags, BF_TQ, s);
+    return launch_bf_rerank(p, space, rows.dim, k, rows.orig, q.padded, c, failed, BfVerify{}, out, s);
 }
 
 // ---- uint8 fast path (see bf_scan_u8_kernel) ----------------------------------------------------------------
@@ -3630,22 +3582,23 @@ BfU8Fast bf_u8_fast_plan(int n, int nq, int k) {
     return f;
 }
 
-hipError_t launch_bf_u8_fast(const BfU8Fast& f, int n, int nq, int k, const uint8_t* base_u8, const uint8_t* base_i8,
-                             const int32_t* aux, const int32_t* auxh, const uint8_t* queries_padded,
-                             int* top8, unsigned long long* cand_fb, int* cnt_fb,
-                             int* thr, uint32_t* list, int* list_cnt, int* tile_fail, const int32_t* ext_ids,
-                             int32_t* out_ids, float* out_dists, int32_t* out_cnt, hipEvent_t scan_begin,
-                             hipEvent_t scan_end, hipStream_t s, const uint8_t* queries_raw) {
+hipError_t launch_bf_u8_fast(const BfU8Fast& f, int nq, int k, const BfU8Rows& rows, const uint8_t* queries_raw,
+                             uint8_t* queries_padded, const BfFastWs& ws, const BfOut& out, const BfScanEvents& ev,
+                             hipStream_t s) {
+    int* top8 = static_cast<int*>(ws.top8);
+    int* thr = static_cast<int*>(ws.thr);
+    int* tile_fail = ws.tile_fail(f);
+    const BfGate failed{tile_fail, f.qg};
     hipError_t e;
     {   // pad the queries (queries_raw [nq][128] -> queries_padded [qpad][128]) + every clear of the batch
         const BfPlan& fb = f.fallback;
-        uint32_t* gthr = reinterpret_cast<uint32_t*>(cnt_fb + (size_t)fb.qpad * fb.nsplit);
+        uint32_t* gthr = reinterpret_cast<uint32_t*>(ws.fb.cnt + (size_t)fb.qpad * fb.nsplit);
         const size_t gwords = (size_t)fb.qpad + (size_t)fb.qpad * fb.nsplit;
         const size_t work = (size_t)f.qpad * 32 > gwords ? (size_t)f.qpad * 32 : gwords;
         size_t grid = (work + 255) / 256;
         if (grid > 2048) grid = 2048;
-        hipLaunchKernelGGL(bf_u8_prep_kernel, dim3((unsigned)grid), dim3(256), 0, s, queries_raw, nq,
-                           const_cast<uint8_t*>(queries_padded), f.qpad, tile_fail, f.nqt, gthr, gwords);
+        hipLaunchKernelGGL(bf_u8_prep_kernel, dim3((unsigned)grid), dim3(256), 0, s, queries_raw, nq, queries_padded, f.qpad,
+                           tile_fail, f.nqt, gthr, gwords);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -3659,10 +3612,10 @@ hipError_t launch_bf_u8_fast(const BfU8Fast& f, int n, int nq, int k, const uint
     };
     // 1. sample pass + thresholds
     BfScanArgs sa{};
-    sa.base_i8 = base_i8;
-    sa.auxh = auxh;
+    sa.base_i8 = rows.i8;
+    sa.auxh = rows.auxh;
     sa.queries = queries_padded;
-    sa.n = n;
+    sa.n = rows.n;
     const int s_nqt = f.qpad / (BF_TQ * f.qg);
     sa.nqt = s_nqt;
     sa.nsplit = f.s_nsplit;
@@ -3687,34 +3640,34 @@ hipError_t launch_bf_u8_fast(const BfU8Fast& f, int n, int nq, int k, const uint
     if (e != hipSuccess) return e;
     // 2. scan with fixed thresholds (tile flags: cleared by the preparation kernel)
     BfScanArgs a{};
-    a.base_i8 = base_i8;
-    a.auxh = auxh;
+    a.base_i8 = rows.i8;
+    a.auxh = rows.auxh;
     a.queries = queries_padded;
     a.thr = thr;
-    a.list = list;
-    a.list_cnt = list_cnt;
-    a.n = n;
+    a.list = ws.list;
+    a.list_cnt = ws.list_cnt;
+    a.n = rows.n;
     a.nqt = f.nqt;
     a.nsplit = f.nsplit;
     a.tps = f.tps;
     a.caph = f.caph;
     a.tile_stride = 1;
-    if (scan_begin) (void)hipEventRecord(scan_begin, s);
+    if (ev.first) (void)hipEventRecord(ev.first, s);
     e = scan(a, 8 * f.nqt * (f.nsplit / 8));
-    if (scan_end) (void)hipEventRecord(scan_end, s);
+    if (ev.second) (void)hipEventRecord(ev.second, s);
     if (e != hipSuccess) return e;
     // 3. exact re-rank of the listed rows + verification
     RerankListArgs r{};
-    r.base = base_u8;
+    r.base = rows.orig;
     r.queries = queries_padded;
-    r.list = list;
-    r.list_cnt = list_cnt;
-    r.ext_ids = ext_ids;
-    r.out_ids = out_ids;
-    r.out_dists = out_dists;
-    r.out_cnt = out_cnt;
+    r.list = ws.list;
+    r.list_cnt = ws.list_cnt;
+    r.ext_ids = out.ext_ids;
+    r.out_ids = out.ids;
+    r.out_dists = out.dists;
+    r.out_cnt = out.cnt;
     r.tile_fail = tile_fail;
-    r.n = n;
+    r.n = rows.n;
     r.k = k;
     r.nsplit = f.nsplit;
     r.caph = f.caph;
@@ -3728,10 +3681,9 @@ hipError_t launch_bf_u8_fast(const BfU8Fast& f, int n, int nq, int k, const uint
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     // 4. fallback for flagged tile groups (workgroups of clear groups leave at once)
-    e = launch_bf_select_u8_ex(f.fallback, base_i8, aux, queries_padded, cand_fb, cnt_fb, 1, tile_fail, f.qg, s, /*cleared=*/true);
+    e = launch_bf_select_u8(f.fallback, rows.i8, rows.aux, queries_padded, ws.fb, failed, s, /*cleared=*/true);
     if (e != hipSuccess) return e;
-    return launch_bf_rerank_ex(f.fallback, SP_L2SQR_SIFT, 128, k, base_u8, queries_padded, cand_fb, cnt_fb, ext_ids, out_ids,
-                               out_dists, out_cnt, tile_fail, BF_TQ * f.qg, s);
+    return launch_bf_rerank(f.fallback, SP_L2SQR_SIFT, 128, k, rows.orig, queries_padded, ws.fb, failed, BfVerify{}, out, s);
 }
 
 // ---- f32 fast path (see bf_scan_f32_kernel) -----------------------------------------------------------------
@@ -3817,16 +3769,15 @@ hipError_t launch_row_maxnorm(const float* rows, int n, int ld, int dim, bool re
     return hipGetLastError();
 }
 
-hipError_t launch_split_bf16(const float* src, int rows, int rows_pad, int ld, int dim, void* hi, void* lo,
-                             const float* aux, float aux_pad, float* auxp, hipStream_t s, int dp, void* h16, float scale,
-                             float* auxp16, float aux16_mul) {
-    const size_t total = (size_t)rows_pad * dp;
+hipError_t launch_split_bf16(const BfSplitSrc& src, const float* aux, float aux_pad, float aux16_mul, const BfF32Tiles& dst,
+                             hipStream_t s) {
+    const size_t total = (size_t)src.n_pad * dst.dp;
     if (total == 0) return hipSuccess;
     size_t grid = (total + 255) / 256;
     if (grid > 16384) grid = 16384;
-    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)grid), dim3(256), 0, s, src, rows, rows_pad, ld, dim,
-                       static_cast<__bf16*>(hi), static_cast<__bf16*>(lo), aux, aux_pad, auxp, dp, static_cast<_Float16*>(h16),
-                       scale, auxp16, aux16_mul);
+    hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)grid), dim3(256), 0, s, src.rows, src.n, src.n_pad, src.ld, src.cols,
+                       static_cast<__bf16*>(dst.hi), static_cast<__bf16*>(dst.lo), aux, aux_pad, dst.auxp, dst.dp,
+                       static_cast<_Float16*>(dst.h16), dst.scale, dst.auxp16, aux16_mul);
     return hipGetLastError();
 }
 
@@ -3883,31 +3834,74 @@ static hipError_t launch_scan_f32_mode(const BfScanF32Args& a, bool sample, int 
     return launch_scan_f32_one<MODE, false, 2>(a, grid, lds, s);
 }
 
-hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int n, int dim, int ldb, int nq, int k, const float* base_orig,
-                              const float* sel_rows, const float* aux, const void* base_hi, const void* base_lo,
-                              const float* auxp, float bmax, float bres, const float* queries_orig, const float* queries_sel,
-                              void* q_hi, void* q_lo, float* top8, unsigned long long* cand_fb, int* cnt_fb, float* thr,
-                              uint32_t* list, int* list_cnt, int* tile_fail, int* flags_fb, const int32_t* ext_ids,
-                              int32_t* out_ids, float* out_dists, int32_t* out_cnt, hipEvent_t scan_begin,
-                              hipEvent_t scan_end, hipStream_t s, const float* queries_raw, float* queries_pad_out,
-                              const float* qaux_cosc, const float* queries_centred, int sel_ld, const BfF16Side& h16) {
-    // centred cosine / angular (f.cosc): queries_sel holds the augmented queries q+ [qpad][sel_ld] of f.sel_dim columns and
-    // base_hi / base_lo the augmented rows (bmax / bres: theirs); queries_centred + qaux_cosc serve the adaptive fallback
-    const int sdim = f.cosc ? f.sel_dim : dim, sld = f.cosc ? sel_ld : ldb;
-    float* thr1 = thr + f.qpad;
-    int* precise = tile_fail + f.nqt;
+// NMSLIB_GPU_DEBUG & 4096: phase clocks of the list re-rank, printed after the launch
+static void dump_rerank_list_clocks(const unsigned long long* d_prof, hipStream_t s) {
+    unsigned long long h[16];
+    (void)hipStreamSynchronize(s);
+    (void)hipMemcpy(h, d_prof, sizeof(h), hipMemcpyDeviceToHost);
+    const double wg = h[10] ? (double)h[10] : 1.0;
+    fprintf(stderr, "[rerank f32 list] workgroups %llu rows/query %.1f P %.1f | us since start: prefix %.2f gather %.2f distances %.2f "
+            "sort %.2f proof %.2f out %.2f\n", h[10], h[8] / wg, h[9] / wg, h[0] / wg / 100, h[1] / wg / 100, h[2] / wg / 100,
+            h[3] / wg / 100, h[4] / wg / 100, h[5] / wg / 100);
+}
+
+// NMSLIB_GPU_DEBUG & 2048: checksums of the intermediate buffers of this batch (determinism screens)
+static void dump_f32_fast_checksums(const BfF32Fast& f, const BfFastWs& ws, hipStream_t s) {
+    (void)hipStreamSynchronize(s);
+    auto sum = [&](const void* d, size_t bytes) -> unsigned long long {
+        std::vector<uint32_t> h(bytes / 4);
+        (void)hipMemcpy(h.data(), d, bytes, hipMemcpyDeviceToHost);
+        unsigned long long x = 1469598103934665603ull;
+        for (uint32_t v : h) x = (x ^ v) * 1099511628211ull;
+        return x;
+    };
+    std::vector<int> cnt((size_t)f.qpad * f.nsplit * 2);
+    (void)hipMemcpy(cnt.data(), ws.list_cnt, cnt.size() * 4, hipMemcpyDeviceToHost);
+    std::vector<uint32_t> lst((size_t)f.qpad * f.nsplit * 2 * f.caph);
+    (void)hipMemcpy(lst.data(), ws.list, lst.size() * 4, hipMemcpyDeviceToHost);
+    unsigned long long lx = 1469598103934665603ull;   // only the entries that exist
+    long long rows = 0;
+    const size_t nl = (size_t)f.nsplit * 2;
+    for (size_t i = 0; i < cnt.size(); ++i) {
+        rows += cnt[i];
+        int have = 0;
+        for (int j = 0; j < f.caph && have < cnt[i]; ++j) {
+            const uint32_t e = lst[((i / nl) * f.caph + j) * nl + i % nl];
+            lx = (lx ^ e) * 1099511628211ull;
+            have += __builtin_popcount(e & 0xffffu);
+        }
+    }
+    fprintf(stderr, "[f32fast] top8 %016llx thr %016llx thr1 %016llx flags %016llx cnt %016llx list %016llx rows %lld\n",
+            sum(ws.top8, bf_fast_ws_bytes(f).top8), sum(ws.thr, (size_t)f.qpad * 4), sum(ws.thr1(f), (size_t)f.qpad * 4),
+            sum(ws.tile_fail(f), (size_t)f.nqt * 8), sum(ws.list_cnt, cnt.size() * 4), lx, rows);
+}
+
+hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, const BfF32Rows& rows, const BfF32Tiles& tiles,
+                              const BfF32Queries& q, const BfFastWs& ws, const BfOut& out, const BfScanEvents& ev,
+                              hipStream_t s) {
+    // centred cosine / angular (f.cosc): q.sel holds the augmented queries q+ [qpad][q.sel_ld] of f.sel_dim columns and
+    // `tiles` the augmented rows (bmax / bres: theirs); q.centred + q.qaux_cosc serve the adaptive fallback
+    const int sdim = f.cosc ? f.sel_dim : rows.dim, sld = f.cosc ? q.sel_ld : rows.ldb;
+    float* top8 = static_cast<float*>(ws.top8);
+    float* thr = static_cast<float*>(ws.thr);
+    float* thr1 = ws.thr1(f);
+    int* tile_fail = ws.tile_fail(f);
+    int* precise = ws.precise(f);
+    void* q_hi = ws.q_tile(f, BfFastWs::Q_HI);
+    void* q_lo = ws.q_tile(f, BfFastWs::Q_LO);
+    void* q_h16 = ws.q_tile(f, BfFastWs::Q_H16);
     hipError_t e;
     {   // pad (when the caller passes the raw queries) + bf16 split + every clear of the batch
         const BfPlan& fb = f.fallback;
-        uint32_t* gthr = reinterpret_cast<uint32_t*>(cnt_fb + (size_t)fb.qpad * fb.nsplit);
+        uint32_t* gthr = reinterpret_cast<uint32_t*>(ws.fb.cnt + (size_t)fb.qpad * fb.nsplit);
         const size_t gwords = 2 * ((size_t)fb.qpad + (size_t)fb.qpad * fb.nsplit);
         size_t work = (size_t)f.qpad * f.dp > gwords ? (size_t)f.qpad * f.dp : gwords;
         size_t grid = (work + 255) / 256;
         if (grid > 2048) grid = 2048;
-        hipLaunchKernelGGL(bf_f32_prep_kernel, dim3((unsigned)grid), dim3(256), 0, s, queries_raw, nq, sdim, queries_sel, f.qpad,
-                           sld, queries_pad_out, f.kch > 1 ? nullptr : static_cast<__bf16*>(q_hi),
+        hipLaunchKernelGGL(bf_f32_prep_kernel, dim3((unsigned)grid), dim3(256), 0, s, q.raw, nq, sdim, q.sel, f.qpad,
+                           sld, q.raw ? q.padded : nullptr, f.kch > 1 ? nullptr : static_cast<__bf16*>(q_hi),
                            f.kch > 1 ? nullptr : static_cast<__bf16*>(q_lo),
-                           tile_fail, 2 * f.nqt, flags_fb, fb.nqt, gthr, gwords, f.dp, static_cast<_Float16*>(h16.q_h16), h16.scale_q);
+                           tile_fail, 2 * f.nqt, ws.flags_fb, fb.nqt, gthr, gwords, f.dp, static_cast<_Float16*>(q_h16), q.scale_q);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     }
@@ -3918,19 +3912,19 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int n, int dim, int
         return launch_scan_f32_mode<SC_COS>(sa, sample, terms, f.qg, grid, lds, s, f.kch);
     };
     BfScanF32Args a{};
-    a.base_hi = static_cast<const __bf16*>(base_hi);
-    a.base_lo = static_cast<const __bf16*>(base_lo);
-    a.auxp = auxp;
+    a.base_hi = static_cast<const __bf16*>(tiles.hi);
+    a.base_lo = static_cast<const __bf16*>(tiles.lo);
+    a.auxp = tiles.auxp;
     a.q_hi = static_cast<const __bf16*>(q_hi);
     a.q_lo = static_cast<const __bf16*>(q_lo);
-    a.base_h16 = h16.base_h16;
+    a.base_h16 = tiles.h16;
     {
         static const int prio = getenv("NMSLIB_GPU_BF16_PRIO") ? atoi(getenv("NMSLIB_GPU_BF16_PRIO")) : 0;
         a.prio_half = prio;
     }
-    a.q_h16 = h16.q_h16;
-    a.auxp16 = h16.auxp16;
-    a.n = n;
+    a.q_h16 = q_h16;
+    a.auxp16 = tiles.auxp16;
+    a.n = rows.n;
     a.nqt = f.nqt;
     // 1. sample pass (one product: the scores carry the error E1) + thresholds + the choice of the scan per query tile
     BfScanF32Args sa = a;
@@ -3947,8 +3941,8 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int n, int dim, int
         const int depth = f.rcap <= 64 && f.s_nsplit >= 32 ? 4 : 8;
         const dim3 tgrid((f.qpad + 3) / 4);
 #define BF_THR_ARGS                                                                                                               \
-    top8, 2 * f.s_nsplit, depth, f.r, f.rcap, nq, f.qpad, queries_sel, sld, sdim, h16.scale * (f.mode == 2 ? 1.0f : bmax), h16.bres16, f.tq, \
-        f.force_precise ? 1 : (dbg_nohit ? 2 : 0), thr, thr1, precise, h16.scale_q, h16.scale * h16.scale_q
+    top8, 2 * f.s_nsplit, depth, f.r, f.rcap, nq, f.qpad, q.sel, sld, sdim, tiles.scale * (f.mode == 2 ? 1.0f : tiles.bmax), tiles.bres16, f.tq, \
+        f.force_precise ? 1 : (dbg_nohit ? 2 : 0), thr, thr1, precise, q.scale_q, tiles.scale * q.scale_q
         if (2 * f.s_nsplit * depth <= 512) hipLaunchKernelGGL(bf_f32_threshold_kernel<8>, tgrid, dim3(256), 0, s, BF_THR_ARGS);
         else hipLaunchKernelGGL(bf_f32_threshold_kernel<16>, tgrid, dim3(256), 0, s, BF_THR_ARGS);   // (s_nsplit <= 64)
 #undef BF_THR_ARGS
@@ -3956,15 +3950,15 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int n, int dim, int
     e = hipGetLastError();
     if (e != hipSuccess) return e;
     // 2. scan with fixed thresholds: every query tile by one of the two kernels (the other's workgroups leave at once)
-    a.list = list;
-    a.list_cnt = list_cnt;
+    a.list = ws.list;
+    a.list_cnt = ws.list_cnt;
     a.nsplit = f.nsplit;
     a.tps = f.tps;
     a.caph = f.caph;
     a.tile_stride = 1;
     a.group_flag = precise;
     const int grid = 8 * f.nqt * (f.nsplit / 8);
-    if (scan_begin) (void)hipEventRecord(scan_begin, s);
+    if (ev.first) (void)hipEventRecord(ev.first, s);
     if (!f.force_precise) {
         a.thr = thr1;
         a.group_want = 0;
@@ -3974,20 +3968,20 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int n, int dim, int
     a.thr = thr;
     a.group_want = 1;
     e = scan(a, false, 3, grid);
-    if (scan_end) (void)hipEventRecord(scan_end, s);
+    if (ev.second) (void)hipEventRecord(ev.second, s);
     if (e != hipSuccess) return e;
     // 3. exact re-rank (reference formula, original rows) + verification
     RerankListF32Args r{};
-    r.base = base_orig;
-    r.queries = queries_orig;
-    r.list = list;
-    r.list_cnt = list_cnt;
-    r.ext_ids = ext_ids;
-    r.out_ids = out_ids;
-    r.out_dists = out_dists;
-    r.out_cnt = out_cnt;
+    r.base = rows.orig;
+    r.queries = q.padded;
+    r.list = ws.list;
+    r.list_cnt = ws.list_cnt;
+    r.ext_ids = out.ext_ids;
+    r.out_ids = out.ids;
+    r.out_dists = out.dists;
+    r.out_cnt = out.cnt;
     r.tile_fail = tile_fail;
-    r.n = n;
+    r.n = rows.n;
     r.k = k;
     r.nsplit = f.nsplit;
     r.caph = f.caph;
@@ -3996,23 +3990,23 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int n, int dim, int
     r.fail_queries = f.tq;
     r.no_split = f.kch > 1 ? 1 : 0;
     r.space = space;
-    r.dim = dim;
-    r.ldb = ldb;
-    r.queries_sel = queries_sel;
+    r.dim = rows.dim;
+    r.ldb = rows.ldb;
+    r.queries_sel = q.sel;
     r.sel_dim = sdim;
     r.sel_ld = sld;
-    r.scale = h16.scale;
-    r.scale_q = h16.scale_q;
-    r.bres16 = h16.bres16;
-    r.qaux = f.cosc ? qaux_cosc : nullptr;
+    r.scale = tiles.scale;
+    r.scale_q = q.scale_q;
+    r.bres16 = tiles.bres16;
+    r.qaux = f.cosc ? q.qaux_cosc : nullptr;
     r.thr = thr;
     r.thr1 = thr1;
     r.precise = precise;
-    r.bmax = bmax;
-    r.bres = bres;
-    static const int dbg_prof = getenv("NMSLIB_GPU_DEBUG") ? atoi(getenv("NMSLIB_GPU_DEBUG")) : 0;
+    r.bmax = tiles.bmax;
+    r.bres = tiles.bres;
+    static const int dbg = getenv("NMSLIB_GPU_DEBUG") ? atoi(getenv("NMSLIB_GPU_DEBUG")) : 0;
     static unsigned long long* d_prof = nullptr;
-    if (dbg_prof & 4096) {
+    if (dbg & 4096) {
         if (!d_prof) (void)hipMalloc(&d_prof, 16 * 8);
         (void)hipMemsetAsync(d_prof, 0, 16 * 8, s);
         r.prof = d_prof;
@@ -4023,52 +4017,14 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int n, int dim, int
     hipLaunchKernelGGL(bf_rerank_f32_list_kernel, dim3(nq), dim3(256), f.lds_rerank, s, r);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (dbg_prof & 4096) {
-        unsigned long long h[16];
-        (void)hipStreamSynchronize(s);
-        (void)hipMemcpy(h, d_prof, sizeof(h), hipMemcpyDeviceToHost);
-        const double wg = h[10] ? (double)h[10] : 1.0;
-        fprintf(stderr, "[rerank f32 list] workgroups %llu rows/query %.1f P %.1f | us since start: prefix %.2f gather %.2f distances %.2f "
-                "sort %.2f proof %.2f out %.2f\n", h[10], h[8] / wg, h[9] / wg, h[0] / wg / 100, h[1] / wg / 100, h[2] / wg / 100,
-                h[3] / wg / 100, h[4] / wg / 100, h[5] / wg / 100);
-    }
-    {   // NMSLIB_GPU_DEBUG & 2048: checksums of the intermediate buffers of this batch (determinism screens)
-        static const int dbg = getenv("NMSLIB_GPU_DEBUG") ? atoi(getenv("NMSLIB_GPU_DEBUG")) : 0;
-        if (dbg & 2048) {
-            (void)hipStreamSynchronize(s);
-            auto sum = [&](const void* d, size_t bytes) -> unsigned long long {
-                std::vector<uint32_t> h(bytes / 4);
-                (void)hipMemcpy(h.data(), d, bytes, hipMemcpyDeviceToHost);
-                unsigned long long x = 1469598103934665603ull;
-                for (uint32_t v : h) x = (x ^ v) * 1099511628211ull;
-                return x;
-            };
-            std::vector<int> cnt((size_t)f.qpad * f.nsplit * 2);
-            (void)hipMemcpy(cnt.data(), list_cnt, cnt.size() * 4, hipMemcpyDeviceToHost);
-            std::vector<uint32_t> lst((size_t)f.qpad * f.nsplit * 2 * f.caph);
-            (void)hipMemcpy(lst.data(), list, lst.size() * 4, hipMemcpyDeviceToHost);
-            unsigned long long lx = 1469598103934665603ull;   // only the entries that exist
-            long long rows = 0;
-            const size_t nl = (size_t)f.nsplit * 2;
-            for (size_t i = 0; i < cnt.size(); ++i) {
-                rows += cnt[i];
-                int have = 0;
-                for (int j = 0; j < f.caph && have < cnt[i]; ++j) {
-                    const uint32_t e = lst[((i / nl) * f.caph + j) * nl + i % nl];
-                    lx = (lx ^ e) * 1099511628211ull;
-                    have += __builtin_popcount(e & 0xffffu);
-                }
-            }
-            fprintf(stderr, "[f32fast] top8 %016llx thr %016llx thr1 %016llx flags %016llx cnt %016llx list %016llx rows %lld\n",
-                    sum(top8, (size_t)f.qpad * f.s_nsplit * 2 * 8 * 4), sum(thr, (size_t)f.qpad * 4), sum(thr1, (size_t)f.qpad * 4),
-                    sum(tile_fail, (size_t)f.nqt * 8), sum(list_cnt, cnt.size() * 4), lx, rows);
-        }
-    }
+    if (dbg & 4096) dump_rerank_list_clocks(d_prof, s);
+    if (dbg & 2048) dump_f32_fast_checksums(f, ws, s);
     // 4. fallback: the adaptive f32 kernel + its re-rank (verified for l2, with its exact tail) for flagged query tiles
     //    (256 * qg queries = 2 * qg of its tiles)
-    return launch_bf_adaptive_f32(f.fallback, space, dim, k, base_orig, sel_rows, aux, queries_orig,
-                                  f.cosc ? queries_centred : queries_sel, f.cosc ? qaux_cosc : nullptr, bmax,
-                                  cand_fb, cnt_fb, flags_fb, ext_ids, out_ids, out_dists, out_cnt, tile_fail, f.tq / 128, s,
+    BfF32Queries fq = q;
+    fq.sel = f.cosc ? q.centred : q.sel;
+    fq.qaux_cosc = f.cosc ? q.qaux_cosc : nullptr;
+    return launch_bf_adaptive_f32(f.fallback, space, k, rows, fq, ws.fb, ws.flags_fb, BfGate{tile_fail, f.tq / 128}, out, s,
                                   /*cleared=*/true);
 }
 

@@ -5,6 +5,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <utility>
+
 namespace gfxknn {
 
 // Space codes (host and device).  Names: include/factory/init_spaces.h:77-86,120.
@@ -89,22 +91,83 @@ hipError_t launch_center_rows(const float* src, const float* mean, int rows, int
                               hipStream_t s);
 
 // ---- brute force: selection (MFMA) + exact re-rank ---------------------------------------
-// qaux_cosc != NULL (cosine / angular only): base and queries are CENTRED copies, aux holds three planes
-// (launch_row_aux_cosc) and qaux_cosc the per-query constants (launch_query_aux_cosc).
-hipError_t launch_bf_select_f32(const BfPlan& p, int space, const float* base, const float* aux,
-                                const float* queries_padded, const float* qaux_cosc, unsigned long long* cand,
-                                int* cand_cnt, hipStream_t s);
 hipError_t launch_row_aux_cosc(const float* orig, const float* centred, int n, int ldb, int dim, double mu_norm, float* aux,
                                hipStream_t s);
 hipError_t launch_query_aux_cosc(const float* orig, const float* centred, int nq, int ldb, int dim, double mu_norm,
                                  float* qaux, hipStream_t s);
-hipError_t launch_bf_select_u8(const BfPlan& p, const uint8_t* base_i8, const int32_t* aux,
-                               const uint8_t* queries_padded, unsigned long long* cand,
-                               int* cand_cnt, hipStream_t s);
-// ... over every tile_stride-th 64-row tile only, and/or only for the query-tile groups flagged in tile_fail
-hipError_t launch_bf_select_u8_ex(const BfPlan& p, const uint8_t* base_i8, const int32_t* aux,
-                                  const uint8_t* queries_padded, unsigned long long* cand, int* cand_cnt,
-                                  int tile_stride, const int* tile_fail, int fail_group, hipStream_t s, bool cleared = false);
+
+// ---- the named parts of a dense brute-force launch (host side) ----
+// Where a launch writes: k results per query (ids[i] = ext_ids[position], or the position without ext_ids) and the
+// number of valid results per query (cnt, optional).
+struct BfOut {
+    const int32_t* ext_ids;
+    int32_t* ids;
+    float* dists;
+    int32_t* cnt;
+};
+// Run only the query groups that an earlier stage flagged: one flag per `tiles` query tiles of BF_TQ queries.
+// flags = null: everything runs.
+struct BfGate {
+    const int* flags = nullptr;
+    int tiles = 1;
+};
+// Survivors of a selection: cand [bf_cand_elems(p)] keys, cnt [bf_cnt_elems(p)] ints (the counts, then the shared
+// thresholds and counted bounds of the selection kernels)
+struct BfCand {
+    unsigned long long* cand;
+    int* cnt;
+};
+// The l2 proof of a re-rank (bf_rerank_kernel): tiles of BF_TQ queries whose proof fails are flagged in flags [p.nqt].
+// flags = null: no verification.
+struct BfVerify {
+    int* flags = nullptr;
+    const float* queries_sel = nullptr;
+    float bmax = 0.f;
+};
+// The float rows as finalize leaves them: the originals (re-rank), the selection rows (the centred copy, or the
+// originals again), the selection rows' aux (launch_row_aux_f32, or the three planes of launch_row_aux_cosc) and largest
+// norm.  The adaptive launchers take n and ldb from their BfPlan, which is made for these rows.
+struct BfF32Rows {
+    const float *orig, *sel, *aux;
+    int n, dim, ldb;
+    float bmax;
+};
+// The float queries of a batch.  The adaptive path reads padded, sel and qaux_cosc; the fast path all of it.
+struct BfF32Queries {
+    const float* raw;        // [nq][dim] as the caller gave them: the fast path pads them into `padded` (null: already done)
+    float* padded;           // [qpad][ldb]: the re-rank's queries
+    const float* sel;        // what the selection sees: padded, its centred copy, or (fast path, centred cosine / angular)
+                             // the augmented queries [qpad][sel_ld] (launch_query_aug_cosc)
+    const float* centred;    // centred cosine / angular on the fast path: the centred copy, for the adaptive fallback
+    const float* qaux_cosc;  // centred cosine / angular: per-query constants (launch_query_aux_cosc), else null
+    int sel_ld;              // row stride of the augmented queries
+    float scale_q;           // fast path: scale of the batch's fp16 queries (l2: the rows' scale -- the start values carry the
+                             // product; centred cosine: rows are divided by their norm, queries are not)
+};
+// The uint8 rows as finalize leaves them (launch_prepare_u8)
+struct BfU8Rows {
+    const uint8_t *orig, *i8;
+    const int32_t *aux, *auxh;
+    int n;
+};
+// HIP events recorded around the scan of a fast path (null: none)
+using BfScanEvents = std::pair<hipEvent_t, hipEvent_t>;
+
+// Selections.  `cleared`: the caller's preparation kernel zeroed the shared thresholds at the start of the batch.
+hipError_t launch_bf_select_u8(const BfPlan& p, const uint8_t* base_i8, const int32_t* aux, const uint8_t* queries_padded,
+                               const BfCand& c, const BfGate& gate, hipStream_t s, bool cleared = false);
+// Direct (VALU) selection for spaces with no inner-product form (l1, linf); SP_L2 = squared differences summed on the
+// ORIGINAL rows (the exact tail of the verified l2 path; cleared_second_region: it uses the second threshold region)
+hipError_t launch_bf_select_direct_f32(const BfPlan& p, int space, const float* base, const float* queries_padded,
+                                       const BfCand& c, const BfGate& gate, hipStream_t s,
+                                       bool cleared_second_region = false);
+// Exact distances of the survivors in the reference's formula, (dist, position) order, top k.
+hipError_t launch_bf_rerank(const BfPlan& p, int space, int dim, int k, const void* base, const void* queries_padded,
+                            const BfCand& c, const BfGate& gate, const BfVerify& verify, const BfOut& out, hipStream_t s);
+// The adaptive f32 path end to end (MFMA selection, re-rank; l2: verification + exact tail).  flags: [p.nqt] ints.
+hipError_t launch_bf_adaptive_f32(const BfPlan& p, int space, int k, const BfF32Rows& rows, const BfF32Queries& q,
+                                  const BfCand& c, int* flags, const BfGate& gate, const BfOut& out, hipStream_t s,
+                                  bool cleared = false);
 
 // uint8 fast path for large batches (bf_kernels.hip: sample pass -> fixed-threshold scan -> list re-rank with
 // verification -> adaptive fallback for flagged tile groups).  Exact like the adaptive path.
@@ -119,23 +182,10 @@ struct BfU8Fast {
     int s_nsplit, s_tps;       // sample pass: splits and sample tiles per split
     BfPlan fallback;           // plan of the adaptive kernel for the fallback
 };
-inline size_t bf_u8_top8_elems(const BfU8Fast& f) { return (size_t)f.qpad * f.s_nsplit * 2 * 8; }
 BfU8Fast bf_u8_fast_plan(int n, int nq, int k);
-inline size_t bf_u8_list_elems(const BfU8Fast& f) { return (size_t)f.qpad * f.nsplit * 2 * f.caph; }
-inline size_t bf_u8_listcnt_elems(const BfU8Fast& f) { return (size_t)f.qpad * f.nsplit * 2; }
-hipError_t launch_bf_u8_fast(const BfU8Fast& f, int n, int nq, int k, const uint8_t* base_u8, const uint8_t* base_i8,
-                             const int32_t* aux, const int32_t* auxh, const uint8_t* queries_padded,
-                             int* top8, unsigned long long* cand_fb, int* cnt_fb,
-                             int* thr, uint32_t* list, int* list_cnt, int* tile_fail, const int32_t* ext_ids,
-                             int32_t* out_ids, float* out_dists, int32_t* out_cnt, hipEvent_t scan_begin,
-                             hipEvent_t scan_end, hipStream_t s, const uint8_t* queries_raw);
 
-hipError_t launch_bf_select_f32_ex(const BfPlan& p, int space, const float* base, const float* aux,
-                                   const float* queries_padded, const float* qaux_cosc, unsigned long long* cand,
-                                   int* cand_cnt, const int* tile_fail, int fail_group, hipStream_t s, bool cleared = false);
-
-// f32 fast path for large batches at D <= 128 (bf_kernels.hip: split-bf16 MFMA selection with sample-fixed thresholds,
-// exact f32 re-rank with verification, adaptive fallback).  Exact like the adaptive path.
+// f32 fast path for large batches (bf_kernels.hip: bf16 / fp16 MFMA selection with sample-fixed thresholds, exact f32
+// re-rank with verification, adaptive fallback).  Exact like the adaptive path.
 struct BfF32Fast {
     bool use;
     int mode;                  // 0 l2, 1 negdotprod (and centred cosine / angular, see cosc), 2 cosine / angular (uncentred)
@@ -155,78 +205,78 @@ struct BfF32Fast {
     BfPlan fallback;
 };
 BfF32Fast bf_f32_fast_plan(int n, int dim, int nq, int k, int space, bool cosine_centred);
-// workspace behind `thr`: [qpad] split-product thresholds, [qpad] one-product thresholds; behind `tile_fail`: [nqt]
-// fallback flags, [nqt] precise flags
-inline size_t bf_f32_thr_bytes(const BfF32Fast& f) { return (size_t)f.qpad * 8 + (size_t)f.nqt * 8 + 64; }
-inline size_t bf_f32_list_elems(const BfF32Fast& f) { return (size_t)f.qpad * f.nsplit * 2 * f.caph; }
-inline size_t bf_f32_listcnt_elems(const BfF32Fast& f) { return (size_t)f.qpad * f.nsplit * 2; }
-inline size_t bf_f32_top8_elems(const BfF32Fast& f) { return (size_t)f.qpad * f.s_nsplit * 2 * 8; }
+
+// Per-batch workspace of a fast path: one block per member, each of at least its bf_fast_ws_bytes().  What lies inside
+// a block is known here and nowhere else.
+struct BfFastWsBytes {
+    size_t top8, thr, list, list_cnt, cand, cnt, flags_fb, queries;
+};
+inline BfFastWsBytes bf_fast_ws_bytes(const BfU8Fast& f) {
+    const size_t lists = (size_t)f.qpad * f.nsplit * 2;
+    return {(size_t)f.qpad * f.s_nsplit * 2 * 8 * 4, (size_t)f.qpad * 4 + (size_t)f.nqt * 4 + 64, lists * f.caph * 4, lists * 4,
+            bf_cand_elems(f.fallback) * 8, bf_cnt_elems(f.fallback) * 4, 0, 0};
+}
+inline BfFastWsBytes bf_fast_ws_bytes(const BfF32Fast& f) {
+    const size_t lists = (size_t)f.qpad * f.nsplit * 2;
+    return {(size_t)f.qpad * f.s_nsplit * 2 * 8 * 4, (size_t)f.qpad * 8 + (size_t)f.nqt * 8 + 64, lists * f.caph * 4, lists * 4,
+            bf_cand_elems(f.fallback) * 8, bf_cnt_elems(f.fallback) * 4, (size_t)f.fallback.nqt * 4 + 64,
+            (size_t)f.qpad * f.dp * 2 * 3};
+}
+struct BfFastWs {
+    void* top8;        // sample pass: the per-lane top-8 scores (u8: int, f32: float)
+    void* thr;         // u8: [qpad] int thresholds, [nqt] fallback flags; f32: [qpad] split-product thresholds, [qpad]
+                       // one-product thresholds, [nqt] fallback flags, [nqt] precise flags
+    uint32_t* list;    // scan: the rows that reached the threshold, per (query, split, half)
+    int* list_cnt;
+    BfCand fb;         // the adaptive fallback's survivors (f.fallback)
+    int* flags_fb;     // f32: the fallback's own proof flags [f.fallback.nqt]
+    void* queries;     // f32: the converted queries, [qpad][dp] bf16 hi, bf16 lo, fp16
+
+    int* tile_fail(const BfU8Fast& f) const { return static_cast<int*>(thr) + f.qpad; }
+    float* thr1(const BfF32Fast& f) const { return static_cast<float*>(thr) + f.qpad; }
+    int* tile_fail(const BfF32Fast& f) const { return reinterpret_cast<int*>(thr1(f) + f.qpad); }
+    int* precise(const BfF32Fast& f) const { return tile_fail(f) + f.nqt; }
+    enum QueryTile { Q_HI = 0, Q_LO = 1, Q_H16 = 2 };
+    void* q_tile(const BfF32Fast& f, QueryTile t) const { return static_cast<char*>(queries) + (size_t)t * f.qpad * f.dp * 2; }
+};
+
+hipError_t launch_bf_u8_fast(const BfU8Fast& f, int nq, int k, const BfU8Rows& rows, const uint8_t* queries_raw,
+                             uint8_t* queries_padded, const BfFastWs& ws, const BfOut& out, const BfScanEvents& ev,
+                             hipStream_t s);
+
 inline int bf_f32_rows_padded(int n) { return (n + BF_BN - 1) / BF_BN * BF_BN + BF_BN; }
-// rows (or queries) -> bf16 hi / lo tiles [rows_pad][128]; auxp [rows_pad] = aux, aux_pad behind `rows` (optional)
-// largest row norm -> *out (device float)
 // out (16 bytes): [0] largest norm, [1] largest bf16 residual, [2] largest |element|, [3] largest fp16 residual of scale16 * row
 hipError_t launch_row_maxnorm(const float* rows, int n, int ld, int dim, bool relative_residual, float* out, hipStream_t s,
                               float scale16 = 0.f);
-// hi / lo / auxp: bf16 tiles of the split-product scan (nullable); h16 / auxp16: fp16(scale * row) tiles and start values
-// (aux * aux16_mul) of the one-product scan (nullable)
-hipError_t launch_split_bf16(const float* src, int rows, int rows_pad, int ld, int dim, void* hi, void* lo,
-                             const float* aux, float aux_pad, float* auxp, hipStream_t s, int dp = 128, void* h16 = nullptr,
-                             float scale = 1.f, float* auxp16 = nullptr, float aux16_mul = 1.f);
-// the one-product scan's side of a float fast-path batch: fp16 tiles of the rows (built at finalize), their start values,
-// the power-of-two scale, the rows' largest fp16 residual (scaled units), and the workspace of the batch's fp16 queries
-struct BfF16Side {
-    const void* base_h16;
-    const float* auxp16;
-    void* q_h16;
-    float scale;       // rows
-    float bres16;
-    float scale_q;     // queries (l2: the rows' scale -- the start values carry the product; centred cosine: rows are divided by
-                       // their norm, queries are not)
+// The resident side of the f32 fast path, cut from the selection rows at finalize (launch_split_bf16): bf16 hi / lo tiles
+// [n_pad][128] and start values auxp [n_pad] of the split-product scan (hi / lo: null when dp > 128); fp16(scale * row)
+// tiles [n_pad][dp] and start values auxp16 of the one-product scan, with the rows' largest fp16 residual (scaled units);
+// largest norm and bf16 residual of the rows the tiles were cut from (centred cosine / angular: the augmented rows).
+struct BfF32Tiles {
+    void *hi, *lo;
+    float* auxp;
+    void* h16;
+    float* auxp16;
+    float scale, bres16;
+    int dp;
+    float bmax, bres;
 };
-hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int n, int dim, int ldb, int nq, int k, const float* base_orig,
-                              const float* sel_rows, const float* aux, const void* base_hi, const void* base_lo,
-                              const float* auxp, float bmax, float bres, const float* queries_orig, const float* queries_sel,
-                              void* q_hi, void* q_lo, float* top8, unsigned long long* cand_fb, int* cnt_fb, float* thr,
-                              uint32_t* list, int* list_cnt, int* tile_fail, int* flags_fb, const int32_t* ext_ids, int32_t* out_ids,
-                              float* out_dists, int32_t* out_cnt, hipEvent_t scan_begin, hipEvent_t scan_end,
-                              hipStream_t s, const float* queries_raw = nullptr, float* queries_pad_out = nullptr,
-                              const float* qaux_cosc = nullptr, const float* queries_centred = nullptr, int sel_ld = 0,
-                              const BfF16Side& h16 = BfF16Side{});
+// src rows [n][ld] of `cols` columns -> the tiles of dst, n_pad rows of dst.dp columns each; auxp = aux (null: 0),
+// auxp16 = aux * aux16_mul, both aux_pad behind the n rows
+struct BfSplitSrc {
+    const float* rows;
+    int n, n_pad, ld, cols;
+};
+hipError_t launch_split_bf16(const BfSplitSrc& src, const float* aux, float aux_pad, float aux16_mul, const BfF32Tiles& dst,
+                             hipStream_t s);
+hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, const BfF32Rows& rows, const BfF32Tiles& tiles,
+                              const BfF32Queries& q, const BfFastWs& ws, const BfOut& out, const BfScanEvents& ev,
+                              hipStream_t s);
 // centred cosine / angular on the fast path: augmented rows / queries (see row_aug_cosc_kernel)
 hipError_t launch_row_aug_cosc(const float* orig, const float* centred, int n, int ldb, int dim, double mu_norm, float lambda,
                                float* out, int ldo, int* zero_rows, hipStream_t s);
 hipError_t launch_query_aug_cosc(const float* centred, const float* qaux, int nq, int qpad, int ldb, int dim, float lambda,
                                  float* out, int ldo, hipStream_t s);
-
-// The adaptive f32 path end to end (selection, re-rank; l2: verification + exact tail).  flags: [p.nqt] ints.
-hipError_t launch_bf_adaptive_f32(const BfPlan& p, int space, int dim, int k, const float* base_orig, const float* sel_rows,
-                                  const float* aux, const float* queries_orig, const float* queries_sel,
-                                  const float* qaux_cosc, float bmax, unsigned long long* cand, int* cand_cnt, int* flags,
-                                  const int32_t* ext_ids, int32_t* out_ids, float* out_dists, int32_t* out_cnt,
-                                  const int* gate, int gate_tiles, hipStream_t s, bool cleared = false);
-hipError_t launch_bf_rerank_verify(const BfPlan& p, int space, int dim, int k, const void* base,
-                                   const void* queries_padded, const unsigned long long* cand,
-                                   const int* cand_cnt, const int32_t* ext_ids, int32_t* out_ids,
-                                   float* out_dists, int32_t* out_cnt, const int* tile_fail, int fail_queries,
-                                   int* verify_flags, const float* queries_sel, float bmax, hipStream_t s);
-hipError_t launch_bf_select_direct_f32_ex(const BfPlan& p, int space, const float* base, const float* queries_padded,
-                                          unsigned long long* cand, int* cand_cnt, const int* tile_fail, int fail_group,
-                                          hipStream_t s, bool cleared_second_region = false);
-// Direct (VALU) selection for spaces with no inner-product form (l1, linf).
-hipError_t launch_bf_select_direct_f32(const BfPlan& p, int space, const float* base,
-                                       const float* queries_padded, unsigned long long* cand,
-                                       int* cand_cnt, hipStream_t s);
-// Exact distances of the survivors in the reference's formula, (dist, position) order, top k.
-hipError_t launch_bf_rerank(const BfPlan& p, int space, int dim, int k, const void* base,
-                            const void* queries_padded, const unsigned long long* cand,
-                            const int* cand_cnt, const int32_t* ext_ids, int32_t* out_ids,
-                            float* out_dists, int32_t* out_cnt, hipStream_t s);
-
-hipError_t launch_bf_rerank_ex(const BfPlan& p, int space, int dim, int k, const void* base,
-                               const void* queries_padded, const unsigned long long* cand,
-                               const int* cand_cnt, const int32_t* ext_ids, int32_t* out_ids,
-                               float* out_dists, int32_t* out_cnt, const int* tile_fail, int fail_queries,
-                               hipStream_t s);
 
 // one pair, one wave (nmslib_get_distance)
 hipError_t launch_pair_distance(int space, const void* a, const void* b, int dim, float* out,
@@ -372,11 +422,16 @@ hipError_t launch_range_dist(int space, const void* rows, int ld, int n, const v
                              float* dist_ws, hipStream_t s);
 
 // Exact scan for k > BF_MAX_K: per query one pass with the reference formula + one stable device radix sort of
-// (distance, position).  dist_ws [n] floats, key_ws [4][n] u32, temp from bf_bigk_temp_bytes(n).
+// (distance, position).  Workspace: dist [n] floats, keys [4][n] u32, temp of bf_bigk_temp_bytes(n).
 size_t bf_bigk_temp_bytes(int n);
-hipError_t launch_bf_bigk(int space, const void* rows, int ld, int n, const void* queries_padded, size_t query_stride_bytes,
-                          int nq, int dim, int k, const int32_t* ext_ids, float* dist_ws, uint32_t* key_ws, void* temp,
-                          size_t temp_bytes, int32_t* out_ids, float* out_dists, int32_t* out_cnt, hipStream_t s);
+struct BfBigkWs {
+    float* dist;
+    uint32_t* keys;
+    void* temp;
+    size_t temp_bytes;
+};
+hipError_t launch_bf_bigk(int space, const void* rows, int ld, int n, int dim, const void* queries_padded,
+                          size_t query_stride_bytes, int nq, int k, const BfBigkWs& ws, const BfOut& out, hipStream_t s);
 
 // count_ws: [range_count_elems(n)] ints, the last one receives the number of matches.
 inline size_t range_count_elems(int n) { return (size_t)(n + 1023) / 1024 + 1; }

@@ -152,28 +152,27 @@ size_t bf_bigk_temp_bytes(int n) {
     return tmp + 256;
 }
 
-hipError_t launch_bf_bigk(int space, const void* rows, int ld, int n, const void* queries_padded, size_t query_stride_bytes,
-                          int nq, int dim, int k, const int32_t* ext_ids, float* dist_ws, uint32_t* key_ws /* [4][n] */,
-                          void* temp, size_t temp_bytes, int32_t* out_ids, float* out_dists, int32_t* out_cnt,
-                          hipStream_t s) {
-    uint32_t* k_in = key_ws;
-    uint32_t* k_out = key_ws + (size_t)n;
-    uint32_t* v_in = key_ws + 2 * (size_t)n;
-    uint32_t* v_out = key_ws + 3 * (size_t)n;
+hipError_t launch_bf_bigk(int space, const void* rows, int ld, int n, int dim, const void* queries_padded,
+                          size_t query_stride_bytes, int nq, int k, const BfBigkWs& ws, const BfOut& out, hipStream_t s) {
+    uint32_t* k_in = ws.keys;   // [4][n]
+    uint32_t* k_out = ws.keys + (size_t)n;
+    uint32_t* v_in = ws.keys + 2 * (size_t)n;
+    uint32_t* v_out = ws.keys + 3 * (size_t)n;
+    size_t temp_bytes = ws.temp_bytes;
     for (int q = 0; q < nq; ++q) {
-        int32_t* oi = out_ids + (size_t)q * k;
-        float* od = out_dists + (size_t)q * k;
-        int32_t* oc = out_cnt ? out_cnt + q : nullptr;
+        int32_t* oi = out.ids + (size_t)q * k;
+        float* od = out.dists + (size_t)q * k;
+        int32_t* oc = out.cnt ? out.cnt + q : nullptr;
         if (n > 0) {
             int grid = (n + 3) / 4;
             if (grid > 65536) grid = 65536;
             hipLaunchKernelGGL(range_dist_kernel, dim3(grid), dim3(256), 0, s, space, rows, ld, n,
-                               static_cast<const char*>(queries_padded) + (size_t)q * query_stride_bytes, dim, dist_ws);
-            hipLaunchKernelGGL(bigk_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s, dist_ws, n, k_in, v_in);
-            hipError_t e = rocprim::radix_sort_pairs(temp, temp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0, 32, s, false);
+                               static_cast<const char*>(queries_padded) + (size_t)q * query_stride_bytes, dim, ws.dist);
+            hipLaunchKernelGGL(bigk_keys_kernel, dim3((n + 255) / 256), dim3(256), 0, s, ws.dist, n, k_in, v_in);
+            hipError_t e = rocprim::radix_sort_pairs(ws.temp, temp_bytes, k_in, k_out, v_in, v_out, (size_t)n, 0, 32, s, false);
             if (e != hipSuccess) return e;
         }
-        hipLaunchKernelGGL(bigk_emit_kernel, dim3((k + 255) / 256), dim3(256), 0, s, k_out, v_out, n, k, ext_ids, oi, od, oc);
+        hipLaunchKernelGGL(bigk_emit_kernel, dim3((k + 255) / 256), dim3(256), 0, s, k_out, v_out, n, k, out.ext_ids, oi, od, oc);
     }
     return hipGetLastError();
 }

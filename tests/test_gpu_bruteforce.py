@@ -788,3 +788,20 @@ def test_f32_fast_path_value_ranges(space, kind, monkeypatch):
     opos, odist, _ = orc.seq_search(space, X, Q[sel], k + 22)
     assert refio.recall_nmslib(ids[sel], opos, odist, k) >= 0.999
     idx.close()
+
+
+@pytest.mark.parametrize("D,dp,bf16_tiles", [(32, 128, True), (200, 256, False)])
+def test_hbm_bytes_counts_the_fast_path_tiles(D, dp, bf16_tiles):
+    """stats()['hbm_bytes'] covers everything finalize leaves resident for the f32 fast path, at the smallest index that
+    prepares it: the rows, the fp16 tiles [n_pad][dp] of the one-product scan, for rows of up to 128 dimensions the bf16 hi
+    and lo tiles of the split-product scan, and both arrays of start values (n_pad = n + 64: the rows padded to the
+    64-row tile plus one tile)."""
+    n = 65536
+    n_pad = n + 64
+    X = np.random.default_rng(91).standard_normal((n, D)).astype(np.float32)
+    idx = make_index("l2", "seq_search", X)
+    idx.knnQueryBatch(X[:1], 1)                                    # finalizes the index
+    want = n * D * 4 + n_pad * dp * 2 * (3 if bf16_tiles else 1) + n_pad * 8
+    got = idx.stats()["hbm_bytes"]
+    idx.close()
+    assert got >= want, (got, want)
