@@ -961,6 +961,9 @@ __global__ __launch_bounds__(256, 2) void bf_select_u8_kernel(BfArgsU8 a) {
 // end of every stage makes all eight waves wait for the slowest, and with ~1 block in 10 holding a hit some wave is on
 // this path in most stages: decoding the mask into row positions there (a divergent loop, or 16 x if-chains) cost
 // 0.09 ms of 0.72 ms at C2.  The re-rank kernels expand the entries (scan_gather_entries).
+// The one-product float scan (bf_scan_bf16_kernel) appends a SECOND word per entry, in a plane of the same layout behind
+// the first: the largest score among the entry's rows.  Its re-rank fetches only the entries that can still hold a
+// top-k row (bf_rerank_f32_list_kernel).  The uint8 scan and the split-product scan keep one-word entries.
 // mask bit (15 - i) <=> accumulator register i.  Built without the scalar registers: a compare writes VCC and the
 // instruction that consumes it (v_addc / v_cndmask) waits ~30 clocks for it -- 16 such pairs cost 0.1 ms of 0.65 at C2;
 // the sign of (score - threshold) shifted in with v_alignbit is two plain VALU instructions per score.
@@ -998,31 +1001,41 @@ __device__ __forceinline__ uint32_t hit_mask_i32(const i32x16& c, int t) {
 // fetched 2 * nsplit lines per query for one or two entries each -- 33 MB at C2, 12 us): the threads of a wave read
 // neighbouring words, and the first four planes are requested together (an entry lists at least one row, so entry
 // i < len exists or is never looked at).
+// TWO_WORDS: the entries carry their rows' largest score in a second plane m_off words behind (one-product float scan).
+// Every position then comes with that score in its high word (f32_ord), and the first position of an entry with
+// kEntryHead set: the entry's one vote in an order statistic over entries.  (Positions stay below 2^31: n is an int.)
+constexpr uint32_t kEntryHead = 0x80000000u;
+template <bool TWO_WORDS = false>
 __device__ __forceinline__ void scan_gather_entries(u64* keys, const int* offs, const uint32_t* list, int q, int nl, int caph,
-                                                    int tps, int tid, int nthreads) {
+                                                    int tps, int tid, int nthreads, size_t m_off = 0) {
     for (int s = tid; s < nl; s += nthreads) {
         const int len = offs[s + 1] - offs[s];
         if (len == 0) continue;
         const uint32_t* e = list + (size_t)q * caph * nl + s;
         const uint32_t row_base = (uint32_t)(s >> 1) * (uint32_t)tps * BF_BN + 4u * (s & 1);
-        uint32_t pre[4];
+        uint32_t pre[4], prem[TWO_WORDS ? 4 : 1];
 #pragma unroll
-        for (int i = 0; i < 4; ++i) pre[i] = (i < len && i < caph) ? e[(size_t)i * nl] : 0u;
+        for (int i = 0; i < 4; ++i) {
+            pre[i] = (i < len && i < caph) ? e[(size_t)i * nl] : 0u;
+            if constexpr (TWO_WORDS) prem[i] = (i < len && i < caph) ? e[(size_t)i * nl + m_off] : 0u;
+        }
         int j = 0;
-        auto expand = [&](const uint32_t ent) __attribute__((always_inline)) {
+        auto expand = [&](const uint32_t ent, const uint32_t emax) __attribute__((always_inline)) {
             uint32_t m = ent & 0xffffu;
             const uint32_t r0 = row_base + (ent >> 16) * 32u;
+            u64 hi = TWO_WORDS ? ((u64)f32_ord(__uint_as_float(emax)) << 32) | kEntryHead : 0ull;
             while (m && j < len) {
                 const int bit = 31 - __builtin_clz(m);   // highest bit first = lowest register = lowest row
                 m &= ~(1u << bit);
                 const int reg = 15 - bit;
-                keys[offs[s] + j++] = (u64)(r0 + (reg & 3) + 8 * (reg >> 2));
+                keys[offs[s] + j++] = hi | (u64)(r0 + (reg & 3) + 8 * (reg >> 2));
+                hi &= ~(u64)kEntryHead;
             }
         };
 #pragma unroll
         for (int i = 0; i < 4; ++i)
-            if (i < caph && j < len) expand(pre[i]);
-        for (int i = 4; i < caph && j < len; ++i) expand(e[(size_t)i * nl]);
+            if (i < caph && j < len) expand(pre[i], TWO_WORDS ? prem[i] : 0u);
+        for (int i = 4; i < caph && j < len; ++i) expand(e[(size_t)i * nl], TWO_WORDS ? e[(size_t)i * nl + m_off] : 0u);
     }
 }
 
@@ -1451,6 +1464,8 @@ struct BfScanF32Args {
     float* top8;              // SAMPLE: [qpad][nsplit][2][8]
     const int* group_flag;    // [nqt] or null: a workgroup runs only if group_flag[its query tile] == group_want
     int group_want;
+    size_t list_m_off;        // one-product scan: words from an entry to its second word in the plane behind the first --
+                              // the largest score among the entry's rows, a float in the scan's units (see hit entries)
 };
 
 // Workgroup = 4 waves, ONE per SIMD, each with the SIMD's whole 512-entry register file; a wave serves QG groups of 32
@@ -1968,15 +1983,28 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
             } else {
                 km = hit_mask_f32(c, thr[g]);
             }
+            // second word of the entry: the largest score among its rows.  A lane with a hit has its best score at or
+            // above the threshold, so that row is in the mask: the maximum of all 16 (taken again here, on the cold
+            // path: the common path keeps nothing alive for it) is the maximum of the masked ones -- except in the
+            // base's last block, where rows beyond n leave the mask: there the masked scores are walked.
+            float em = block_max(c, ax);
             if (row0 + 32 > a.n) {
                 int nvalid = a.n - row0;
                 asm volatile("" : "+s"(nvalid));
 #pragma unroll
                 for (int i = 0; i < 16; ++i)
                     if (acc_row(i, h) >= nvalid) km &= ~(0x8000u >> i);
+                em = -INFINITY;
+#pragma unroll
+                for (int i = 0; i < 16; ++i)
+                    if (km & (0x8000u >> i)) em = fmaxf(em, score_of(c, i, ax));
             }
             if (km) {
-                if (ecnt[g] < a.caph) lp[g][(size_t)ecnt[g] * (2 * a.nsplit)] = ((uint32_t)(row0 - r_begin) >> 5 << 16) | km;
+                if (ecnt[g] < a.caph) {
+                    uint32_t* ep = lp[g] + (size_t)ecnt[g] * (2 * a.nsplit);
+                    ep[0] = ((uint32_t)(row0 - r_begin) >> 5 << 16) | km;
+                    ep[a.list_m_off] = __float_as_uint(em);
+                }
                 ecnt[g]++;
                 cnt[g] += __builtin_popcount(km);
             }
@@ -2416,8 +2444,25 @@ struct RerankListF32Args {
     float scale, scale_q, bres16;   // one-product tiles: the fp16 scan's scales of rows / queries, the rows' largest fp16 residual (scaled)
     int sel_dim, sel_ld;       // columns / row stride of queries_sel (dim / ldb, or the augmented queries' when qaux is set)
     const float* qaux;         // centred cosine / angular: [qpad][4] = |q'|^2, |q| - |mu|, |q|, flag (0: zero-norm query); else null
+    size_t list_m_off;         // one-product tiles: words from an entry to its second word (BfScanF32Args::list_m_off)
     unsigned long long* prof;  // NMSLIB_GPU_DEBUG & 4096: phase clocks (100 MHz), summed over the workgroups
 };
+
+// kappa of the cut in bf_rerank_f32_list_kernel: the r-th largest second word over the ENTRIES among the `total` gathered
+// positions (one vote per entry: the position with kEntryHead), as an ordered key; 0 with fewer than r entries.  An
+// entry of +inf ("never prune": nothing is known of its rows but that one reached the threshold) votes with t_ord.
+template <int NPER>
+__device__ __forceinline__ uint32_t entry_rth_largest(const u64* keys, int total, int r, int lane, uint32_t t_ord) {
+    uint32_t key[NPER];
+#pragma unroll
+    for (int i = 0; i < NPER; ++i) {
+        const int j = i * 64 + lane;
+        const u64 kv = j < total ? keys[j] : 0ull;
+        const uint32_t hi = (uint32_t)(kv >> 32);
+        key[i] = ((uint32_t)kv & kEntryHead) ? (hi == 0xFF800000u ? t_ord : hi) : 0u;   // (f32_ord(+inf) = 0xFF800000)
+    }
+    return wave_rth_largest_u32<NPER>(key, r);
+}
 
 __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Args a) {
     const unsigned long long t0 = a.prof ? wall_clock64() : 0;
@@ -2427,8 +2472,8 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
     extern __shared__ __attribute__((aligned(16))) char smem[];
     u64* keys = reinterpret_cast<u64*>(smem);              // [p2max]
     int* offs = reinterpret_cast<int*>(keys + a.p2max);    // [2 * nsplit + 1]
-    __shared__ int s_over, s_split;
-    __shared__ float s_qn2, s_e1, s_thr;
+    __shared__ int s_over, s_split, s_rows;
+    __shared__ float s_qn2, s_e1, s_thr, s_cut;
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nl = 2 * a.nsplit;
     // exclusive prefix sum of the (clipped) list lengths: wave 0, each lane a run of consecutive lists
@@ -2479,7 +2524,8 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
         }
     }
     __syncthreads();
-    const int total = offs[nl];
+    const int listed = offs[nl];
+    int total = listed;   // (from the cut on: the rows that are fetched)
     if ((a.no_split && a.precise[q / a.fail_queries] != 0) ||      // (no scan served this tile: its lists are stale)
         (a.qaux && a.qaux[(size_t)q * 4 + 3] == 0.f)) {            // (zero-norm query, centred cosine: every distance is 1)
         if (tid == 0) atomicOr(&a.tile_fail[q / a.fail_queries], 1);
@@ -2493,14 +2539,60 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
         return;
     }
     lap(0);
-    scan_gather_entries(keys, offs, a.list, q, nl, a.caph, a.tps, tid, blockDim.x);
-    __syncthreads();
+    if (s_split) {
+        // (split-product tiles: one-word entries -- bf_scan_f32_kernel sits at 256 registers and is left as it is --, which
+        //  stands for a second word of +inf throughout: every listed row is fetched)
+        scan_gather_entries(keys, offs, a.list, q, nl, a.caph, a.tps, tid, blockDim.x);
+        __syncthreads();
+        if (tid == 0) s_cut = -INFINITY;
+    } else {
+        // THE CUT (one-product tiles).  The threshold T that made the lists is loose by construction -- the 8th best of a
+        // 1/16 sample lets ~10 times the wanted rows through --, and every entry carries m, the largest scan score among
+        // its rows, within E1 (one_product_error) of that row's exact score.  Let kappa be the want-th largest m over the
+        // entries (ONE order statistic, no sort; want = k + slack as above).
+        //   - Each entry stands for at least one row of its own whose scan score is its m (entries are distinct
+        //     (lane, block) pairs): at least `want` distinct rows have an exact score >= kappa - E1.
+        //   - Every row of an entry with m < kappa - 2 E1 has a scan score <= m, an exact score < kappa - 2 E1 + E1: it is
+        //     strictly farther than all of those `want` >= k rows and cannot be in the top k.
+        // Such entries are dropped (2.1 E1, the threshold kernel's factor, for the roundings of the subtraction); an entry
+        // that stays keeps all the rows of its mask.  The proof at the end treats a dropped row like an unlisted one:
+        // it runs against max(T, kappa - 2.1 E1).  More than 1024 positions, or fewer than `want` entries: no cut.
+        scan_gather_entries<true>(keys, offs, a.list, q, nl, a.caph, a.tps, tid, blockDim.x, a.list_m_off);
+        __syncthreads();
+        // (every wave takes the same statistic of the same keys: no broadcast; wave 0 then closes the gaps in place --
+        //  chunk by chunk in ascending order, a chunk is read whole before its survivors are written at or below it)
+        uint32_t kap = 0u;
+        const uint32_t t_ord = f32_ord(s_thr);
+        if (total <= 256) kap = entry_rth_largest<4>(keys, total, want, lane, t_ord);
+        else if (total <= 1024) kap = entry_rth_largest<16>(keys, total, want, lane, t_ord);
+        const float kappa = ord_f32(kap);
+        const float cut = (kap != 0u && fabsf(kappa) < INFINITY) ? kappa - 2.1f * s_e1 : -INFINITY;
+        __syncthreads();   // (all waves have read the keys)
+        if (wave == 0) {
+            int w = 0;
+            for (int j0 = 0; j0 < total; j0 += 64) {
+                const int j = j0 + lane;
+                const u64 kv = j < total ? keys[j] : 0ull;
+                const bool keep = j < total && !(ord_f32((uint32_t)(kv >> 32)) < cut);
+                const unsigned long long bal = __builtin_amdgcn_ballot_w64(keep);
+                if (keep) keys[w + __popcll(bal & ((1ull << lane) - 1ull))] = (u64)((uint32_t)kv & ~kEntryHead);
+                w += __popcll(bal);
+            }
+            if (lane == 0) {
+                s_rows = w;
+                s_cut = w < total ? cut : -INFINITY;
+            }
+        }
+        __syncthreads();
+        total = s_rows;
+    }
     lap(1);
     const int P = next_pow2(total < 2 ? 2 : total);
     if (a.prof && tid == 0) {
-        atomicAdd(&a.prof[8], (unsigned long long)total);
+        atomicAdd(&a.prof[8], (unsigned long long)listed);
         atomicAdd(&a.prof[9], (unsigned long long)P);
         atomicAdd(&a.prof[10], 1ull);
+        atomicAdd(&a.prof[11], (unsigned long long)total);   // rows fetched (after the cut)
     }
     // exact distances: 16 lanes per row, 4 rows per wave and pass, 4 passes requested together -- 64 rows of the query
     // in flight per workgroup round (the kernel is a chain of memory round trips).  Bit-identical to
@@ -2686,6 +2778,7 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
     // <= 3 * 2^-16, plus the f32 accumulation of the MFMAs (~2^-19).  Unlisted rows scored below the threshold T, so
     // their exact score is below T + E; if the exact score S_k of the k-th result is at least that, every unlisted row
     // is strictly farther than the k-th result.  Otherwise the adaptive kernel redoes the query's tile group.
+    // (One-product tiles: "unlisted" reads "unlisted or dropped by the cut" -- rows that scored below max(T, kappa - 2.1 E1).)
     if (total < a.n) {
         const bool split_product = s_split != 0;
         if (tid == 0) {
@@ -2713,7 +2806,7 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
                 sk = (a.space == SP_ANGULAR ? cosf(dk) : 1.0f - dk) * qn;
                 e = 6.1036e-5f * qn;
             }
-            const float t = s_thr;
+            const float t = fmaxf(s_thr, s_cut);
             if (!split_product) {   // one fp16 product: threshold, bound and score in the scan's units (scale^2)
                 const float unit = a.scale * a.scale_q;
                 sk *= unit;
@@ -3840,9 +3933,9 @@ static void dump_rerank_list_clocks(const unsigned long long* d_prof, hipStream_
     (void)hipStreamSynchronize(s);
     (void)hipMemcpy(h, d_prof, sizeof(h), hipMemcpyDeviceToHost);
     const double wg = h[10] ? (double)h[10] : 1.0;
-    fprintf(stderr, "[rerank f32 list] workgroups %llu rows/query %.1f P %.1f | us since start: prefix %.2f gather %.2f distances %.2f "
-            "sort %.2f proof %.2f out %.2f\n", h[10], h[8] / wg, h[9] / wg, h[0] / wg / 100, h[1] / wg / 100, h[2] / wg / 100,
-            h[3] / wg / 100, h[4] / wg / 100, h[5] / wg / 100);
+    fprintf(stderr, "[rerank f32 list] workgroups %llu rows/query %.1f fetched/query %.1f P %.1f | us since start: prefix %.2f "
+            "gather %.2f distances %.2f sort %.2f proof %.2f out %.2f\n", h[10], h[8] / wg, h[11] / wg, h[9] / wg, h[0] / wg / 100,
+            h[1] / wg / 100, h[2] / wg / 100, h[3] / wg / 100, h[4] / wg / 100, h[5] / wg / 100);
 }
 
 // NMSLIB_GPU_DEBUG & 2048: checksums of the intermediate buffers of this batch (determinism screens)
@@ -3957,6 +4050,7 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
     a.caph = f.caph;
     a.tile_stride = 1;
     a.group_flag = precise;
+    a.list_m_off = ws.list_m_off(f);
     const int grid = 8 * f.nqt * (f.nsplit / 8);
     if (ev.first) (void)hipEventRecord(ev.first, s);
     if (!f.force_precise) {
@@ -4002,6 +4096,7 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
     r.thr = thr;
     r.thr1 = thr1;
     r.precise = precise;
+    r.list_m_off = ws.list_m_off(f);
     r.bmax = tiles.bmax;
     r.bres = tiles.bres;
     static const int dbg = getenv("NMSLIB_GPU_DEBUG") ? atoi(getenv("NMSLIB_GPU_DEBUG")) : 0;

@@ -218,7 +218,8 @@ inline BfFastWsBytes bf_fast_ws_bytes(const BfU8Fast& f) {
 }
 inline BfFastWsBytes bf_fast_ws_bytes(const BfF32Fast& f) {
     const size_t lists = (size_t)f.qpad * f.nsplit * 2;
-    return {(size_t)f.qpad * f.s_nsplit * 2 * 8 * 4, (size_t)f.qpad * 8 + (size_t)f.nqt * 8 + 64, lists * f.caph * 4, lists * 4,
+    // (list: two planes -- the entries, and behind them the second words of the one-product scan's entries)
+    return {(size_t)f.qpad * f.s_nsplit * 2 * 8 * 4, (size_t)f.qpad * 8 + (size_t)f.nqt * 8 + 64, 2 * lists * f.caph * 4, lists * 4,
             bf_cand_elems(f.fallback) * 8, bf_cnt_elems(f.fallback) * 4, (size_t)f.fallback.nqt * 4 + 64,
             (size_t)f.qpad * f.dp * 2 * 3};
 }
@@ -226,12 +227,14 @@ struct BfFastWs {
     void* top8;        // sample pass: the per-lane top-8 scores (u8: int, f32: float)
     void* thr;         // u8: [qpad] int thresholds, [nqt] fallback flags; f32: [qpad] split-product thresholds, [qpad]
                        // one-product thresholds, [nqt] fallback flags, [nqt] precise flags
-    uint32_t* list;    // scan: the rows that reached the threshold, per (query, split, half)
+    uint32_t* list;    // scan: the rows that reached the threshold, per (query, split, half): hit entries [qpad][caph][lists];
+                       // f32: a second plane of the same shape behind it (one-product scan: the entries' largest scores)
     int* list_cnt;
     BfCand fb;         // the adaptive fallback's survivors (f.fallback)
     int* flags_fb;     // f32: the fallback's own proof flags [f.fallback.nqt]
     void* queries;     // f32: the converted queries, [qpad][dp] bf16 hi, bf16 lo, fp16
 
+    size_t list_m_off(const BfF32Fast& f) const { return (size_t)f.qpad * f.caph * f.nsplit * 2; }   // in words
     int* tile_fail(const BfU8Fast& f) const { return static_cast<int*>(thr) + f.qpad; }
     float* thr1(const BfF32Fast& f) const { return static_cast<float*>(thr) + f.qpad; }
     int* tile_fail(const BfF32Fast& f) const { return reinterpret_cast<int*>(thr1(f) + f.qpad); }
