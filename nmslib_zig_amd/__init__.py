@@ -354,6 +354,9 @@ class Index:
         self.built = True
 
     def setQueryTimeParams(self, **params):
+        """hnsw: efSearch / ef, algoType; engine extensions gpu_rows="f32"|"f16" (the walk reads an fp16 copy of the rows,
+        the result is re-ranked in f32; also an index parameter of buildIndex) and gpu_rerank=R (how many entries of the
+        final array are re-ranked).  The two extensions stay as set until set again."""
         p = Params(self.alloc, **params)
         try:
             _check(lib().nmslib_set_query_time_params(self.h, p.h), self.alloc)

@@ -1,5 +1,6 @@
 // Engine: host logic around the gfx950 kernels (see engine.hpp).
 #include "engine.hpp"
+#include "f16_pack.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -344,6 +345,10 @@ void Engine::reset() {
     fast_nqt_ = 0;
     hnsw_fix_valid_ = false;
     have_counters_ = false;
+    d_rows16_.release();
+    rows16_failed_ = false;
+    rows_f16_index_ = rows_f16_ = false;
+    rerank_ = 0;
 }
 
 size_t Engine::memory_usage() const {
@@ -356,14 +361,20 @@ size_t Engine::memory_usage() const {
                hbm_bytes();
     size_t total = ids_.size() * (16 + stored_row_bytes());
     total += ids_.size() * dim_ * sizeof(float);
-    return total;
+    return total + rows16_bytes();
+}
+
+size_t Engine::rows16_bytes() const {
+    size_t b = d_rows16_.bytes();
+    for (const auto& c : shards_) b += c->rows16_bytes();
+    return b;
 }
 
 size_t Engine::hbm_bytes() const {
     size_t sh = 0;
     for (const auto& c : shards_) sh += c->hbm_bytes();
     return sh + d_rows_.bytes() + d_aux_.bytes() + d_ids_.bytes() + d_links0_.bytes() + d_up_off_.bytes() + d_up_links_.bytes() +
-           d_rownorm_.bytes() + brute_.bytes() + d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes() + d_st_ptr_.bytes() + d_st_data_.bytes();
+           d_rownorm_.bytes() + d_rows16_.bytes() + brute_.bytes() + d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes() + d_st_ptr_.bytes() + d_st_data_.bytes();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -396,7 +407,13 @@ void Engine::create_index(const std::vector<std::string>& params) {
         ps.get("gpu_build_batch", bp.gpu_build_batch);
         ps.get("gpu_build_div", bp.gpu_build_div);
         ps.get("gpu_shards", gpu_shards_);  // engine extension: row shards over the visible GPUs (0 = all)
+        std::string gpu_rows = "f32";       // engine extension: f16 = the search walks an fp16 copy of the rows
+        ps.get("gpu_rows", gpu_rows);
         ps.check_unused();
+        const bool f16 = parse_gpu_rows(gpu_rows);
+        if (f16) check_rows16_served();
+        rows_f16_index_ = rows_f16_ = f16;
+        rerank_ = 0;
         if (defer && bp.gpu_build < 0) bp.gpu_build = 0;  // deferred upload = no device work now
         bp_ = bp;
         ef_ = 200;  // the shim forces efSearch=200 per query (nmslib_c.cpp:330,986)
@@ -446,13 +463,43 @@ void Engine::set_query_params(const std::vector<std::string>& params) {
         std::transform(algo.begin(), algo.end(), algo.begin(), ::tolower);
         if (algo != "v1merge" && algo != "old" && algo != "hybrid")
             throw std::runtime_error("algoType should be one of the following: old, v1merge");
+        // engine extensions (absent: unchanged)
+        const bool has_rows = ps.has("gpu_rows"), has_rerank = ps.has("gpu_rerank");
+        std::string gpu_rows = "f32";
+        long long rerank = 0;
+        ps.get("gpu_rows", gpu_rows);
+        ps.get("gpu_rerank", rerank);
         ps.check_unused();
         if (ef < 1) throw std::runtime_error("ef must be positive");
+        const bool f16 = has_rows && parse_gpu_rows(gpu_rows);
+        if (f16) check_rows16_served();
+        if (has_rerank && rerank < 1)
+            throw EngineError(Err::InvalidArgument, "gpu_rerank must be at least 1 (it is clamped to [k, max(ef, k)]), got " +
+                                                        std::to_string(rerank));
         ef_ = (int)ef;
         algo_ = algo;
+        if (has_rows) rows_f16_ = f16;
+        if (has_rerank) rerank_ = (int)std::min<long long>(rerank, INT32_MAX);
     } else {
         ps.check_unused();  // SeqSearch has no query-time parameters
     }
+}
+
+bool Engine::parse_gpu_rows(const std::string& v) {
+    if (v == "f32") return false;
+    if (v == "f16") return true;
+    throw EngineError(Err::InvalidArgument, "gpu_rows must be f32 or f16, got '" + v + "'");
+}
+
+void Engine::check_rows16_served() const {
+    if (is_u8())
+        throw EngineError(Err::InvalidArgument, "gpu_rows=f16: l2sqr_sift rows are uint8 (128 bytes each, less than an fp16 "
+                                                "copy would take); the fp16 copy serves the float dense spaces");
+    if (str_space_ || sparse_ || diverg_)
+        throw EngineError(Err::InvalidArgument, std::string("gpu_rows=f16: ") +
+                                                    (str_space_ ? "a string" : sparse_ ? "a sparse" : "a divergence") +
+                                                    " index has no dense float rows to copy; the fp16 copy serves hnsw "
+                                                    "over l2, l1, linf, cosinesimil, angulardist and negdotprod");
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -483,6 +530,8 @@ void Engine::check_device() {
 void Engine::upload_rows() {
     const size_t n = size();
     auto t0 = clk::now();
+    dg_.rows16 = nullptr;  // the fp16 copy follows the rows
+    rows16_failed_ = false;
     if (is_u8()) {
         ldb_ = 128;
         d_rows_.ensure(std::max<size_t>(n, 1) * 128);
@@ -581,6 +630,40 @@ void Engine::upload_graph() {
     dg_.maxlevel = g.maxlevel;
     dg_.enterpoint = g.enterpoint;
     hip_check(hipStreamSynchronize(stream_), "graph upload");
+}
+
+// The fp16 traversal copy of the rows the search kernels read (cosine on the optimized index: the normalised rows), scaled by
+// one power of two per index (f16_pack.hpp).  An index that cannot spare the HBM keeps working on its f32 rows.
+bool Engine::ensure_rows16() {
+    if (dg_.rows16) return true;
+    if (rows16_failed_ || is_u8() || d_n_ == 0 || !dg_.rows) return false;
+    const size_t n = d_n_;
+    const int ld16 = (int)f16pack::row_stride(dim_);
+    int e = 0;
+    try {
+        DevBuf d_bm;
+        d_bm.ensure(16);
+        float bm[4] = {0.f, 0.f, 0.f, 0.f};  // [2]: largest |element|
+        hip_check(launch_row_maxnorm(d_rows_.as<float>(), (int)n, ldb_, (int)dim_, false, d_bm.as<float>(), stream_),
+                  "fp16 rows: range");
+        hip_check(hipMemcpyAsync(bm, d_bm.ptr(), 16, hipMemcpyDeviceToHost, stream_), "fp16 rows: range");
+        hip_check(hipStreamSynchronize(stream_), "fp16 rows: range");
+        e = f16pack::scale_exp(bm[2]);
+        d_rows16_.ensure(n * (size_t)ld16 * 2);
+        hip_check(launch_hnsw_pack_rows16(d_rows_.as<float>(), (int)n, ldb_, (int)dim_, f16pack::scale_of(e), d_rows16_.ptr(),
+                                          ld16, stream_),
+                  "fp16 rows");
+        hip_check(hipStreamSynchronize(stream_), "fp16 rows");
+    } catch (const EngineError& x) {
+        if (x.code != Err::OutOfMemory) throw;
+        d_rows16_.release();  // (nothing partial stays behind)
+        rows16_failed_ = true;
+        return false;
+    }
+    dg_.rows16 = d_rows16_.ptr();
+    dg_.ld16 = ld16;
+    dg_.inv_scale16 = f16pack::scale_of(-e);
+    return true;
 }
 
 bool Engine::use_gpu_build() const {
@@ -901,6 +984,7 @@ void Engine::finalize() {
         build_graph_gpu();
         graph_dirty_ = false;
         dirty_ = false;
+        if (rows_f16_index_) (void)ensure_rows16();
         return;
     }
     ensure_graph();  // host-side construction first: it needs no device
@@ -909,6 +993,7 @@ void Engine::finalize() {
     if (method_ == Method::Brute) prepare_brute();
     else upload_graph();
     dirty_ = false;
+    if (method_ == Method::Hnsw && rows_f16_index_) (void)ensure_rows16();
 }
 
 // restores the calling thread's current device on every way out of a scope that visits other devices
@@ -964,6 +1049,7 @@ void Engine::finalize_sharded(int nshards) {
         c->dim_ = dim_;
         c->method_ = method_;
         c->bp_ = bp_;
+        c->rows_f16_index_ = c->rows_f16_ = rows_f16_index_;
         c->created_ = true;
         c->forced_device_ = (device_ + s) % count;
         shards_.push_back(std::move(c));
@@ -1018,6 +1104,8 @@ void Engine::knn_sharded(const void* d_queries, size_t nq, size_t elem_count, si
         hip_check(hipSetDevice(c.device_), "hipSetDevice");
         c.ef_ = ef_;
         c.algo_ = algo_;
+        c.rows_f16_ = rows_f16_;
+        c.rerank_ = rerank_;
         hip_check(hipStreamWaitEvent(c.stream_, shard_ready_, 0), "hipStreamWaitEvent");
         const void* q = d_queries;
         if (c.device_ != device_) {
@@ -1115,7 +1203,7 @@ void Engine::fast_tile_counts(size_t* tiles, size_t* precise, size_t* fallback) 
 
 size_t Engine::hnsw_redone() {
     if (!shards_.empty()) return shards_[0]->hnsw_redone();
-    if (last_path != 4 || !hnsw_fix_valid_) return 0;
+    if ((last_path != 4 && last_path != 5) || !hnsw_fix_valid_) return 0;
     int32_t v = 0;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hip_check(hipStreamSynchronize(last_stream_ ? last_stream_ : stream_), "stats");
@@ -1172,21 +1260,33 @@ void Engine::knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids
         }
         return;
     }
+    // (SearchOld and the HBM-array kernel above stay on the f32 rows whatever gpu_rows says)
+    if (rows_f16_ && ensure_rows16()) {
+        knn_hnsw_f16(d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
+        return;
+    }
+    hnsw_search_lds(dg_, false, d_queries, nq, k, ef, out, true, stream);
+}
+
+void Engine::hnsw_search_lds(const HnswDeviceGraph& g, bool rows_f16, const void* d_queries, size_t nq, size_t k, int ef,
+                             const HnswOut& out, bool timed, hipStream_t stream) {
     const HnswQueries queries = HnswQueries::external(d_queries);
-    HnswSearchPlan p = hnsw_make_plan(dg_, (int)nq, (int)k, ef, false);
+    HnswSearchPlan p = hnsw_make_plan(g, (int)nq, (int)k, ef, false);
+    p.rows_f16 = rows_f16 ? 1 : 0;
     have_counters_ = true;
     if (p.table_size == 0) {
         uint32_t* bitset = cleared_bitset(nq, p.bitset_words, stream);
         prof_begin(stream);
-        hip_check(launch_hnsw_search(dg_, p, queries, bitset, HnswOverflow{}, out, stream), "hnsw_search");
-        prof_end(stream);
+        hip_check(launch_hnsw_search(g, p, queries, bitset, HnswOverflow{}, out, stream), "hnsw_search");
+        if (timed) prof_end(stream);
         return;
     }
     // The LDS visited table is exact but finite.  Queries that fill it append themselves to a list on the device and
     // are re-run by a second, small launch of the bitset variant that walks that list -- the host never looks at it,
     // so the call only enqueues work (include/nmslib_gpu.h).
     const int fix_slots = (int)std::min<size_t>(nq, 128);
-    HnswSearchPlan pb = hnsw_make_plan(dg_, (int)nq, (int)k, ef, true);
+    HnswSearchPlan pb = hnsw_make_plan(g, (int)nq, (int)k, ef, true);
+    pb.rows_f16 = p.rows_f16;
     ws_fix_.ensure((nq + 16) * 4);
     // (not cleared_bitset: the workgroups that walk the list clear their own slot on the device)
     ws_bitset_.ensure((size_t)fix_slots * pb.bitset_words * 4);
@@ -1195,11 +1295,35 @@ void Engine::knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids
     hip_check(hipMemsetAsync(fix_count, 0, 4, stream), "clear overflow count");
     hnsw_fix_valid_ = true;
     prof_begin(stream);
-    hip_check(launch_hnsw_search(dg_, p, queries, nullptr, HnswOverflow{0, fix_list, fix_count}, out, stream), "hnsw_search");
-    prof_end(stream);
-    hip_check(launch_hnsw_search(dg_, pb, queries, ws_bitset_.as<uint32_t>(), HnswOverflow{fix_slots, fix_list, fix_count},
+    hip_check(launch_hnsw_search(g, p, queries, nullptr, HnswOverflow{0, fix_list, fix_count}, out, stream), "hnsw_search");
+    if (timed) prof_end(stream);
+    hip_check(launch_hnsw_search(g, pb, queries, ws_bitset_.as<uint32_t>(), HnswOverflow{fix_slots, fix_list, fix_count},
                                  out, stream),
               "hnsw_search(bitset)");
+}
+
+// The walk reads the fp16 copy; what it ends with is re-ranked against the f32 rows, so every distance returned is the f32
+// distance.  The walk is the search launch asked for cap = max(ef, k) results: the fp16 kernels then write their whole sorted
+// array, in array order and as internal positions.  ndc / hops / hops_up describe the walk; the timed interval is walk +
+// overflow launch + re-rank.
+void Engine::knn_hnsw_f16(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
+                          hipStream_t stream) {
+    const int ef = ef_;
+    const size_t cap = std::max<size_t>(ef, k);
+    last_path = 5;
+    const HnswOut fin = hnsw_out(d_ids, d_dists, d_cnt, nq);
+    ws_rr_ids_.ensure(nq * cap * 4);
+    ws_rr_d_.ensure(nq * cap * 4);
+    ws_rr_cnt_.ensure(nq * 4);
+    HnswOut walk = fin;
+    walk.ids = ws_rr_ids_.as<int32_t>();
+    walk.dists = ws_rr_d_.as<float>();
+    walk.cnt = ws_rr_cnt_.as<int32_t>();
+    hnsw_search_lds(dg_, true, d_queries, nq, cap, ef, walk, false, stream);
+    const size_t rerank = rerank_ > 0 ? std::min(cap, std::max<size_t>(k, (size_t)rerank_)) : cap;
+    hip_check(launch_hnsw_rerank(dg_, (int)nq, (int)k, (int)cap, (int)rerank, d_queries, walk.ids, walk.cnt, fin, stream),
+              "hnsw_rerank");
+    prof_end(stream);
 }
 
 // Hnsw::SearchOld (hnsw_distfunc_opt.cc:46-150) on the GPU: no limit on ef or k.  Queues that outgrow LDS live in

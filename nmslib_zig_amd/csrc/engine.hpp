@@ -252,6 +252,7 @@ class Engine {
 
     double upload_seconds = 0, build_seconds = 0;
     int last_path = 0;  // see nmslib_gpu_stats_t
+    size_t rows16_bytes() const;  // the fp16 traversal copy (gpu_rows=f16), shards included
     // flags of the last fast-path slice (device): [fast_nqt_] fallback flags, then (float rows) [fast_nqt_] precise flags
     const int* fast_flags_ = nullptr;
     int fast_nqt_ = 0;
@@ -341,6 +342,16 @@ class Engine {
                       int32_t* d_cnt, hipStream_t stream);
     // Hnsw::Search, hnsw.cc:724: algoType=old, or hybrid with ef >= 1000, runs SearchOld
     bool search_old() const { return algo_ == "old" || (algo_ == "hybrid" && ef_ >= 1000); }
+    // SearchV1Merge on the LDS kernels: the launch, and behind it the bitset launch for queries whose visited table
+    // filled up; timed: the first launch is the timed interval (else the caller closes it with prof_end)
+    void hnsw_search_lds(const HnswDeviceGraph& g, bool rows_f16, const void* d_queries, size_t nq, size_t k, int ef,
+                         const HnswOut& out, bool timed, hipStream_t stream);
+    // gpu_rows=f16: the walk over the fp16 copy, then the f32 re-rank of its sorted array
+    void knn_hnsw_f16(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
+                      hipStream_t stream);
+    bool ensure_rows16();  // makes the copy if there is none; false: no copy (allocation failed, no rows): stay on f32
+    static bool parse_gpu_rows(const std::string& v);  // "f32" -> false, "f16" -> true, else InvalidArgument
+    void check_rows16_served() const;                  // InvalidArgument for indexes without float rows
     HnswOut hnsw_out(int32_t* d_ids, float* d_dists, int32_t* d_cnt, size_t nq);
     uint32_t* cleared_bitset(size_t m, size_t words, hipStream_t stream);
 
@@ -380,11 +391,17 @@ class Engine {
     std::vector<float> graph_rows_;  // rows as stored inside a loaded index (cosine: normalised)
     int ef_ = 200;                   // the shim's default (nmslib_c.cpp:330)
     std::string algo_ = "hybrid";
+    // engine extensions, index-time gpu_rows and query-time gpu_rows / gpu_rerank: they stay as set until set again
+    bool rows_f16_index_ = false;    // make the fp16 copy at finalize
+    bool rows_f16_ = false;          // walk the fp16 copy (made at the next batch if there is none)
+    int rerank_ = 0;                 // entries of the walk's sorted array that are re-ranked in f32; 0 = all
+    bool rows16_failed_ = false;     // the copy did not fit into HBM: f32 until the rows change
 
     // device state
     int device_ = -1;
     hipStream_t stream_ = nullptr;
     DevBuf d_rows_, d_aux_, d_ids_, d_links0_, d_up_off_, d_up_links_, d_rownorm_;
+    DevBuf d_rows16_;  // fp16(scale * rows) [n][dg_.ld16], see dg_.rows16
     BruteDense brute_;
     size_t d_n_ = 0;
     int ldb_ = 0;
@@ -397,6 +414,7 @@ class Engine {
         wb_req_key2_, wb_req_dist2_, wb_sort_tmp_, wb_active_, wb_nactive_, wb_extra_ids_, wb_extra_d_, wb_extra_n_;  // construction workspaces (released after the build)
     DevBuf ws_bq_, ws_split_;  // sparse / string batches: the packed queries; per-split lists (string HNSW: per-query state)
     DevBuf ws_fix_;       // visited-overflow list of the HNSW search (count + query ids), device only
+    DevBuf ws_rr_ids_, ws_rr_d_, ws_rr_cnt_;  // fp16 walk: its sorted arrays (positions, fp16-row distances) and their lengths
     size_t ctr_off_ = 0;  // offset of the current slice inside the per-batch counter arrays
     bool have_counters_ = false;
     bool prof_ = false;

@@ -38,8 +38,9 @@ struct HnswArgs {
 constexpr uint32_t HT_EMPTY = 0xFFFFFFFFu;  // free slot of the LDS visited table
 
 // hnsw_mw_kernels.hip: one workgroup per query (control wave + gather waves); sa_emax = sorted-array items per lane
-// (2 or 4).  Same results, bit for bit, as hnsw_search_kernel<SPACE, false, sa_emax, false>.
-hipError_t launch_hnsw_search_mw(const HnswArgs& a, size_t lds_bytes, int sa_emax, hipStream_t s);
+// (2 or 4); rows_f16: the gather reads g.rows16.  Same results, bit for bit, as hnsw_search_kernel<SPACE, false, sa_emax,
+// false, ROW> over the same rows.
+hipError_t launch_hnsw_search_mw(const HnswArgs& a, size_t lds_bytes, int sa_emax, bool rows_f16, hipStream_t s);
 // control-wave phase cycles accumulated since the last call (NMSLIB_HNSW_PROF), then cleared
 void hnsw_mw_read_prof(unsigned long long out[12]);
 

@@ -97,12 +97,78 @@ __device__ __forceinline__ int group8_sum_i(int v) {
     return v;
 }
 
+// ---- the row type of a gather -------------------------------------------------------------------------------------
+// float: the rows the graph was built on (g.rows, stride g.ldv).  half_t: the fp16 traversal copy (g.rows16, stride
+// g.ld16; fp16(2^e * row)).  Either way a lane's load is 16 bytes = kPer elements, the 8 lanes of a row cover kSpan
+// consecutive elements, and a step of four such loads per lane covers kStep dimensions (128 floats / 256 halves).
+// Per-lane element order, the same in every kernel (it fixes the bits of a distance): steps ascending, the four loads of
+// a step ascending, the elements of a load ascending.
+typedef _Float16 half_t;
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+template <class ROW>
+struct RowTraits;
+template <>
+struct RowTraits<float> {
+    using Vec = f32x4;
+    static constexpr int kPer = 4, kSpan = 32, kStep = 128;
+};
+template <>
+struct RowTraits<half_t> {
+    using Vec = f16x8;
+    static constexpr int kPer = 8, kSpan = 64, kStep = 256;
+};
+template <class ROW>
+__device__ __forceinline__ const ROW* graph_rows(const HnswDeviceGraph& g) {
+    if constexpr (std::is_same<ROW, half_t>::value) return reinterpret_cast<const half_t*>(g.rows16);
+    else return reinterpret_cast<const float*>(g.rows);
+}
+template <class ROW>
+__device__ __forceinline__ int graph_ld(const HnswDeviceGraph& g) {
+    if constexpr (std::is_same<ROW, half_t>::value) return g.ld16;
+    else return g.ldv;
+}
+// the query elements that face one load of a row (f32 in LDS); !ok: past the row, zeros
+template <class ROW>
+struct QueryVec {
+    f32x4 v[RowTraits<ROW>::kPer / 4];
+};
+template <class ROW>
+__device__ __forceinline__ QueryVec<ROW> load_query(const float* qd, bool ok) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    QueryVec<ROW> q;
+#pragma unroll
+    for (int h = 0; h < RowTraits<ROW>::kPer / 4; ++h) {
+        const f32x4 x = *reinterpret_cast<const f32x4*>(qd + 4 * h);
+        q.v[h] = ok ? x : zero;
+    }
+    return q;
+}
+// one load of a row against the query; halves become floats and lose the copy's scale (a power of two: exact), then
+// take the f32 formula
+template <int SPACE, class ROW>
+__device__ __forceinline__ void accum_load(const QueryVec<ROW>& q, const typename RowTraits<ROW>::Vec& b, bool ok,
+                                           float inv_scale, float& s0, float& s1, float& s2) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (std::is_same<ROW, half_t>::value) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const f32x4 x = {(float)b[4 * h] * inv_scale, (float)b[4 * h + 1] * inv_scale, (float)b[4 * h + 2] * inv_scale,
+                             (float)b[4 * h + 3] * inv_scale};
+            accum4<SPACE>(q.v[h], ok ? x : zero, s0, s1, s2);
+        }
+    } else {
+        accum4<SPACE>(q.v[0], ok ? b : zero, s0, s1, s2);
+    }
+}
+
 // Distances of the query to the m rows listed in nbr[0..m) -> nd[0..m).
 // 8 lanes per row; 8 rows per pass; 4 passes issued together (32 rows in flight).
-template <int SPACE>
+template <int SPACE, class ROW = float>
 __device__ __forceinline__ void frontier_distances(const HnswDeviceGraph& g, const float* qv,
                                                    const uint8_t* qb, int qnorm, const int* nbr,
                                                    float* nd, int m, int lane) {
+    using RT = RowTraits<ROW>;
     const int g8 = lane >> 3, sub = lane & 7;
     for (int base_i = 0; base_i < m; base_i += 32) {
         int ids[4];
@@ -134,35 +200,34 @@ __device__ __forceinline__ void frontier_distances(const HnswDeviceGraph& g, con
             }
         } else {
             float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-            const float* rows = reinterpret_cast<const float*>(g.rows);
-            // 128 floats of the 4 rows per pass: all 16 row loads are issued before the first one is waited for
-            // (random 512-byte gathers are latency-bound: the loads in flight per wave are the throughput).
-            // Out-of-range tails read a clamped address and are zeroed on both sides, so no load sits under
+            const ROW* rows = graph_rows<ROW>(g);
+            const int ld = graph_ld<ROW>(g);
+            // one step (128 floats / 256 halves) of the 4 rows per pass: all 16 row loads are issued before the first one
+            // is waited for (random gathers of whole rows are latency-bound: the loads in flight per wave are the
+            // throughput).  Out-of-range tails read a clamped address and are zeroed on both sides, so no load sits under
             // a divergent branch.
-            const float* rp[4];
+            const ROW* rp[4];
 #pragma unroll
-            for (int p = 0; p < 4; ++p) rp[p] = rows + (size_t)ids[p] * g.ldv;
-            const int dlast = g.ldv - 4;
-            for (int d0 = sub * 4; d0 < g.ldv; d0 += 128) {
-                f32x4 bb[4][4];
+            for (int p = 0; p < 4; ++p) rp[p] = rows + (size_t)ids[p] * ld;
+            const int dlast = ld - RT::kPer;
+            for (int d0 = sub * RT::kPer; d0 < ld; d0 += RT::kStep) {
+                typename RT::Vec bb[4][4];
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
-                    const int d = d0 + 32 * it;
+                    const int d = d0 + RT::kSpan * it;
                     const int dc = d < dlast ? d : dlast;
 #pragma unroll
-                    for (int p = 0; p < 4; ++p) bb[it][p] = *reinterpret_cast<const f32x4*>(rp[p] + dc);
+                    for (int p = 0; p < 4; ++p) bb[it][p] = *reinterpret_cast<const typename RT::Vec*>(rp[p] + dc);
                 }
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
-                    const int d = d0 + 32 * it;
-                    const bool ok = d < g.ldv;
+                    const int d = d0 + RT::kSpan * it;
+                    const bool ok = d < ld;
                     const int dc = d < dlast ? d : dlast;
-                    f32x4 qq = *reinterpret_cast<const f32x4*>(qv + dc);
-                    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-                    qq = ok ? qq : zero;
+                    const QueryVec<ROW> qq = load_query<ROW>(qv + dc, ok);
 #pragma unroll
-                    for (int p = 0; p < 4; ++p) accum4<SPACE>(qq, ok ? bb[it][p] : zero, s0[p], s1[p], s2[p]);
+                    for (int p = 0; p < 4; ++p) accum_load<SPACE, ROW>(qq, bb[it][p], ok, g.inv_scale16, s0[p], s1[p], s2[p]);
                 }
             }
 #pragma unroll
@@ -182,19 +247,21 @@ __device__ __forceinline__ void frontier_distances(const HnswDeviceGraph& g, con
     }
 }
 
-// Split-phase form of frontier_distances for the software-pipelined search loop: issue() requests the first 128 floats
-// (u8: the whole row) of the first 32 rows and returns; finish() consumes them, fetches whatever is left (longer rows,
-// rows 32..m) and writes nd[0..m).  Same arithmetic, same order as frontier_distances (bit-identical results).
-template <int SPACE>
+// Split-phase form of frontier_distances for the software-pipelined search loop: issue() requests the first step (128
+// floats / 256 halves; u8: the whole row) of the first 32 rows and returns; finish() consumes them, fetches whatever is
+// left (longer rows, rows 32..m) and writes nd[0..m).  Same arithmetic, same order as frontier_distances (bit-identical
+// results).
+template <int SPACE, class ROW = float>
 struct FrontierLoads {
-    f32x4 bb[4][4];
+    typename RowTraits<ROW>::Vec bb[4][4];
     i32x4 bu[4];
     int ids[4];
 };
 
-template <int SPACE>
-__device__ __forceinline__ void frontier_issue(FrontierLoads<SPACE>& L, const HnswDeviceGraph& g, const int* nbr, int m,
+template <int SPACE, class ROW>
+__device__ __forceinline__ void frontier_issue(FrontierLoads<SPACE, ROW>& L, const HnswDeviceGraph& g, const int* nbr, int m,
                                                int lane) {
+    using RT = RowTraits<ROW>;
     const int g8 = lane >> 3, sub = lane & 7;
 #pragma unroll
     for (int p = 0; p < 4; ++p) {
@@ -207,23 +274,26 @@ __device__ __forceinline__ void frontier_issue(FrontierLoads<SPACE>& L, const Hn
             L.bu[p] = *reinterpret_cast<const i32x4*>(reinterpret_cast<const uint8_t*>(g.rows) + (size_t)L.ids[p] * 128 +
                                                        sub * 16);
     } else {
-        const float* rows = reinterpret_cast<const float*>(g.rows);
-        const int dlast = g.ldv - 4;
+        const ROW* rows = graph_rows<ROW>(g);
+        const int ld = graph_ld<ROW>(g);
+        const int dlast = ld - RT::kPer;
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-            const int d = sub * 4 + 32 * it;
+            const int d = sub * RT::kPer + RT::kSpan * it;
             const int dc = d < dlast ? d : dlast;
 #pragma unroll
-            for (int p = 0; p < 4; ++p) L.bb[it][p] = *reinterpret_cast<const f32x4*>(rows + (size_t)L.ids[p] * g.ldv + dc);
+            for (int p = 0; p < 4; ++p)
+                L.bb[it][p] = *reinterpret_cast<const typename RT::Vec*>(rows + (size_t)L.ids[p] * ld + dc);
         }
     }
     __builtin_amdgcn_sched_barrier(0);
 }
 
-template <int SPACE>
-__device__ __forceinline__ void frontier_finish(FrontierLoads<SPACE>& L, const HnswDeviceGraph& g, const float* qv,
+template <int SPACE, class ROW>
+__device__ __forceinline__ void frontier_finish(FrontierLoads<SPACE, ROW>& L, const HnswDeviceGraph& g, const float* qv,
                                                 const uint8_t* qb, int qnorm, const int* nbr, float* nd, int m,
                                                 int lane) {
+    using RT = RowTraits<ROW>;
     const int g8 = lane >> 3, sub = lane & 7;
     if constexpr (DistTraits<SPACE>::kU8) {
         const i32x4 qq = *reinterpret_cast<const i32x4*>(qb + sub * 16);
@@ -238,30 +308,29 @@ __device__ __forceinline__ void frontier_finish(FrontierLoads<SPACE>& L, const H
         }
     } else {
         float s0[4] = {0.f, 0.f, 0.f, 0.f}, s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-        const float* rows = reinterpret_cast<const float*>(g.rows);
-        const int dlast = g.ldv - 4;
-        const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-        for (int d0 = sub * 4; d0 < g.ldv; d0 += 128) {
-            if (d0 != sub * 4) {  // chunks after the first: fetched here (rows longer than 128 floats)
+        const ROW* rows = graph_rows<ROW>(g);
+        const int ld = graph_ld<ROW>(g);
+        const int dlast = ld - RT::kPer;
+        for (int d0 = sub * RT::kPer; d0 < ld; d0 += RT::kStep) {
+            if (d0 != sub * RT::kPer) {  // steps after the first: fetched here (rows longer than one step)
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
-                    const int d = d0 + 32 * it;
+                    const int d = d0 + RT::kSpan * it;
                     const int dc = d < dlast ? d : dlast;
 #pragma unroll
                     for (int p = 0; p < 4; ++p)
-                        L.bb[it][p] = *reinterpret_cast<const f32x4*>(rows + (size_t)L.ids[p] * g.ldv + dc);
+                        L.bb[it][p] = *reinterpret_cast<const typename RT::Vec*>(rows + (size_t)L.ids[p] * ld + dc);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
-                const int d = d0 + 32 * it;
-                const bool ok = d < g.ldv;
+                const int d = d0 + RT::kSpan * it;
+                const bool ok = d < ld;
                 const int dc = d < dlast ? d : dlast;
-                f32x4 qq = *reinterpret_cast<const f32x4*>(qv + dc);
-                qq = ok ? qq : zero;
+                const QueryVec<ROW> qq = load_query<ROW>(qv + dc, ok);
 #pragma unroll
-                for (int p = 0; p < 4; ++p) accum4<SPACE>(qq, ok ? L.bb[it][p] : zero, s0[p], s1[p], s2[p]);
+                for (int p = 0; p < 4; ++p) accum_load<SPACE, ROW>(qq, L.bb[it][p], ok, g.inv_scale16, s0[p], s1[p], s2[p]);
             }
         }
 #pragma unroll
@@ -278,7 +347,7 @@ __device__ __forceinline__ void frontier_finish(FrontierLoads<SPACE>& L, const H
         }
     }
     __builtin_amdgcn_wave_barrier();
-    if (m > 32) frontier_distances<SPACE>(g, qv, qb, qnorm, nbr + 32, nd + 32, m - 32, lane);
+    if (m > 32) frontier_distances<SPACE, ROW>(g, qv, qb, qnorm, nbr + 32, nd + 32, m - 32, lane);
 }
 
 }  // namespace gfxknn

@@ -53,7 +53,7 @@ __device__ __forceinline__ int collect_unvisited_any(const int* list, int* nbr, 
 }
 // one greedy step on an upper level over a list of any length: the FIRST neighbour attaining the minimum, if it is closer
 // than curdist (the sequential "if (d < curdist)" scan of hnsw.cc / hnsw_distfunc_opt.cc:176-196).  Returns the list length.
-template <int SPACE>
+template <int SPACE, class ROW = float>
 __device__ __forceinline__ int greedy_step_any(const HnswDeviceGraph& g, const int* list, const float* qv, const uint8_t* qb,
                                                int qnorm, int* nbr, float* nd, int lane, int& cur, float& curdist,
                                                bool& changed) {
@@ -62,7 +62,7 @@ __device__ __forceinline__ int greedy_step_any(const HnswDeviceGraph& g, const i
         if (c0 + lane < cnt) nbr[c0 + lane] = list[c0 + lane + 1];
     __builtin_amdgcn_wave_barrier();
     if (cnt > 0) {
-        frontier_distances<SPACE>(g, qv, qb, qnorm, nbr, nd, cnt, lane);
+        frontier_distances<SPACE, ROW>(g, qv, qb, qnorm, nbr, nd, cnt, lane);
         u64 key = ~0ull;
         for (int c0 = 0; c0 < cnt; c0 += 64) {
             const int i = c0 + lane;
@@ -87,7 +87,7 @@ __device__ __forceinline__ int greedy_step_any(const HnswDeviceGraph& g, const i
     return cnt;
 }
 
-template <int SPACE, bool BITSET, int SA_EMAX, bool WIDE>
+template <int SPACE, bool BITSET, int SA_EMAX, bool WIDE, class ROW>
 __device__ __forceinline__ void hnsw_search_body(const HnswArgs& a, char* smem, const int q, uint32_t* const bits) {
     const HnswDeviceGraph& g = a.g;
     const int lane = threadIdx.x;
@@ -179,7 +179,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswArgs& a, char* smem, 
     int cur = start >= 0 ? start : g.enterpoint;
     if (lane == 0) nbr[0] = cur;
     __builtin_amdgcn_wave_barrier();
-    frontier_distances<SPACE>(g, qv, qb, qnorm, nbr, nd, 1, lane);
+    frontier_distances<SPACE, ROW>(g, qv, qb, qnorm, nbr, nd, 1, lane);
     float curdist = nd[0];
     ndc += 1;
     for (int lvl = (start >= 0 ? 0 : g.maxlevel); lvl > a.level; --lvl) {
@@ -189,7 +189,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswArgs& a, char* smem, 
             const int64_t off = g.up_off[cur] + (int64_t)(lvl - 1) * (g.maxM + 1);
             if (WIDE && g.maxM > 62) {   // upper-level lists longer than one word per lane
                 hops_up++;
-                ndc += greedy_step_any<SPACE>(g, g.up_links + off, qv, qb, qnorm, nbr, nd, lane, cur, curdist, changed);
+                ndc += greedy_step_any<SPACE, ROW>(g, g.up_links + off, qv, qb, qnorm, nbr, nd, lane, cur, curdist, changed);
                 continue;
             }
             const int v = (lane <= g.maxM) ? g.up_links[off + lane] : 0;
@@ -199,7 +199,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswArgs& a, char* smem, 
             __builtin_amdgcn_wave_barrier();
             hops_up++;
             if (cntl > 0) {
-                frontier_distances<SPACE>(g, qv, qb, qnorm, nbr, nd, cntl, lane);
+                frontier_distances<SPACE, ROW>(g, qv, qb, qnorm, nbr, nd, cntl, lane);
                 ndc += cntl;
                 // sequential "if (d < curdist)" scan == first index attaining the minimum
                 u64 key = ~0ull;
@@ -250,7 +250,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswArgs& a, char* smem, 
     // this expansion are merged in (it is the array's next unused item and every accepted key is larger), its visited
     // filter runs and its row gather is issued first, and the merge executes while those rows are in flight.
     int pipe_node = -1, pipe_m = 0;
-    FrontierLoads<SPACE> fl;
+    FrontierLoads<SPACE, ROW> fl;
     long long pc[6] = {0, 0, 0, 0, 0, 0};
     long long pt = a.prof ? (long long)__builtin_readcyclecounter() : 0;
     auto lap = [&](int ph) __attribute__((always_inline)) {
@@ -349,11 +349,11 @@ __device__ __forceinline__ void hnsw_search_body(const HnswArgs& a, char* smem, 
                 }
                 pre2_node = -1;
             }
-            if (m > 0) frontier_issue<SPACE>(fl, g, nbr, m, lane);
+            if (m > 0) frontier_issue<SPACE, ROW>(fl, g, nbr, m, lane);
         }
         if (m == 0) continue;
         ndc += m;
-        frontier_finish<SPACE>(fl, g, qv, qb, qnorm, nbr, nd, m, lane);
+        frontier_finish<SPACE, ROW>(fl, g, qv, qb, qnorm, nbr, nd, m, lane);
         lap(3);
 
         // (more than 64 new rows only with wide lists: rounds of 64; without equal keys the final array does
@@ -442,7 +442,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswArgs& a, char* smem, 
                     pre_ok = false;
                 }
                 pre2_node = -1;
-                if (mp > 0) frontier_issue<SPACE>(fl, g, nbr, mp, lane);
+                if (mp > 0) frontier_issue<SPACE, ROW>(fl, g, nbr, mp, lane);
             }
             lap(4);
             // All accepted items at once when no two keys involved are equal (the normal case): the result of
@@ -597,15 +597,19 @@ __device__ __forceinline__ void hnsw_search_body(const HnswArgs& a, char* smem, 
 
     // ---- results: first k items, ties ordered by internal id (KNNQueue holds
     //      pair<dist, Object*> and data_rearranged_ addresses grow with the id) ----
+    //      (the fp16 walk hands its array to the f32 re-rank as it stands: array order, internal positions)
+    constexpr bool kRaw = std::is_same<ROW, half_t>::value;
     const int kk = overflow ? 0 : (a.k < n ? a.k : n);
     for (int i = lane; i < a.k; i += 64) {
         if (i < kk) {
             const float ki = keys[i];
             const int id = idu[i] & 0x7FFFFFFF;
             int r = i;
-            for (int j = i - 1; j >= 0 && keys[j] == ki; --j) r -= ((idu[j] & 0x7FFFFFFF) > id) ? 1 : 0;
-            for (int j = i + 1; j < kk && keys[j] == ki; ++j) r += ((idu[j] & 0x7FFFFFFF) < id) ? 1 : 0;
-            a.out_ids[(size_t)q * a.k + r] = g.ext_ids ? g.ext_ids[id] : id;
+            if constexpr (!kRaw) {
+                for (int j = i - 1; j >= 0 && keys[j] == ki; --j) r -= ((idu[j] & 0x7FFFFFFF) > id) ? 1 : 0;
+                for (int j = i + 1; j < kk && keys[j] == ki; ++j) r += ((idu[j] & 0x7FFFFFFF) < id) ? 1 : 0;
+            }
+            a.out_ids[(size_t)q * a.k + r] = (g.ext_ids && !kRaw) ? g.ext_ids[id] : id;
             a.out_dists[(size_t)q * a.k + r] = ki;
         } else {
             a.out_ids[(size_t)q * a.k + i] = -1;
@@ -622,7 +626,7 @@ __device__ __forceinline__ void hnsw_search_body(const HnswArgs& a, char* smem, 
     }
 }
 
-template <int SPACE, bool BITSET, int SA_EMAX, bool WIDE>
+template <int SPACE, bool BITSET, int SA_EMAX, bool WIDE, class ROW>
 __global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     if constexpr (BITSET) {
@@ -636,14 +640,14 @@ __global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
                 __builtin_amdgcn_wave_barrier();
                 __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                hnsw_search_body<SPACE, true, SA_EMAX, WIDE>(a, smem, a.fix_list[slot], bits);
+                hnsw_search_body<SPACE, true, SA_EMAX, WIDE, ROW>(a, smem, a.fix_list[slot], bits);
                 __builtin_amdgcn_wave_barrier();
             }
             return;
         }
-        hnsw_search_body<SPACE, true, SA_EMAX, WIDE>(a, smem, blockIdx.x, a.bitset + (size_t)blockIdx.x * a.bitset_words);
+        hnsw_search_body<SPACE, true, SA_EMAX, WIDE, ROW>(a, smem, blockIdx.x, a.bitset + (size_t)blockIdx.x * a.bitset_words);
     } else {
-        hnsw_search_body<SPACE, false, SA_EMAX, WIDE>(a, smem, blockIdx.x, nullptr);
+        hnsw_search_body<SPACE, false, SA_EMAX, WIDE, ROW>(a, smem, blockIdx.x, nullptr);
     }
 }
 
@@ -1343,11 +1347,11 @@ static HnswArgs hnsw_args(const HnswDeviceGraph& g, int nq, int k, int ef, int c
     return a;
 }
 
-template <int SPACE, int EMAX, bool WIDE>
+template <int SPACE, int EMAX, bool WIDE, class ROW>
 static hipError_t launch_space_w(const HnswArgs& a, const HnswSearchPlan& p, hipStream_t s) {
     hipError_t e;
     if (p.table_size == 0) {
-        auto kern = hnsw_search_kernel<SPACE, true, EMAX, WIDE>;
+        auto kern = hnsw_search_kernel<SPACE, true, EMAX, WIDE, ROW>;
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
         if (e != hipSuccess) return e;
@@ -1364,12 +1368,12 @@ static hipError_t launch_space_w(const HnswArgs& a, const HnswSearchPlan& p, hip
             const int mode = em ? atoi(em) : 1;
             const int max_nq = eq ? atoi(eq) : 0x7fffffff;
             if (mode && (mode == 2 || a.nq <= max_nq)) {   // (construction mode included: stored rows as queries, any level)
-                const hipError_t me = launch_hnsw_search_mw(a, p.lds_bytes + 16, EMAX, s);
+                const hipError_t me = launch_hnsw_search_mw(a, p.lds_bytes + 16, EMAX, std::is_same<ROW, half_t>::value, s);
                 if (me != hipSuccess) return me;
                 return hipGetLastError();
             }
         }
-        auto kern = hnsw_search_kernel<SPACE, false, EMAX, WIDE>;
+        auto kern = hnsw_search_kernel<SPACE, false, EMAX, WIDE, ROW>;
         e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes);
         if (e != hipSuccess) return e;
@@ -1378,17 +1382,25 @@ static hipError_t launch_space_w(const HnswArgs& a, const HnswSearchPlan& p, hip
     return hipGetLastError();
 }
 
-template <int SPACE, int EMAX>
+template <int SPACE, int EMAX, class ROW>
 static hipError_t launch_space_e(const HnswArgs& a, const HnswSearchPlan& p, hipStream_t s) {
-    if (a.g.maxM0 > 62 || a.g.maxM > 62) return launch_space_w<SPACE, EMAX, true>(a, p, s);
-    return launch_space_w<SPACE, EMAX, false>(a, p, s);
+    if (a.g.maxM0 > 62 || a.g.maxM > 62) return launch_space_w<SPACE, EMAX, true, ROW>(a, p, s);
+    return launch_space_w<SPACE, EMAX, false, ROW>(a, p, s);
 }
 
+template <int SPACE, class ROW>
+static hipError_t launch_space_r(const HnswArgs& a, const HnswSearchPlan& p, hipStream_t s) {
+    if (p.cap <= 128) return launch_space_e<SPACE, 2, ROW>(a, p, s);
+    if (p.cap <= 256) return launch_space_e<SPACE, 4, ROW>(a, p, s);
+    return launch_space_e<SPACE, SA_EMAX_MAX, ROW>(a, p, s);
+}
+
+// p.rows_f16: the kernels that walk the fp16 copy (float spaces, external queries; construction stays on the f32 rows)
 template <int SPACE>
 static hipError_t launch_space(const HnswArgs& a, const HnswSearchPlan& p, hipStream_t s) {
-    if (p.cap <= 128) return launch_space_e<SPACE, 2>(a, p, s);
-    if (p.cap <= 256) return launch_space_e<SPACE, 4>(a, p, s);
-    return launch_space_e<SPACE, SA_EMAX_MAX>(a, p, s);
+    if (!p.rows_f16) return launch_space_r<SPACE, float>(a, p, s);
+    if constexpr (SPACE == SP_L2SQR_SIFT) return hipErrorInvalidValue;
+    else return (a.g.rows16 && !a.query_rows) ? launch_space_r<SPACE, half_t>(a, p, s) : hipErrorInvalidValue;
 }
 
 // NMSLIB_HNSW_PROF: waits for the launch, prints the cycles per query of each phase of both kernels and clears them
@@ -1425,7 +1437,7 @@ hipError_t launch_hnsw_search(const HnswDeviceGraph& g, const HnswSearchPlan& p,
     a.fix_mode = (p.table_size == 0) ? fix.fix_slots : 0;
     a.no_pipe = getenv("NMSLIB_HNSW_PIPE") ? atoi(getenv("NMSLIB_HNSW_PIPE")) == 0 : 0;
     static const int prof = getenv("NMSLIB_HNSW_PROF") ? atoi(getenv("NMSLIB_HNSW_PROF")) : 0;
-    a.prof = (prof && !q.query_rows) ? 1 : 0;
+    a.prof = (prof && !q.query_rows && !p.rows_f16) ? 1 : 0;
     const bool clocked = g.space == SP_L2SQR || g.space == SP_NORMCOS;  // the spaces whose kernels carry the phase clocks
     const hipError_t e = (a.prof && !clocked)
                              ? hipErrorInvalidValue

@@ -55,14 +55,17 @@ __device__ __forceinline__ float wave_min_f32(float v) {
     return fminf(fminf(r0, r1), fminf(r2, r3));
 }
 
-template <int SPACE>
+template <int SPACE, class ROW>
 __device__ __forceinline__ void mw_gather_loop(const HnswArgs& a, const float* qv, const int* nbr, float* nd,
                                                const int* ctl, const int w, const int lane) {
+    using RT = RowTraits<ROW>;
+    using Vec = typename RT::Vec;
     const HnswDeviceGraph& g = a.g;
     const int g8 = lane >> 3, sub = lane & 7;
-    const float* rows = reinterpret_cast<const float*>(g.rows);
-    const int dlast = g.ldv - 4;
-    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+    const ROW* rows = graph_rows<ROW>(g);
+    const int ld = graph_ld<ROW>(g);
+    const int dlast = ld - RT::kPer;
+    const float inv = g.inv_scale16;
     // (the guard only bounds the damage of a protocol error: a wave that ended lets s_barrier through)
     for (int guard = 0; guard < (1 << 26); ++guard) {
         mw_barrier();  // A: list published
@@ -73,47 +76,46 @@ __device__ __forceinline__ void mw_gather_loop(const HnswArgs& a, const float* q
         for (int base = w * 8; base < m; base += 8 * MW_NW) {
             const int idx = base + g8;
             if (base != w * 8) id = nbr[idx];
-            const float* rp = rows + (size_t)id * g.ldv;
+            const ROW* rp = rows + (size_t)id * ld;
             float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-            auto fetch = [&](f32x4 (&bb)[4], int cb) __attribute__((always_inline)) {
+            auto fetch = [&](Vec (&bb)[4], int cb) __attribute__((always_inline)) {
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
-                    const int d = cb + sub * 4 + 32 * it;
-                    bb[it] = *reinterpret_cast<const f32x4*>(rp + (d < dlast ? d : dlast));
+                    const int d = cb + sub * RT::kPer + RT::kSpan * it;
+                    bb[it] = *reinterpret_cast<const Vec*>(rp + (d < dlast ? d : dlast));
                 }
             };
-            // a whole step of 128 floats: nothing to mask
-            auto consume_full = [&](const f32x4 (&bb)[4], int cb) __attribute__((always_inline)) {
+            // a whole step (128 floats / 256 halves): nothing to mask
+            auto consume_full = [&](const Vec (&bb)[4], int cb) __attribute__((always_inline)) {
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
-                    const f32x4 qq = *reinterpret_cast<const f32x4*>(qv + cb + sub * 4 + 32 * it);
-                    accum4<SPACE>(qq, bb[it], s0, s1, s2);
+                    const QueryVec<ROW> qq = load_query<ROW>(qv + cb + sub * RT::kPer + RT::kSpan * it, true);
+                    accum_load<SPACE, ROW>(qq, bb[it], true, inv, s0, s1, s2);
                 }
             };
             // the last, partial step: elements past the row contribute zeros on both sides (same sums, bit for bit)
-            auto consume_tail = [&](const f32x4 (&bb)[4], int cb) __attribute__((always_inline)) {
+            auto consume_tail = [&](const Vec (&bb)[4], int cb) __attribute__((always_inline)) {
 #pragma unroll
                 for (int it = 0; it < 4; ++it) {
-                    const int d = cb + sub * 4 + 32 * it;
-                    const bool ok = d < g.ldv;
-                    f32x4 qq = *reinterpret_cast<const f32x4*>(qv + (d < dlast ? d : dlast));
-                    qq = ok ? qq : zero;
-                    accum4<SPACE>(qq, ok ? bb[it] : zero, s0, s1, s2);
+                    const int d = cb + sub * RT::kPer + RT::kSpan * it;
+                    const bool ok = d < ld;
+                    const QueryVec<ROW> qq = load_query<ROW>(qv + (d < dlast ? d : dlast), ok);
+                    accum_load<SPACE, ROW>(qq, bb[it], ok, inv, s0, s1, s2);
                 }
             };
-            // 128 floats of the row per step; the next step's loads are requested before this step is consumed
-            f32x4 cur[4], nxt[4];
+            // one step of the row at a time; the next step's loads are requested before this step is consumed
+            Vec cur[4], nxt[4];
             int cb = 0;
             fetch(cur, 0);
             while (true) {
-                if (cb + 128 < g.ldv) {
-                    fetch(nxt, cb + 128);
+                if (cb + RT::kStep < ld) {
+                    fetch(nxt, cb + RT::kStep);
                     consume_full(cur, cb);
 #pragma unroll
                     for (int it = 0; it < 4; ++it) cur[it] = nxt[it];
-                    cb += 128;
+                    cb += RT::kStep;
                 } else {
-                    if (cb + 128 == g.ldv) consume_full(cur, cb);
+                    if (cb + RT::kStep == ld) consume_full(cur, cb);
                     else consume_tail(cur, cb);
                     break;
                 }
@@ -153,7 +155,7 @@ __device__ __forceinline__ int mbcnt64(u64 m) {  // set bits of m below this lan
 // the lowest set bit of ballot(id >= 0), picking it is a readlane, one accepted item is inserted with two ballots and
 // one wave_shr:1 per register (SortArrBI::push_or_replace_non_empty_exp, :159-199), several at once by counting
 // (hnsw_search_body's merge) through an LDS scatter.
-template <int SPACE, int E, bool PROF>
+template <int SPACE, int E, bool PROF, class ROW>
 __device__ __forceinline__ void mw_control(const HnswArgs& a, const int q, float* keys, int* idu, int* nbr, float* nd,
                                            int* ctl, uint32_t* table, const int lane) {
     const HnswDeviceGraph& g = a.g;
@@ -537,6 +539,8 @@ __device__ __forceinline__ void mw_control(const HnswArgs& a, const int q, float
         }
     }
     __builtin_amdgcn_wave_barrier();
+    //      (the fp16 walk hands its array to the f32 re-rank as it stands: array order, internal positions)
+    constexpr bool kRaw = std::is_same<ROW, half_t>::value;
     const bool redo = status != 0;
     const int kk = redo ? 0 : (a.k < n ? a.k : n);
     for (int i = lane; i < a.k; i += 64) {
@@ -544,9 +548,11 @@ __device__ __forceinline__ void mw_control(const HnswArgs& a, const int q, float
             const float ki = keys[i];
             const int id = idu[i] & 0x7FFFFFFF;
             int r = i;
-            for (int j = i - 1; j >= 0 && keys[j] == ki; --j) r -= ((idu[j] & 0x7FFFFFFF) > id) ? 1 : 0;
-            for (int j = i + 1; j < kk && keys[j] == ki; ++j) r += ((idu[j] & 0x7FFFFFFF) < id) ? 1 : 0;
-            a.out_ids[(size_t)q * a.k + r] = g.ext_ids ? g.ext_ids[id] : id;
+            if constexpr (!kRaw) {
+                for (int j = i - 1; j >= 0 && keys[j] == ki; --j) r -= ((idu[j] & 0x7FFFFFFF) > id) ? 1 : 0;
+                for (int j = i + 1; j < kk && keys[j] == ki; ++j) r += ((idu[j] & 0x7FFFFFFF) < id) ? 1 : 0;
+            }
+            a.out_ids[(size_t)q * a.k + r] = (g.ext_ids && !kRaw) ? g.ext_ids[id] : id;
             a.out_dists[(size_t)q * a.k + r] = ki;
         } else {
             a.out_ids[(size_t)q * a.k + i] = -1;
@@ -563,7 +569,7 @@ __device__ __forceinline__ void mw_control(const HnswArgs& a, const int q, float
     }
 }
 
-template <int SPACE, int SA_EMAX, bool PROF>
+template <int SPACE, int SA_EMAX, bool PROF, class ROW>
 __global__ __launch_bounds__(MW_THREADS) void hnsw_search_mw_kernel(HnswArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const HnswDeviceGraph& g = a.g;
@@ -617,12 +623,12 @@ __global__ __launch_bounds__(MW_THREADS) void hnsw_search_mw_kernel(HnswArgs a) 
         if (threadIdx.x == 0) ctl[0] = 0;
     }
     __syncthreads();
-    if (wave == 0) mw_control<SPACE, SA_EMAX, PROF>(a, q, keys, idu, nbr, nd, ctl, table, lane);
-    else mw_gather_loop<SPACE>(a, qv, nbr, nd, ctl, wave - 1, lane);
+    if (wave == 0) mw_control<SPACE, SA_EMAX, PROF, ROW>(a, q, keys, idu, nbr, nd, ctl, table, lane);
+    else mw_gather_loop<SPACE, ROW>(a, qv, nbr, nd, ctl, wave - 1, lane);
 }
 
 
-template <int SPACE>
+template <int SPACE, class ROW>
 static hipError_t launch_mw_space(const HnswArgs& a, size_t lds, int sa_emax, hipStream_t s) {
     auto go = [&](auto kern) -> hipError_t {
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
@@ -631,18 +637,21 @@ static hipError_t launch_mw_space(const HnswArgs& a, size_t lds, int sa_emax, hi
         hipLaunchKernelGGL(kern, dim3(a.nq), dim3(MW_THREADS), lds, s, a);
         return hipGetLastError();
     };
-    if constexpr (SPACE == SP_L2SQR) {
-        if (a.prof && sa_emax <= 2) return go(hnsw_search_mw_kernel<SPACE, 2, true>);
+    if constexpr (SPACE == SP_L2SQR && std::is_same<ROW, float>::value) {
+        if (a.prof && sa_emax <= 2) return go(hnsw_search_mw_kernel<SPACE, 2, true, ROW>);
     }
-    if (sa_emax <= 2) return go(hnsw_search_mw_kernel<SPACE, 2, false>);
-    return go(hnsw_search_mw_kernel<SPACE, 4, false>);
+    if (sa_emax <= 2) return go(hnsw_search_mw_kernel<SPACE, 2, false, ROW>);
+    return go(hnsw_search_mw_kernel<SPACE, 4, false, ROW>);
 }
 
-hipError_t launch_hnsw_search_mw(const HnswArgs& a, size_t lds_bytes, int sa_emax, hipStream_t s) {
+hipError_t launch_hnsw_search_mw(const HnswArgs& a, size_t lds_bytes, int sa_emax, bool rows_f16, hipStream_t s) {
     if (sa_emax > MW_MAX_EMAX || a.g.maxM0 > 62 || a.g.maxM > 62) return hipErrorInvalidValue;
+    // (the fp16 walk serves external queries only: graphs are built from the f32 rows)
+    if (rows_f16 && (!a.g.rows16 || a.query_rows)) return hipErrorInvalidValue;
     return hnsw_dispatch_space(a.g.space, [&](auto sp) {
         if constexpr (sp.value == SP_L2SQR_SIFT) return hipErrorInvalidValue;  // (no multi-wave kernel over u8 rows)
-        else return launch_mw_space<sp.value>(a, lds_bytes, sa_emax, s);
+        else return rows_f16 ? launch_mw_space<sp.value, half_t>(a, lds_bytes, sa_emax, s)
+                             : launch_mw_space<sp.value, float>(a, lds_bytes, sa_emax, s);
     });
 }
 

@@ -297,6 +297,11 @@ struct HnswDeviceGraph {
     int maxM, maxM0, maxlevel, enterpoint;
     int space;                 // search-time SpaceCode (SP_L2SQR, SP_NORMCOS, ...)
     int normalize_query;       // cosine on the optimized index
+    // fp16 traversal copy of the f32 rows (gpu_rows=f16; null without one): fp16(2^e * row), row stride ld16 halves (a
+    // multiple of 8, zero padded), inv_scale16 = 2^-e
+    const void* rows16;
+    int ld16;
+    float inv_scale16;
 };
 struct HnswSearchPlan {
     int nq, k, ef, cap;        // cap = max(ef, k)
@@ -307,6 +312,8 @@ struct HnswSearchPlan {
     // SearchOld kernel only (hnsw_make_plan_old): candidate heap and queue placement
     int heap_lds, heap_cap;    // heap entries in LDS / in total per query (the rest lives in the HBM workspace)
     int a_in_lds, r_in_lds;    // closest-queue values (ef floats) / result queue (k pairs) in LDS?
+    int rows_f16;              // launch_hnsw_search: the walk reads g.rows16 and emits its array for the re-rank: array order,
+                               // internal positions (set by the caller; the planners leave 0)
 };
 // entries of the frontier arrays: a multiple of 64 that holds the longest adjacency list (level 0 or above)
 inline int hnsw_nbcap(const HnswDeviceGraph& g) {
@@ -367,6 +374,15 @@ struct HnswOverflow {
 // caller without an overflow list re-runs those with a bitset plan).
 hipError_t launch_hnsw_search(const HnswDeviceGraph& g, const HnswSearchPlan& p, const HnswQueries& q, uint32_t* bitset,
                               const HnswOverflow& fix, const HnswOut& out, hipStream_t s);
+// fp16(scale * rows) -> rows16 [n][ld16] (f16_pack.hpp's rounding; columns dim .. ld16 are zero)
+hipError_t launch_hnsw_pack_rows16(const float* rows, int n, int ldv, int dim, float scale, void* rows16, int ld16,
+                                   hipStream_t s);
+// Exact f32 re-rank behind an fp16 walk.  cand [nq][cap]: the sorted arrays of the walk as internal positions (what a
+// launch with rows_f16 and k = cap writes: the fp16 kernels emit array order and positions), cand_n [nq] their lengths.  One wave per query: f32 distances of
+// the first min(rerank, cand_n) entries on g.rows (the bits the f32 walk computes for those rows), ordered by (distance,
+// position); k results with external ids, -1 / +inf padding and the count go to out.
+hipError_t launch_hnsw_rerank(const HnswDeviceGraph& g, int nq, int k, int cap, int rerank, const void* queries,
+                              const int32_t* cand, const int32_t* cand_n, const HnswOut& out, hipStream_t s);
 // SearchOld; ws_a / ws_r / ws_heap: the per-query HBM workspaces above (may be unused)
 hipError_t launch_hnsw_search_old(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries, uint32_t* bitset,
                                   void* ws_a, void* ws_r, void* ws_heap, const HnswOut& out, hipStream_t s);
