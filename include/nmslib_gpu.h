@@ -86,7 +86,8 @@ typedef struct {
     size_t shards;         /* row shards behind this handle (index parameter gpu_shards); 1 = single GPU */
     size_t last_path;      /* selection path of the last brute-force batch: 0 adaptive f32 MFMA, 1 bf16 fast path,
                               2 adaptive int8, 3 int8 fast path; 4 = HNSW; 5 = HNSW with the walk on the fp16 copy
-                              of the rows and an f32 re-rank (gpu_rows=f16) */
+                              of the rows and an f32 re-rank (gpu_rows=f16), and the brute-force scan for k > 512;
+                              6 = l1 fast path (8-bit SAD filter, exact f32 re-rank) */
     /* fast paths, last slice of the last batch (reading them waits for the stream): query tiles in the slice, tiles the
        threshold kernel sent through the split-bf16-product scan instead of the one-product scan (float rows only), and
        tiles whose verification failed and were redone by the adaptive kernel */

@@ -4,13 +4,18 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstring>
 
 #include "engine.hpp"
+#include "l1_quant.hpp"
 
 namespace gfxknn {
 
 void BruteDense::release() {
     have_bf16 = false;
+    have_l1 = false;
+    l1_u8.release();
+    l1_cols.release();
     bf_hi.release();
     bf_lo.release();
     f16_hi.release();
@@ -20,7 +25,7 @@ void BruteDense::release() {
 
 size_t BruteDense::bytes() const {
     size_t total = 0;
-    for (const DevBuf* b : {&rows_i8, &auxh, &rows_sel, &mean, &bf_hi, &bf_lo, &auxp, &f16_hi, &auxp16}) total += b->bytes();
+    for (const DevBuf* b : {&rows_i8, &auxh, &rows_sel, &mean, &bf_hi, &bf_lo, &auxp, &f16_hi, &auxp16, &l1_u8, &l1_cols}) total += b->bytes();
     return total;
 }
 
@@ -77,6 +82,55 @@ void Engine::make_fast_tiles(const BfSplitSrc& src, int dp, const float* aux, fl
     b.auxp16.ensure(n_pad * 4);
     hip_check(launch_split_bf16(src, aux, aux_pad, aux16_mul, b.tiles(dp, false), stream_), "split rows");
     b.have_bf16 = true;
+}
+
+// The resident side of the l1 fast path (l1_quant.hpp): column ranges -> common step -> byte copy in the scan's layout and
+// the columns' largest residuals.  Declined data (a non-finite element, no usable step) and a failed allocation leave the
+// index on the adaptive kernel.
+void Engine::make_l1_copy() {
+    BruteDense& b = brute_;
+    const size_t n = size();
+    const size_t dim = dim_, ld = (size_t)ldb_;
+    try {
+        DevBuf d_range, d_rmax;
+        d_range.ensure((2 * ld + 1) * 4);
+        hip_check(launch_l1_col_range(d_rows_.as<float>(), (int)n, ldb_, (int)dim, d_range.as<uint32_t>(), stream_), "l1 column ranges");
+        std::vector<uint32_t> range(2 * ld + 1);
+        hip_check(hipMemcpyAsync(range.data(), d_range.ptr(), range.size() * 4, hipMemcpyDeviceToHost, stream_), "l1 column ranges");
+        hip_check(hipStreamSynchronize(stream_), "l1 column ranges");
+        if (range[2 * ld] != 0) return;   // a non-finite element
+        auto from_ord = [](uint32_t o) {
+            const uint32_t bits = o ^ ((o >> 31) ? 0x80000000u : 0xFFFFFFFFu);
+            float f;
+            memcpy(&f, &bits, 4);
+            return f;
+        };
+        std::vector<float> cols(3 * dim, 0.f);   // lo, hi, rmax
+        for (size_t c = 0; c < dim; ++c) {
+            cols[c] = from_ord(range[c]);
+            cols[dim + c] = from_ord(range[ld + c]);
+        }
+        bool ok = false;
+        const double step = l1q::step_of(l1q::max_range(cols.data(), cols.data() + dim, dim), &ok);
+        if (!ok) return;
+        const size_t d4 = (dim + 3) / 4;
+        b.l1_cols.ensure(cols.size() * 4);
+        b.l1_u8.ensure((size_t)bf_l1_rows_padded((int)n) * d4 * 4);
+        d_rmax.ensure(dim * 4);
+        hip_check(hipMemcpyAsync(b.l1_cols.ptr(), cols.data(), cols.size() * 4, hipMemcpyHostToDevice, stream_), "l1 columns");
+        hip_check(launch_l1_quantise_rows(d_rows_.as<float>(), (int)n, ldb_, (int)dim, b.l1_cols.as<float>(), step,
+                                          b.l1_u8.as<uint32_t>(), d_rmax.as<uint32_t>(), stream_),
+                  "l1 byte copy");
+        hip_check(hipMemcpyAsync(b.l1_cols.as<float>() + 2 * dim, d_rmax.ptr(), dim * 4, hipMemcpyDeviceToDevice, stream_), "l1 residuals");
+        hip_check(hipStreamSynchronize(stream_), "l1 byte copy");   // (`cols` and d_rmax go out of scope)
+        b.l1_step = step;
+        b.have_l1 = true;
+    } catch (const EngineError& e) {
+        if (e.code != Err::OutOfMemory) throw;
+        (void)hipGetLastError();
+        b.l1_u8.release();
+        b.l1_cols.release();
+    }
 }
 
 // The brute-force branch of finalize(): the rows are in HBM (upload_rows)
@@ -201,6 +255,7 @@ void Engine::prepare_brute() {
                         space_ == SP_NEGDOT ? nullptr : d_aux_.as<float>(), space_ == SP_L2 ? -INFINITY : 0.f,
                         space_ == SP_L2 ? b.f16_scale * b.f16_scale : 1.f);
     }
+    if (space_ == SP_L1 && n >= 65536 && dim_ <= (size_t)BF_L1_MAX_DIM) make_l1_copy();
     hip_check(hipStreamSynchronize(stream_), "finalize");
 }
 
@@ -301,6 +356,32 @@ void Engine::knn_brute(const void* d_queries, size_t nq, size_t k, int32_t* d_id
             fast_flags_ = ws.tile_fail(f);
             fast_nqt_ = f.nqt;
             fast_has_precise_ = true;
+            return;
+        }
+    }
+    if (space_ == SP_L1 && b.have_l1) {
+        // large batches: v_sad_u8 filter over the byte copy, exact re-rank, proof (bf_l1_kernels.hip)
+        const char* env = getenv("NMSLIB_GPU_L1_FAST");
+        const BfL1Fast f = bf_l1_fast_plan((int)d_n_, dim_eff, (int)nq, (int)k);
+        if (f.use && !(env && atoi(env) == 0)) {
+            ws_qpad_.ensure((size_t)f.qpad * ldb_ * 4);
+            BfL1Ws ws{};
+            ws.qt = static_cast<uint32_t*>(b.ws_l1_qt.ensure((size_t)f.d4 * f.qpad * 4));
+            ws.xe = static_cast<double*>(b.ws_l1_xe.ensure((size_t)f.qpad * 16));
+            ws.cand.cand = static_cast<unsigned long long*>(b.ws_l1_cand.ensure((size_t)f.qpad * f.nsplit * f.kprime * 8));
+            ws.cand.cnt = static_cast<int*>(b.ws_l1_cnt.ensure((size_t)f.qpad * f.nsplit * 4));
+            ws.flags = static_cast<int*>(b.ws_flags.ensure((size_t)f.nqt * 4 + 64));
+            ws.fb.cand = static_cast<unsigned long long*>(ws_cand_.ensure(bf_cand_elems(f.fallback) * 8));
+            ws.fb.cnt = static_cast<int*>(ws_cnt_.ensure(bf_cnt_elems(f.fallback) * 4));
+            const float* cols = b.l1_cols.as<float>();
+            const BfL1Rows copy{b.l1_u8.as<uint32_t>(), cols, cols + dim_, cols + 2 * dim_, b.l1_step};
+            hip_check(launch_bf_l1_fast(f, (int)nq, (int)k, rows, copy, static_cast<const float*>(d_queries), ws_qpad_.as<float>(),
+                                        ws, out, prof_pair(), stream),
+                      "bf_l1_fast");
+            last_path = 6;
+            fast_flags_ = ws.flags;
+            fast_nqt_ = f.nqt;
+            fast_has_precise_ = false;
             return;
         }
     }

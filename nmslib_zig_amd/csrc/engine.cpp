@@ -1188,7 +1188,7 @@ void Engine::fast_tile_counts(size_t* tiles, size_t* precise, size_t* fallback) 
         shards_[0]->fast_tile_counts(tiles, precise, fallback);
         return;
     }
-    if ((last_path != 1 && last_path != 3) || !fast_flags_ || fast_nqt_ <= 0) return;
+    if ((last_path != 1 && last_path != 3 && last_path != 6) || !fast_flags_ || fast_nqt_ <= 0) return;
     std::vector<int> h((size_t)fast_nqt_ * 2, 0);
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hip_check(hipStreamSynchronize(last_stream_ ? last_stream_ : stream_), "stats");

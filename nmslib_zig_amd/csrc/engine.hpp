@@ -143,11 +143,17 @@ struct BruteDense {
     float f16_scale_q = 1.f;             // scale of a batch's fp16 queries (the rows' scale, except centred cosine)
     float cosc_lambda = 1.f;             // centred cosine on the fast path: scale of the two constant columns (row_aug_cosc_kernel)
     float bmax_c = 0, bres_c = 0;        // largest norm / bf16 rounding residual of the augmented rows
-    // per-batch workspaces (grow-only, not resident data): the blocks of BfFastWs; the augmented queries of centred
+    // l1 fast path: the 8-bit copy of the rows in the scan's layout, per column lo / hi / rmax ([3][dim]
+    // floats) and the common step; have_l1 = false: declined (l1_quant.hpp) or no room in HBM, the index stays adaptive
+    DevBuf l1_u8, l1_cols;
+    double l1_step = 0;
+    bool have_l1 = false;
+    // per-batch workspaces (grow-only, not resident data): the blocks of BfFastWs and of BfL1Ws; the augmented queries of centred
     // cosine on the fast path; verified l2 path: query tiles whose proof failed (exact tail)
     DevBuf ws_top8, ws_thr, ws_list, ws_listcnt, ws_f32_q, ws_qaug, ws_flags;
+    DevBuf ws_l1_qt, ws_l1_xe, ws_l1_cand, ws_l1_cnt;
 
-    void release();        // drops the fast-path tiles
+    void release();        // drops the fast paths' resident data
     size_t bytes() const;  // every resident buffer (no workspace)
     // the tiles as a launch part; dp: the plan's row length; augmented: they were cut from the augmented rows
     BfF32Tiles tiles(int dp, bool augmented) const;
@@ -334,6 +340,7 @@ class Engine {
     void prepare_brute();
     void measure_rows_f16(const float* rows, size_t n, int ld, int dim, bool relative, float* bm);
     void make_fast_tiles(const BfSplitSrc& src, int dp, const float* aux, float aux_pad, float aux16_mul);
+    void make_l1_copy();   // the l1 fast path's resident side; leaves have_l1 = false when declined or out of memory
     void knn_brute(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
                    int32_t* d_cnt, hipStream_t stream);
     void knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,

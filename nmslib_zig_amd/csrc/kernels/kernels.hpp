@@ -281,6 +281,48 @@ hipError_t launch_row_aug_cosc(const float* orig, const float* centred, int n, i
 hipError_t launch_query_aug_cosc(const float* centred, const float* qaux, int nq, int qpad, int ldb, int dim, float lambda,
                                  float* out, int ldo, hipStream_t s);
 
+// l1 fast path for large batches (bf_l1_kernels.hip: v_sad_u8 filter scan over an 8-bit copy of the rows, exact f32
+// re-rank of the per-split lists, per-query proof, adaptive fallback for flagged tiles).  Exact like the adaptive path.
+constexpr int BF_L1_MAX_DIM = 256;    // a SAD over 256 bytes still fits the 16-bit score field of the scan's keys
+constexpr int BF_L1_ROW_TILE = 128;   // rows per scan step: the copy is padded to a multiple of it
+inline int bf_l1_rows_padded(int n) { return (n + BF_L1_ROW_TILE - 1) / BF_L1_ROW_TILE * BF_L1_ROW_TILE; }
+struct BfL1Fast {
+    bool use;
+    int d4;                            // dwords per row of the copy: ceil(dim / 4)
+    int qpad, nqt;                     // queries padded to BF_TQ; query tiles
+    int nsplit, rows_per_split;        // row splits, each with its own lists
+    int kprime;                        // keys kept per (query, split)
+    size_t lds_scan;
+    BfPlan list;                       // the lists as launch_bf_rerank reads them (nsplit, cap = kprime, p2max)
+    BfPlan fallback;                   // plan of the adaptive kernel for the fallback
+};
+BfL1Fast bf_l1_fast_plan(int n, int dim, int nq, int k);
+// The copy as finalize leaves it: u8 [n_pad / 64][d4][64] dwords (dword j of row r at ((r / 64) * d4 + j) * 64 + r % 64),
+// the columns' smallest and largest elements, their largest residuals and the common step (l1_quant.hpp)
+struct BfL1Rows {
+    const uint32_t* u8;
+    const float *lo, *hi, *rmax;
+    double step;
+};
+// Per-batch workspace: qt [d4][qpad] dwords, xe [qpad][2] doubles (excess, bound), cand / cnt of the lists
+// ([qpad][nsplit][kprime] keys, [qpad][nsplit] counts), flags [nqt], fb: the adaptive fallback's survivors (f.fallback)
+struct BfL1Ws {
+    uint32_t* qt;
+    double* xe;
+    BfCand cand;
+    int* flags;
+    BfCand fb;
+};
+// range [2 * ld + 1] words: per column the smallest, then the largest element as ordered bits (larger float -> larger
+// word: bits ^ 0x80000000 for positive floats, ~bits for negative ones), then a flag for non-finite elements.  ld <= 256.
+hipError_t launch_l1_col_range(const float* rows, int n, int ld, int dim, uint32_t* range, hipStream_t s);
+// rows -> the byte copy (bf_l1_rows_padded(n) rows) and rmax_bits [dim]: the largest residuals, f32 bits rounded up
+hipError_t launch_l1_quantise_rows(const float* rows, int n, int ld, int dim, const float* lo, double step, uint32_t* out,
+                                   uint32_t* rmax_bits, hipStream_t s);
+hipError_t launch_bf_l1_fast(const BfL1Fast& f, int nq, int k, const BfF32Rows& rows, const BfL1Rows& copy,
+                             const float* queries_raw, float* queries_padded, const BfL1Ws& ws, const BfOut& out,
+                             const BfScanEvents& ev, hipStream_t s);
+
 // one pair, one wave (nmslib_get_distance)
 hipError_t launch_pair_distance(int space, const void* a, const void* b, int dim, float* out,
                                 hipStream_t s);

@@ -37,7 +37,7 @@ def main():
     for dname, gen in datasets.items():
         X = gen(a.n)
         Q = gen(a.nq + 7)[7:]
-        for space in ("l2", "cosinesimil", "negdotprod"):
+        for space in ("l2", "cosinesimil", "negdotprod", "l1"):
             idx = nz.Index(space, "seq_search")
             idx.addDenseBatch(X)
             idx.buildIndex()
