@@ -97,6 +97,10 @@ typedef struct {
     /* HNSW with the LDS visited table, last batch (reading it waits for the stream): queries whose table filled up and
        that the HBM-bitset kernel answered again.  0 on every BASELINE configuration. */
     size_t hnsw_redone;
+    /* the last finalize: rows it inserted into the graph that was resident (index parameter gpu_append=1; 0 = it built
+       the index in full), and rows it copied from the host to HBM */
+    size_t rows_appended;
+    size_t rows_uploaded;
 } nmslib_gpu_stats_t;
 nmslib_error_t nmslib_gpu_get_stats(nmslib_index_handle_t index, nmslib_gpu_stats_t* out);
 

@@ -860,6 +860,8 @@ nmslib_error_t nmslib_gpu_get_stats(nmslib_index_handle_t handle, nmslib_gpu_sta
         out->last_path = (size_t)e->last_path;
         e->fast_tile_counts(&out->fast_tiles, &out->fast_tiles_precise, &out->fast_tiles_fallback);
         out->hnsw_redone = e->hnsw_redone();
+        out->rows_appended = e->rows_appended;
+        out->rows_uploaded = e->rows_uploaded;
     });
 }
 

@@ -71,6 +71,8 @@ void Engine::upload_diverg() {
     if (n) hip_check(hipMemcpyAsync(d_ids_.ptr(), ids_.data(), n * 4, hipMemcpyHostToDevice, stream_), "ids H2D");
     hip_check(hipStreamSynchronize(stream_), "diverg upload");
     d_n_ = n;
+    rows_uploaded = n;
+    rows_appended = 0;
     upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 

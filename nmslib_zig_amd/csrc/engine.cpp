@@ -92,7 +92,23 @@ void* DevBuf::ensure(size_t bytes) {
     // NMSLIB_GPU_POISON=<byte>: fill every new workspace with that byte, so that a kernel reading memory nobody wrote
     // shows up in the tests instead of depending on what the allocator hands back
     static const char* poison = getenv("NMSLIB_GPU_POISON");
-    if (poison) hip_check(hipMemset(p_, atoi(poison) & 0xFF, bytes), "poison");
+    if (poison) {
+        // (waited for: the fill runs on the null stream, the buffer's first user may be a stream that does not wait for it)
+        hip_check(hipMemset(p_, atoi(poison) & 0xFF, bytes), "poison");
+        hip_check(hipStreamSynchronize(nullptr), "poison");
+    }
+    return p_;
+}
+void* DevBuf::grow_keep(size_t bytes, size_t keep, hipStream_t s) {
+    if (bytes <= n_ && p_) return p_;
+    DevBuf grown;
+    grown.ensure(bytes);
+    if (keep > n_) keep = n_;
+    if (p_ && keep) {
+        hip_check(hipMemcpyAsync(grown.p_, p_, keep, hipMemcpyDeviceToDevice, s), "grow: copy");
+        hip_check(hipStreamSynchronize(s), "grow: copy");  // the old block is freed below
+    }
+    swap(grown);
     return p_;
 }
 void DevBuf::swap(DevBuf& o) {
@@ -333,6 +349,9 @@ void Engine::reset() {
     graph_rows_.clear();
     loaded_graph_ = false;
     graph_builder_ = 0;
+    built_n_ = 0;
+    host_links_stale_ = false;
+    rows_appended = rows_uploaded = 0;
     created_ = false;
     dirty_ = true;
     graph_dirty_ = true;
@@ -406,12 +425,21 @@ void Engine::create_index(const std::vector<std::string>& params) {
         ps.get("gpu_build", bp.gpu_build);  // engine extension: batched construction on the GPU (1), host (0)
         ps.get("gpu_build_batch", bp.gpu_build_batch);
         ps.get("gpu_build_div", bp.gpu_build_div);
+        if (!str_space_) {  // the dense spaces' GPU builder (a string graph is built on the host: unknown parameters there)
+            ps.get("gpu_build_cut", bp.gpu_build_cut);  // engine extension: a batch boundary at this position
+            ps.get("gpu_append", bp.gpu_append);        // engine extension: later rows go into the GPU-built graph (1)
+        }
         ps.get("gpu_shards", gpu_shards_);  // engine extension: row shards over the visible GPUs (0 = all)
         std::string gpu_rows = "f32";       // engine extension: f16 = the search walks an fp16 copy of the rows
         ps.get("gpu_rows", gpu_rows);
         ps.check_unused();
         const bool f16 = parse_gpu_rows(gpu_rows);
         if (f16) check_rows16_served();
+        if (bp.gpu_append != 0 && bp.gpu_append != 1)
+            throw EngineError(Err::IndexBuildFailed, "gpu_append must be 0 or 1, got " + std::to_string(bp.gpu_append));
+        if (bp.gpu_build_cut < 0)
+            throw EngineError(Err::IndexBuildFailed, "gpu_build_cut must be a row position (0 = off), got " +
+                                                         std::to_string(bp.gpu_build_cut));
         rows_f16_index_ = rows_f16_ = f16;
         rerank_ = 0;
         if (defer && bp.gpu_build < 0) bp.gpu_build = 0;  // deferred upload = no device work now
@@ -441,6 +469,8 @@ void Engine::create_index(const std::vector<std::string>& params) {
     graph_dirty_ = true;
     loaded_graph_ = false;
     graph_builder_ = 0;
+    built_n_ = 0;
+    host_links_stale_ = false;
     if (!ids_.empty()) {
         if (defer) ensure_graph();
         else finalize();
@@ -527,37 +557,49 @@ void Engine::check_device() {
     hip_check(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking), "hipStreamCreate");
 }
 
-void Engine::upload_rows() {
-    const size_t n = size();
+// Rows [first, n) go to HBM.  first = 0: all of them, into buffers sized for n.  first > 0 (gpu_append): the buffers grow keeping
+// rows [0, first), and only the new rows cross PCIe.
+void Engine::upload_rows(size_t first) {
+    const size_t n = size(), added = n - first;
     auto t0 = clk::now();
     dg_.rows16 = nullptr;  // the fp16 copy follows the rows
     rows16_failed_ = false;
+    auto room = [&](DevBuf& b, size_t row_bytes) {
+        if (first) b.grow_keep(n * row_bytes, first * row_bytes, stream_);
+        else b.ensure(std::max<size_t>(n, 1) * row_bytes);
+    };
     if (is_u8()) {
         ldb_ = 128;
-        d_rows_.ensure(std::max<size_t>(n, 1) * 128);
-        if (n) hip_check(hipMemcpy(d_rows_.ptr(), rows_u8(), n * 128, hipMemcpyHostToDevice), "upload rows");
+        room(d_rows_, 128);
+        if (added)
+            hip_check(hipMemcpy(d_rows_.as<uint8_t>() + first * 128, rows_u8() + first * 128, added * 128, hipMemcpyHostToDevice),
+                      "upload rows");
     } else {
         ldb_ = f32_row_stride((int)dim_);
-        d_rows_.ensure(std::max<size_t>(n, 1) * ldb_ * 4);
+        room(d_rows_, (size_t)ldb_ * 4);
         const float* src = rows_f32();
         if (loaded_graph_ && !graph_rows_.empty()) src = graph_rows_.data();
-        if (n) {
-            hip_check(hipMemset(d_rows_.ptr(), 0, n * ldb_ * 4), "clear rows");
-            hip_check(hipMemcpy2D(d_rows_.ptr(), (size_t)ldb_ * 4, src, dim_ * 4, dim_ * 4, n, hipMemcpyHostToDevice),
+        if (added) {
+            float* dst = d_rows_.as<float>() + first * (size_t)ldb_;
+            hip_check(hipMemset(dst, 0, added * ldb_ * 4), "clear rows");
+            hip_check(hipMemcpy2D(dst, (size_t)ldb_ * 4, src + first * dim_, dim_ * 4, dim_ * 4, added, hipMemcpyHostToDevice),
                       "upload rows");
         }
     }
-    d_ids_.ensure(std::max<size_t>(n, 1) * 4);
+    room(d_ids_, 4);
     if (parent_) {
         // shard child: results carry GLOBAL positions; the parent maps them to external ids after the merge, so
         // that ties are ordered exactly as in the unsharded index (distance, position)
-        std::vector<int32_t> pos(n);
-        for (size_t i = 0; i < n; ++i) pos[i] = (int32_t)(view_lo_ + i);
-        if (n) hip_check(hipMemcpy(d_ids_.ptr(), pos.data(), n * 4, hipMemcpyHostToDevice), "upload positions");
-    } else if (n) {
-        hip_check(hipMemcpy(d_ids_.ptr(), ids_.data(), n * 4, hipMemcpyHostToDevice), "upload ids");
+        std::vector<int32_t> pos(added);
+        for (size_t i = 0; i < added; ++i) pos[i] = (int32_t)(view_lo_ + first + i);
+        if (added)
+            hip_check(hipMemcpy(d_ids_.as<int32_t>() + first, pos.data(), added * 4, hipMemcpyHostToDevice), "upload positions");
+    } else if (added) {
+        hip_check(hipMemcpy(d_ids_.as<int32_t>() + first, ids_.data() + first, added * 4, hipMemcpyHostToDevice), "upload ids");
     }
     d_n_ = n;
+    rows_uploaded = added;
+    rows_appended = 0;
     upload_seconds = std::chrono::duration<double>(clk::now() - t0).count();
 }
 
@@ -567,13 +609,16 @@ void Engine::build_graph() {
         const void* rows = is_u8() ? static_cast<const void*>(rows_u8()) : static_cast<const void*>(rows_f32());
         hnsw_build_host(space_, rows, size(), dim_, bp_, graph_);
         graph_builder_ = 1;
+        built_n_ = 0;
+        host_links_stale_ = false;
     }
     build_seconds = std::chrono::duration<double>(clk::now() - t0).count();
 }
 
-void Engine::prepare_graph_rows() {
+// first > 0 (gpu_append): rows [0, first) are prepared already and dg_ describes their graph; only rows [first, n) are touched
+void Engine::prepare_graph_rows(size_t first) {
     // search-time distance of the flat ("optimized") index, hnsw.cc:369-412
-    const size_t n = size();
+    const size_t n = size(), added = n - first;
     int sspace = space_;
     bool normalize = false;
     const bool optimized = !bp_.skip_optimized;
@@ -585,19 +630,22 @@ void Engine::prepare_graph_rows() {
         }
     }
     if (normalize && !(loaded_graph_ && !graph_rows_.empty()))
-        hip_check(launch_normalize_rows(d_rows_.as<float>(), (int)n, ldb_, (int)dim_, stream_), "normalize rows");
+        hip_check(launch_normalize_rows(d_rows_.as<float>() + first * (size_t)ldb_, (int)added, ldb_, (int)dim_, stream_),
+                  "normalize rows");
     if (is_u8()) {
-        d_rownorm_.ensure(std::max<size_t>(n, 1) * 4);
-        std::vector<int32_t> norms(n);
-        for (size_t i = 0; i < n; ++i) {
+        if (first) d_rownorm_.grow_keep(n * 4, first * 4, stream_);
+        else d_rownorm_.ensure(std::max<size_t>(n, 1) * 4);
+        std::vector<int32_t> norms(added);
+        for (size_t i = 0; i < added; ++i) {
             int32_t s = 0;
-            const uint8_t* r8 = rows_u8() + i * 128;
+            const uint8_t* r8 = rows_u8() + (first + i) * 128;
             for (int t = 0; t < 128; ++t) s += (int32_t)r8[t] * (int32_t)r8[t];
             norms[i] = s;
         }
-        if (n) hip_check(hipMemcpy(d_rownorm_.ptr(), norms.data(), n * 4, hipMemcpyHostToDevice), "row norms");
+        if (added)
+            hip_check(hipMemcpy(d_rownorm_.as<int32_t>() + first, norms.data(), added * 4, hipMemcpyHostToDevice), "row norms");
     }
-    dg_ = HnswDeviceGraph{};
+    if (!first) dg_ = HnswDeviceGraph{};
     dg_.rows = d_rows_.ptr();
     dg_.row_norm = d_rownorm_.as<int32_t>();
     dg_.ext_ids = d_ids_.as<int32_t>();
@@ -649,11 +697,9 @@ bool Engine::ensure_rows16() {
         hip_check(hipMemcpyAsync(bm, d_bm.ptr(), 16, hipMemcpyDeviceToHost, stream_), "fp16 rows: range");
         hip_check(hipStreamSynchronize(stream_), "fp16 rows: range");
         e = f16pack::scale_exp(bm[2]);
+        rows16_max_ = bm[2];
         d_rows16_.ensure(n * (size_t)ld16 * 2);
-        hip_check(launch_hnsw_pack_rows16(d_rows_.as<float>(), (int)n, ldb_, (int)dim_, f16pack::scale_of(e), d_rows16_.ptr(),
-                                          ld16, stream_),
-                  "fp16 rows");
-        hip_check(hipStreamSynchronize(stream_), "fp16 rows");
+        pack_rows16(0, n, e);
     } catch (const EngineError& x) {
         if (x.code != Err::OutOfMemory) throw;
         d_rows16_.release();  // (nothing partial stays behind)
@@ -663,7 +709,16 @@ bool Engine::ensure_rows16() {
     dg_.rows16 = d_rows16_.ptr();
     dg_.ld16 = ld16;
     dg_.inv_scale16 = f16pack::scale_of(-e);
+    rows16_exp_ = e;
     return true;
+}
+
+void Engine::pack_rows16(size_t first, size_t n, int e) {
+    const size_t ld16 = f16pack::row_stride(dim_);
+    hip_check(launch_hnsw_pack_rows16(d_rows_.as<float>() + first * (size_t)ldb_, (int)(n - first), ldb_, (int)dim_,
+                                      f16pack::scale_of(e), d_rows16_.as<uint16_t>() + first * ld16, (int)ld16, stream_),
+              "fp16 rows");
+    hip_check(hipStreamSynchronize(stream_), "fp16 rows");
 }
 
 bool Engine::use_gpu_build() const {
@@ -698,6 +753,8 @@ void Engine::build_graph_gpu() {
     if (efC < 1 || efC > 1024)
         throw EngineError(Err::IndexBuildFailed, "HNSW: efConstruction must be in [1, 1024] for the GPU builder");
     graph_builder_ = 2;
+    built_n_ = 0;  // (set again below: a build that throws leaves no graph to append to)
+    host_links_stale_ = false;
     const bool post = bp_.post != 0 && n > 1;
     const std::vector<int32_t> draws = hnsw_random_levels(post ? 2 * n : n, bp_);
     build_graph_gpu_pass(std::vector<int32_t>(draws.begin(), draws.begin() + (ptrdiff_t)n), false);
@@ -748,18 +805,23 @@ void Engine::build_graph_gpu() {
                       "up_links D2H");
         hip_check(hipStreamSynchronize(s), "graph download");
     }
+    release_build_workspaces();
+    built_n_ = n;
+    build_seconds = n ? std::chrono::duration<double>(clk::now() - t0).count() : 0;
+}
+
+void Engine::release_build_workspaces() {
     for (DevBuf* b : {&wb_pts_, &wb_src_, &wb_starts_, &wb_cand_ids_, &wb_cand_d_, &wb_cand_n_, &wb_status_,
                       &wb_req_key_, &wb_req_dist_, &wb_req_key2_, &wb_req_dist2_, &wb_sort_tmp_, &wb_active_, &wb_nactive_, &wb_extra_ids_, &wb_extra_d_, &wb_extra_n_})
         b->release();
-    build_seconds = n ? std::chrono::duration<double>(clk::now() - t0).count() : 0;
 }
 
 // One insertion pass over all rows: position 0 is node 0, position i > 0 is node i, or node n - i in reverse order.
 // Leaves the graph in d_links0_ / d_up_off_ / d_up_links_ (dg_) and its levels, offsets and entry point in graph_.
+// This part allocates and clears the graph with node 0 in it; build_graph_gpu_insert adds the other positions.
 void Engine::build_graph_gpu_pass(const std::vector<int32_t>& levels, bool reverse) {
     const size_t n = size();
     const int M = bp_.M, maxM = bp_.maxM, maxM0 = bp_.maxM0, efC = bp_.efConstruction;
-    auto node_at = [&](size_t pos) { return reverse && pos ? n - pos : pos; };
     HostGraph& g = graph_;
     g = HostGraph{};
     g.n = (int)n;
@@ -792,10 +854,24 @@ void Engine::build_graph_gpu_pass(const std::vector<int32_t>& levels, bool rever
     hip_check(hipMemsetAsync(d_links0_.ptr(), 0, l0_ints * 4, s), "clear links0");
     hip_check(hipMemsetAsync(d_up_links_.ptr(), 0, std::max<size_t>(up_ints, 1) * 4, s), "clear up_links");
     hip_check(hipMemcpyAsync(d_up_off_.ptr(), g.up_off.data(), n * 8, hipMemcpyHostToDevice, s), "up_off");
+    g.maxlevel = dg_.maxlevel = g.levels[0];
+    g.enterpoint = dg_.enterpoint = 0;
+    build_graph_gpu_insert(1, reverse);
+}
 
+// Inserts positions [first, n) into the graph of positions [0, first) that dg_ / graph_ describe (lists on the device, cleared
+// for the new nodes; levels, offsets, top level and entry point in graph_), batch by batch.  The schedule of a batch depends
+// on the positions before it only, never on n: inserting [first, n) into a finished graph of `first` nodes is what a pass
+// over all n does from its batch boundary at `first` on (gpu_build_cut puts one there).
+void Engine::build_graph_gpu_insert(size_t first, bool reverse) {
+    const size_t n = size();
+    const int M = bp_.M, efC = bp_.efConstruction;
+    auto node_at = [&](size_t pos) { return reverse && pos ? n - pos : pos; };
+    HostGraph& g = graph_;
+    hipStream_t s = stream_;
     HnswDeviceGraph bgraph = dg_;
     bgraph.ext_ids = nullptr;  // construction works on internal positions
-    int maxlevel = g.levels[0], enterpoint = 0;
+    int maxlevel = g.maxlevel, enterpoint = g.enterpoint;
     const int max_batch = bp_.gpu_build_batch > 0 ? bp_.gpu_build_batch : 4096;
     const int batch_div = bp_.gpu_build_div > 0 ? bp_.gpu_build_div : 16;
     // reverse-link requests of one level of one batch: M slots per new node, sorted on the device
@@ -814,11 +890,13 @@ void Engine::build_graph_gpu_pass(const std::vector<int32_t>& levels, bool rever
 
     std::vector<int32_t> pts, src, status;
     std::vector<size_t> base;
-    size_t next = 1;
+    const size_t cut = bp_.gpu_build_cut > 0 ? (size_t)bp_.gpu_build_cut : 0;
+    size_t next = first;
     while (next < n) {
         const size_t sz = next;
         size_t bsz = std::min<size_t>(std::max<size_t>(sz / (size_t)batch_div, 1), (size_t)max_batch);
         size_t end = std::min(n, next + bsz);
+        if (next < cut) end = std::min(end, cut);
         for (size_t i = next; i < end; ++i)
             if (g.levels[node_at(i)] > maxlevel) {
                 end = i + 1;
@@ -935,6 +1013,111 @@ void Engine::build_graph_gpu_pass(const std::vector<int32_t>& levels, bool rever
     dg_.enterpoint = enterpoint;
 }
 
+// gpu_append=1: the resident graph is the GPU builder's over rows [0, built_n_), complete and not post-processed, and all that
+// happened since is add_row.  (finalize() has dealt with shards and checked use_gpu_build() before it asks.)
+bool Engine::can_append() const {
+    return bp_.gpu_append == 1 && graph_builder_ == 2 && built_n_ >= 1 && size() > built_n_ && d_n_ == built_n_ &&
+           (size_t)graph_.n == built_n_ && bp_.post == 0 && !parent_ && shards_.empty() && !loaded_graph_;
+}
+
+// Rows [n0, n1) added after a GPU build go into the resident graph: the buffers grow to n1 rows keeping
+// their contents, only the new rows are uploaded and prepared, the level stream goes on where the build left it, and the
+// builder's batch loop is entered at position n0.  The result is the graph a build of all n1 rows makes with a batch boundary
+// at n0 (gpu_build_cut).  false: a buffer could not grow or the insertion ran out of memory; the caller builds in full from
+// the host rows.
+bool Engine::append_rows_gpu() {
+    const auto t0 = clk::now();
+    const size_t n0 = built_n_, n1 = size(), added = n1 - n0;
+    const int maxM = bp_.maxM;
+    const size_t l0_row = (size_t)(bp_.maxM0 + 1) * 4, ld16 = f16pack::row_stride(dim_);
+    HostGraph& g = graph_;
+    hipStream_t s = stream_;
+    built_n_ = 0;  // (set again at the end: an append that throws leaves no graph to append to)
+    const std::vector<int32_t> levels = hnsw_random_levels(n1, bp_);  // one stream: its first n0 draws are g.levels
+    size_t up_ints = graph_up_ints_;
+    std::vector<int64_t> up_off(added, -1);
+    for (size_t i = n0; i < n1; ++i)
+        if (levels[i] > 0) {
+            up_off[i - n0] = (int64_t)up_ints;
+            up_ints += (size_t)levels[i] * (maxM + 1);
+        }
+    const bool have16 = dg_.rows16 != nullptr;  // (upload_rows takes the copy out of dg_ until the new rows are in it)
+    try {
+        upload_rows(n0);
+        prepare_graph_rows(n0);
+        d_links0_.grow_keep(n1 * l0_row, n0 * l0_row, s);
+        d_up_off_.grow_keep(n1 * 8, n0 * 8, s);
+        d_up_links_.grow_keep(std::max<size_t>(up_ints, 1) * 4, graph_up_ints_ * 4, s);
+        if (have16) d_rows16_.grow_keep(n1 * ld16 * 2, n0 * ld16 * 2, s);
+        dg_.links0 = d_links0_.as<int32_t>();
+        dg_.up_off = d_up_off_.as<int64_t>();
+        dg_.up_links = d_up_links_.as<int32_t>();
+        // the graph's host side and the new nodes' empty lists
+        g.n = (int)n1;
+        g.levels.insert(g.levels.end(), levels.begin() + (ptrdiff_t)n0, levels.end());
+        g.up_off.insert(g.up_off.end(), up_off.begin(), up_off.end());
+        hip_check(hipMemsetAsync(d_links0_.as<char>() + n0 * l0_row, 0, added * l0_row, s), "clear links0");
+        if (up_ints > graph_up_ints_)
+            hip_check(hipMemsetAsync(d_up_links_.as<int32_t>() + graph_up_ints_, 0, (up_ints - graph_up_ints_) * 4, s),
+                      "clear up_links");
+        hip_check(hipMemcpyAsync(d_up_off_.as<int64_t>() + n0, up_off.data(), added * 8, hipMemcpyHostToDevice, s), "up_off");
+        graph_up_ints_ = up_ints;
+        host_links_stale_ = true;
+        hnsw_fix_valid_ = false;
+        build_graph_gpu_insert(n0, false);
+    } catch (const EngineError& x) {
+        if (x.code != Err::OutOfMemory) throw;
+        // a buffer could not grow, or the insertion's workspaces did not fit beside the grown index: make room, build in full
+        (void)hipStreamSynchronize(s);
+        release_build_workspaces();
+        for (DevBuf* b : {&d_links0_, &d_up_off_, &d_up_links_, &d_rows16_}) b->release();
+        host_links_stale_ = false;
+        return false;
+    }
+    release_build_workspaces();
+    // the fp16 copy: the new rows at the copy's scale; all rows again (on the device) if the new ones move the scale
+    if (have16) {
+        DevBuf d_bm;
+        d_bm.ensure(16);
+        float bm[4] = {0.f, 0.f, 0.f, 0.f};
+        hip_check(launch_row_maxnorm(d_rows_.as<float>() + n0 * (size_t)ldb_, (int)added, ldb_, (int)dim_, false,
+                                     d_bm.as<float>(), s),
+                  "fp16 rows: range");
+        hip_check(hipMemcpyAsync(bm, d_bm.ptr(), 16, hipMemcpyDeviceToHost, s), "fp16 rows: range");
+        hip_check(hipStreamSynchronize(s), "fp16 rows: range");
+        rows16_max_ = std::max(rows16_max_, bm[2]);
+        const int e = f16pack::scale_exp(rows16_max_);
+        pack_rows16(e == rows16_exp_ ? n0 : 0, n1, e);
+        rows16_exp_ = e;
+        dg_.rows16 = d_rows16_.ptr();
+        dg_.inv_scale16 = f16pack::scale_of(-e);
+    } else if (rows_f16_index_) {
+        (void)ensure_rows16();
+    }
+    built_n_ = n1;
+    rows_appended = added;
+    build_seconds = std::chrono::duration<double>(clk::now() - t0).count() - upload_seconds;
+    return true;
+}
+
+// After an append the adjacency lists of graph_ are behind the device's (old nodes got new links too); the file writer
+// reads them, so they are fetched when it asks.
+void Engine::sync_host_graph() {
+    if (!host_links_stale_) return;
+    host_links_stale_ = false;
+    if (graph_builder_ != 2 || built_n_ != (size_t)graph_.n) return;  // (graph_ is no longer the appended graph)
+    check_device();
+    HostGraph& g = graph_;
+    const size_t l0_ints = (size_t)g.n * (size_t)(g.maxM0 + 1);
+    g.links0.resize(l0_ints);
+    g.up_links.resize(graph_up_ints_);
+    hip_check(hipMemcpyAsync(g.links0.data(), d_links0_.ptr(), l0_ints * 4, hipMemcpyDeviceToHost, stream_), "links0 D2H");
+    if (graph_up_ints_)
+        hip_check(hipMemcpyAsync(g.up_links.data(), d_up_links_.ptr(), graph_up_ints_ * 4, hipMemcpyDeviceToHost, stream_),
+                  "up_links D2H");
+    hip_check(hipStreamSynchronize(stream_), "graph download");
+}
+
 void Engine::ensure_graph() {
     if (method_ != Method::Hnsw || !graph_dirty_) return;
     if (str_space_) {
@@ -980,6 +1163,11 @@ void Engine::finalize() {
     }
     if (method_ == Method::Hnsw && graph_dirty_ && use_gpu_build()) {
         check_device();
+        if (can_append() && append_rows_gpu()) {
+            graph_dirty_ = false;
+            dirty_ = false;
+            return;
+        }
         upload_rows();
         build_graph_gpu();
         graph_dirty_ = false;
@@ -1074,6 +1262,8 @@ void Engine::finalize_sharded(int nshards) {
             throw EngineError(Err::IndexBuildFailed, "shard " + std::to_string(s) + ": " + errors[(size_t)s]);
         }
     build_seconds = std::chrono::duration<double>(clk::now() - t0).count();
+    rows_uploaded = n;
+    rows_appended = 0;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     d_ids_.ensure(std::max<size_t>(n, 1) * 4);  // position -> external id, applied after the merge
     hip_check(hipMemcpy(d_ids_.ptr(), ids_.data(), n * 4, hipMemcpyHostToDevice), "upload ids");
@@ -1578,6 +1768,7 @@ void Engine::save(const std::string& path, bool save_data) {
         throw EngineError(Err::DataIO, "a sharded HNSW index holds one graph per GPU and has no single-file form; "
                                        "build with gpu_shards=1 to save it in the reference's format");
     ensure_graph();  // persistence is host-side: no device needed
+    sync_host_graph();  // (but for the lists of a graph that grew on the device)
     const size_t n = ids_.size();
     if (save_data) {
         std::ofstream out(path + ".dat", std::ios::binary);

@@ -74,7 +74,10 @@ class DevBuf {
         swap(o);
         return *this;
     }
-    void* ensure(size_t bytes);  // grow-only
+    void* ensure(size_t bytes);  // grow-only; a growth does NOT keep the contents
+    // grow to `bytes` keeping the first `keep` bytes: new allocation, device-to-device copy on `s`, then the old block is
+    // freed (both exist for the copy).  Throws like ensure; after a failed allocation the old block is untouched.
+    void* grow_keep(size_t bytes, size_t keep, hipStream_t s);
     void release();
     void swap(DevBuf& o);
     void* ptr() const { return p_; }
@@ -108,6 +111,8 @@ struct HnswBuildParams {
     int gpu_build = -1;       // engine extension: 1 = batched construction on the GPU, 0 = host, -1 = auto
     int gpu_build_batch = 0;  // max nodes inserted per batch (0 = default)
     int gpu_build_div = 0;    // a batch is at most 1/div of the graph built so far (0 = default)
+    int gpu_build_cut = 0;    // GPU builder: no batch spans position N (0 = off); see DESIGN.md 4.6a
+    int gpu_append = 0;       // 1 = rows added after a GPU build are inserted into the resident graph
 };
 
 
@@ -257,6 +262,8 @@ class Engine {
     void collect_profile(double* total_ms, uint64_t* launches);
 
     double upload_seconds = 0, build_seconds = 0;
+    // the last finalize: rows it inserted into an existing graph (0: a full build), rows it copied to HBM
+    size_t rows_appended = 0, rows_uploaded = 0;
     int last_path = 0;  // see nmslib_gpu_stats_t
     size_t rows16_bytes() const;  // the fp16 traversal copy (gpu_rows=f16), shards included
     // flags of the last fast-path slice (device): [fast_nqt_] fallback flags, then (float rows) [fast_nqt_] precise flags
@@ -329,12 +336,18 @@ class Engine {
     void string_query(const char* s, size_t len, Err parse_err, std::vector<uint32_t>& words) const;
     size_t ham_words() const { return st_bits_ > 0 ? (size_t)(st_bits_ + 31) / 32 : 0; }
     void ensure_graph();
-    void upload_rows();
+    void upload_rows(size_t first = 0);           // rows [first, n); first > 0 keeps what is resident
     void build_graph();
     bool use_gpu_build() const;
     void build_graph_gpu();
     void build_graph_gpu_pass(const std::vector<int32_t>& levels, bool reverse);
-    void prepare_graph_rows();
+    void build_graph_gpu_insert(size_t first, bool reverse);  // positions [first, n) into the graph of dg_ / graph_
+    void release_build_workspaces();
+    bool can_append() const;
+    bool append_rows_gpu();   // gpu_append=1; false: a buffer could not grow, take the full path
+    void sync_host_graph();   // the lists of graph_ follow the device's after an append (read by save)
+    void pack_rows16(size_t first, size_t n, int e);  // rows [first, n) of the fp16 copy at scale 2^e
+    void prepare_graph_rows(size_t first = 0);
     void upload_graph();
     // dense brute force (brute.cpp)
     void prepare_brute();
@@ -393,6 +406,8 @@ class Engine {
     bool loaded_graph_ = false;  // graph came from a file: never rebuild it
     int graph_builder_ = 0;      // who built graph_: 0 nobody (no graph yet, or loaded), 1 the host builder, 2 the GPU builder
     size_t graph_up_ints_ = 0;   // ints of the upper-level lists of the graph on the device (GPU builder)
+    size_t built_n_ = 0;         // rows the GPU builder's resident graph covers (0: none, or it was not completed)
+    bool host_links_stale_ = false;  // an append changed the lists on the device; graph_.links0 / up_links are behind
     HnswBuildParams bp_;
     HostGraph graph_;
     std::vector<float> graph_rows_;  // rows as stored inside a loaded index (cosine: normalised)
@@ -403,6 +418,8 @@ class Engine {
     bool rows_f16_ = false;          // walk the fp16 copy (made at the next batch if there is none)
     int rerank_ = 0;                 // entries of the walk's sorted array that are re-ranked in f32; 0 = all
     bool rows16_failed_ = false;     // the copy did not fit into HBM: f32 until the rows change
+    int rows16_exp_ = 0;             // the copy's scale is 2^rows16_exp_, chosen for rows16_max_ = the largest |element|
+    float rows16_max_ = 0;
 
     // device state
     int device_ = -1;

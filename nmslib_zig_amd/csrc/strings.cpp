@@ -173,6 +173,8 @@ void Engine::upload_strings() {
     }
     hip_check(hipStreamSynchronize(stream_), "string upload");
     d_n_ = n;
+    rows_uploaded = n;
+    rows_appended = 0;
     upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
