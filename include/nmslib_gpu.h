@@ -38,6 +38,14 @@ nmslib_error_t nmslib_gpu_finalize(nmslib_index_handle_t index);
  *               hnsw.cc:724) read a per-query status word back and wait for the stream before returning (queues that
  *               outgrew their workspace are re-run with larger ones, at most twice).  Every other path -- brute force,
  *               both fast paths, SearchV1Merge incl. its visited-table overflow -- never blocks the caller.
+ * Alignment: d_queries, d_ids, d_dists and d_counts need the alignment of their element type only (4 bytes; uint8
+ *               queries: none).  Every kernel reads the caller's queries and writes the results element by element.
+ * Order:     batches of one index are executed in the order of the calls, whatever streams they are given -- they
+ *               share the index's workspaces.  A call on another stream than the index's previous work (a device batch,
+ *               or a host-pointer entry of nmslib_c.h, which uses a stream of the index's own) first makes its stream
+ *               wait for that work; the same stream again costs nothing.  The buffers passed to a call follow ordinary
+ *               stream order on that call's stream: the queries must be ready there, the results are ready there.  A
+ *               stream given to a call has to stay valid until the index has been given another one or is destroyed.
  * Replaces the per-query loop of nmslib_knn_query_batch (nmslib_c.cpp:1015-1023). */
 nmslib_error_t nmslib_gpu_knn_query_batch_device(nmslib_index_handle_t index,
                                                  const void* d_queries, size_t query_count,

@@ -128,6 +128,7 @@ size_t Engine::range_diverg_host(const float* query, size_t elem_count, double r
 float Engine::pair_distance_diverg(size_t p1, size_t p2) {
     // IndexTimeDistance(data[p1], data[p2]) (nmslib_c.cpp:1166) from the host rows: no finalize needed
     check_device();
+    order_after_last(stream_);
     const size_t plane = (size_t)diverg_groups((int)dim_) * 2 * 4;
     std::vector<float> two(2 * dim_), h(2 * plane);
     std::memcpy(two.data(), &rows_f32_[p1 * dim_], dim_ * 4);

@@ -260,8 +260,19 @@ Engine::~Engine() {
     }
     for (hipEvent_t e : shard_events_) (void)hipEventDestroy(e);
     if (shard_ready_) (void)hipEventDestroy(shard_ready_);
+    if (order_event_) (void)hipEventDestroy(order_event_);
     if (pinned_) (void)hipHostFree(pinned_);
     if (stream_) (void)hipStreamDestroy(stream_);
+}
+
+void Engine::order_after_last(hipStream_t next) {
+    if (have_last_ && last_stream_ != next) {
+        if (!order_event_) hip_check(hipEventCreateWithFlags(&order_event_, hipEventDisableTiming), "hipEventCreate");
+        hip_check(hipEventRecord(order_event_, last_stream_), "hipEventRecord");
+        hip_check(hipStreamWaitEvent(next, order_event_, 0), "hipStreamWaitEvent");
+    }
+    last_stream_ = next;
+    have_last_ = true;
 }
 
 std::pair<hipEvent_t, hipEvent_t> Engine::prof_pair() {
@@ -1136,6 +1147,10 @@ void Engine::ensure_graph() {
 void Engine::finalize() {
     if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
     if (!dirty_) return;
+    if (have_last_) {   // batches in flight read the rows that are replaced here
+        check_device();
+        order_after_last(stream_);
+    }
     if (sparse_) {
         upload_sparse();
         dirty_ = false;
@@ -1342,7 +1357,7 @@ void Engine::knn_device(const void* d_queries, size_t nq, size_t elem_count, siz
     if (sparse_ || str_space_)
         throw EngineError(Err::SpaceIncompatible, "the device-resident batch takes dense queries; sparse and string "
                                                   "queries go through nmslib_knn_query_batch");
-    last_stream_ = stream;
+    order_after_last(stream);   // (row shards: the parent's stream; every child keeps to its own)
     if (!shards_.empty()) {
         if (size() > 0 && elem_count != dim_)
             throw EngineError(Err::QueryExecutionFailed, "query dimension does not match the index");
@@ -1633,13 +1648,17 @@ void Engine::knn_host(const void* queries, size_t nq, size_t elem_count, size_t 
     if (diverg_ && !ids_.empty()) check_diverg_query_length(elem_count, dim_);  // refused before any device work
     if (dirty_) finalize();
     check_device();
-    if (diverg_) return knn_diverg_host(static_cast<const float*>(queries), nq, elem_count, k, ids, dists, cnt);
+    if (diverg_) {
+        order_after_last(stream_);
+        return knn_diverg_host(static_cast<const float*>(queries), nq, elem_count, k, ids, dists, cnt);
+    }
     const size_t qbytes = nq * elem_count * elem_bytes();
     // device: queries | ids | dists | counts in ONE block each way; host: one pinned block
     ws_q_.ensure(qbytes);
     const ResultBlock out = result_block(nq, k);
     char* hp = static_cast<char*>(pinned(std::max(qbytes, 2 * nq * k * 4 + nq * 4)));
     std::memcpy(hp, queries, qbytes);
+    order_after_last(stream_);
     hip_check(hipMemcpyAsync(ws_q_.ptr(), hp, qbytes, hipMemcpyHostToDevice, stream_), "queries H2D");
     knn_device(ws_q_.ptr(), nq, elem_count, k, out.ids, out.dists, out.cnt, stream_);
     fetch_results(nq, k, "knn", ids, dists, cnt);
@@ -1684,7 +1703,10 @@ size_t Engine::range_host(const void* query, size_t elem_count, double radius, s
     if (dirty_) finalize();
     check_device();
     const size_t n = d_n_;
-    if (diverg_) return range_diverg_host(static_cast<const float*>(query), elem_count, radius, capacity, ids, dists);
+    if (diverg_) {
+        order_after_last(stream_);
+        return range_diverg_host(static_cast<const float*>(query), elem_count, radius, capacity, ids, dists);
+    }
     if (n == 0 || capacity == 0) return 0;
     if (elem_count != dim_) throw EngineError(Err::QueryExecutionFailed, "query dimension does not match the index");
     if (!shards_.empty()) {
@@ -1705,6 +1727,7 @@ size_t Engine::range_host(const void* query, size_t elem_count, double radius, s
     const int elem = is_u8() ? 1 : 4;
     ws_qpad_.ensure((size_t)ld * elem);
     ws_q_.ensure(elem_count * elem);
+    order_after_last(stream_);
     return range_select(false, r, capacity, ids, dists, [&](float* d, float*) {
         hip_check(hipMemcpyAsync(ws_q_.ptr(), query, elem_count * elem, hipMemcpyHostToDevice, stream_), "query H2D");
         hip_check(launch_pad_rows(ws_q_.ptr(), 1, (int)dim_, ws_qpad_.ptr(), 1, ld, elem, stream_), "pad query");
@@ -1729,6 +1752,7 @@ float Engine::pair_distance(size_t p1, size_t p2) {
     check_device();
     const size_t rb = is_u8() ? 128 : (size_t)f32_row_stride((int)dim_) * 4;
     ws_pair_.ensure(2 * rb + 16);
+    order_after_last(stream_);
     hip_check(hipMemsetAsync(ws_pair_.ptr(), 0, 2 * rb + 16, stream_), "pair clear");
     char* base = ws_pair_.as<char>();
     hip_check(hipMemcpyAsync(base, host_row(p1), row_bytes(), hipMemcpyHostToDevice, stream_), "pair H2D");

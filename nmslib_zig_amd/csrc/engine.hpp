@@ -274,6 +274,10 @@ class Engine {
     // HNSW (LDS visited table): queries of the last batch that were re-run by the bitset kernel (waits for the batch)
     size_t hnsw_redone();
     hipStream_t last_stream_ = nullptr;  // stream of the most recent batch (the statistics wait for THAT one)
+    // Batches of one index run in the order of the calls, whatever streams they are given: they share the workspaces.
+    // Called under `mu` before anything is enqueued on `next`: when the last work went to another stream, `next` waits
+    // for an event recorded there.  The same stream again is a pointer compare.
+    void order_after_last(hipStream_t next);
     bool hnsw_fix_valid_ = false;
     size_t hbm_bytes() const;
 
@@ -295,6 +299,8 @@ class Engine {
     std::vector<std::unique_ptr<Engine>> shards_;
     std::vector<hipEvent_t> shard_events_;
     hipEvent_t shard_ready_ = nullptr;
+    hipEvent_t order_event_ = nullptr;  // order_after_last: made at the first change of stream
+    bool have_last_ = false;            // last_stream_ names a stream that work of this index went to (nullptr: the null stream)
     const Engine* parent_ = nullptr;  // shard child: rows [view_lo_, view_lo_ + view_n_) of the parent, no copy
     size_t view_lo_ = 0, view_n_ = 0;
     int forced_device_ = -1;

@@ -56,6 +56,7 @@ void Engine::knn_sparse_host(const SparseElem* const* queries, const size_t* cou
     if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
     if (dirty_) finalize();
     check_device();
+    order_after_last(stream_);
     if (k == 0) throw EngineError(Err::InvalidArgument, "k must be positive");
     if (k > (size_t)INT32_MAX / 2) throw EngineError(Err::QueryTooLarge, "k is too large");
     size_t total = 0;
@@ -97,6 +98,7 @@ size_t Engine::range_sparse_host(const SparseElem* query, size_t count, double r
     if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
     if (dirty_) finalize();
     check_device();
+    order_after_last(stream_);
     const size_t n = d_n_;
     if (n == 0 || capacity == 0) return 0;
     // RangeQuery<dist_t>(space, obj, static_cast<dist_t>(radius)), nmslib_c.cpp:1092-1093
@@ -124,6 +126,7 @@ size_t Engine::range_sparse_host(const SparseElem* query, size_t count, double r
 float Engine::pair_distance_sparse(size_t p1, size_t p2) {
     // IndexTimeDistance(data[p1], data[p2]) (nmslib_c.cpp:1166) from the host rows: no finalize needed
     check_device();
+    order_after_last(stream_);
     const size_t n1 = sparse_row_len(p1), n2 = sparse_row_len(p2), tot = n1 + n2;
     const size_t ids_b = align8(tot * 4);
     std::vector<char> h(32 + ids_b + tot * 4);

@@ -290,6 +290,7 @@ void Engine::knn_string_host(const char* const* queries, const size_t* lens, siz
     if (!lev && st_bits_ < 0) throw EngineError(Err::QueryExecutionFailed, "bit_hamming: the index holds no rows");
     if (dirty_) finalize();
     check_device();
+    order_after_last(stream_);
     // device / pinned layout of the batch: leven q_off int64 [nq+1] | q_len int32 [nq] | Peq u64; bit_hamming words
     const size_t off_b = (nq + 1) * 8, len_b = align8(nq * 4);
     const size_t qbytes = lev ? off_b + len_b + peq_words * 8 : qwords.size() * 4;
@@ -350,6 +351,7 @@ size_t Engine::range_string_host(const char* query, size_t len, double radius, s
     string_query(query, len, Err::Runtime, qw);
     if (dirty_) finalize();
     check_device();
+    order_after_last(stream_);
     const size_t n = d_n_;
     if (n == 0 || capacity == 0) return 0;
     // RangeQuery<int>(space, obj, static_cast<int>(radius)), nmslib_c.cpp:1092-1093: the radius truncates to int
@@ -381,6 +383,7 @@ float Engine::pair_distance_string(size_t p1, size_t p2) {
     // IndexTimeDistance(data[p1], data[p2]) (nmslib_c.cpp:1166) on the device store
     if (dirty_) finalize();
     check_device();
+    order_after_last(stream_);
     ws_pair_.ensure(16);
     float* out = ws_pair_.as<float>();
     if (space_ == SP_LEVEN) {

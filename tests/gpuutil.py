@@ -72,3 +72,101 @@ def ids_match_modulo_near_ties(got_ids, want_ids, want_key, eps, got_key=None):
                 bad.append((q, start))
             start = i
     return bad
+
+
+# ---- the device-resident entry (include/nmslib_gpu.h) on a stream of the caller's choice ----------------------------
+ID_SENTINEL = 0x5A5A5A5A     # what the output buffers hold before a call: ids, counts, and NaN distances
+CNT_SENTINEL = -7
+_GUARD = 64                  # sentinel elements kept behind every output (and the `off` elements in front of it)
+
+
+def _offset_buffer(n, dtype, off):
+    """-> (raw, view): `view` holds n elements and starts `off` ELEMENTS past the 256-byte-aligned start of `raw`, which
+    goes on for _GUARD elements behind the view."""
+    import torch
+    raw = torch.empty(off + n + _GUARD, dtype=dtype, device="cuda")
+    assert raw.data_ptr() % 256 == 0, "the allocator returned a block off a 256-byte boundary"
+    return raw, raw[off:off + n]
+
+
+class DeviceCall:
+    """One batch enqueued by enqueue_knn: the buffers stay alive here; result() reads them after the stream was waited for."""
+
+    def __init__(self, nq, k, qraw, ids, ds, cnt, off):
+        self.nq, self.k, self.qraw, self.ids, self.ds, self.cnt, self.off = nq, k, qraw, ids, ds, cnt, off
+
+    def result(self):
+        """-> ids [nq, k] int32, dists [nq, k] float32, counts [nq] int32; the elements around the outputs still hold
+        their sentinels (a kernel that writes outside what it was given fails here)."""
+        out = []
+        for raw, sentinel in ((self.ids, ID_SENTINEL), (self.ds, None), (self.cnt, CNT_SENTINEL)):
+            h = raw.cpu().numpy()
+            n = len(h) - self.off - _GUARD
+            guard = np.r_[h[:self.off], h[self.off + n:]]
+            if sentinel is None:
+                assert np.isnan(guard).all(), "distances were written outside the output buffer"
+            else:
+                assert (guard == sentinel).all(), "ids / counts were written outside the output buffer"
+            out.append(h[self.off:self.off + n])
+        return out[0].reshape(self.nq, self.k), out[1].reshape(self.nq, self.k), out[2]
+
+
+def enqueue_knn(idx, Q, k, stream, counts=True, q_off=0, out_off=0, before=None, after=None):
+    """What knn_on_stream enqueues, without waiting for `stream`.  The queries are staged in HBM first (on torch's
+    current stream, waited for), so that everything put on `stream` is device work in stream order: before(qbuf), the
+    copy of the queries into qbuf, the sentinel fills, the call, after(qbuf)."""
+    import torch
+    Q = np.ascontiguousarray(Q)
+    nq, qdim = Q.shape
+    tdt = torch.uint8 if Q.dtype == np.uint8 else torch.float32
+    staged = torch.from_numpy(Q).cuda().reshape(-1)
+    torch.cuda.current_stream().synchronize()
+    qraw, qbuf = _offset_buffer(nq * qdim, tdt, q_off)
+    ids_raw, ids = _offset_buffer(nq * k, torch.int32, out_off)
+    ds_raw, ds = _offset_buffer(nq * k, torch.float32, out_off)
+    cnt_raw, cnt = _offset_buffer(nq, torch.int32, out_off)
+    with torch.cuda.stream(stream):
+        if before is not None:
+            before(qbuf)
+        qbuf.copy_(staged)
+        ids_raw.fill_(ID_SENTINEL)
+        ds_raw.fill_(float("nan"))
+        cnt_raw.fill_(CNT_SENTINEL)
+        # (addresses from the allocations: an empty view has no data pointer)
+        at = lambda raw, off: raw.data_ptr() + off * raw.element_size()   # noqa: E731
+        idx.knn_device(at(qraw, q_off), nq, qdim, k, at(ids_raw, out_off), at(ds_raw, out_off),
+                       at(cnt_raw, out_off) if counts else None, stream.cuda_stream)
+        if after is not None:
+            after(qbuf)
+    return DeviceCall(nq, k, (qraw, staged), ids_raw, ds_raw, cnt_raw, out_off)
+
+
+def knn_on_stream(idx, Q, k, stream=None, counts=True, q_off=0, out_off=0, before=None, after=None):
+    """One batch through nmslib_gpu_knn_query_batch_device on `stream` (None: a fresh torch.cuda.Stream(), which does
+    not synchronise with the null stream).  The queries lie q_off ELEMENTS past a 256-byte-aligned allocation, ids /
+    distances / counts out_off elements past theirs; before the call they are filled, on the stream, with ID_SENTINEL /
+    NaN / CNT_SENTINEL.  counts=False passes d_counts = NULL (the counts come back as sentinels).  before(qbuf) /
+    after(qbuf) run on the stream ahead of the upload and right behind the call.  The stream is waited for.
+    -> ids, dists, counts (numpy)"""
+    import torch
+    if stream is None:
+        stream = torch.cuda.Stream()
+    call = enqueue_knn(idx, Q, k, stream, counts, q_off, out_off, before, after)
+    stream.synchronize()
+    return call.result()
+
+
+def expect_path(idx, code, **more):
+    """The chain the last batch took (nmslib_gpu_stats_t.last_path), and any other statistic given by name."""
+    st = idx.stats()
+    assert st["last_path"] == code, f"last_path {st['last_path']}, expected {code}: {st}"
+    for name, want in more.items():
+        assert st[name] == want, f"{name} {st[name]}, expected {want}: {st}"
+    return st
+
+
+def same_bits(got, want):
+    """ids, distances (as uint32) and counts of two answers are identical."""
+    np.testing.assert_array_equal(got[0], want[0])
+    np.testing.assert_array_equal(np.ascontiguousarray(got[1]).view(np.uint32), np.ascontiguousarray(want[1]).view(np.uint32))
+    np.testing.assert_array_equal(got[2], want[2])
