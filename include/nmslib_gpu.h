@@ -123,6 +123,27 @@ nmslib_error_t nmslib_gpu_graph_builder(nmslib_index_handle_t index, int* builde
 nmslib_error_t nmslib_gpu_string_hnsw_links(nmslib_index_handle_t index, size_t node, int level, int32_t* out,
                                             size_t capacity, size_t* count, int* enterpoint, int* maxlevel);
 
+/* Deleted rows.  Marks every stored row whose external id is one of
+ * ids[0 .. count) as deleted.  *marked (optional) = rows newly marked by this call.  Later k-NN and range results never contain
+ * a marked row.
+ *   A tombstone belongs to a position: the call marks the rows that carry the id when it is made (all of them -- ids need
+ *   not be unique), and a row added later under the same id is live: "update" = delete the id, add the new row under it.
+ *   An id no row carries, an id listed twice and a row marked already add nothing to *marked and are no errors.
+ *   Positions do not move: nmslib_data_qty still counts the row, nmslib_get_data_point*, nmslib_borrow_data_dense and
+ *   nmslib_get_distance still serve it.  nmslib_reset_index clears the marks with the rows; nmslib_create_index keeps them.
+ *   nmslib_save_index on an index with a marked row -> NMSLIB_ERROR_DATA_IO_FAILED (no file format has a place for them).
+ * Served: hnsw, brute_force and seq_search over the dense spaces (float rows and l2sqr_sift) on one device, before and after
+ * nmslib_create_index, with or without a device (gpu_defer=1: host state until the index reaches the GPU).  Sparse, string
+ * and divergence indexes and gpu_shards > 1 -> NMSLIB_ERROR_SPACE_INCOMPATIBLE.  ids == NULL with count > 0, or a NULL
+ * handle -> NMSLIB_ERROR_NULL_POINTER.
+ * hnsw: marked rows stay in the graph as stepping stones; a batch asked for k results is the first k unmarked entries of the
+ * search for max(efSearch, k) results, so a count can fall below k when most of what the search finds is marked.  The call
+ * is ordered with the index's other work like every host entry: a batch enqueued before it sees the old state.
+ * brute_force / seq_search: the index is prepared again at its next use, over the unmarked rows only. */
+nmslib_error_t nmslib_gpu_delete_ids(nmslib_index_handle_t index, const int32_t* ids, size_t count, size_t* marked);
+/* Rows of this index that are marked deleted. */
+nmslib_error_t nmslib_gpu_deleted_rows(nmslib_index_handle_t index, size_t* count);
+
 #ifdef __cplusplus
 }
 #endif

@@ -176,6 +176,8 @@ def lib():
         "nmslib_gpu_get_stats": (C.c_int, [vp, C.POINTER(GpuStats)]),
         "nmslib_gpu_kernel_timing": (C.c_int, [vp, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_uint64)]),
         "nmslib_gpu_graph_builder": (C.c_int, [vp, C.POINTER(C.c_int)]),
+        "nmslib_gpu_delete_ids": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
+        "nmslib_gpu_deleted_rows": (C.c_int, [vp, C.POINTER(sz)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)   # AttributeError here = a declared symbol is not exported
@@ -202,7 +204,8 @@ ABI_SYMBOLS_C = [  # the 37 symbols of the reference boundary
 ABI_SYMBOLS_GPU = ["nmslib_gpu_device_count", "nmslib_gpu_finalize",
                    "nmslib_gpu_knn_query_batch_device", "nmslib_gpu_last_batch_counters",
                    "nmslib_gpu_merge_topk", "nmslib_gpu_merge_topk_strided", "nmslib_gpu_get_stats", "nmslib_gpu_kernel_timing",
-                   "nmslib_gpu_string_hnsw_links", "nmslib_gpu_graph_builder"]
+                   "nmslib_gpu_string_hnsw_links", "nmslib_gpu_graph_builder", "nmslib_gpu_delete_ids",
+                   "nmslib_gpu_deleted_rows"]
 
 
 class TrackingAllocator:
@@ -523,6 +526,23 @@ class Index:
         b = C.c_int()
         _check(lib().nmslib_gpu_graph_builder(self.h, C.byref(b)), self.alloc)
         return b.value
+
+    def deleteIds(self, ids):
+        """nmslib_gpu_delete_ids: marks every stored row that carries one of `ids` as deleted -> rows newly marked.  Later
+        k-NN and range results never contain them; positions do not move, and a row added later under a deleted id is live
+        (update = deleteIds([id]), then add the new row under it).  hnsw: results are the first k live entries of the search
+        for max(efSearch, k), so counts can fall below k under heavy deletion; brute_force / seq_search: the index is
+        prepared again at its next use."""
+        a = np.ascontiguousarray(ids, np.int32).reshape(-1)
+        m = C.c_size_t()
+        _check(lib().nmslib_gpu_delete_ids(self.h, a.ctypes.data if a.size else None, a.size, C.byref(m)), self.alloc)
+        return m.value
+
+    def deletedRows(self):
+        """Rows of this index that are marked deleted."""
+        n = C.c_size_t()
+        _check(lib().nmslib_gpu_deleted_rows(self.h, C.byref(n)), self.alloc)
+        return n.value
 
     # -- metadata / stored data -------------------------------------------------------------------
     def getDistance(self, a, b):

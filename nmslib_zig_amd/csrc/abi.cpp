@@ -874,6 +874,27 @@ nmslib_error_t nmslib_gpu_graph_builder(nmslib_index_handle_t handle, int* build
     });
 }
 
+nmslib_error_t nmslib_gpu_delete_ids(nmslib_index_handle_t handle, const int32_t* ids, size_t count, size_t* marked) {
+    if (marked) *marked = 0;
+    if (!handle) FAIL(NMSLIB_ERROR_NULL_POINTER, "Invalid index");
+    if (!ids && count > 0) FAIL(NMSLIB_ERROR_NULL_POINTER, "ids is NULL with a positive count");
+    return guarded(NMSLIB_ERROR_RUNTIME, "Failed to delete rows", [&] {
+        Engine* e = H(handle)->engine;
+        std::lock_guard<std::mutex> lk(e->mu);
+        const size_t m = e->delete_ids(ids, count);
+        if (marked) *marked = m;
+    });
+}
+
+nmslib_error_t nmslib_gpu_deleted_rows(nmslib_index_handle_t handle, size_t* count) {
+    if (!handle || !count) FAIL(NMSLIB_ERROR_NULL_POINTER, "Invalid arguments");
+    Engine* e = H(handle)->engine;
+    std::lock_guard<std::mutex> lk(e->mu);
+    *count = e->deleted_rows();
+    SET_LAST(NMSLIB_SUCCESS, "Deleted rows counted");
+    return NMSLIB_SUCCESS;
+}
+
 nmslib_error_t nmslib_gpu_string_hnsw_links(nmslib_index_handle_t index, size_t node, int level, int32_t* out,
                                             size_t capacity, size_t* count, int* enterpoint, int* maxlevel) {
     if (!index || !count || !enterpoint || !maxlevel || node >= nmslib_data_qty(index) || level < 0)

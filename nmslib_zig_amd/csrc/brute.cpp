@@ -89,7 +89,7 @@ void Engine::make_fast_tiles(const BfSplitSrc& src, int dp, const float* aux, fl
 // index on the adaptive kernel.
 void Engine::make_l1_copy() {
     BruteDense& b = brute_;
-    const size_t n = size();
+    const size_t n = d_n_;  // the rows upload_rows made resident (the live ones of an index with deleted rows)
     const size_t dim = dim_, ld = (size_t)ldb_;
     try {
         DevBuf d_range, d_rmax;
@@ -136,7 +136,7 @@ void Engine::make_l1_copy() {
 // The brute-force branch of finalize(): the rows are in HBM (upload_rows)
 void Engine::prepare_brute() {
     BruteDense& b = brute_;
-    const size_t n = size();
+    const size_t n = d_n_;  // the rows upload_rows made resident (the live ones of an index with deleted rows)
     if (is_u8()) {
         const size_t n_pad = (size_t)bf_u8_rows_padded((int)n);
         d_aux_.ensure(n_pad * 4);

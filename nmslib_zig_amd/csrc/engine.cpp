@@ -10,6 +10,7 @@
 #include <set>
 #include <sstream>
 #include <thread>
+#include <unordered_set>
 
 namespace gfxknn {
 
@@ -262,6 +263,8 @@ Engine::~Engine() {
     if (shard_ready_) (void)hipEventDestroy(shard_ready_);
     if (order_event_) (void)hipEventDestroy(order_event_);
     if (pinned_) (void)hipHostFree(pinned_);
+    if (tomb_event_) (void)hipEventDestroy(tomb_event_);
+    if (tomb_pinned_) (void)hipHostFree(tomb_pinned_);
     if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -345,10 +348,68 @@ void Engine::stored_row(size_t pos, void* dst) const {
     }
 }
 
+static const char* const kDeleteServed =
+    "deleting rows is served for hnsw, brute_force and seq_search over the dense spaces (float rows and l2sqr_sift) on one "
+    "device";
+
+size_t Engine::delete_ids(const int32_t* ids, size_t count) {
+    if (sparse_ || str_space_ || diverg_)
+        throw EngineError(Err::SpaceIncompatible, std::string(sparse_ ? "a sparse" : str_space_ ? "a string" : "a divergence") +
+                                                      " index does not delete rows: " + kDeleteServed);
+    if (gpu_shards_ > 1)
+        throw EngineError(Err::SpaceIncompatible, "an index with gpu_shards=" + std::to_string(gpu_shards_) +
+                                                      " does not delete rows: " + kDeleteServed);
+    if (count == 0) return 0;
+    const std::unordered_set<int32_t> listed(ids, ids + count);
+    const size_t n = ids_.size();
+    size_t marked = 0;
+    for (size_t i = 0; i < n; ++i) {
+        if (!listed.count(ids_[i]) || is_dead(i)) continue;
+        if (tomb_.size() <= (i >> 5)) tomb_.resize((n + 31) / 32, 0);
+        tomb_[i >> 5] |= 1u << (i & 31);
+        ++marked;
+    }
+    if (!marked) return 0;
+    n_dead_ += marked;
+    if (!shards_.empty()) dirty_ = graph_dirty_ = true;  // shards made without being asked for: back to one device
+    if (!created_) return marked;
+    if (method_ == Method::Brute) dirty_ = true;  // the scan's index is prepared again, over the live rows
+    else if (!dirty_) upload_tombstones();        // a resident graph: the filter's bitset follows now
+    return marked;
+}
+
+// The whole bitset goes to the device again (125 KB at 1M rows), from a pinned block of its own: the copy is enqueued behind
+// the index's other work and the call does not wait for it.  A batch enqueued before sees the old bits, a later one the new.
+void Engine::upload_tombstones() {
+    check_device();
+    const size_t words = (size() + 31) / 32;
+    tomb_.resize(words, 0);
+    if (words == 0) return;
+    if (tomb_event_) hip_check(hipEventSynchronize(tomb_event_), "tombstones");  // the last copy has left the pinned block
+    else hip_check(hipEventCreateWithFlags(&tomb_event_, hipEventDisableTiming), "hipEventCreate");
+    if (tomb_pinned_words_ < words) {
+        if (tomb_pinned_) (void)hipHostFree(tomb_pinned_);
+        tomb_pinned_ = nullptr;
+        tomb_pinned_words_ = 0;
+        void* p = nullptr;
+        hip_check(hipHostMalloc(&p, words * 4 + words, hipHostMallocDefault), "hipHostMalloc");  // (room to grow with appends)
+        tomb_pinned_ = static_cast<uint32_t*>(p);
+        tomb_pinned_words_ = words + words / 4;
+    }
+    std::memcpy(tomb_pinned_, tomb_.data(), words * 4);
+    order_after_last(stream_);  // batches in flight read the old bits (and a buffer that grows is freed)
+    d_tomb_.ensure(words * 4);
+    hip_check(hipMemcpyAsync(d_tomb_.ptr(), tomb_pinned_, words * 4, hipMemcpyHostToDevice, stream_), "tombstones H2D");
+    hip_check(hipEventRecord(tomb_event_, stream_), "hipEventRecord");
+}
+
 void Engine::reset() {
     ids_.clear();
     rows_f32_.clear();
     rows_u8_.clear();
+    tomb_.clear();
+    n_dead_ = 0;
+    d_tomb_.release();
     sp_ptr_.assign(1, 0);
     sp_ids_.clear();
     sp_vals_.clear();
@@ -391,7 +452,7 @@ size_t Engine::memory_usage() const {
                hbm_bytes();
     size_t total = ids_.size() * (16 + stored_row_bytes());
     total += ids_.size() * dim_ * sizeof(float);
-    return total + rows16_bytes();
+    return total + rows16_bytes() + d_tomb_.bytes();
 }
 
 size_t Engine::rows16_bytes() const {
@@ -404,7 +465,7 @@ size_t Engine::hbm_bytes() const {
     size_t sh = 0;
     for (const auto& c : shards_) sh += c->hbm_bytes();
     return sh + d_rows_.bytes() + d_aux_.bytes() + d_ids_.bytes() + d_links0_.bytes() + d_up_off_.bytes() + d_up_links_.bytes() +
-           d_rownorm_.bytes() + d_rows16_.bytes() + brute_.bytes() + d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes() + d_st_ptr_.bytes() + d_st_data_.bytes();
+           d_rownorm_.bytes() + d_rows16_.bytes() + d_tomb_.bytes() + brute_.bytes() + d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes() + d_st_ptr_.bytes() + d_st_data_.bytes();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -475,6 +536,9 @@ void Engine::create_index(const std::vector<std::string>& params) {
         throw EngineError(Err::IndexBuildFailed,
                           "method '" + method_name_ + "' is not served by the GPU engine (hnsw, brute_force, seq_search)");
     }
+    if (n_dead_ && gpu_shards_ > 1)
+        throw EngineError(Err::SpaceIncompatible, "gpu_shards=" + std::to_string(gpu_shards_) + " on an index with deleted rows: " +
+                                                      kDeleteServed);
     created_ = true;
     dirty_ = true;
     graph_dirty_ = true;
@@ -570,8 +634,28 @@ void Engine::check_device() {
 
 // Rows [first, n) go to HBM.  first = 0: all of them, into buffers sized for n.  first > 0 (gpu_append): the buffers grow keeping
 // rows [0, first), and only the new rows cross PCIe.
+//
+// Exact scan with tombstones: the live rows and their ids are staged contiguously, in position order, and go up in the place of
+// all rows -- from here on the index is the one a caller gets by adding the live rows only (d_n_ = their number).
 void Engine::upload_rows(size_t first) {
-    const size_t n = size(), added = n - first;
+    std::vector<float> live_f32;
+    std::vector<uint8_t> live_u8;
+    std::vector<int32_t> live_ids;
+    const bool compact = method_ == Method::Brute && n_dead_ > 0 && !parent_;
+    if (compact) {
+        const size_t all = size(), rb = row_bytes();
+        live_ids.reserve(all - n_dead_);
+        if (is_u8()) live_u8.resize((all - n_dead_) * rb);
+        else live_f32.resize((all - n_dead_) * dim_);
+        char* dst = is_u8() ? reinterpret_cast<char*>(live_u8.data()) : reinterpret_cast<char*>(live_f32.data());
+        for (size_t i = 0; i < all; ++i) {
+            if (is_dead(i)) continue;
+            std::memcpy(dst + live_ids.size() * rb, host_row(i), rb);
+            live_ids.push_back(ids_[i]);
+        }
+    }
+    const size_t n = compact ? live_ids.size() : size(), added = n - first;
+    const int32_t* src_ids = compact ? live_ids.data() : ids_.data();
     auto t0 = clk::now();
     dg_.rows16 = nullptr;  // the fp16 copy follows the rows
     rows16_failed_ = false;
@@ -583,12 +667,13 @@ void Engine::upload_rows(size_t first) {
         ldb_ = 128;
         room(d_rows_, 128);
         if (added)
-            hip_check(hipMemcpy(d_rows_.as<uint8_t>() + first * 128, rows_u8() + first * 128, added * 128, hipMemcpyHostToDevice),
+            hip_check(hipMemcpy(d_rows_.as<uint8_t>() + first * 128, (compact ? live_u8.data() : rows_u8()) + first * 128,
+                                added * 128, hipMemcpyHostToDevice),
                       "upload rows");
     } else {
         ldb_ = f32_row_stride((int)dim_);
         room(d_rows_, (size_t)ldb_ * 4);
-        const float* src = rows_f32();
+        const float* src = compact ? live_f32.data() : rows_f32();
         if (loaded_graph_ && !graph_rows_.empty()) src = graph_rows_.data();
         if (added) {
             float* dst = d_rows_.as<float>() + first * (size_t)ldb_;
@@ -606,7 +691,7 @@ void Engine::upload_rows(size_t first) {
         if (added)
             hip_check(hipMemcpy(d_ids_.as<int32_t>() + first, pos.data(), added * 4, hipMemcpyHostToDevice), "upload positions");
     } else if (added) {
-        hip_check(hipMemcpy(d_ids_.as<int32_t>() + first, ids_.data() + first, added * 4, hipMemcpyHostToDevice), "upload ids");
+        hip_check(hipMemcpy(d_ids_.as<int32_t>() + first, src_ids + first, added * 4, hipMemcpyHostToDevice), "upload ids");
     }
     d_n_ = n;
     rows_uploaded = added;
@@ -1147,6 +1232,13 @@ void Engine::ensure_graph() {
 void Engine::finalize() {
     if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
     if (!dirty_) return;
+    finalize_index();
+    // the graph holds the deleted rows as before (a rebuild too: positions do not move), so they stay marked; rows that came
+    // since are live
+    if (method_ == Method::Hnsw && n_dead_ > 0) upload_tombstones();
+}
+
+void Engine::finalize_index() {
     if (have_last_) {   // batches in flight read the rows that are replaced here
         check_device();
         order_after_last(stream_);
@@ -1215,6 +1307,7 @@ struct DeviceGuard {
 // ---------------------------------------------------------------------------------------------
 int Engine::resolve_shards() const {
     if (loaded_graph_ || parent_ || ids_.empty()) return 1;
+    if (n_dead_) return 1;  // deleted rows are served on one device (delete_ids refuses an index that asked for shards)
     int want = gpu_shards_;
     if (want < 0) {
         if (const char* env = getenv("NMSLIB_GPU_SHARDS")) want = atoi(env);
@@ -1436,15 +1529,57 @@ uint32_t* Engine::cleared_bitset(size_t m, size_t words, hipStream_t stream) {
 
 void Engine::knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
                       hipStream_t stream) {
+    if (n_dead_ > 0) knn_hnsw_live(d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
+    else hnsw_walk(false, d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
+}
+
+// Deleted rows.  Stage 1: the search as it would run anyway, asked for cap = max(ef, k) results as positions,
+// into a workspace.  Stage 2: hnsw_live_topk_kernel writes the first k live ones of them to the caller's buffers.  The
+// counters are the walk's; the timed interval ends behind the filter.
+void Engine::knn_hnsw_live(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
+                           hipStream_t stream) {
+    const size_t cap = std::max<size_t>((size_t)ef_, k);
+    // cap is unbounded on the SearchOld path: the slices of the batch are cut further where their results would not fit the
+    // budget its own workspaces keep to
+    const size_t slice = std::max<size_t>(1, std::min<size_t>(nq, ((size_t)4 << 30) / (cap * 8)));
+    const size_t qbytes = dim_ * elem_bytes(), off0 = ctr_off_;
+    const HnswOut out = hnsw_out(d_ids, d_dists, d_cnt, nq);
+    ws_live_ids_.ensure(slice * cap * 4);
+    ws_live_d_.ensure(slice * cap * 4);
+    ws_live_cnt_.ensure(slice * 4);
+    for (size_t q0 = 0; q0 < nq; q0 += slice) {
+        const size_t m = std::min(slice, nq - q0);
+        ctr_off_ = off0 + q0;  // the walk's counters go to this slice's place in the batch's arrays
+        hnsw_walk(true, static_cast<const char*>(d_queries) + q0 * qbytes, m, cap, ws_live_ids_.as<int32_t>(),
+                  ws_live_d_.as<float>(), ws_live_cnt_.as<int32_t>(), stream);
+        hip_check(launch_hnsw_live_topk(ws_live_ids_.as<int32_t>(), ws_live_d_.as<float>(), ws_live_cnt_.as<int32_t>(), (int)m,
+                                        (int)cap, d_tomb_.as<uint32_t>(), (int)d_n_, dg_.ext_ids, (int)k, out.at(q0, k),
+                                        stream),
+                  "hnsw_live_topk");
+        prof_end(stream);  // (the interval the walk opened: its end moves behind the filter)
+    }
+    ctr_off_ = off0;
+}
+
+// positions: the launches get the graph without ext_ids, so that every kernel emits internal positions (the builder and the
+// fp16 walk rely on the same)
+void Engine::hnsw_walk(bool positions, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
+                       int32_t* d_cnt, hipStream_t stream) {
     const int ef = ef_;
     last_path = 4;
     hnsw_fix_valid_ = false;
+    auto graph = [&] {  // (read where a path is taken: ensure_rows16 below names the fp16 copy in dg_)
+        HnswDeviceGraph g = dg_;
+        if (positions) g.ext_ids = nullptr;
+        return g;
+    };
     if (search_old()) {
-        knn_hnsw_old(d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
+        knn_hnsw_old(graph(), d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
         return;
     }
     const HnswOut out = hnsw_out(d_ids, d_dists, d_cnt, nq);
     if (std::max<size_t>(ef, k) > 1024 || hnsw_nbcap(dg_) > HNSW_NBCAP_LDS) {
+        const HnswDeviceGraph g = graph();
         // beyond the LDS kernels' sorted array, or adjacency lists longer than their frontier arrays (maxM0 > 254): the
         // same algorithm with the array in HBM and lists walked in chunks (slices of bounded workspace)
         const size_t cap = std::max<size_t>(ef, k), words = (d_n_ + 31) / 32;
@@ -1458,7 +1593,7 @@ void Engine::knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids
             ws_old_r_.ensure(m * cap * 4);
             uint32_t* bitset = cleared_bitset(m, words, stream);
             if (q0 == 0) prof_begin(stream);
-            hip_check(launch_hnsw_search_big(dg_, (int)m, (int)k, ef, static_cast<const char*>(d_queries) + q0 * qbytes,
+            hip_check(launch_hnsw_search_big(g, (int)m, (int)k, ef, static_cast<const char*>(d_queries) + q0 * qbytes,
                                              bitset, ws_old_a_.as<float>(), ws_old_r_.as<int32_t>(), out.at(q0, k), stream),
                       "hnsw_search(big)");
             if (q0 + slice >= nq) prof_end(stream);
@@ -1467,10 +1602,10 @@ void Engine::knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids
     }
     // (SearchOld and the HBM-array kernel above stay on the f32 rows whatever gpu_rows says)
     if (rows_f16_ && ensure_rows16()) {
-        knn_hnsw_f16(d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
+        knn_hnsw_f16(graph(), d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
         return;
     }
-    hnsw_search_lds(dg_, false, d_queries, nq, k, ef, out, true, stream);
+    hnsw_search_lds(graph(), false, d_queries, nq, k, ef, out, true, stream);
 }
 
 void Engine::hnsw_search_lds(const HnswDeviceGraph& g, bool rows_f16, const void* d_queries, size_t nq, size_t k, int ef,
@@ -1511,8 +1646,8 @@ void Engine::hnsw_search_lds(const HnswDeviceGraph& g, bool rows_f16, const void
 // distance.  The walk is the search launch asked for cap = max(ef, k) results: the fp16 kernels then write their whole sorted
 // array, in array order and as internal positions.  ndc / hops / hops_up describe the walk; the timed interval is walk +
 // overflow launch + re-rank.
-void Engine::knn_hnsw_f16(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
-                          hipStream_t stream) {
+void Engine::knn_hnsw_f16(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, int32_t* d_ids,
+                          float* d_dists, int32_t* d_cnt, hipStream_t stream) {
     const int ef = ef_;
     const size_t cap = std::max<size_t>(ef, k);
     last_path = 5;
@@ -1524,17 +1659,17 @@ void Engine::knn_hnsw_f16(const void* d_queries, size_t nq, size_t k, int32_t* d
     walk.ids = ws_rr_ids_.as<int32_t>();
     walk.dists = ws_rr_d_.as<float>();
     walk.cnt = ws_rr_cnt_.as<int32_t>();
-    hnsw_search_lds(dg_, true, d_queries, nq, cap, ef, walk, false, stream);
+    hnsw_search_lds(g, true, d_queries, nq, cap, ef, walk, false, stream);
     const size_t rerank = rerank_ > 0 ? std::min(cap, std::max<size_t>(k, (size_t)rerank_)) : cap;
-    hip_check(launch_hnsw_rerank(dg_, (int)nq, (int)k, (int)cap, (int)rerank, d_queries, walk.ids, walk.cnt, fin, stream),
+    hip_check(launch_hnsw_rerank(g, (int)nq, (int)k, (int)cap, (int)rerank, d_queries, walk.ids, walk.cnt, fin, stream),
               "hnsw_rerank");
     prof_end(stream);
 }
 
 // Hnsw::SearchOld (hnsw_distfunc_opt.cc:46-150) on the GPU: no limit on ef or k.  Queues that outgrow LDS live in
 // per-query HBM workspaces, so very large batches go through in slices of bounded workspace.
-void Engine::knn_hnsw_old(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
-                          hipStream_t stream) {
+void Engine::knn_hnsw_old(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, int32_t* d_ids,
+                          float* d_dists, int32_t* d_cnt, hipStream_t stream) {
     const int ef = ef_;
     const HnswOut out = hnsw_out(d_ids, d_dists, d_cnt, nq);
     const size_t qbytes = dim_ * elem_bytes();
@@ -1542,19 +1677,19 @@ void Engine::knn_hnsw_old(const void* d_queries, size_t nq, size_t k, int32_t* d
     int heap_cap = 0;
     std::vector<int32_t> status(nq);
     for (int attempt = 0; attempt < 3; ++attempt) {
-        HnswSearchPlan p0 = hnsw_make_plan_old(dg_, 1, (int)k, ef, force_bitset, heap_cap);
+        HnswSearchPlan p0 = hnsw_make_plan_old(g, 1, (int)k, ef, force_bitset, heap_cap);
         const size_t per_q = hnsw_old_ws_a(p0) + hnsw_old_ws_r(p0) + hnsw_old_ws_heap(p0) + p0.bitset_words * 4;
         const size_t budget = (size_t)4 << 30;
         const size_t slice = std::max<size_t>(1, std::min<size_t>(nq, per_q ? budget / per_q : nq));
         for (size_t q0 = 0; q0 < nq; q0 += slice) {
             const size_t m = std::min(slice, nq - q0);
-            HnswSearchPlan p = hnsw_make_plan_old(dg_, (int)m, (int)k, ef, force_bitset, heap_cap);
+            HnswSearchPlan p = hnsw_make_plan_old(g, (int)m, (int)k, ef, force_bitset, heap_cap);
             uint32_t* bitset = p.table_size == 0 ? cleared_bitset(m, p.bitset_words, stream) : nullptr;
             ws_old_a_.ensure(std::max<size_t>(16, m * hnsw_old_ws_a(p)));
             ws_old_r_.ensure(std::max<size_t>(16, m * hnsw_old_ws_r(p)));
             ws_old_heap_.ensure(std::max<size_t>(16, m * hnsw_old_ws_heap(p)));
             if (q0 == 0) prof_begin(stream);  // all slices of one attempt are one timed interval
-            hip_check(launch_hnsw_search_old(dg_, p, static_cast<const char*>(d_queries) + q0 * qbytes, bitset,
+            hip_check(launch_hnsw_search_old(g, p, static_cast<const char*>(d_queries) + q0 * qbytes, bitset,
                                              ws_old_a_.ptr(), ws_old_r_.ptr(), ws_old_heap_.ptr(), out.at(q0, k), stream),
                       "hnsw_search_old");
             if (q0 + slice >= nq) prof_end(stream);
@@ -1788,6 +1923,10 @@ void Engine::save(const std::string& path, bool save_data) {
     if (sparse_)  // SeqSearch has no SaveIndex (include/index.h:56-58); the object file is not written either
         throw EngineError(Err::DataIO, "SaveIndex is not implemented for method: Sequential search (sparse index; "
                                        "the data file is not written)");
+    if (n_dead_)  // (before anything is written: a file without the marks would bring the rows back at load)
+        throw EngineError(Err::DataIO, "the index has " + std::to_string(n_dead_) + " deleted rows and neither file format "
+                                       "(the index file, the .dat object file) has a place for deleted rows; nothing is "
+                                       "written");
     if (method_ == Method::Hnsw && !loaded_graph_ && (shards_.size() > 1 || (dirty_ && resolve_shards() > 1)))
         throw EngineError(Err::DataIO, "a sharded HNSW index holds one graph per GPU and has no single-file form; "
                                        "build with gpu_shards=1 to save it in the reference's format");

@@ -196,6 +196,13 @@ class Engine {
     int32_t ext_id(size_t pos) const { return ids_[pos]; }
     void reset();
 
+    // ---- deleted rows (nmslib_gpu_delete_ids) ----
+    // Marks every row that carries one of ids[0 .. count) now; returns how many rows were newly marked.  A tombstone
+    // belongs to a position: positions do not move and a row added later under the same id is live.  HNSW: the resident
+    // bitset follows at once and the results are filtered; exact scan: the index is prepared again without the rows.
+    size_t delete_ids(const int32_t* ids, size_t count);
+    size_t deleted_rows() const { return n_dead_; }
+
     // ---- sparse vectors (data type 1; sparse.cpp) ----
     bool is_sparse() const { return sparse_; }
     // one row of strictly increasing ids (validated by the caller)
@@ -342,6 +349,9 @@ class Engine {
     void string_query(const char* s, size_t len, Err parse_err, std::vector<uint32_t>& words) const;
     size_t ham_words() const { return st_bits_ > 0 ? (size_t)(st_bits_ + 31) / 32 : 0; }
     void ensure_graph();
+    void finalize_index();                        // finalize() without the tombstones' upload
+    bool is_dead(size_t pos) const { return (pos >> 5) < tomb_.size() && ((tomb_[pos >> 5] >> (pos & 31)) & 1u); }
+    void upload_tombstones();                     // the bitset of all size() rows -> d_tomb_, ordered behind the index's work
     void upload_rows(size_t first = 0);           // rows [first, n); first > 0 keeps what is resident
     void build_graph();
     bool use_gpu_build() const;
@@ -364,7 +374,13 @@ class Engine {
                    int32_t* d_cnt, hipStream_t stream);
     void knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
                   int32_t* d_cnt, hipStream_t stream);
-    void knn_hnsw_old(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
+    // the search of one slice on whichever path it takes; positions: on dg_ without ext_ids, so that positions come out
+    void hnsw_walk(bool positions, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
+                   int32_t* d_cnt, hipStream_t stream);
+    // an index with tombstones: the walk for max(ef, k) positions into a workspace, then the first k live ones
+    void knn_hnsw_live(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
+                       hipStream_t stream);
+    void knn_hnsw_old(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
                       int32_t* d_cnt, hipStream_t stream);
     // Hnsw::Search, hnsw.cc:724: algoType=old, or hybrid with ef >= 1000, runs SearchOld
     bool search_old() const { return algo_ == "old" || (algo_ == "hybrid" && ef_ >= 1000); }
@@ -373,8 +389,8 @@ class Engine {
     void hnsw_search_lds(const HnswDeviceGraph& g, bool rows_f16, const void* d_queries, size_t nq, size_t k, int ef,
                          const HnswOut& out, bool timed, hipStream_t stream);
     // gpu_rows=f16: the walk over the fp16 copy, then the f32 re-rank of its sorted array
-    void knn_hnsw_f16(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
-                      hipStream_t stream);
+    void knn_hnsw_f16(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
+                      int32_t* d_cnt, hipStream_t stream);
     bool ensure_rows16();  // makes the copy if there is none; false: no copy (allocation failed, no rows): stay on f32
     static bool parse_gpu_rows(const std::string& v);  // "f32" -> false, "f16" -> true, else InvalidArgument
     void check_rows16_served() const;                  // InvalidArgument for indexes without float rows
@@ -388,6 +404,14 @@ class Engine {
     std::vector<int32_t> ids_;
     std::vector<float> rows_f32_;
     std::vector<uint8_t> rows_u8_;
+    // deleted rows: bit = position (rows beyond the last word are live), how many bits are set; HNSW: the copy the filter
+    // kernel reads, its pinned staging block and the event behind the last copy out of it
+    std::vector<uint32_t> tomb_;
+    size_t n_dead_ = 0;
+    DevBuf d_tomb_;
+    uint32_t* tomb_pinned_ = nullptr;
+    size_t tomb_pinned_words_ = 0;
+    hipEvent_t tomb_event_ = nullptr;
     bool diverg_ = false;  // a divergence space: rows_f32_ on the host, values + logarithms in d_rows_
     // sparse rows: host CSR (get_data_point / borrow) and its copy in HBM after finalize
     bool sparse_ = false;
@@ -445,6 +469,7 @@ class Engine {
     DevBuf ws_bq_, ws_split_;  // sparse / string batches: the packed queries; per-split lists (string HNSW: per-query state)
     DevBuf ws_fix_;       // visited-overflow list of the HNSW search (count + query ids), device only
     DevBuf ws_rr_ids_, ws_rr_d_, ws_rr_cnt_;  // fp16 walk: its sorted arrays (positions, fp16-row distances) and their lengths
+    DevBuf ws_live_ids_, ws_live_d_, ws_live_cnt_;  // tombstones: the walk's max(ef, k) results per query of a slice, their counts
     size_t ctr_off_ = 0;  // offset of the current slice inside the per-batch counter arrays
     bool have_counters_ = false;
     bool prof_ = false;

@@ -425,6 +425,13 @@ hipError_t launch_hnsw_pack_rows16(const float* rows, int n, int ldv, int dim, f
 // position); k results with external ids, -1 / +inf padding and the count go to out.
 hipError_t launch_hnsw_rerank(const HnswDeviceGraph& g, int nq, int k, int cap, int rerank, const void* queries,
                               const int32_t* cand, const int32_t* cand_n, const HnswOut& out, hipStream_t s);
+// Deleted rows (hnsw_live_kernels.hip): cand / cand_d [nq][cap] are the results of a search launched for cap results
+// without ext_ids (internal positions, in the search's order), cand_n [nq] their counts.  One wave per query: the first k
+// entries whose bit in tomb ([ceil(n / 32)] words, bit = position) is clear, in their order, with external ids; -1 / +inf
+// padding and the count go to out (out.cnt is required).  Nothing beyond cand_n[q] entries is read.
+hipError_t launch_hnsw_live_topk(const int32_t* cand, const float* cand_d, const int32_t* cand_n, int nq, int cap,
+                                 const uint32_t* tomb, int n, const int32_t* ext_ids, int k, const HnswOut& out,
+                                 hipStream_t s);
 // SearchOld; ws_a / ws_r / ws_heap: the per-query HBM workspaces above (may be unused)
 hipError_t launch_hnsw_search_old(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries, uint32_t* bitset,
                                   void* ws_a, void* ws_r, void* ws_heap, const HnswOut& out, hipStream_t s);

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/nmslib_c.h"
+#include "../../include/nmslib_gpu.h"
 
 namespace nmslib {
 
@@ -164,6 +165,18 @@ class Index {
         return d;
     }
     size_t dataQty() const { return nmslib_data_qty(h_); }
+    // engine extension (include/nmslib_gpu.h): marks every stored row that carries one of the ids as deleted -> rows newly
+    // marked; later results never contain them, positions do not move, a row added later under a deleted id is live
+    size_t deleteIds(const int32_t* ids, size_t count) {
+        size_t marked = 0;
+        check(nmslib_gpu_delete_ids(h_, ids, count, &marked), alloc_, "deleteIds");
+        return marked;
+    }
+    size_t deletedRows() {
+        size_t n = 0;
+        check(nmslib_gpu_deleted_rows(h_, &n), alloc_, "deletedRows");
+        return n;
+    }
     std::string getSpaceType() { return str(&nmslib_get_space_type) == "cosinesimil" ? "cosine" : str(&nmslib_get_space_type); }
     std::string getMethod() { return str(&nmslib_get_method); }
     void save(const std::string& path, bool save_data) { check(nmslib_save_index(h_, path.c_str(), save_data), alloc_, "save"); }
