@@ -766,14 +766,32 @@ void Engine::upload_graph() {
                       "up_links");
     }
     prepare_graph_rows();
-    dg_.links0 = d_links0_.as<int32_t>();
-    dg_.up_off = d_up_off_.as<int64_t>();
-    dg_.up_links = d_up_links_.as<int32_t>();
+    bind_graph_buffers();
     dg_.maxM = g.maxM;
     dg_.maxM0 = g.maxM0;
     dg_.maxlevel = g.maxlevel;
     dg_.enterpoint = g.enterpoint;
     hip_check(hipStreamSynchronize(stream_), "graph upload");
+}
+
+// dg_ names the graph's three buffers (after they were allocated, or grew and moved)
+void Engine::bind_graph_buffers() {
+    dg_.links0 = d_links0_.as<int32_t>();
+    dg_.up_off = d_up_off_.as<int64_t>();
+    dg_.up_links = d_up_links_.as<int32_t>();
+}
+
+// largest |element| of the resident rows [first, n)
+float Engine::rows_max_abs(size_t first, size_t n) {
+    DevBuf d_bm;
+    d_bm.ensure(16);
+    float bm[4] = {0.f, 0.f, 0.f, 0.f};  // [2]: largest |element|
+    hip_check(launch_row_maxnorm(d_rows_.as<float>() + first * (size_t)ldb_, (int)(n - first), ldb_, (int)dim_, false,
+                                 d_bm.as<float>(), stream_),
+              "fp16 rows: range");
+    hip_check(hipMemcpyAsync(bm, d_bm.ptr(), 16, hipMemcpyDeviceToHost, stream_), "fp16 rows: range");
+    hip_check(hipStreamSynchronize(stream_), "fp16 rows: range");
+    return bm[2];
 }
 
 // The fp16 traversal copy of the rows the search kernels read (cosine on the optimized index: the normalised rows), scaled by
@@ -785,15 +803,8 @@ bool Engine::ensure_rows16() {
     const int ld16 = (int)f16pack::row_stride(dim_);
     int e = 0;
     try {
-        DevBuf d_bm;
-        d_bm.ensure(16);
-        float bm[4] = {0.f, 0.f, 0.f, 0.f};  // [2]: largest |element|
-        hip_check(launch_row_maxnorm(d_rows_.as<float>(), (int)n, ldb_, (int)dim_, false, d_bm.as<float>(), stream_),
-                  "fp16 rows: range");
-        hip_check(hipMemcpyAsync(bm, d_bm.ptr(), 16, hipMemcpyDeviceToHost, stream_), "fp16 rows: range");
-        hip_check(hipStreamSynchronize(stream_), "fp16 rows: range");
-        e = f16pack::scale_exp(bm[2]);
-        rows16_max_ = bm[2];
+        rows16_max_ = rows_max_abs(0, n);
+        e = f16pack::scale_exp(rows16_max_);
         d_rows16_.ensure(n * (size_t)ld16 * 2);
         pack_rows16(0, n, e);
     } catch (const EngineError& x) {
@@ -815,403 +826,6 @@ void Engine::pack_rows16(size_t first, size_t n, int e) {
                                       f16pack::scale_of(e), d_rows16_.as<uint16_t>() + first * ld16, (int)ld16, stream_),
               "fp16 rows");
     hip_check(hipStreamSynchronize(stream_), "fp16 rows");
-}
-
-bool Engine::use_gpu_build() const {
-    if (loaded_graph_ || method_ != Method::Hnsw) return false;
-    // what only the host builder does (the reference's "no limits"): lists beyond four words per lane and selection
-    // heuristic 3 (its candidate pool is an unordered set of node addresses) -- also when gpu_build=1 asks for the
-    // GPU.  A new node's M links must fit its own lists (the select kernel writes them without a shrink step).
-    if (bp_.M > 127 || bp_.maxM > 127 || bp_.maxM0 > 254 || bp_.M > bp_.maxM || bp_.M > bp_.maxM0 || bp_.delaunay == 3)
-        return false;
-    if (bp_.gpu_build >= 0) return bp_.gpu_build != 0;
-    // auto: indexThreadQty=1 asks for the reference's sequential insertion order (bit-identical graph,
-    // host builder); anything else is the concurrent build, whose schedule is free -> the GPU, unless the
-    // parameters exceed what its kernels hold in LDS (the host builder has the reference's "no limits")
-    if (bp_.efConstruction > 1024) return false;
-    return bp_.threads != 1;
-}
-
-// Batched construction on the GPU (kernels/hnsw_build_kernels.hip).  Insertion order, level stream and
-// per-node algorithm are the reference's (Hnsw::add, hnsw.cc:534-609); what differs is visibility:
-// the nodes of one batch are searched against the graph as it was before the batch, then linked.
-// Batches grow with the graph (size/16, at most gpu_build_batch), a node that raises the top level
-// closes its batch.  All searches of a batch (every level, top down) precede all link updates.
-//
-// post = 1, 2 (hnsw.cc:251-330): a second pass inserts the rows in reverse order (node 0, then n-1 .. 1, levels drawn
-// on from the same stream, as hnsw_build.cpp does); the result is the second graph with level-0 lists made from both
-// (hnsw_build_post_kernel).
-void Engine::build_graph_gpu() {
-    auto t0 = clk::now();
-    const size_t n = size();
-    hnsw_check_params(bp_);
-    const int maxM0 = bp_.maxM0, efC = bp_.efConstruction;
-    if (efC < 1 || efC > 1024)
-        throw EngineError(Err::IndexBuildFailed, "HNSW: efConstruction must be in [1, 1024] for the GPU builder");
-    graph_builder_ = 2;
-    built_n_ = 0;  // (set again below: a build that throws leaves no graph to append to)
-    host_links_stale_ = false;
-    const bool post = bp_.post != 0 && n > 1;
-    const std::vector<int32_t> draws = hnsw_random_levels(post ? 2 * n : n, bp_);
-    build_graph_gpu_pass(std::vector<int32_t>(draws.begin(), draws.begin() + (ptrdiff_t)n), false);
-    HostGraph& g = graph_;
-    hipStream_t s = stream_;
-    if (post) {
-        DevBuf first;
-        first.swap(d_links0_);
-        std::vector<int32_t> levels2(n);
-        levels2[0] = draws[n];
-        for (size_t pos = 1; pos < n; ++pos) levels2[n - pos] = draws[n + pos];
-        build_graph_gpu_pass(levels2, true);
-        // post = 1 keeps whole unions (up to 2 * maxM0) and then widens maxM0 to the longest list
-        const int wide = (bp_.post == 1 ? 2 * maxM0 : maxM0) + 1;
-        DevBuf out;
-        out.ensure(n * (size_t)wide * 4);
-        wb_nactive_.ensure(64);
-        hip_check(hipMemsetAsync(out.ptr(), 0, n * (size_t)wide * 4, s), "clear post lists");
-        hip_check(hipMemsetAsync(wb_nactive_.ptr(), 0, 4, s), "clear post length");
-        HnswDeviceGraph pg = dg_;
-        pg.ext_ids = nullptr;
-        hip_check(launch_hnsw_build_post(pg, d_links0_.as<int32_t>(), first.as<int32_t>(), maxM0, bp_.post, bp_.delaunay,
-                                         out.as<int32_t>(), wide, wb_nactive_.as<int32_t>(), s),
-                  "build post");
-        if (bp_.post == 1) {
-            int32_t longest = 0;
-            hip_check(hipMemcpyAsync(&longest, wb_nactive_.ptr(), 4, hipMemcpyDeviceToHost, s), "post length");
-            hip_check(hipStreamSynchronize(s), "build post");
-            g.maxM0 = std::max(longest, 1);
-            d_links0_.release();
-            d_links0_.ensure(n * (size_t)(g.maxM0 + 1) * 4);
-            hip_check(launch_hnsw_build_repack(out.as<int32_t>(), wide, d_links0_.as<int32_t>(), g.maxM0 + 1, (int)n, s),
-                      "build post repack");
-            hip_check(hipStreamSynchronize(s), "build post repack");  // `out` is freed below
-        } else {
-            d_links0_.swap(out);
-        }
-        dg_.links0 = d_links0_.as<int32_t>();
-        dg_.maxM0 = g.maxM0;
-    }
-    if (n) {
-        const size_t l0_ints = n * (size_t)(g.maxM0 + 1);
-        g.links0.resize(l0_ints);
-        g.up_links.resize(graph_up_ints_);
-        hip_check(hipMemcpyAsync(g.links0.data(), d_links0_.ptr(), l0_ints * 4, hipMemcpyDeviceToHost, s), "links0 D2H");
-        if (graph_up_ints_)
-            hip_check(hipMemcpyAsync(g.up_links.data(), d_up_links_.ptr(), graph_up_ints_ * 4, hipMemcpyDeviceToHost, s),
-                      "up_links D2H");
-        hip_check(hipStreamSynchronize(s), "graph download");
-    }
-    release_build_workspaces();
-    built_n_ = n;
-    build_seconds = n ? std::chrono::duration<double>(clk::now() - t0).count() : 0;
-}
-
-void Engine::release_build_workspaces() {
-    for (DevBuf* b : {&wb_pts_, &wb_src_, &wb_starts_, &wb_cand_ids_, &wb_cand_d_, &wb_cand_n_, &wb_status_,
-                      &wb_req_key_, &wb_req_dist_, &wb_req_key2_, &wb_req_dist2_, &wb_sort_tmp_, &wb_active_, &wb_nactive_, &wb_extra_ids_, &wb_extra_d_, &wb_extra_n_})
-        b->release();
-}
-
-// One insertion pass over all rows: position 0 is node 0, position i > 0 is node i, or node n - i in reverse order.
-// Leaves the graph in d_links0_ / d_up_off_ / d_up_links_ (dg_) and its levels, offsets and entry point in graph_.
-// This part allocates and clears the graph with node 0 in it; build_graph_gpu_insert adds the other positions.
-void Engine::build_graph_gpu_pass(const std::vector<int32_t>& levels, bool reverse) {
-    const size_t n = size();
-    const int M = bp_.M, maxM = bp_.maxM, maxM0 = bp_.maxM0, efC = bp_.efConstruction;
-    HostGraph& g = graph_;
-    g = HostGraph{};
-    g.n = (int)n;
-    g.M = M;
-    g.maxM = maxM;
-    g.maxM0 = maxM0;
-    g.efConstruction = efC;
-    g.delaunay = bp_.delaunay;
-    g.levels = levels;
-    g.up_off.assign(n, -1);
-    size_t up_ints = 0;
-    for (size_t i = 0; i < n; ++i)
-        if (g.levels[i] > 0) {
-            g.up_off[i] = (int64_t)up_ints;
-            up_ints += (size_t)g.levels[i] * (maxM + 1);
-        }
-    const size_t l0_ints = n * (size_t)(maxM0 + 1);
-    d_links0_.ensure(std::max<size_t>(l0_ints, 1) * 4);
-    d_up_off_.ensure(std::max<size_t>(n, 1) * 8);
-    d_up_links_.ensure(std::max<size_t>(up_ints, 1) * 4);
-    if (!reverse) prepare_graph_rows();  // (once: it normalises the cosine rows in place)
-    dg_.links0 = d_links0_.as<int32_t>();
-    dg_.up_off = d_up_off_.as<int64_t>();
-    dg_.up_links = d_up_links_.as<int32_t>();
-    dg_.maxM = maxM;
-    dg_.maxM0 = maxM0;
-    graph_up_ints_ = up_ints;
-    if (n == 0) return;
-    hipStream_t s = stream_;
-    hip_check(hipMemsetAsync(d_links0_.ptr(), 0, l0_ints * 4, s), "clear links0");
-    hip_check(hipMemsetAsync(d_up_links_.ptr(), 0, std::max<size_t>(up_ints, 1) * 4, s), "clear up_links");
-    hip_check(hipMemcpyAsync(d_up_off_.ptr(), g.up_off.data(), n * 8, hipMemcpyHostToDevice, s), "up_off");
-    g.maxlevel = dg_.maxlevel = g.levels[0];
-    g.enterpoint = dg_.enterpoint = 0;
-    build_graph_gpu_insert(1, reverse);
-}
-
-// Inserts positions [first, n) into the graph of positions [0, first) that dg_ / graph_ describe (lists on the device, cleared
-// for the new nodes; levels, offsets, top level and entry point in graph_), batch by batch.  The schedule of a batch depends
-// on the positions before it only, never on n: inserting [first, n) into a finished graph of `first` nodes is what a pass
-// over all n does from its batch boundary at `first` on (gpu_build_cut puts one there).
-void Engine::build_graph_gpu_insert(size_t first, bool reverse) {
-    const size_t n = size();
-    const int M = bp_.M, efC = bp_.efConstruction;
-    auto node_at = [&](size_t pos) { return reverse && pos ? n - pos : pos; };
-    HostGraph& g = graph_;
-    hipStream_t s = stream_;
-    HnswDeviceGraph bgraph = dg_;
-    bgraph.ext_ids = nullptr;  // construction works on internal positions
-    int maxlevel = g.maxlevel, enterpoint = g.enterpoint;
-    const int max_batch = bp_.gpu_build_batch > 0 ? bp_.gpu_build_batch : 4096;
-    const int batch_div = bp_.gpu_build_div > 0 ? bp_.gpu_build_div : 16;
-    // reverse-link requests of one level of one batch: M slots per new node, sorted on the device
-    const size_t req_max = (size_t)max_batch * (size_t)M;
-    wb_req_key_.ensure(req_max * 8);
-    wb_req_dist_.ensure(req_max * 4);
-    wb_req_key2_.ensure(req_max * 8);
-    wb_req_dist2_.ensure(req_max * 4);
-    const size_t sort_tmp = hnsw_build_sort_temp_bytes((int)req_max, (int)n);
-    wb_sort_tmp_.ensure(sort_tmp);
-    wb_active_.ensure(req_max * 4);
-    wb_nactive_.ensure(64);
-    wb_extra_ids_.ensure((size_t)max_batch * 64 * 4);  // batch-mates: 64 per new node of a level slice
-    wb_extra_d_.ensure((size_t)max_batch * 64 * 4);
-    wb_extra_n_.ensure((size_t)max_batch * 4);
-
-    std::vector<int32_t> pts, src, status;
-    std::vector<size_t> base;
-    const size_t cut = bp_.gpu_build_cut > 0 ? (size_t)bp_.gpu_build_cut : 0;
-    size_t next = first;
-    while (next < n) {
-        const size_t sz = next;
-        size_t bsz = std::min<size_t>(std::max<size_t>(sz / (size_t)batch_div, 1), (size_t)max_batch);
-        size_t end = std::min(n, next + bsz);
-        if (next < cut) end = std::min(end, cut);
-        for (size_t i = next; i < end; ++i)
-            if (g.levels[node_at(i)] > maxlevel) {
-                end = i + 1;
-                break;
-            }
-        // (node, level) pairs of the batch, level-major (top level first); src = the same node's pair one level up
-        const int top = maxlevel;
-        pts.clear();
-        src.clear();
-        base.assign((size_t)top + 2, 0);
-        std::vector<int32_t> prev_slot(end - next, -1), cur_slot(end - next, -1);
-        for (int l = top; l >= 0; --l) {
-            base[l] = pts.size();
-            for (size_t i = next; i < end; ++i) {
-                if (std::min(g.levels[node_at(i)], top) < l) continue;
-                cur_slot[i - next] = (int32_t)pts.size();
-                pts.push_back((int32_t)node_at(i));
-                src.push_back(prev_slot[i - next]);
-            }
-            prev_slot = cur_slot;
-            std::fill(cur_slot.begin(), cur_slot.end(), -1);
-        }
-        // base[l] .. base[l-1] (or npairs for l == 0) is level l's slice
-        const size_t npairs = pts.size();
-        auto slice_end = [&](int l) { return l == 0 ? npairs : base[l - 1]; };
-        wb_pts_.ensure(npairs * 4);
-        wb_src_.ensure(npairs * 4);
-        wb_starts_.ensure(npairs * 4);
-        wb_cand_ids_.ensure(npairs * (size_t)efC * 4);
-        wb_cand_d_.ensure(npairs * (size_t)efC * 4);
-        wb_cand_n_.ensure(npairs * 4);
-        wb_status_.ensure(npairs * 4);
-        ws_ndc_.ensure(npairs * 4);
-        ws_hops_.ensure(npairs * 4);
-        ws_hops_up_.ensure(npairs * 4);
-        hip_check(hipMemcpyAsync(wb_pts_.ptr(), pts.data(), npairs * 4, hipMemcpyHostToDevice, s), "batch nodes");
-        hip_check(hipMemcpyAsync(wb_src_.ptr(), src.data(), npairs * 4, hipMemcpyHostToDevice, s), "batch sources");
-        bgraph.maxlevel = maxlevel;
-        bgraph.enterpoint = enterpoint;
-
-        const HnswOut out{wb_cand_ids_.as<int32_t>(), wb_cand_d_.as<float>(), wb_cand_n_.as<int32_t>(), ws_ndc_.as<int32_t>(),
-                          ws_hops_.as<int32_t>(), ws_hops_up_.as<int32_t>(), wb_status_.as<int32_t>()};
-        for (int attempt = 0; attempt < 2; ++attempt) {
-            const bool force_bitset = attempt == 1;
-            bool used_table = false;
-            for (int l = top; l >= 0; --l) {
-                const size_t b0 = base[l], m = slice_end(l) - b0;
-                if (m == 0) continue;
-                hip_check(launch_hnsw_build_starts(wb_src_.as<int32_t>() + b0, wb_cand_ids_.as<int32_t>(),
-                                                   wb_cand_n_.as<int32_t>(), efC, wb_starts_.as<int32_t>() + b0, (int)m, s),
-                          "build starts");
-                HnswSearchPlan p = hnsw_make_plan(bgraph, (int)m, efC, efC, force_bitset);
-                uint32_t* bitset = nullptr;
-                if (p.table_size == 0) bitset = cleared_bitset(m, p.bitset_words, s);
-                else used_table = true;
-                hip_check(launch_hnsw_search(bgraph, p,
-                                             HnswQueries::stored(wb_pts_.as<int32_t>() + b0, wb_starts_.as<int32_t>() + b0, l),
-                                             bitset, HnswOverflow{}, out.at(b0, efC), s),
-                          "build search");
-            }
-            if (!used_table) break;
-            status.resize(npairs);
-            hip_check(hipMemcpyAsync(status.data(), wb_status_.ptr(), npairs * 4, hipMemcpyDeviceToHost, s), "status");
-            hip_check(hipStreamSynchronize(s), "build search");
-            bool any = false;
-            for (int32_t v : status) any |= (v != 0);
-            if (!any) break;  // else: the LDS visited table overflowed somewhere -> redo with HBM bitsets
-        }
-
-        HnswBuildGraph bg{};
-        bg.g = bgraph;
-        bg.links0 = d_links0_.as<int32_t>();
-        bg.up_links = d_up_links_.as<int32_t>();
-        bg.M = M;
-        bg.delaunay = bp_.delaunay;
-        for (int l = top; l >= 0; --l) {
-            const size_t b0 = base[l], m = slice_end(l) - b0;
-            if (m == 0) continue;
-            const int total = (int)(m * (size_t)M);
-            hip_check(launch_hnsw_build_mates(bg, l, wb_pts_.as<int32_t>() + b0, (int)m, wb_cand_d_.as<float>() + b0 * efC,
-                                              wb_cand_n_.as<int32_t>() + b0, efC, wb_extra_ids_.as<int32_t>(),
-                                              wb_extra_d_.as<float>(), wb_extra_n_.as<int32_t>(), s),
-                      "build batch-mates");
-            hip_check(launch_hnsw_build_select(bg, l, wb_pts_.as<int32_t>() + b0, (int)m,
-                                               wb_cand_ids_.as<int32_t>() + b0 * efC, wb_cand_d_.as<float>() + b0 * efC,
-                                               wb_cand_n_.as<int32_t>() + b0, efC, wb_extra_ids_.as<int32_t>(),
-                                               wb_extra_d_.as<float>(), wb_extra_n_.as<int32_t>(),
-                                               wb_req_key_.as<unsigned long long>(), wb_req_dist_.as<float>(), s),
-                      "build select");
-            hip_check(launch_hnsw_build_sort_requests(wb_req_key_.as<unsigned long long>(), wb_req_dist_.as<float>(), total,
-                                                      wb_req_key2_.as<unsigned long long>(), wb_req_dist2_.as<float>(),
-                                                      wb_sort_tmp_.ptr(), sort_tmp, wb_active_.as<int32_t>(),
-                                                      wb_nactive_.as<int32_t>(), s),
-                      "build sort");
-            // distinct targets: the sz nodes linked before the batch and the slice's own nodes (batch-mates select each
-            // other); a smaller grid would drop whichever targets the head scan numbered last
-            const size_t max_active = std::min<size_t>(sz + m, (size_t)total);
-            hip_check(launch_hnsw_build_link(bg, l, wb_active_.as<int32_t>(), wb_nactive_.as<int32_t>(), (int)max_active,
-                                             wb_req_key2_.as<unsigned long long>(), wb_req_dist2_.as<float>(), total, s),
-                      "build link");
-        }
-        for (size_t i = next; i < end; ++i)
-            if (g.levels[node_at(i)] > maxlevel) {
-                maxlevel = g.levels[node_at(i)];
-                enterpoint = (int)node_at(i);
-            }
-        // pts/src are reused by the next batch: the copies above must have been consumed
-        hip_check(hipStreamSynchronize(s), "build batch");
-        next = end;
-    }
-    g.maxlevel = maxlevel;
-    g.enterpoint = enterpoint;
-    dg_.maxlevel = maxlevel;
-    dg_.enterpoint = enterpoint;
-}
-
-// gpu_append=1: the resident graph is the GPU builder's over rows [0, built_n_), complete and not post-processed, and all that
-// happened since is add_row.  (finalize() has dealt with shards and checked use_gpu_build() before it asks.)
-bool Engine::can_append() const {
-    return bp_.gpu_append == 1 && graph_builder_ == 2 && built_n_ >= 1 && size() > built_n_ && d_n_ == built_n_ &&
-           (size_t)graph_.n == built_n_ && bp_.post == 0 && !parent_ && shards_.empty() && !loaded_graph_;
-}
-
-// Rows [n0, n1) added after a GPU build go into the resident graph: the buffers grow to n1 rows keeping
-// their contents, only the new rows are uploaded and prepared, the level stream goes on where the build left it, and the
-// builder's batch loop is entered at position n0.  The result is the graph a build of all n1 rows makes with a batch boundary
-// at n0 (gpu_build_cut).  false: a buffer could not grow or the insertion ran out of memory; the caller builds in full from
-// the host rows.
-bool Engine::append_rows_gpu() {
-    const auto t0 = clk::now();
-    const size_t n0 = built_n_, n1 = size(), added = n1 - n0;
-    const int maxM = bp_.maxM;
-    const size_t l0_row = (size_t)(bp_.maxM0 + 1) * 4, ld16 = f16pack::row_stride(dim_);
-    HostGraph& g = graph_;
-    hipStream_t s = stream_;
-    built_n_ = 0;  // (set again at the end: an append that throws leaves no graph to append to)
-    const std::vector<int32_t> levels = hnsw_random_levels(n1, bp_);  // one stream: its first n0 draws are g.levels
-    size_t up_ints = graph_up_ints_;
-    std::vector<int64_t> up_off(added, -1);
-    for (size_t i = n0; i < n1; ++i)
-        if (levels[i] > 0) {
-            up_off[i - n0] = (int64_t)up_ints;
-            up_ints += (size_t)levels[i] * (maxM + 1);
-        }
-    const bool have16 = dg_.rows16 != nullptr;  // (upload_rows takes the copy out of dg_ until the new rows are in it)
-    try {
-        upload_rows(n0);
-        prepare_graph_rows(n0);
-        d_links0_.grow_keep(n1 * l0_row, n0 * l0_row, s);
-        d_up_off_.grow_keep(n1 * 8, n0 * 8, s);
-        d_up_links_.grow_keep(std::max<size_t>(up_ints, 1) * 4, graph_up_ints_ * 4, s);
-        if (have16) d_rows16_.grow_keep(n1 * ld16 * 2, n0 * ld16 * 2, s);
-        dg_.links0 = d_links0_.as<int32_t>();
-        dg_.up_off = d_up_off_.as<int64_t>();
-        dg_.up_links = d_up_links_.as<int32_t>();
-        // the graph's host side and the new nodes' empty lists
-        g.n = (int)n1;
-        g.levels.insert(g.levels.end(), levels.begin() + (ptrdiff_t)n0, levels.end());
-        g.up_off.insert(g.up_off.end(), up_off.begin(), up_off.end());
-        hip_check(hipMemsetAsync(d_links0_.as<char>() + n0 * l0_row, 0, added * l0_row, s), "clear links0");
-        if (up_ints > graph_up_ints_)
-            hip_check(hipMemsetAsync(d_up_links_.as<int32_t>() + graph_up_ints_, 0, (up_ints - graph_up_ints_) * 4, s),
-                      "clear up_links");
-        hip_check(hipMemcpyAsync(d_up_off_.as<int64_t>() + n0, up_off.data(), added * 8, hipMemcpyHostToDevice, s), "up_off");
-        graph_up_ints_ = up_ints;
-        host_links_stale_ = true;
-        hnsw_fix_valid_ = false;
-        build_graph_gpu_insert(n0, false);
-    } catch (const EngineError& x) {
-        if (x.code != Err::OutOfMemory) throw;
-        // a buffer could not grow, or the insertion's workspaces did not fit beside the grown index: make room, build in full
-        (void)hipStreamSynchronize(s);
-        release_build_workspaces();
-        for (DevBuf* b : {&d_links0_, &d_up_off_, &d_up_links_, &d_rows16_}) b->release();
-        host_links_stale_ = false;
-        return false;
-    }
-    release_build_workspaces();
-    // the fp16 copy: the new rows at the copy's scale; all rows again (on the device) if the new ones move the scale
-    if (have16) {
-        DevBuf d_bm;
-        d_bm.ensure(16);
-        float bm[4] = {0.f, 0.f, 0.f, 0.f};
-        hip_check(launch_row_maxnorm(d_rows_.as<float>() + n0 * (size_t)ldb_, (int)added, ldb_, (int)dim_, false,
-                                     d_bm.as<float>(), s),
-                  "fp16 rows: range");
-        hip_check(hipMemcpyAsync(bm, d_bm.ptr(), 16, hipMemcpyDeviceToHost, s), "fp16 rows: range");
-        hip_check(hipStreamSynchronize(s), "fp16 rows: range");
-        rows16_max_ = std::max(rows16_max_, bm[2]);
-        const int e = f16pack::scale_exp(rows16_max_);
-        pack_rows16(e == rows16_exp_ ? n0 : 0, n1, e);
-        rows16_exp_ = e;
-        dg_.rows16 = d_rows16_.ptr();
-        dg_.inv_scale16 = f16pack::scale_of(-e);
-    } else if (rows_f16_index_) {
-        (void)ensure_rows16();
-    }
-    built_n_ = n1;
-    rows_appended = added;
-    build_seconds = std::chrono::duration<double>(clk::now() - t0).count() - upload_seconds;
-    return true;
-}
-
-// After an append the adjacency lists of graph_ are behind the device's (old nodes got new links too); the file writer
-// reads them, so they are fetched when it asks.
-void Engine::sync_host_graph() {
-    if (!host_links_stale_) return;
-    host_links_stale_ = false;
-    if (graph_builder_ != 2 || built_n_ != (size_t)graph_.n) return;  // (graph_ is no longer the appended graph)
-    check_device();
-    HostGraph& g = graph_;
-    const size_t l0_ints = (size_t)g.n * (size_t)(g.maxM0 + 1);
-    g.links0.resize(l0_ints);
-    g.up_links.resize(graph_up_ints_);
-    hip_check(hipMemcpyAsync(g.links0.data(), d_links0_.ptr(), l0_ints * 4, hipMemcpyDeviceToHost, stream_), "links0 D2H");
-    if (graph_up_ints_)
-        hip_check(hipMemcpyAsync(g.up_links.data(), d_up_links_.ptr(), graph_up_ints_ * 4, hipMemcpyDeviceToHost, stream_),
-                  "up_links D2H");
-    hip_check(hipStreamSynchronize(stream_), "graph download");
 }
 
 void Engine::ensure_graph() {

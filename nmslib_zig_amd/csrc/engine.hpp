@@ -164,6 +164,20 @@ struct BruteDense {
     BfF32Tiles tiles(int dp, bool augmented) const;
 };
 
+// ---- GPU HNSW builder (hnsw_gpu_build.cpp): construction workspaces, released after the build ----
+struct BatchPairs;  // hnsw_batch_plan.hpp
+struct HnswBuildWs {
+    // per (node, level) pair of a batch: the node, its pair one level up, its start node, its efConstruction candidates
+    DevBuf pts, src, starts, cand_ids, cand_d, cand_n, status;
+    // per level slice: batch-mates (64 per new node); reverse-link requests (M per new node), sorted, and their distinct targets
+    DevBuf extra_ids, extra_d, extra_n, req_key, req_dist, req_key2, req_dist2, sort_tmp, active, nactive;
+    size_t sort_tmp_bytes = 0;  // what the request sort asked for (reserve_batches)
+
+    void release() { *this = HnswBuildWs{}; }
+    void reserve_batches(int max_batch, int M, size_t n);  // what holds for every batch of a pass over n rows
+    void reserve_pairs(size_t npairs, int efC);            // one batch's pairs
+};
+
 // ---- the index ---------------------------------------------------------------------------------
 enum class Method { Brute, Hnsw };
 
@@ -358,13 +372,17 @@ class Engine {
     void build_graph_gpu();
     void build_graph_gpu_pass(const std::vector<int32_t>& levels, bool reverse);
     void build_graph_gpu_insert(size_t first, bool reverse);  // positions [first, n) into the graph of dg_ / graph_
-    void release_build_workspaces();
+    void search_batch(const HnswDeviceGraph& bgraph, const BatchPairs& pairs);
+    void link_batch(const HnswDeviceGraph& bgraph, const BatchPairs& pairs, size_t linked);
+    void download_graph_links();
     bool can_append() const;
     bool append_rows_gpu();   // gpu_append=1; false: a buffer could not grow, take the full path
     void sync_host_graph();   // the lists of graph_ follow the device's after an append (read by save)
     void pack_rows16(size_t first, size_t n, int e);  // rows [first, n) of the fp16 copy at scale 2^e
     void prepare_graph_rows(size_t first = 0);
     void upload_graph();
+    void bind_graph_buffers();                  // dg_.links0 / up_off / up_links = the three buffers
+    float rows_max_abs(size_t first, size_t n);  // largest |element| of the resident rows [first, n)
     // dense brute force (brute.cpp)
     void prepare_brute();
     void measure_rows_f16(const float* rows, size_t n, int ld, int dim, bool relative, float* bm);
@@ -464,8 +482,7 @@ class Engine {
     // workspaces
     DevBuf ws_q_, ws_qpad_, ws_qsel_, ws_qaux_, ws_cand_, ws_cnt_, ws_ids_, ws_dists_, ws_outcnt_, ws_status_, ws_bitset_;
     DevBuf ws_ndc_, ws_hops_, ws_hops_up_, ws_pair_, ws_rdist_, ws_rcnt_, ws_old_a_, ws_old_r_, ws_old_heap_;
-    DevBuf wb_pts_, wb_src_, wb_starts_, wb_cand_ids_, wb_cand_d_, wb_cand_n_, wb_status_, wb_req_key_, wb_req_dist_,
-        wb_req_key2_, wb_req_dist2_, wb_sort_tmp_, wb_active_, wb_nactive_, wb_extra_ids_, wb_extra_d_, wb_extra_n_;  // construction workspaces (released after the build)
+    HnswBuildWs bw_;
     DevBuf ws_bq_, ws_split_;  // sparse / string batches: the packed queries; per-split lists (string HNSW: per-query state)
     DevBuf ws_fix_;       // visited-overflow list of the HNSW search (count + query ids), device only
     DevBuf ws_rr_ids_, ws_rr_d_, ws_rr_cnt_;  // fp16 walk: its sorted arrays (positions, fp16-row distances) and their lengths
