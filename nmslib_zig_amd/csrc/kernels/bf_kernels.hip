@@ -19,6 +19,7 @@
 // Survivors are appended to a per-(query, split) buffer in HBM (L2-resident); when a buffer
 // nears capacity the owning wave sorts it in LDS, keeps k', and raises the threshold.
 #include <cstdio>
+#include <mutex>
 #include <type_traits>
 #include <vector>
 #include <cstdlib>
@@ -2464,6 +2465,48 @@ __device__ __forceinline__ uint32_t entry_rth_largest(const u64* keys, int total
     return wave_rth_largest_u32<NPER>(key, r);
 }
 
+// One step of a row's fma chains (wave_exact_distance_f32's loop body) for the score family SPACE; `on`: the chain's
+// 64-dimension step exists (that function stops at the last 64-chunk: a step beyond it leaves the chain's bits alone).
+template <int SPACE>
+__device__ __forceinline__ void rerank_chain_step(float x, float y, bool on, float& p0, float& p1, float& p2) {
+    if constexpr (SPACE == SP_L2) {
+        const float t = x - y;
+        p0 = on ? fmaf(t, t, p0) : p0;
+    } else {
+        p0 = on ? fmaf(x, y, p0) : p0;
+        if constexpr (SPACE != SP_NEGDOT) {
+            p1 = on ? fmaf(x, x, p1) : p1;
+            p2 = on ? fmaf(y, y, p2) : p2;
+        }
+    }
+}
+// The distance of one row from its 16 lanes' chains: wave_exact_distance_f32's xor-32 and xor-16 steps inside the lane,
+// xor 8 / 4 / 2 / 1 across the 16 lanes, then the reference's finish.
+template <int SPACE>
+__device__ __forceinline__ float rerank_chain_finish(const float* p0, const float* p1, const float* p2) {
+    auto tree = [&](const float* p) __attribute__((always_inline)) -> float {
+        float s = (p[0] + p[2]) + (p[1] + p[3]);     // xor 32, then xor 16
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+        return s;
+    };
+    const float s0 = tree(p0);
+    if constexpr (SPACE == SP_L2) return sqrtf(s0);
+    else if constexpr (SPACE == SP_NEGDOT) return -s0;
+    else {
+        const float sim = normdot_finish(s0, tree(p1), tree(p2));
+        if constexpr (SPACE == SP_ANGULAR) return acosf(sim);
+        else return fmaxf(0.0f, 1.0f - sim);
+    }
+}
+
+constexpr int kRerankExtSlots = 64;   // fetched rows whose external ids are kept in LDS (one round of the distance phase)
+
+// One instantiation per score family (SPACE: SP_L2, SP_NEGDOT, SP_COSINE, SP_ANGULAR; COSC: the centred form of the last
+// two, a.qaux set) and row-length class (LONG: rows of more than 128 dimensions, in 64-dimension steps): what is fixed
+// per index is fixed at compile time, so that the rows of up to 128 dimensions -- the served shape -- fit 128 registers
+// and four workgroups share a CU (DESIGN 4.1b "Residency").
+template <int SPACE, bool COSC, bool LONG>
 __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Args a) {
     const unsigned long long t0 = a.prof ? wall_clock64() : 0;
     auto lap = [&](int i) __attribute__((always_inline)) {
@@ -2476,9 +2519,23 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
     __shared__ float s_qn2, s_e1, s_thr, s_cut;
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int nl = 2 * a.nsplit;
-    // exclusive prefix sum of the (clipped) list lengths: wave 0, each lane a run of consecutive lists
     if (tid == 0) s_over = 0;
     __syncthreads();
+    // the query's values in the distance phase's layout (rows of up to 128 dimensions): requested here, beside the list
+    // lengths, instead of as one more round trip in front of the row loads
+    const float* qq = a.queries + (size_t)q * a.ldb;
+    const int sub = lane & 15, rg = lane >> 4;
+    float qv[8];
+    bool ok[8];
+    if constexpr (!LONG) {
+#pragma unroll
+        for (int c = 0; c < 8; ++c) {
+            const int d = sub + 16 * c;          // c = 0..3: dimension of virtual lane sub + 16c; c = 4..7: the same + 64
+            ok[c] = d < a.dim;
+            qv[c] = ok[c] ? qq[d] : 0.f;
+        }
+    }
+    // exclusive prefix sum of the (clipped) list lengths: wave 0, each lane a run of consecutive lists
     if (tid < 64) {
         const int per = (nl + 63) / 64;
         int sum = 0, over = 0;
@@ -2487,7 +2544,9 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
             if (s < nl) {
                 const int c = a.list_cnt[(size_t)q * nl + s];
                 over |= c > a.caph;
-                sum += c < a.caph ? c : a.caph;
+                const int cc = c < a.caph ? c : a.caph;
+                offs[s] = cc;   // (read once: the lane finds its own clipped lengths here in the second pass)
+                sum += cc;
             }
         }
         int incl = sum;
@@ -2500,9 +2559,9 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
         for (int i = 0; i < per; ++i) {
             const int s = tid * per + i;
             if (s < nl) {
+                const int cc = offs[s];
                 offs[s] = run;
-                const int c = a.list_cnt[(size_t)q * nl + s];
-                run += c < a.caph ? c : a.caph;
+                run += cc;
             }
         }
         if (tid == 63) offs[nl] = incl;
@@ -2515,7 +2574,7 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
         float ss = 0.f;
         for (int d = lane; d < a.sel_dim; d += 64) ss = fmaf(qs[d], qs[d], ss);
         ss = wave_sum(ss);
-        const float e1 = split_product ? 0.f : one_product_error(qs, a.sel_dim, lane, a.scale * (a.space == SP_L2 || a.space == SP_NEGDOT || a.qaux ? a.bmax : 1.0f), a.bres16, a.scale_q);
+        const float e1 = split_product ? 0.f : one_product_error(qs, a.sel_dim, lane, a.scale * (SPACE == SP_L2 || SPACE == SP_NEGDOT || COSC ? a.bmax : 1.0f), a.bres16, a.scale_q);
         if (lane == 0) {
             s_qn2 = ss;
             s_e1 = e1;
@@ -2527,7 +2586,7 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
     const int listed = offs[nl];
     int total = listed;   // (from the cut on: the rows that are fetched)
     if ((a.no_split && a.precise[q / a.fail_queries] != 0) ||      // (no scan served this tile: its lists are stale)
-        (a.qaux && a.qaux[(size_t)q * 4 + 3] == 0.f)) {            // (zero-norm query, centred cosine: every distance is 1)
+        (COSC && a.qaux[(size_t)q * 4 + 3] == 0.f)) {              // (zero-norm query, centred cosine: every distance is 1)
         if (tid == 0) atomicOr(&a.tile_fail[q / a.fail_queries], 1);
         return;
     }
@@ -2599,23 +2658,20 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
     // wave_exact_distance_f32 (the adaptive path's re-rank; a query must get the same floats whichever path served it):
     // lane `sub` plays that function's lanes sub, sub+16, sub+32, sub+48 (dimensions v and v + 64 each), adds them in
     // the order of its xor-32 and xor-16 steps, and the xor 8 / 4 / 2 / 1 steps run across the 16 lanes.
-    const float* qq = a.queries + (size_t)q * a.ldb;
-    const int sub = lane & 15, rg = lane >> 4;
-    if (a.dim <= 128) {
-        // (rows of up to 128 dimensions: every load of a round issued up front -- the shape this kernel was tuned in)
-        float qv[8];
-        bool ok[8];
-    #pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const int d = sub + 16 * c;          // c = 0..3: dimension of virtual lane sub + 16c; c = 4..7: the same + 64
-            ok[c] = d < a.dim;
-            qv[c] = ok[c] ? qq[d] : 0.f;
-        }
+    // The external ids of up to kRerankExtSlots fetched rows (the cut leaves ~15 at C2) are requested with the rows and kept
+    // beside their positions: the output phase finds them here instead of paying one more dependent round trip.
+    __shared__ u64 s_ext[kRerankExtSlots];   // (id << 32 | position) of row j
+    const bool ext_early = a.ext_ids != nullptr && total <= kRerankExtSlots;
+    if constexpr (!LONG) {
+        // (rows of up to 128 dimensions: every load of a round issued up front -- the shape this kernel was tuned in;
+        //  the query's values qv / ok came in at the top)
+        const bool step1 = a.dim > 64;    // (wave_exact_distance_f32 stops at the last 64-chunk)
         // (four passes of 4 rows per wave requested together: 64 rows of the query in flight per workgroup round; eight
         //  passes -- two round trips instead of three at ~150 listed rows -- measured no faster: 35 vs 31 us for this phase)
         constexpr int kU = 4;
         for (int j0 = wave * (4 * kU); j0 < total; j0 += 16 * kU) {
             uint32_t pos[kU];
+            int32_t ext[kU];
             float xv[kU][8];
     #pragma unroll
             for (int u = 0; u < kU; ++u) {
@@ -2624,6 +2680,7 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
                 const float* row = a.base + (size_t)pos[u] * a.ldb + sub;
     #pragma unroll
                 for (int c = 0; c < 8; ++c) xv[u][c] = ok[c] ? row[16 * c] : 0.f;
+                ext[u] = (ext_early && sub == 0 && j < total) ? a.ext_ids[pos[u]] : 0;
             }
             __builtin_amdgcn_wave_barrier();
     #pragma unroll
@@ -2632,37 +2689,12 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
     #pragma unroll
                 for (int v = 0; v < 4; ++v) {
                     p0[v] = p1[v] = p2[v] = 0.f;
-    #pragma unroll
-                    for (int c = 0; c < 2; ++c) {
-                        if (64 * c >= a.dim) continue;    // (wave_exact_distance_f32 stops at the last 64-chunk)
-                        const float x = xv[u][v + 4 * c], y = qv[v + 4 * c];
-                        if (a.space == SP_L2) {
-                            const float t = x - y;
-                            p0[v] = fmaf(t, t, p0[v]);
-                        } else {
-                            p0[v] = fmaf(x, y, p0[v]);
-                            if (a.space != SP_NEGDOT) {
-                                p1[v] = fmaf(x, x, p1[v]);
-                                p2[v] = fmaf(y, y, p2[v]);
-                            }
-                        }
-                    }
+                    rerank_chain_step<SPACE>(xv[u][v], qv[v], true, p0[v], p1[v], p2[v]);
+                    rerank_chain_step<SPACE>(xv[u][v + 4], qv[v + 4], step1, p0[v], p1[v], p2[v]);
                 }
-                auto tree = [&](const float* p) __attribute__((always_inline)) -> float {
-                    float s = (p[0] + p[2]) + (p[1] + p[3]);     // xor 32, then xor 16
-    #pragma unroll
-                    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-                    return s;
-                };
-                const float s0 = tree(p0);
-                float d;
-                if (a.space == SP_L2) d = sqrtf(s0);
-                else if (a.space == SP_NEGDOT) d = -s0;
-                else {
-                    const float sim = normdot_finish(s0, tree(p1), tree(p2));
-                    d = a.space == SP_ANGULAR ? acosf(sim) : fmaxf(0.0f, 1.0f - sim);
-                }
+                const float d = rerank_chain_finish<SPACE>(p0, p1, p2);
                 const int j = j0 + 4 * u + rg;
+                if (ext_early && sub == 0 && j < total) s_ext[j] = ((u64)(uint32_t)ext[u] << 32) | pos[u];
                 if (sub == 0 && j < total) keys[j] = ((u64)f32_ord(d) << 32) | pos[u];
             }
         }
@@ -2673,12 +2705,14 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
         const int nstep = (a.dim + 63) >> 6;
         for (int j0 = wave * 16; j0 < total; j0 += 64) {
             uint32_t pos[4];
+            int32_t ext[4];
             const float* rowp[4];
     #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int j = j0 + 4 * u + rg;
                 pos[u] = (uint32_t)keys[j < total ? j : total - 1];
                 rowp[u] = a.base + (size_t)pos[u] * a.ldb + sub;
+                ext[u] = (ext_early && sub == 0 && j < total) ? a.ext_ids[pos[u]] : 0;
             }
             float p0[4][4], p1[4][4], p2[4][4];   // [row][virtual lane]
     #pragma unroll
@@ -2686,8 +2720,7 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
     #pragma unroll
                 for (int v = 0; v < 4; ++v) p0[u][v] = p1[u][v] = p2[u][v] = 0.f;
             for (int c0 = 0; c0 < nstep; c0 += 2) {
-                float xv[4][8], qv[8];
-                bool ok[8];
+                float xv[4][8];
     #pragma unroll
                 for (int c = 0; c < 8; ++c) {
                     const int d = sub + 16 * (c & 3) + 64 * (c0 + (c >> 2));   // c = 0..3: step c0, c = 4..7: step c0 + 1
@@ -2701,41 +2734,18 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
     #pragma unroll
                     for (int v = 0; v < 4; ++v) {
     #pragma unroll
-                        for (int c = 0; c < 2; ++c) {
-                            if (64 * (c0 + c) >= a.dim) continue;    // (wave_exact_distance_f32 stops at the last 64-chunk)
-                            const float x = xv[u][v + 4 * c], y = qv[v + 4 * c];
-                            if (a.space == SP_L2) {
-                                const float t = x - y;
-                                p0[u][v] = fmaf(t, t, p0[u][v]);
-                            } else {
-                                p0[u][v] = fmaf(x, y, p0[u][v]);
-                                if (a.space != SP_NEGDOT) {
-                                    p1[u][v] = fmaf(x, x, p1[u][v]);
-                                    p2[u][v] = fmaf(y, y, p2[u][v]);
-                                }
-                            }
-                        }
+                        for (int c = 0; c < 2; ++c)   // (wave_exact_distance_f32 stops at the last 64-chunk)
+                            rerank_chain_step<SPACE>(xv[u][v + 4 * c], qv[v + 4 * c], 64 * (c0 + c) < a.dim, p0[u][v], p1[u][v],
+                                                     p2[u][v]);
                     }
                 }
             }
             __builtin_amdgcn_wave_barrier();
     #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                auto tree = [&](const float* p) __attribute__((always_inline)) -> float {
-                    float s = (p[0] + p[2]) + (p[1] + p[3]);     // xor 32, then xor 16
-    #pragma unroll
-                    for (int o = 8; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-                    return s;
-                };
-                const float s0 = tree(p0[u]);
-                float d;
-                if (a.space == SP_L2) d = sqrtf(s0);
-                else if (a.space == SP_NEGDOT) d = -s0;
-                else {
-                    const float sim = normdot_finish(s0, tree(p1[u]), tree(p2[u]));
-                    d = a.space == SP_ANGULAR ? acosf(sim) : fmaxf(0.0f, 1.0f - sim);
-                }
+                const float d = rerank_chain_finish<SPACE>(p0[u], p1[u], p2[u]);
                 const int j = j0 + 4 * u + rg;
+                if (ext_early && sub == 0 && j < total) s_ext[j] = ((u64)(uint32_t)ext[u] << 32) | pos[u];
                 if (sub == 0 && j < total) keys[j] = ((u64)f32_ord(d) << 32) | pos[u];
             }
         }
@@ -2785,25 +2795,25 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
             const float qn2 = s_qn2, qn = sqrtf(qn2);
             const float dk = ord_f32((uint32_t)(keys[found - 1] >> 32));
             float sk, e, extra = 0.f;
-            if (a.qaux) {
+            if constexpr (COSC) {
                 // centred cosine / angular: the score is -(1 - cos)|q|, the inner product of the augmented vectors (qn, bmax:
                 // theirs).  Beyond the scan's error: the f32 rounding of the augmented columns (2^-22 of the sum of the
                 // products' magnitudes) and of the reference formula itself -- its similarity carries a few ulp of 1.0, and the
                 // proof is about the distances the reference computes: 2e-6 |q| in score units.
                 const float sh = sinf(0.5f * dk);
-                const float omc = a.space == SP_ANGULAR ? 2.0f * sh * sh : dk;
+                const float omc = SPACE == SP_ANGULAR ? 2.0f * sh * sh : dk;
                 const float qnorm = a.qaux[(size_t)q * 4 + 2];
                 sk = -omc * qnorm;
                 e = 6.1036e-5f * qn * a.bmax;
                 extra = 1e-6f * qn * a.bmax + 2e-6f * qnorm;
-            } else if (a.space == SP_L2) {
+            } else if constexpr (SPACE == SP_L2) {
                 sk = 0.5f * (qn2 - dk * dk);
                 e = 6.1036e-5f * qn * a.bmax;
-            } else if (a.space == SP_NEGDOT) {
+            } else if constexpr (SPACE == SP_NEGDOT) {
                 sk = -dk;
                 e = 6.1036e-5f * qn * a.bmax;
             } else {  // cosine / angular: score = q.b / |b| = similarity * |q|
-                sk = (a.space == SP_ANGULAR ? cosf(dk) : 1.0f - dk) * qn;
+                sk = (SPACE == SP_ANGULAR ? cosf(dk) : 1.0f - dk) * qn;
                 e = 6.1036e-5f * qn;
             }
             const float t = fmaxf(s_thr, s_cut);
@@ -2824,7 +2834,14 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
         if (i < found) {
             const u64 key = keys[i];
             const uint32_t pos = (uint32_t)key;
-            id = a.ext_ids ? a.ext_ids[pos] : (int32_t)pos;
+            if (ext_early) {   // (fetched rows are distinct positions: exactly one slot holds this one)
+                for (int j = 0; j < total; ++j) {
+                    const u64 pe = s_ext[j];
+                    if ((uint32_t)pe == pos) id = (int32_t)(uint32_t)(pe >> 32);
+                }
+            } else {
+                id = a.ext_ids ? a.ext_ids[pos] : (int32_t)pos;
+            }
             d = ord_f32((uint32_t)(key >> 32));
         }
         a.out_ids[(size_t)q * a.k + i] = id;
@@ -3938,6 +3955,52 @@ static void dump_rerank_list_clocks(const unsigned long long* d_prof, hipStream_
             h[1] / wg / 100, h[2] / wg / 100, h[3] / wg / 100, h[4] / wg / 100, h[5] / wg / 100);
 }
 
+// the list re-rank's instantiation for an index: score family, centred form (qaux), row-length class
+using RerankListF32Fn = void (*)(RerankListF32Args);
+template <bool LONG>
+static RerankListF32Fn rerank_list_f32_rows(int space, bool cosc) {
+    if (space == SP_L2) return bf_rerank_f32_list_kernel<SP_L2, false, LONG>;
+    if (space == SP_NEGDOT) return bf_rerank_f32_list_kernel<SP_NEGDOT, false, LONG>;
+    if (space == SP_ANGULAR)
+        return cosc ? bf_rerank_f32_list_kernel<SP_ANGULAR, true, LONG> : bf_rerank_f32_list_kernel<SP_ANGULAR, false, LONG>;
+    return cosc ? bf_rerank_f32_list_kernel<SP_COSINE, true, LONG> : bf_rerank_f32_list_kernel<SP_COSINE, false, LONG>;
+}
+static RerankListF32Fn rerank_list_f32_instance(int space, bool cosc, bool long_rows) {
+    return long_rows ? rerank_list_f32_rows<true>(space, cosc) : rerank_list_f32_rows<false>(space, cosc);
+}
+
+// NMSLIB_GPU_DEBUG & 4096: how many of the list re-rank's workgroups a CU holds (asked of the runtime once per
+// instantiation and LDS size) and how many rounds of resident workgroups the batch therefore takes
+static void dump_rerank_list_residency(RerankListF32Fn fn, size_t lds, int nq) {
+    struct Seen {
+        RerankListF32Fn fn;
+        size_t lds;
+        int per_cu, cus;
+    };
+    static std::mutex mu;
+    static std::vector<Seen> seen;
+    std::lock_guard<std::mutex> lock(mu);
+    const Seen* hit = nullptr;
+    for (const Seen& c : seen)
+        if (c.fn == fn && c.lds == lds) hit = &c;
+    if (!hit) {
+        Seen c{fn, lds, 0, 0};
+        int dev = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&c.per_cu, reinterpret_cast<const void*>(fn), 256, lds) != hipSuccess ||
+            hipGetDevice(&dev) != hipSuccess ||
+            hipDeviceGetAttribute(&c.cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) {
+            (void)hipGetLastError();
+            fprintf(stderr, "[rerank f32 list] residency: the runtime did not answer\n");
+            return;
+        }
+        seen.push_back(c);
+        hit = &seen.back();
+    }
+    const long long resident = (long long)hit->per_cu * hit->cus;
+    fprintf(stderr, "[rerank f32 list] resident workgroups per CU %d x %d CUs = %lld, batch of %d: %lld round(s)\n", hit->per_cu,
+            hit->cus, resident, nq, resident > 0 ? (nq + resident - 1) / resident : 0);
+}
+
 // NMSLIB_GPU_DEBUG & 2048: checksums of the intermediate buffers of this batch (determinism screens)
 static void dump_f32_fast_checksums(const BfF32Fast& f, const BfFastWs& ws, hipStream_t s) {
     (void)hipStreamSynchronize(s);
@@ -4106,13 +4169,16 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
         (void)hipMemsetAsync(d_prof, 0, 16 * 8, s);
         r.prof = d_prof;
     }
-    e = hipFuncSetAttribute(reinterpret_cast<const void*>(bf_rerank_f32_list_kernel),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_rerank);
+    const RerankListF32Fn rerank = rerank_list_f32_instance(space, r.qaux != nullptr, rows.dim > 128);
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(rerank), hipFuncAttributeMaxDynamicSharedMemorySize, (int)f.lds_rerank);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(bf_rerank_f32_list_kernel, dim3(nq), dim3(256), f.lds_rerank, s, r);
+    hipLaunchKernelGGL(rerank, dim3(nq), dim3(256), f.lds_rerank, s, r);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
-    if (dbg & 4096) dump_rerank_list_clocks(d_prof, s);
+    if (dbg & 4096) {
+        dump_rerank_list_clocks(d_prof, s);
+        dump_rerank_list_residency(rerank, f.lds_rerank, nq);
+    }
     if (dbg & 2048) dump_f32_fast_checksums(f, ws, s);
     // 4. fallback: the adaptive f32 kernel + its re-rank (verified for l2, with its exact tail) for flagged query tiles
     //    (256 * qg queries = 2 * qg of its tiles)
