@@ -144,6 +144,31 @@ nmslib_error_t nmslib_gpu_delete_ids(nmslib_index_handle_t index, const int32_t*
 /* Rows of this index that are marked deleted. */
 nmslib_error_t nmslib_gpu_deleted_rows(nmslib_index_handle_t index, size_t* count);
 
+/* Consolidate: the rows marked by nmslib_gpu_delete_ids leave the
+ * index.  *removed (optional) = rows dropped, *repaired (optional) = (node, level) adjacency lists that were rewritten.
+ *   Positions move.  Live rows keep their relative order; the new position of a row is its rank among the live rows.
+ *   nmslib_data_qty becomes the live count; nmslib_get_data_point*, nmslib_borrow_data_dense and nmslib_get_distance
+ *   address the new positions.  External ids do not change.  nmslib_gpu_deleted_rows is 0 afterwards, nmslib_save_index
+ *   works again, and a later nmslib_gpu_delete_ids works on the new positions.
+ *   No marked row: NMSLIB_SUCCESS, *removed = *repaired = 0, nothing is launched and nothing changes.
+ *   Every row marked: rows and marks go as with nmslib_reset_index, the index parameters stay; *removed = the row count.
+ * hnsw with a resident graph (the index has been on the GPU; built in this process by either builder, any `post`,
+ * gpu_rows=f16 included): every list of a live node that holds a deleted node keeps its live entries and is filled up to
+ * its old length from the live neighbours of its deleted entries (one hop, the closest max(efConstruction, maxM0) <= 1024
+ * of them, the graph's selection test); then rows, ids, norms, the fp16 copy and all lists are compacted in HBM and the
+ * marks are released.  No row and no list crosses PCIe.  Searches afterwards run as on an index that never had a deleted
+ * row: no filter, counts of k, and with gpu_append=1 later rows are appended.  Rows added since the last use are put into
+ * the graph first, as a query would do.
+ * hnsw without a resident graph (gpu_defer=1 before the first use, or no device), brute_force and seq_search: the host
+ * rows, ids and marks are compacted and the index is built / prepared again at its next use: it is then the index of the
+ * live rows alone.
+ * The call is ordered behind the index's earlier work on whatever stream and returns when the device work is done: it is
+ * a maintenance call and may block.
+ * Sparse, string and divergence indexes, gpu_shards > 1, a graph loaded from a file, delaunay_type=3 and lists wider than
+ * the GPU builder's (M or maxM > 127, maxM0 > 254) -> NMSLIB_ERROR_SPACE_INCOMPATIBLE, also when no row is marked: the
+ * refusal is decided first, as in nmslib_gpu_delete_ids.  NULL handle -> NMSLIB_ERROR_NULL_POINTER. */
+nmslib_error_t nmslib_gpu_consolidate(nmslib_index_handle_t index, size_t* removed, size_t* repaired);
+
 #ifdef __cplusplus
 }
 #endif

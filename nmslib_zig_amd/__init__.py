@@ -178,6 +178,7 @@ def lib():
         "nmslib_gpu_graph_builder": (C.c_int, [vp, C.POINTER(C.c_int)]),
         "nmslib_gpu_delete_ids": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
         "nmslib_gpu_deleted_rows": (C.c_int, [vp, C.POINTER(sz)]),
+        "nmslib_gpu_consolidate": (C.c_int, [vp, C.POINTER(sz), C.POINTER(sz)]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)   # AttributeError here = a declared symbol is not exported
@@ -205,7 +206,7 @@ ABI_SYMBOLS_GPU = ["nmslib_gpu_device_count", "nmslib_gpu_finalize",
                    "nmslib_gpu_knn_query_batch_device", "nmslib_gpu_last_batch_counters",
                    "nmslib_gpu_merge_topk", "nmslib_gpu_merge_topk_strided", "nmslib_gpu_get_stats", "nmslib_gpu_kernel_timing",
                    "nmslib_gpu_string_hnsw_links", "nmslib_gpu_graph_builder", "nmslib_gpu_delete_ids",
-                   "nmslib_gpu_deleted_rows"]
+                   "nmslib_gpu_deleted_rows", "nmslib_gpu_consolidate"]
 
 
 class TrackingAllocator:
@@ -543,6 +544,16 @@ class Index:
         n = C.c_size_t()
         _check(lib().nmslib_gpu_deleted_rows(self.h, C.byref(n)), self.alloc)
         return n.value
+
+    def consolidate(self):
+        """nmslib_gpu_consolidate: the rows marked by deleteIds leave the index -> (rows removed, adjacency lists rewritten).
+        Positions move: a live row's new position is its rank among the live rows; ids do not change.  A resident hnsw
+        graph is repaired around the deleted nodes and compacted on the GPU (no filter and counts of k afterwards, save()
+        works again); without a resident graph, and for brute_force / seq_search, the host side is compacted and the index
+        is built / prepared again at its next use.  Blocks until the device is done."""
+        removed, repaired = C.c_size_t(), C.c_size_t()
+        _check(lib().nmslib_gpu_consolidate(self.h, C.byref(removed), C.byref(repaired)), self.alloc)
+        return removed.value, repaired.value
 
     # -- metadata / stored data -------------------------------------------------------------------
     def getDistance(self, a, b):

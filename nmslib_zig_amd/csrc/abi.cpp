@@ -895,6 +895,17 @@ nmslib_error_t nmslib_gpu_deleted_rows(nmslib_index_handle_t handle, size_t* cou
     return NMSLIB_SUCCESS;
 }
 
+nmslib_error_t nmslib_gpu_consolidate(nmslib_index_handle_t handle, size_t* removed, size_t* repaired) {
+    if (removed) *removed = 0;
+    if (repaired) *repaired = 0;
+    if (!handle) FAIL(NMSLIB_ERROR_NULL_POINTER, "Invalid index");
+    return guarded(NMSLIB_ERROR_RUNTIME, "Failed to consolidate", [&] {
+        Engine* e = H(handle)->engine;
+        std::lock_guard<std::mutex> lk(e->mu);
+        e->consolidate(removed, repaired);
+    });
+}
+
 nmslib_error_t nmslib_gpu_string_hnsw_links(nmslib_index_handle_t index, size_t node, int level, int32_t* out,
                                             size_t capacity, size_t* count, int* enterpoint, int* maxlevel) {
     if (!index || !count || !enterpoint || !maxlevel || node >= nmslib_data_qty(index) || level < 0)

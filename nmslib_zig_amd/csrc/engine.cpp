@@ -423,6 +423,7 @@ void Engine::reset() {
     graph_builder_ = 0;
     built_n_ = 0;
     host_links_stale_ = false;
+    save_resident_rows_ = false;
     rows_appended = rows_uploaded = 0;
     created_ = false;
     dirty_ = true;
@@ -546,6 +547,7 @@ void Engine::create_index(const std::vector<std::string>& params) {
     graph_builder_ = 0;
     built_n_ = 0;
     host_links_stale_ = false;
+    save_resident_rows_ = false;
     if (!ids_.empty()) {
         if (defer) ensure_graph();
         else finalize();
@@ -707,6 +709,7 @@ void Engine::build_graph() {
         graph_builder_ = 1;
         built_n_ = 0;
         host_links_stale_ = false;
+        save_resident_rows_ = false;
     }
     build_seconds = std::chrono::duration<double>(clk::now() - t0).count();
 }
@@ -1612,16 +1615,18 @@ void Engine::save(const std::string& path, bool save_data) {
         wr(out, (int32_t)dist_func);
         wr(out, (uint64_t)3);    // searchMethod_
         std::vector<char> rec(mem_per_obj);
-        std::vector<float> row(dim_);
+        std::vector<float> row(dim_), resident;
+        const bool from_device = fetch_resident_rows(resident);  // (a consolidated cosine graph: normalised already)
         for (size_t i = 0; i < n; ++i) {
             const int32_t id = ids_[i], label = -1;
             const uint64_t dl = dim_ * 4;
             std::memcpy(&rec[0], &id, 4);
             std::memcpy(&rec[4], &label, 4);
             std::memcpy(&rec[8], &dl, 8);
-            const float* src = (loaded_graph_ && !graph_rows_.empty()) ? &graph_rows_[i * dim_] : &rows_f32_[i * dim_];
+            const float* src = from_device ? &resident[i * dim_]
+                               : (loaded_graph_ && !graph_rows_.empty()) ? &graph_rows_[i * dim_] : &rows_f32_[i * dim_];
             std::memcpy(row.data(), src, dim_ * 4);
-            if (space_ == SP_COSINE && !(loaded_graph_ && !graph_rows_.empty())) {
+            if (space_ == SP_COSINE && !from_device && !(loaded_graph_ && !graph_rows_.empty())) {
                 float s = 0;  // NormalizeVect, hnsw.h:486-497
                 for (size_t d = 0; d < dim_; ++d) s += row[d] * row[d];
                 if (s != 0.0f) {

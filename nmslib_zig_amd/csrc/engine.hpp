@@ -216,6 +216,11 @@ class Engine {
     // bitset follows at once and the results are filtered; exact scan: the index is prepared again without the rows.
     size_t delete_ids(const int32_t* ids, size_t count);
     size_t deleted_rows() const { return n_dead_; }
+    // nmslib_gpu_consolidate (hnsw_consolidate.cpp): the marked rows leave the index and positions move
+    // (a live row's new position is its rank among the live rows).  A resident HNSW graph is repaired around the deleted
+    // nodes and compacted on the device; anything else compacts its host side and is built / prepared again at its next
+    // use.  removed / repaired (optional): rows dropped, (node, level) lists rewritten.  Returns when the device is done.
+    void consolidate(size_t* removed, size_t* repaired);
 
     // ---- sparse vectors (data type 1; sparse.cpp) ----
     bool is_sparse() const { return sparse_; }
@@ -366,6 +371,10 @@ class Engine {
     void finalize_index();                        // finalize() without the tombstones' upload
     bool is_dead(size_t pos) const { return (pos >> 5) < tomb_.size() && ((tomb_[pos >> 5] >> (pos & 31)) & 1u); }
     void upload_tombstones();                     // the bitset of all size() rows -> d_tomb_, ordered behind the index's work
+    // consolidate: host rows and ids at newpos (-1: dropped), marks cleared; the all-rows-marked case; the resident graph
+    void compact_host_rows(const std::vector<int32_t>& newpos, size_t live);
+    void drop_all_rows();
+    void consolidate_resident(const std::vector<int32_t>& newpos, size_t live, size_t& repaired);
     void upload_rows(size_t first = 0);           // rows [first, n); first > 0 keeps what is resident
     void build_graph();
     bool use_gpu_build() const;
@@ -377,7 +386,10 @@ class Engine {
     void download_graph_links();
     bool can_append() const;
     bool append_rows_gpu();   // gpu_append=1; false: a buffer could not grow, take the full path
-    void sync_host_graph();   // the lists of graph_ follow the device's after an append (read by save)
+    void sync_host_graph();   // the lists of graph_ follow the device's after an append or a consolidate (read by save)
+    // cosine on the optimized index after a consolidate: the normalised rows as the device holds them, [n][dim]; false: the
+    // file writer normalises the host rows itself, as it always did
+    bool fetch_resident_rows(std::vector<float>& rows);
     void pack_rows16(size_t first, size_t n, int e);  // rows [first, n) of the fp16 copy at scale 2^e
     void prepare_graph_rows(size_t first = 0);
     void upload_graph();
@@ -453,9 +465,11 @@ class Engine {
     bool graph_dirty_ = true;    // rows added since the graph was last built
     bool loaded_graph_ = false;  // graph came from a file: never rebuild it
     int graph_builder_ = 0;      // who built graph_: 0 nobody (no graph yet, or loaded), 1 the host builder, 2 the GPU builder
-    size_t graph_up_ints_ = 0;   // ints of the upper-level lists of the graph on the device (GPU builder)
-    size_t built_n_ = 0;         // rows the GPU builder's resident graph covers (0: none, or it was not completed)
-    bool host_links_stale_ = false;  // an append changed the lists on the device; graph_.links0 / up_links are behind
+    size_t graph_up_ints_ = 0;   // ints of the upper-level lists of the graph on the device (GPU builder, consolidate)
+    size_t built_n_ = 0;         // rows the GPU builder's resident graph covers (0: none, or it was not completed); after a
+                                 // consolidate: the rows of the compacted graph, whoever built it
+    bool save_resident_rows_ = false;  // a consolidate compacted the resident graph: the index file gets the device's normalised rows
+    bool host_links_stale_ = false;  // an append or a consolidate changed the lists on the device; graph_.links0 / up_links are behind
     HnswBuildParams bp_;
     HostGraph graph_;
     std::vector<float> graph_rows_;  // rows as stored inside a loaded index (cosine: normalised)

@@ -75,6 +75,7 @@ void Engine::build_graph_gpu() {
     graph_builder_ = 2;
     built_n_ = 0;  // (set again below: a build that throws leaves no graph to append to)
     host_links_stale_ = false;
+    save_resident_rows_ = false;
     const bool post = bp_.post != 0 && n > 1;
     const std::vector<int32_t> draws = hnsw_random_levels(post ? 2 * n : n, bp_);
     build_graph_gpu_pass(std::vector<int32_t>(draws.begin(), draws.begin() + (ptrdiff_t)n), false);
@@ -316,12 +317,13 @@ bool Engine::append_rows_gpu() {
     return true;
 }
 
-// After an append the adjacency lists of graph_ are behind the device's (old nodes got new links too); the file writer
-// reads them, so they are fetched when it asks.
+// After an append the adjacency lists of graph_ are behind the device's (old nodes got new links too), after a consolidate
+// (hnsw_consolidate.cpp; a host-built graph too) the host has none at all; the file writer reads them, so they are fetched
+// when it asks.
 void Engine::sync_host_graph() {
     if (!host_links_stale_) return;
     host_links_stale_ = false;
-    if (graph_builder_ != 2 || built_n_ != (size_t)graph_.n) return;  // (graph_ is no longer the appended graph)
+    if (built_n_ != (size_t)graph_.n) return;  // (graph_ is no longer the graph on the device)
     check_device();
     download_graph_links();
 }

@@ -484,6 +484,35 @@ hipError_t launch_hnsw_build_post(const HnswDeviceGraph& g, const int32_t* secon
 // lists of stride sstride copied into lists of stride dstride (unused slots 0)
 hipError_t launch_hnsw_build_repack(const int32_t* src, int sstride, int32_t* dst, int dstride, int n, hipStream_t s);
 
+// ---- consolidating a graph with deleted rows (hnsw_consolidate_kernels.hip) ----
+struct HnswConsolidate {
+    HnswDeviceGraph g;           // the resident graph over all n rows, deleted ones included
+    int32_t* links0;             // same memory as g.links0 / g.up_links, non-const: lists are repaired in place
+    int32_t* up_links;
+    const uint32_t* tomb;        // bit = position, [ceil(n / 32)] words
+    const int32_t* levels;       // [n]
+    int delaunay, P;             // selection (0, 1, 2); candidates kept per list (1 .. 1024)
+    unsigned long long* ndist;   // optional (device): the repair adds its distance evaluations (rows fetched) to it
+};
+// Every (node, level) list of a live node that holds a deleted entry -> work [work_cap][2] (node, level), in any order;
+// *nwork (cleared by the caller) counts them.
+hipError_t launch_hnsw_cons_worklist(const HnswConsolidate& c, int32_t* work, int work_cap, int32_t* nwork, hipStream_t s);
+// One wave per worklist entry: the list keeps its live entries and is filled up to its old length from the live
+// neighbours of its deleted entries (the P closest, by (distance, position); delaunay 2 and 1: a candidate is taken unless
+// a kept node is strictly closer to it than the list's node; 1: then the closest rejected ones; 0: the closest).  In place.
+hipError_t launch_hnsw_cons_repair(const HnswConsolidate& c, const int32_t* work, int nwork, hipStream_t s);
+// Rows of row_bytes (a multiple of 4) each: row r of src goes to row newpos[r] of dst unless its tombstone bit is set.
+hipError_t launch_hnsw_cons_scatter_rows(const void* src, void* dst, size_t row_bytes, int n, const uint32_t* tomb,
+                                         const int32_t* newpos, hipStream_t s);
+// The same for level-0 lists of `stride` ints (count, entries): entries are renumbered by newpos, unused slots become 0.
+hipError_t launch_hnsw_cons_links0(const int32_t* src, int32_t* dst, int stride, int n, const uint32_t* tomb,
+                                   const int32_t* newpos, hipStream_t s);
+// ... and for the upper-level blocks of the nup live nodes listed in up_nodes (old positions): block old_off[u] of
+// levels[u] * (maxM + 1) ints goes to new_off[newpos[u]].
+hipError_t launch_hnsw_cons_up_links(const int32_t* src, const int64_t* old_off, const int32_t* levels, int32_t* dst,
+                                     const int64_t* new_off, const int32_t* up_nodes, int nup, int maxM, int n,
+                                     const int32_t* newpos, hipStream_t s);
+
 // ---- range search on the brute-force index (range_kernels.hip) ----------------------------------
 // dist_ws[r] = the reference's distance of row r to the query, r < n
 hipError_t launch_range_dist(int space, const void* rows, int ld, int n, const void* query_padded, int dim,

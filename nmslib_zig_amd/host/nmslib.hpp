@@ -177,6 +177,13 @@ class Index {
         check(nmslib_gpu_deleted_rows(h_, &n), alloc_, "deletedRows");
         return n;
     }
+    // engine extension: the marked rows leave the index, positions move to the ranks among the live rows, a resident HNSW
+    // graph is repaired and compacted on the GPU -> (rows removed, adjacency lists rewritten)
+    std::pair<size_t, size_t> consolidate() {
+        size_t removed = 0, repaired = 0;
+        check(nmslib_gpu_consolidate(h_, &removed, &repaired), alloc_, "consolidate");
+        return {removed, repaired};
+    }
     std::string getSpaceType() { return str(&nmslib_get_space_type) == "cosinesimil" ? "cosine" : str(&nmslib_get_space_type); }
     std::string getMethod() { return str(&nmslib_get_method); }
     void save(const std::string& path, bool save_data) { check(nmslib_save_index(h_, path.c_str(), save_data), alloc_, "save"); }
