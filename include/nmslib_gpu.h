@@ -95,7 +95,9 @@ typedef struct {
     size_t last_path;      /* selection path of the last brute-force batch: 0 adaptive f32 MFMA, 1 bf16 fast path,
                               2 adaptive int8, 3 int8 fast path; 4 = HNSW; 5 = HNSW with the walk on the fp16 copy
                               of the rows and an f32 re-rank (gpu_rows=f16), and the brute-force scan for k > 512;
-                              6 = l1 fast path (8-bit SAD filter, exact f32 re-rank) */
+                              6 = l1 fast path (8-bit SAD filter, exact f32 re-rank); 7 = HNSW under a filter whose rows
+                              were scanned exactly instead of walked (nmslib_gpu_filter_create).  A filtered batch on an
+                              exact-scan index reports the path it took over the allowed rows */
     /* fast paths, last slice of the last batch (reading them waits for the stream): query tiles in the slice, tiles the
        threshold kernel sent through the split-bf16-product scan instead of the one-product scan (float rows only), and
        tiles whose verification failed and were redone by the adaptive kernel */
@@ -168,6 +170,56 @@ nmslib_error_t nmslib_gpu_deleted_rows(nmslib_index_handle_t index, size_t* coun
  * the GPU builder's (M or maxM > 127, maxM0 > 254) -> NMSLIB_ERROR_SPACE_INCOMPATIBLE, also when no row is marked: the
  * refusal is decided first, as in nmslib_gpu_delete_ids.  NULL handle -> NMSLIB_ERROR_NULL_POINTER. */
 nmslib_error_t nmslib_gpu_consolidate(nmslib_index_handle_t index, size_t* removed, size_t* repaired);
+
+/* Filtered k-NN: a search restricted to the rows a bitset allows.
+ * A filter names POSITIONS (the order in which the rows were added; nmslib_data_qty of them when it is made) and is prepared
+ * on the device once; any number of batches then run under it.  A filtered batch answers as the unfiltered entries do:
+ * external ids, unused slots padded with -1 / +inf, counts reported; no result is a row whose bit is clear or that is deleted.
+ *   nmslib_gpu_filter_create: allow_bits is host memory, one bit per position (bit p & 31 of word p >> 5, the layout of the
+ *     tombstone bitset), allow_words >= ceil(nmslib_data_qty / 32); bits at or beyond the row count are ignored.  scan_rows:
+ *     see "hnsw" below; 0 = default.  The call finalizes a dirty index first, as a query would, and returns when the device
+ *     is done: it is a maintenance call and may block.
+ *   nmslib_gpu_filter_info: rows the filter allows that are not deleted now (0 for a stale filter), and the device memory
+ *     the filter holds.  That memory is reported here only: the index's hbm_bytes and nmslib_index_memory_usage do not
+ *     count it.
+ *   nmslib_gpu_filter_destroy: NULL is a no-op.  Filters belong to their index and are freed with it at the latest; a filter
+ *     handle must not be used after nmslib_index_destroy.  Every entry runs under the index's mutex.
+ * What a filter is: it stays valid as long as positions keep their meaning.  Rows added after it was made are not allowed
+ * (appended with gpu_append=1 or put in by a full rebuild).  Rows deleted after it was made drop out of the results.  A
+ * nmslib_gpu_consolidate that removed at least one row and nmslib_reset_index make it stale: a query with a stale filter, or
+ * with a filter of another index -> NMSLIB_ERROR_INVALID_ARGUMENT, the message says which.
+ * hnsw: a batch runs the search it would run anyway (whichever path: fp16 walk with its re-rank, SearchOld, the HBM-array
+ *   kernel) for k' = max(efSearch, k) results and keeps the first k that are allowed and not deleted, so a count can fall
+ *   below k when few of the rows the search finds are allowed -- as with deleted rows.  A filter that allows
+ *   m <= max(efSearch, k, scan_rows) live rows (m counted when the filter is made; at most 4096) is answered instead by an
+ *   exact scan of those rows: the f32 distances the walk returns for them, ordered by (distance, position), counts of
+ *   min(k, m).  The walk evaluates at least k' distances, the scan m <= k': the rule needs no tuning; scan_rows (<= 4096)
+ *   raises the bound for a caller who has measured.  A scan whose keys and query would not fit into the 160 KB of LDS of a
+ *   workgroup (4096 rows of more than 32 252 dimensions) is left to the walk.  The scan reports ndc = m, hops = hops_up = 0 through
+ *   nmslib_gpu_last_batch_counters, and last_path 7.
+ * brute_force / seq_search: the filter is the index of the allowed live rows alone, gathered and prepared in HBM (no row
+ *   crosses PCIe); a batch takes every path such an index would take.  When the index has been prepared again since (rows
+ *   added or deleted), the next filtered batch gathers and prepares again before it runs and may block; every other batch
+ *   only enqueues.
+ * The device entry keeps the contract of nmslib_gpu_knn_query_batch_device (alignment, order across streams, d_counts may be
+ * NULL); the host entry takes host pointers: ids / dists [query_count][k], counts [query_count] (may be NULL).
+ * Served: hnsw, brute_force and seq_search over l2, l1, linf, cosinesimil, angulardist, negdotprod and l2sqr_sift on one
+ * device.  Sparse, string and divergence indexes and gpu_shards > 1 -> NMSLIB_ERROR_SPACE_INCOMPATIBLE at create, decided
+ * before a device is needed; an exact-scan index that automatic sharding has spread over several devices -> the same code,
+ * at create and for a batch under a filter made before.  A NULL index, out, or allow_bits with rows present -> NMSLIB_ERROR_NULL_POINTER; too few words,
+ * or scan_rows > 4096 -> NMSLIB_ERROR_INVALID_ARGUMENT; no device -> NMSLIB_ERROR_RUNTIME. */
+typedef struct nmslib_gpu_filter* nmslib_gpu_filter_t;
+nmslib_error_t nmslib_gpu_filter_create(nmslib_index_handle_t index, const uint32_t* allow_bits, size_t allow_words,
+                                        size_t scan_rows, nmslib_gpu_filter_t* out);
+void nmslib_gpu_filter_destroy(nmslib_gpu_filter_t f);
+nmslib_error_t nmslib_gpu_filter_info(nmslib_gpu_filter_t f, size_t* allowed_live_rows, size_t* hbm_bytes);
+nmslib_error_t nmslib_gpu_knn_query_batch_filtered(nmslib_index_handle_t index, nmslib_gpu_filter_t f, const void* queries,
+                                                   size_t query_count, size_t elem_count, size_t k, int32_t* ids,
+                                                   float* dists, int32_t* counts);
+nmslib_error_t nmslib_gpu_knn_query_batch_filtered_device(nmslib_index_handle_t index, nmslib_gpu_filter_t f,
+                                                          const void* d_queries, size_t query_count, size_t elem_count,
+                                                          size_t k, int32_t* d_ids, float* d_dists, int32_t* d_counts,
+                                                          void* stream);
 
 #ifdef __cplusplus
 }

@@ -179,6 +179,11 @@ def lib():
         "nmslib_gpu_delete_ids": (C.c_int, [vp, vp, sz, C.POINTER(sz)]),
         "nmslib_gpu_deleted_rows": (C.c_int, [vp, C.POINTER(sz)]),
         "nmslib_gpu_consolidate": (C.c_int, [vp, C.POINTER(sz), C.POINTER(sz)]),
+        "nmslib_gpu_filter_create": (C.c_int, [vp, vp, sz, sz, C.POINTER(vp)]),
+        "nmslib_gpu_filter_destroy": (None, [vp]),
+        "nmslib_gpu_filter_info": (C.c_int, [vp, C.POINTER(sz), C.POINTER(sz)]),
+        "nmslib_gpu_knn_query_batch_filtered": (C.c_int, [vp, vp, vp, sz, sz, sz, vp, vp, vp]),
+        "nmslib_gpu_knn_query_batch_filtered_device": (C.c_int, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)   # AttributeError here = a declared symbol is not exported
@@ -206,7 +211,9 @@ ABI_SYMBOLS_GPU = ["nmslib_gpu_device_count", "nmslib_gpu_finalize",
                    "nmslib_gpu_knn_query_batch_device", "nmslib_gpu_last_batch_counters",
                    "nmslib_gpu_merge_topk", "nmslib_gpu_merge_topk_strided", "nmslib_gpu_get_stats", "nmslib_gpu_kernel_timing",
                    "nmslib_gpu_string_hnsw_links", "nmslib_gpu_graph_builder", "nmslib_gpu_delete_ids",
-                   "nmslib_gpu_deleted_rows", "nmslib_gpu_consolidate"]
+                   "nmslib_gpu_deleted_rows", "nmslib_gpu_consolidate", "nmslib_gpu_filter_create",
+                   "nmslib_gpu_filter_destroy", "nmslib_gpu_filter_info", "nmslib_gpu_knn_query_batch_filtered",
+                   "nmslib_gpu_knn_query_batch_filtered_device"]
 
 
 class TrackingAllocator:
@@ -555,6 +562,41 @@ class Index:
         _check(lib().nmslib_gpu_consolidate(self.h, C.byref(removed), C.byref(repaired)), self.alloc)
         return removed.value, repaired.value
 
+    # -- filtered search (nmslib_gpu_filter_*) ------------------------------------------------------
+    def makeFilter(self, mask, scan_rows=0):
+        """nmslib_gpu_filter_create: a subset of the index's positions, prepared on the GPU -> Filter.  mask: a bool array of
+        length dataQty() (True = allowed), or the bitset itself as uint32 words (bit p & 31 of word p >> 5).  scan_rows
+        (hnsw): a subset of at most max(efSearch, k, scan_rows) rows is scanned exactly instead of walked; 0 = default."""
+        mask = np.asarray(mask)
+        if mask.dtype == np.uint32:
+            words = np.ascontiguousarray(mask).reshape(-1)
+        else:
+            if mask.dtype != np.bool_ or mask.ndim != 1 or mask.size != self.dataQty():
+                raise ValueError("mask: a bool array of length dataQty(), or uint32 words")
+            words = np.packbits(np.ascontiguousarray(mask), bitorder="little")
+            words = np.concatenate([words, np.zeros(-len(words) % 4, np.uint8)]).view("<u4").astype(np.uint32)
+        f = C.c_void_p()
+        _check(lib().nmslib_gpu_filter_create(self.h, words.ctypes.data if words.size else None, words.size, scan_rows,
+                                              C.byref(f)), self.alloc)
+        return Filter(self, f)
+
+    def knnQueryBatchFiltered(self, flt, queries, k):
+        """nmslib_gpu_knn_query_batch_filtered: knnQueryBatch over the rows the filter allows -> ids [Q,k], dists [Q,k],
+        counts [Q].  hnsw: counts can fall below k when few of the rows the search finds are allowed; a filter of at most
+        max(efSearch, k, scan_rows) rows is answered exactly."""
+        q = np.ascontiguousarray(queries, np.uint8 if self.data_type == "DenseUInt8Vector" else np.float32)
+        nq = q.shape[0]
+        ids = np.full((nq, k), -1, np.int32)
+        ds = np.full((nq, k), np.inf, np.float32)
+        cnt = np.zeros(nq, np.int32)
+        _check(lib().nmslib_gpu_knn_query_batch_filtered(self.h, flt.h, q.ctypes.data, nq, q.shape[1], k, ids.ctypes.data,
+                                                         ds.ctypes.data, cnt.ctypes.data), self.alloc)
+        return ids, ds, cnt
+
+    def knn_device_filtered(self, flt, d_queries_ptr, nq, dim, k, d_ids_ptr, d_dists_ptr, d_cnt_ptr=None, stream=None):
+        _check(lib().nmslib_gpu_knn_query_batch_filtered_device(self.h, flt.h, d_queries_ptr, nq, dim, k, d_ids_ptr,
+                                                                d_dists_ptr, d_cnt_ptr, stream), self.alloc)
+
     # -- metadata / stored data -------------------------------------------------------------------
     def getDistance(self, a, b):
         v = C.c_float()
@@ -620,6 +662,43 @@ class Index:
         if getattr(self, "h", None):
             lib().nmslib_index_destroy(self.h)
             self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Filter:
+    """A nmslib_gpu_filter_t of Index.makeFilter.  It belongs to its index and goes with it: close() after the index was
+    closed does nothing."""
+
+    def __init__(self, index, handle):
+        self.index = index
+        self.h = handle
+
+    def _info(self):
+        if not self.h or not self.index.h:
+            raise NmslibError(2, "the filter or its index is closed")
+        a, b = C.c_size_t(), C.c_size_t()
+        _check(lib().nmslib_gpu_filter_info(self.h, C.byref(a), C.byref(b)), self.index.alloc)
+        return a.value, b.value
+
+    @property
+    def allowed(self):
+        """Rows the filter allows that are not deleted now."""
+        return self._info()[0]
+
+    @property
+    def hbm_bytes(self):
+        """Device memory the filter holds (not part of the index's hbm_bytes)."""
+        return self._info()[1]
+
+    def close(self):
+        if self.h and self.index.h:
+            lib().nmslib_gpu_filter_destroy(self.h)
+        self.h = None
 
     def __del__(self):
         try:

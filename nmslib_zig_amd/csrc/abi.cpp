@@ -906,6 +906,77 @@ nmslib_error_t nmslib_gpu_consolidate(nmslib_index_handle_t handle, size_t* remo
     });
 }
 
+// ---- filtered search: a nmslib_gpu_filter_t is a gfxknn::Filter owned by its engine ----
+
+static gfxknn::Filter* F(nmslib_gpu_filter_t f) { return reinterpret_cast<gfxknn::Filter*>(f); }
+
+nmslib_error_t nmslib_gpu_filter_create(nmslib_index_handle_t handle, const uint32_t* allow_bits, size_t allow_words,
+                                        size_t scan_rows, nmslib_gpu_filter_t* out) {
+    if (out) *out = nullptr;
+    if (!handle) FAIL(NMSLIB_ERROR_NULL_POINTER, "Invalid index");
+    if (!out) FAIL(NMSLIB_ERROR_NULL_POINTER, "out is NULL");
+    Engine* e = H(handle)->engine;
+    std::lock_guard<std::mutex> lk(e->mu);
+    if (!allow_bits && e->size() > 0) FAIL(NMSLIB_ERROR_NULL_POINTER, "allow_bits is NULL with rows present");
+    return guarded(NMSLIB_ERROR_RUNTIME, "Failed to create filter", [&] {
+        *out = reinterpret_cast<nmslib_gpu_filter_t>(e->filter_create(allow_bits, allow_words, scan_rows));
+    });
+}
+
+void nmslib_gpu_filter_destroy(nmslib_gpu_filter_t f) {
+    if (!f) return;
+    Engine* e = F(f)->owner;
+    try {
+        std::lock_guard<std::mutex> lk(e->mu);
+        e->filter_destroy(F(f));
+    } catch (const std::exception& x) {
+        SET_LAST(NMSLIB_ERROR_RUNTIME, std::string("Failed to destroy filter: ") + x.what());
+    }
+}
+
+nmslib_error_t nmslib_gpu_filter_info(nmslib_gpu_filter_t f, size_t* allowed_live_rows, size_t* hbm_bytes) {
+    if (!f) FAIL(NMSLIB_ERROR_NULL_POINTER, "Invalid filter");
+    Engine* e = F(f)->owner;
+    return guarded(NMSLIB_ERROR_RUNTIME, "Failed to read the filter", [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        e->filter_info(F(f), allowed_live_rows, hbm_bytes);
+    });
+}
+
+nmslib_error_t nmslib_gpu_knn_query_batch_filtered(nmslib_index_handle_t handle, nmslib_gpu_filter_t f, const void* queries,
+                                                   size_t query_count, size_t elem_count, size_t k, int32_t* ids,
+                                                   float* dists, int32_t* counts) {
+    if (!handle || !f) FAIL(NMSLIB_ERROR_NULL_POINTER, "Invalid index or filter");
+    if (!queries || !ids || !dists || k == 0 || elem_count == 0)
+        FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid filtered batch inputs");
+    Engine* e = H(handle)->engine;
+    return guarded(NMSLIB_ERROR_QUERY_EXECUTION_FAILED, "Filtered KNN batch failed", [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        const int32_t *rid = nullptr, *rcnt = nullptr;
+        const float* rd = nullptr;
+        e->knn_host(queries, query_count, elem_count, k, &rid, &rd, &rcnt, F(f));
+        if (query_count == 0) return;
+        std::memcpy(ids, rid, query_count * k * sizeof(int32_t));
+        std::memcpy(dists, rd, query_count * k * sizeof(float));
+        if (counts) std::memcpy(counts, rcnt, query_count * sizeof(int32_t));
+    });
+}
+
+nmslib_error_t nmslib_gpu_knn_query_batch_filtered_device(nmslib_index_handle_t handle, nmslib_gpu_filter_t f,
+                                                          const void* d_queries, size_t query_count, size_t elem_count,
+                                                          size_t k, int32_t* d_ids, float* d_dists, int32_t* d_counts,
+                                                          void* stream) {
+    if (!handle || !f) FAIL(NMSLIB_ERROR_NULL_POINTER, "Invalid index or filter");
+    if (!d_queries || !d_ids || !d_dists || k == 0 || elem_count == 0)
+        FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid filtered device batch inputs");
+    Engine* e = H(handle)->engine;
+    return guarded(NMSLIB_ERROR_QUERY_EXECUTION_FAILED, "Filtered KNN device batch failed", [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        e->knn_device(d_queries, query_count, elem_count, k, d_ids, d_dists, d_counts, static_cast<hipStream_t>(stream),
+                      F(f));
+    });
+}
+
 nmslib_error_t nmslib_gpu_string_hnsw_links(nmslib_index_handle_t index, size_t node, int level, int32_t* out,
                                             size_t capacity, size_t* count, int* enterpoint, int* maxlevel) {
     if (!index || !count || !enterpoint || !maxlevel || node >= nmslib_data_qty(index) || level < 0)

@@ -410,6 +410,8 @@ void Engine::reset() {
     tomb_.clear();
     n_dead_ = 0;
     d_tomb_.release();
+    d_livepos_.release();
+    ++pos_epoch_;  // (filters of the old rows are stale)
     sp_ptr_.assign(1, 0);
     sp_ids_.clear();
     sp_vals_.clear();
@@ -466,7 +468,7 @@ size_t Engine::hbm_bytes() const {
     size_t sh = 0;
     for (const auto& c : shards_) sh += c->hbm_bytes();
     return sh + d_rows_.bytes() + d_aux_.bytes() + d_ids_.bytes() + d_links0_.bytes() + d_up_off_.bytes() + d_up_links_.bytes() +
-           d_rownorm_.bytes() + d_rows16_.bytes() + d_tomb_.bytes() + brute_.bytes() + d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes() + d_st_ptr_.bytes() + d_st_data_.bytes();
+           d_rownorm_.bytes() + d_rows16_.bytes() + d_tomb_.bytes() + d_livepos_.bytes() + brute_.bytes() + d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes() + d_st_ptr_.bytes() + d_st_data_.bytes();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -642,11 +644,13 @@ void Engine::check_device() {
 void Engine::upload_rows(size_t first) {
     std::vector<float> live_f32;
     std::vector<uint8_t> live_u8;
-    std::vector<int32_t> live_ids;
+    std::vector<int32_t> live_ids, live_pos;
     const bool compact = method_ == Method::Brute && n_dead_ > 0 && !parent_;
+    ++prepared_;
     if (compact) {
         const size_t all = size(), rb = row_bytes();
         live_ids.reserve(all - n_dead_);
+        live_pos.reserve(all - n_dead_);
         if (is_u8()) live_u8.resize((all - n_dead_) * rb);
         else live_f32.resize((all - n_dead_) * dim_);
         char* dst = is_u8() ? reinterpret_cast<char*>(live_u8.data()) : reinterpret_cast<char*>(live_f32.data());
@@ -654,6 +658,7 @@ void Engine::upload_rows(size_t first) {
             if (is_dead(i)) continue;
             std::memcpy(dst + live_ids.size() * rb, host_row(i), rb);
             live_ids.push_back(ids_[i]);
+            live_pos.push_back((int32_t)i);
         }
     }
     const size_t n = compact ? live_ids.size() : size(), added = n - first;
@@ -694,6 +699,13 @@ void Engine::upload_rows(size_t first) {
             hip_check(hipMemcpy(d_ids_.as<int32_t>() + first, pos.data(), added * 4, hipMemcpyHostToDevice), "upload positions");
     } else if (added) {
         hip_check(hipMemcpy(d_ids_.as<int32_t>() + first, src_ids + first, added * 4, hipMemcpyHostToDevice), "upload ids");
+    }
+    // the resident rows' positions (one int32 each), for a filter's compaction: a filter names positions
+    if (compact && n) {
+        d_livepos_.ensure(n * 4);
+        hip_check(hipMemcpy(d_livepos_.ptr(), live_pos.data(), n * 4, hipMemcpyHostToDevice), "upload positions");
+    } else {
+        d_livepos_.release();
     }
     d_n_ = n;
     rows_uploaded = added;
@@ -1054,8 +1066,9 @@ void Engine::knn_sharded(const void* d_queries, size_t nq, size_t elem_count, si
 // Queries
 // ---------------------------------------------------------------------------------------------
 void Engine::knn_device(const void* d_queries, size_t nq, size_t elem_count, size_t k, int32_t* d_ids,
-                        float* d_dists, int32_t* d_cnt, hipStream_t stream) {
+                        float* d_dists, int32_t* d_cnt, hipStream_t stream, Filter* f) {
     if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
+    if (f) check_filter(f);
     if (diverg_)
         throw EngineError(Err::SpaceIncompatible, "the device-resident batch is not served over a divergence space: a "
                                                   "query's logarithms are taken on the host, so divergence queries "
@@ -1067,6 +1080,7 @@ void Engine::knn_device(const void* d_queries, size_t nq, size_t elem_count, siz
     if (sparse_ || str_space_)
         throw EngineError(Err::SpaceIncompatible, "the device-resident batch takes dense queries; sparse and string "
                                                   "queries go through nmslib_knn_query_batch");
+    if (f) filter_begin_batch(*f);
     order_after_last(stream);   // (row shards: the parent's stream; every child keeps to its own)
     if (!shards_.empty()) {
         if (size() > 0 && elem_count != dim_)
@@ -1092,7 +1106,8 @@ void Engine::knn_device(const void* d_queries, size_t nq, size_t elem_count, siz
         ctr_off_ = q0;
         const void* qs = static_cast<const char*>(d_queries) + q0 * qbytes;
         int32_t* cnt = d_cnt ? d_cnt + q0 : nullptr;
-        if (method_ == Method::Brute) knn_brute(qs, m, k, d_ids + q0 * k, d_dists + q0 * k, cnt, stream);
+        if (f) knn_filtered_slice(*f, qs, m, k, d_ids + q0 * k, d_dists + q0 * k, cnt, stream);
+        else if (method_ == Method::Brute) knn_brute(qs, m, k, d_ids + q0 * k, d_dists + q0 * k, cnt, stream);
         else knn_hnsw(qs, m, k, d_ids + q0 * k, d_dists + q0 * k, cnt, stream);
     }
 }
@@ -1395,8 +1410,9 @@ static void check_diverg_query_length(size_t elem_count, size_t dim) {
 }
 
 void Engine::knn_host(const void* queries, size_t nq, size_t elem_count, size_t k, const int32_t** ids, const float** dists,
-                      const int32_t** cnt) {
+                      const int32_t** cnt, Filter* f) {
     if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
+    if (f) check_filter(f);  // (refused before the index is finalized for it)
     if (diverg_ && !ids_.empty()) check_diverg_query_length(elem_count, dim_);  // refused before any device work
     if (dirty_) finalize();
     check_device();
@@ -1412,7 +1428,7 @@ void Engine::knn_host(const void* queries, size_t nq, size_t elem_count, size_t 
     std::memcpy(hp, queries, qbytes);
     order_after_last(stream_);
     hip_check(hipMemcpyAsync(ws_q_.ptr(), hp, qbytes, hipMemcpyHostToDevice, stream_), "queries H2D");
-    knn_device(ws_q_.ptr(), nq, elem_count, k, out.ids, out.dists, out.cnt, stream_);
+    knn_device(ws_q_.ptr(), nq, elem_count, k, out.ids, out.dists, out.cnt, stream_, f);
     fetch_results(nq, k, "knn", ids, dists, cnt);
 }
 

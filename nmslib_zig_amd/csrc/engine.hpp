@@ -187,6 +187,8 @@ struct SparseElem {
     float value;
 };
 
+struct Filter;  // filtered search, below the engine
+
 class Engine {
    public:
     // space_params: the space factory's parameters ("p" of lp_sparse); the dense factories ignore theirs
@@ -221,6 +223,14 @@ class Engine {
     // nodes and compacted on the device; anything else compacts its host side and is built / prepared again at its next
     // use.  removed / repaired (optional): rows dropped, (node, level) lists rewritten.  Returns when the device is done.
     void consolidate(size_t* removed, size_t* repaired);
+
+    // ---- filtered search (nmslib_gpu_filter_*; filter.cpp) ----
+    // bits: one bit per position, `words` words of host memory.  Finalizes a dirty index, may block.  The filter belongs to
+    // this engine and goes with it.
+    Filter* filter_create(const uint32_t* bits, size_t words, size_t scan_rows);
+    void filter_destroy(Filter* f);
+    void filter_info(const Filter* f, size_t* allowed_live_rows, size_t* hbm_bytes) const;
+    // a filtered batch is knn_device / knn_host with the filter as their last argument
 
     // ---- sparse vectors (data type 1; sparse.cpp) ----
     bool is_sparse() const { return sparse_; }
@@ -261,12 +271,13 @@ class Engine {
     bool index_created() const { return created_; }
     void finalize();  // upload + build if dirty (nmslib_initialize_pool / lazy)
 
-    // k-NN: device-resident batch (the hot entry) and host convenience wrapper
+    // k-NN: device-resident batch (the hot entry) and host convenience wrapper.  f (optional): a filter of this index, the
+    // batch then runs over the rows it allows (filter.cpp)
     void knn_device(const void* d_queries, size_t nq, size_t elem_count, size_t k, int32_t* d_ids,
-                    float* d_dists, int32_t* d_cnt, hipStream_t stream);
+                    float* d_dists, int32_t* d_cnt, hipStream_t stream, Filter* f = nullptr);
     // host buffers in, results in this engine's pinned staging block (valid until the next call; the caller holds `mu`)
     void knn_host(const void* queries, size_t nq, size_t elem_count, size_t k, const int32_t** ids, const float** dists,
-                  const int32_t** cnt);
+                  const int32_t** cnt, Filter* f = nullptr);
     float pair_distance(size_t p1, size_t p2);
     // RangeQuery on the brute-force index: matches in insertion order, the first `capacity`; returns how many were written
     size_t range_host(const void* query, size_t elem_count, double radius, size_t capacity, int32_t* ids, float* dists);
@@ -370,6 +381,24 @@ class Engine {
     void ensure_graph();
     void finalize_index();                        // finalize() without the tombstones' upload
     bool is_dead(size_t pos) const { return (pos >> 5) < tomb_.size() && ((tomb_[pos >> 5] >> (pos & 31)) & 1u); }
+    // filtered search (filter.cpp)
+    void check_filter_served() const;             // SpaceIncompatible for what filters do not serve (needs no device)
+    void check_filter(const Filter* f) const;     // InvalidArgument: another index's filter, a stale one
+    void filter_compact(Filter& f, const uint32_t* tomb, const int32_t* row_pos, size_t n_rows, DevBuf& list, size_t list_max,
+                        size_t& count);
+    void filter_gather(Filter& f);                // exact scan: f.sub = the index of the allowed live rows
+    // a filtered batch, from knn_device: what has to happen before anything is enqueued (refusals; the exact scan's gather
+    // when the index was prepared again: may block), and one slice of the batch
+    void filter_begin_batch(Filter& f);
+    void knn_filtered_slice(Filter& f, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
+                            hipStream_t stream);
+    void filter_forget_flags(const Filter& f);    // the statistics' pointer into f's child, before its workspaces go
+    void knn_hnsw_filtered(Filter& f, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
+                           int32_t* d_cnt, hipStream_t stream);
+    std::vector<std::unique_ptr<Filter>> filters_;
+    uint64_t pos_epoch_ = 0;     // counts what moves positions: a consolidate that removed a row, a reset
+    uint64_t prepared_ = 0;      // counts upload_rows: an exact-scan filter gathered at another count gathers again
+    DevBuf d_livepos_;           // exact scan with deleted rows: the position of every resident row (upload_rows)
     void upload_tombstones();                     // the bitset of all size() rows -> d_tomb_, ordered behind the index's work
     // consolidate: host rows and ids at newpos (-1: dropped), marks cleared; the all-rows-marked case; the resident graph
     void compact_host_rows(const std::vector<int32_t>& newpos, size_t live);
@@ -508,6 +537,22 @@ class Engine {
     std::pair<hipEvent_t, hipEvent_t> prof_pair();  // a new pair of prof_events_ (nulls: not profiling)
     void prof_begin(hipStream_t s);
     void prof_end(hipStream_t s);
+};
+
+// ---- filtered search (filter.cpp): a subset of an index's positions, prepared on the device ----
+struct Filter {
+    Engine* owner = nullptr;
+    uint64_t epoch = 0;     // the owner's position epoch when the filter was made: a consolidate, a reset make it stale
+    size_t n = 0;           // rows of the index when it was made: positions at or beyond n are not allowed
+    size_t scan_rows = 0;   // HNSW: the caller's bound of the subset route (0 = none)
+    std::vector<uint32_t> bits;  // the allow bitset, ceil(n / 32) words, bits at or beyond n clear
+    DevBuf d_allow;         // ... in HBM
+    // HNSW: m = allowed live rows when the filter was made, their ascending positions when m <= HNSW_SUBSET_MAX
+    size_t m = 0;
+    DevBuf d_list;
+    // exact scan: the index of the allowed live rows alone, and the owner's prepare count it was gathered at
+    std::unique_ptr<Engine> sub;
+    uint64_t gathered_at = 0;
 };
 
 }  // namespace gfxknn

@@ -1,0 +1,232 @@
+// Filtered k-NN (nmslib_gpu_filter_*): a filter names a subset of an index's positions by a bitset and is
+// turned, on the device, into what the index kind needs.
+//   exact scan: the index of the allowed live rows alone -- a child engine whose rows and ids are gathered in HBM and
+//               prepared by prepare_brute, so that a filtered batch is knn_brute on it, every path included;
+//   HNSW:       the walk for max(ef, k) results filtered through the bitset and the tombstones, or (filter_plan.hpp) an exact
+//               scan of the listed rows when the subset is no larger than that result array.
+#include <algorithm>
+
+#include "engine.hpp"
+#include "filter_plan.hpp"
+
+namespace gfxknn {
+
+static_assert(kFilterSubsetMax == (size_t)HNSW_SUBSET_MAX, "the routing rule and the kernel name one capacity");
+
+static const char* const kFilterServed =
+    "filtered search is served for hnsw, brute_force and seq_search over the dense spaces (l2, l1, linf, cosinesimil, "
+    "angulardist, negdotprod, l2sqr_sift) on one device";
+
+void Engine::check_filter_served() const {
+    if (sparse_ || str_space_ || diverg_)
+        throw EngineError(Err::SpaceIncompatible, std::string(sparse_ ? "a sparse" : str_space_ ? "a string" : "a divergence") +
+                                                      " index takes no filter: " + kFilterServed);
+    if (gpu_shards_ > 1)
+        throw EngineError(Err::SpaceIncompatible, "an index with gpu_shards=" + std::to_string(gpu_shards_) +
+                                                      " takes no filter: " + kFilterServed);
+}
+
+void Engine::check_filter(const Filter* f) const {
+    if (!f || f->owner != this) throw EngineError(Err::InvalidArgument, "the filter belongs to another index");
+    if (f->epoch != pos_epoch_)
+        throw EngineError(Err::InvalidArgument, "the filter is stale: positions have moved since it was made (a consolidate "
+                                                "that removed rows, or a reset); make a new one");
+}
+
+// The rows the filter takes among n_rows device rows (row r at position row_pos[r], or r), ascending, into `list` when there
+// are at most list_max of them; count = how many.  Waits for the count.
+void Engine::filter_compact(Filter& f, const uint32_t* tomb, const int32_t* row_pos, size_t n_rows, DevBuf& list,
+                            size_t list_max, size_t& count) {
+    const size_t words = (n_rows + 31) / 32;
+    DevBuf mask, prefix, d_count;
+    mask.ensure(std::max<size_t>(words, 1) * 4);
+    prefix.ensure(std::max<size_t>(words, 1) * 4);
+    d_count.ensure(16);
+    hip_check(launch_filter_count(f.d_allow.as<uint32_t>(), (int)f.n, tomb, row_pos, (int)n_rows, mask.as<uint32_t>(),
+                                  prefix.as<int32_t>(), d_count.as<int32_t>(), stream_),
+              "filter count");
+    int32_t c = 0;
+    hip_check(hipMemcpyAsync(&c, d_count.ptr(), 4, hipMemcpyDeviceToHost, stream_), "filter count");
+    hip_check(hipStreamSynchronize(stream_), "filter count");
+    count = (size_t)std::max(c, 0);
+    if (count == 0 || count > list_max) return;
+    list.ensure(count * 4);
+    hip_check(launch_filter_write(mask.as<uint32_t>(), prefix.as<int32_t>(), (int)n_rows, list.as<int32_t>(), stream_),
+              "filter list");
+    hip_check(hipStreamSynchronize(stream_), "filter list");  // (mask and prefix go out of scope)
+}
+
+Filter* Engine::filter_create(const uint32_t* bits, size_t words, size_t scan_rows) {
+    check_filter_served();
+    const size_t n = size(), need = (n + 31) / 32;
+    if (words < need)
+        throw EngineError(Err::InvalidArgument, "allow_words = " + std::to_string(words) + " is fewer than the " +
+                                                    std::to_string(need) + " words that " + std::to_string(n) + " rows take");
+    if (scan_rows > kFilterSubsetMax)
+        throw EngineError(Err::InvalidArgument, "scan_rows = " + std::to_string(scan_rows) + " is beyond the subset scan's " +
+                                                    std::to_string(kFilterSubsetMax) + " rows");
+    if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
+    if (dirty_) finalize();
+    check_device();
+    if (!shards_.empty())
+        throw EngineError(Err::SpaceIncompatible, "an index spread over " + std::to_string(shards_.size()) +
+                                                      " devices takes no filter: " + kFilterServed);
+    std::unique_ptr<Filter> f(new Filter);
+    f->owner = this;
+    f->epoch = pos_epoch_;
+    f->n = n;
+    f->scan_rows = scan_rows;
+    f->bits.assign(bits, bits + need);
+    if (n & 31) f->bits[need - 1] &= (1u << (n & 31)) - 1u;  // bits at or beyond n are ignored
+    f->d_allow.ensure(std::max<size_t>(need, 1) * 4);
+    order_after_last(stream_);
+    hip_check(hipMemcpyAsync(f->d_allow.ptr(), f->bits.data(), need * 4, hipMemcpyHostToDevice, stream_), "filter bits H2D");
+    if (method_ == Method::Brute) {
+        filter_gather(*f);
+    } else {
+        const uint32_t* tomb = n_dead_ > 0 ? d_tomb_.as<uint32_t>() : nullptr;
+        filter_compact(*f, tomb, nullptr, d_n_, f->d_list, kFilterSubsetMax, f->m);
+    }
+    hip_check(hipStreamSynchronize(stream_), "filter");  // (the pageable source of the copy above)
+    filters_.push_back(std::move(f));
+    return filters_.back().get();
+}
+
+void Engine::filter_destroy(Filter* f) {
+    for (auto it = filters_.begin(); it != filters_.end(); ++it)
+        if (it->get() == f) {
+            if (device_ >= 0 && have_last_) {  // a batch in flight may read what is freed here
+                check_device();
+                hip_check(hipStreamSynchronize(last_stream_), "filter destroy");
+            }
+            filter_forget_flags(*f);
+            filters_.erase(it);
+            return;
+        }
+}
+
+void Engine::filter_info(const Filter* f, size_t* allowed_live_rows, size_t* hbm_bytes) const {
+    if (!f || f->owner != this) throw EngineError(Err::InvalidArgument, "the filter belongs to another index");
+    if (allowed_live_rows) {
+        size_t live = 0;
+        for (size_t w = 0; w < f->bits.size(); ++w)
+            live += (size_t)__builtin_popcount(f->bits[w] & ~(w < tomb_.size() ? tomb_[w] : 0u));
+        *allowed_live_rows = f->epoch == pos_epoch_ ? live : 0;
+    }
+    if (hbm_bytes) *hbm_bytes = f->d_allow.bytes() + f->d_list.bytes() + (f->sub ? f->sub->hbm_bytes() : 0);
+}
+
+// Exact scan: the allowed rows among the resident ones (all rows, or the live rows of an index with deleted rows, whose
+// positions upload_rows kept) are listed, their rows and ids gathered in HBM, and the child prepared as finalize prepares an
+// index: centring decision, aux, fast-path tiles, the l1 byte copy.  No row crosses PCIe.  Waits for the device.
+void Engine::filter_gather(Filter& f) {
+    order_after_last(stream_);
+    DevBuf list;
+    size_t m = 0;
+    filter_compact(f, nullptr, d_livepos_.bytes() ? d_livepos_.as<int32_t>() : nullptr, d_n_, list, d_n_, m);
+    if (!f.sub) {
+        f.sub.reset(new Engine(space_name_, method_name_, is_u8() ? 2 : 0, 0));
+        f.sub->method_ = method_;
+        f.sub->created_ = true;
+        f.sub->forced_device_ = device_;
+        f.sub->check_device();
+    }
+    Engine& c = *f.sub;
+    filter_forget_flags(f);  // (the child's workspaces are released below)
+    c.fast_flags_ = nullptr;
+    c.fast_nqt_ = 0;
+    const size_t rb = is_u8() ? 128 : (size_t)ldb_ * 4;
+    c.dim_ = dim_;
+    c.ldb_ = ldb_;
+    c.d_rows_.ensure(std::max<size_t>(m, 1) * rb);
+    c.d_ids_.ensure(std::max<size_t>(m, 1) * 4);
+    hip_check(launch_filter_gather_rows(d_rows_.ptr(), list.as<int32_t>(), (int)m, rb, c.d_rows_.ptr(), stream_), "filter rows");
+    hip_check(launch_filter_gather_ids(d_ids_.as<int32_t>(), list.as<int32_t>(), (int)m, c.d_ids_.as<int32_t>(), stream_),
+              "filter ids");
+    hip_check(hipStreamSynchronize(stream_), "filter gather");  // (`list` goes out of scope; the child prepares on its own stream)
+    c.d_n_ = m;
+    c.dirty_ = false;
+    c.brute_ = BruteDense();
+    c.prepare_brute();
+    f.m = m;
+    f.gathered_at = prepared_;
+}
+
+// A filtered batch (knn_device with a filter), before anything is enqueued.  An index spread over several devices since the
+// filter was made is refused as at create.  The exact scan's index has been prepared again since the gather (an add, a
+// delete): this batch gathers again and waits.
+void Engine::filter_begin_batch(Filter& f) {
+    if (!shards_.empty())
+        throw EngineError(Err::SpaceIncompatible, "an index spread over " + std::to_string(shards_.size()) +
+                                                      " devices takes no filter: " + kFilterServed);
+    if (method_ == Method::Brute && f.gathered_at != prepared_) filter_gather(f);
+}
+
+// One slice of a filtered batch (knn_device's slices and counter workspaces).  Exact scan: knn_brute on the filter's child; the
+// batch is this index's, so its timed intervals, path and fast-path flags are read here.
+void Engine::knn_filtered_slice(Filter& f, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
+                                int32_t* d_cnt, hipStream_t stream) {
+    if (method_ == Method::Hnsw) {
+        knn_hnsw_filtered(f, d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
+        return;
+    }
+    Engine& c = *f.sub;
+    c.prof_ = prof_;
+    c.knn_brute(d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
+    prof_events_.insert(prof_events_.end(), c.prof_events_.begin(), c.prof_events_.end());
+    c.prof_events_.clear();
+    have_counters_ = false;
+    last_path = c.last_path;
+    fast_flags_ = c.fast_flags_;   // (a workspace of the child: filter_forget_flags before it goes)
+    fast_nqt_ = c.fast_nqt_;
+    fast_has_precise_ = c.fast_has_precise_;
+}
+
+// The statistics of the last batch point into the child's workspace when that batch ran under f: they are dropped before the
+// workspace is freed (the filter is destroyed, or its child prepared again), as reset() and the consolidate drop theirs.
+void Engine::filter_forget_flags(const Filter& f) {
+    if (!f.sub || !fast_flags_ || fast_flags_ != f.sub->fast_flags_) return;
+    fast_flags_ = nullptr;
+    fast_nqt_ = 0;
+}
+
+// One slice of a filtered HNSW batch.  Subset route: hnsw_subset_knn_kernel over the filter's list (last_path 7).  Walk route:
+// knn_hnsw_live's two stages with the two-bitset filter behind the walk; the counters are the walk's.
+void Engine::knn_hnsw_filtered(Filter& f, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
+                               int32_t* d_cnt, hipStream_t stream) {
+    const uint32_t* tomb = n_dead_ > 0 ? d_tomb_.as<uint32_t>() : nullptr;
+    if (filter_route(f.m, (size_t)ef_, k, f.scan_rows, hnsw_subset_query_bytes(dg_)) == FilterRoute::Subset) {
+        HnswDeviceGraph g = dg_;
+        g.rows16 = nullptr;  // always the f32 rows: the bits of the f32 walk
+        have_counters_ = true;
+        hnsw_fix_valid_ = false;
+        last_path = 7;
+        prof_begin(stream);
+        hip_check(launch_hnsw_subset_knn(g, (int)nq, (int)k, d_queries, f.d_list.as<int32_t>(), (int)f.m, tomb,
+                                         hnsw_out(d_ids, d_dists, d_cnt, nq), stream),
+                  "hnsw_subset_knn");
+        prof_end(stream);
+        return;
+    }
+    const size_t cap = filter_walk_results((size_t)ef_, k);
+    const size_t slice = std::max<size_t>(1, std::min<size_t>(nq, ((size_t)4 << 30) / (cap * 8)));  // (knn_hnsw_live's budget)
+    const size_t qbytes = dim_ * elem_bytes(), off0 = ctr_off_;
+    const HnswOut out = hnsw_out(d_ids, d_dists, d_cnt, nq);
+    ws_live_ids_.ensure(slice * cap * 4);
+    ws_live_d_.ensure(slice * cap * 4);
+    ws_live_cnt_.ensure(slice * 4);
+    for (size_t q0 = 0; q0 < nq; q0 += slice) {
+        const size_t m = std::min(slice, nq - q0);
+        ctr_off_ = off0 + q0;
+        hnsw_walk(true, static_cast<const char*>(d_queries) + q0 * qbytes, m, cap, ws_live_ids_.as<int32_t>(),
+                  ws_live_d_.as<float>(), ws_live_cnt_.as<int32_t>(), stream);
+        hip_check(launch_hnsw_filter_topk(ws_live_ids_.as<int32_t>(), ws_live_d_.as<float>(), ws_live_cnt_.as<int32_t>(), (int)m,
+                                          (int)cap, f.d_allow.as<uint32_t>(), (int)f.n, tomb, (int)d_n_, dg_.ext_ids, (int)k,
+                                          out.at(q0, k), stream),
+                  "hnsw_filter_topk");
+        prof_end(stream);
+    }
+    ctr_off_ = off0;
+}
+
+}  // namespace gfxknn

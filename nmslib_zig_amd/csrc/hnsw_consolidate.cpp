@@ -41,6 +41,7 @@ void Engine::consolidate(size_t* removed, size_t* repaired) {
                                                           kConsolidateServed);
     }
     if (n_dead_ == 0) return;
+    ++pos_epoch_;  // positions move: filters made before name other rows now (filter.cpp)
     const size_t n = ids_.size(), dead = n_dead_;
     size_t fixed = 0;
     if (dead == n) {

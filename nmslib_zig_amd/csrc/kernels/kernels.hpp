@@ -440,6 +440,35 @@ hipError_t launch_hnsw_search_old(const HnswDeviceGraph& g, const HnswSearchPlan
 hipError_t launch_hnsw_search_big(const HnswDeviceGraph& g, int nq, int k, int ef, const void* queries, uint32_t* bitset,
                                   float* ws_keys, int32_t* ws_idu, const HnswOut& out, hipStream_t s);
 
+// ---- filtered search (filter_kernels.hip) ---------------------------------------
+// the subset-scan kernel's capacity: 32 KB of 64-bit keys, which with the query stays under 64 KB of LDS
+constexpr int HNSW_SUBSET_MAX = 4096;
+// Ordered compaction of a bitset, in two steps (the caller sizes the list from the count in between).
+// Device row r stands at position row_pos[r] (row_pos = nullptr: r itself).  A row is taken when its position is below n_pos,
+// its bit in allow ([ceil(n_pos / 32)] words, bit = position) is set and its bit in tomb (optional; covers every position
+// below n_pos) is clear.  Bits at or beyond n_pos are never read as set, also in the last word.
+// count: mask / prefix [ceil(n_rows / 32)] words each (32 rows per word: who is taken, how many are taken in the words
+// before), *count = rows taken.  write: list[0 .. *count) = the rows taken, ascending.
+hipError_t launch_filter_count(const uint32_t* allow, int n_pos, const uint32_t* tomb, const int32_t* row_pos, int n_rows,
+                               uint32_t* mask, int32_t* prefix, int32_t* count, hipStream_t s);
+hipError_t launch_filter_write(const uint32_t* mask, const int32_t* prefix, int n_rows, int32_t* list, hipStream_t s);
+// dst row i = src row list[i] for i < m; rows of row_bytes bytes (a multiple of 16; both matrices 16-byte aligned)
+hipError_t launch_filter_gather_rows(const void* src, const int32_t* list, int m, size_t row_bytes, void* dst, hipStream_t s);
+// dst[i] = src[list[i]]
+hipError_t launch_filter_gather_ids(const int32_t* src, const int32_t* list, int m, int32_t* dst, hipStream_t s);
+// The result filter of hnsw_live_topk with two bitsets: the first k entries whose position is below n_allow with its bit in
+// allow set and whose bit in tomb (optional, n positions) is clear.
+hipError_t launch_hnsw_filter_topk(const int32_t* cand, const float* cand_d, const int32_t* cand_n, int nq, int cap,
+                                   const uint32_t* allow, int n_allow, const uint32_t* tomb, int n, const int32_t* ext_ids,
+                                   int k, const HnswOut& out, hipStream_t s);
+// Exact k-NN over the m <= HNSW_SUBSET_MAX positions of list (ascending), one workgroup per query: the distances of the f32
+// walk on g.rows (u8 rows: the integer distance), rows with their bit in tomb (optional) set left out, order (distance,
+// position).  out: k results with external ids, -1 / +inf padding, the count; ndc = m, hops = hops_up = 0.
+// the bytes of a staged query: ldv floats, or the 128 bytes of a u8 query (what filter_plan.hpp's LDS arithmetic takes)
+inline size_t hnsw_subset_query_bytes(const HnswDeviceGraph& g) { return g.space == SP_L2SQR_SIFT ? 128 : (size_t)g.ldv * 4; }
+hipError_t launch_hnsw_subset_knn(const HnswDeviceGraph& g, int nq, int k, const void* queries, const int32_t* list, int m,
+                                  const uint32_t* tomb, const HnswOut& out, hipStream_t s);
+
 // ---- HNSW construction on the GPU (hnsw_build_kernels.hip) ------------------------------------
 struct HnswBuildGraph {          // mutable twin of HnswDeviceGraph
     HnswDeviceGraph g;           // rows, links0, up_off, up_links (written by the link kernels)
