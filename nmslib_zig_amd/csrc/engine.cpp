@@ -1442,14 +1442,15 @@ size_t Engine::range_select(bool two_dists, float r, size_t capacity, int32_t* i
     const size_t cnt_elems = range_count_elems(n);
     ws_rdist_.ensure((two_dists ? 2 : 1) * d_n_ * 4);
     ws_rcnt_.ensure(cnt_elems * 4);
+    // no more than d_n_ rows can match: a caller's declared capacity beyond that asks HBM for nothing
+    capacity = std::min<size_t>(capacity, d_n_);
     ws_ids_.ensure(capacity * 4);
     ws_dists_.ensure(capacity * 4);
     float* filter = ws_rdist_.as<float>();
     float* report = two_dists ? filter + d_n_ : filter;
     launch(filter, report);
-    hip_check(launch_range_select(filter, report, n, r, d_ids_.as<int32_t>(), ws_rcnt_.as<int>(),
-                                  (int)std::min<size_t>(capacity, INT32_MAX), ws_ids_.as<int32_t>(),
-                                  ws_dists_.as<float>(), stream_),
+    hip_check(launch_range_select(filter, report, n, r, d_ids_.as<int32_t>(), ws_rcnt_.as<int>(), (int)capacity,
+                                  ws_ids_.as<int32_t>(), ws_dists_.as<float>(), stream_),
               "range select");
     int total = 0;
     hip_check(hipMemcpyAsync(&total, ws_rcnt_.as<int>() + (cnt_elems - 1), 4, hipMemcpyDeviceToHost, stream_),

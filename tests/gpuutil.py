@@ -1,4 +1,6 @@
 """Helpers for the -m gpu tests: every query goes through the C ABI of libnmslib_c.so."""
+import ctypes as C
+
 import numpy as np
 
 import nmslib_zig_amd as nz
@@ -154,6 +156,22 @@ def knn_on_stream(idx, Q, k, stream=None, counts=True, q_off=0, out_off=0, befor
     call = enqueue_knn(idx, Q, k, stream, counts, q_off, out_off, before, after)
     stream.synchronize()
     return call.result()
+
+
+def range_fill_guarded(idx, query, radius, capacity, declared=None):
+    """One nmslib_range_query_fill whose id and distance buffers go on for _GUARD sentinel elements (ID_SENTINEL / NaN, as
+    DeviceCall.result has them) behind their `capacity` elements: a write past the end fails here.  `declared` is what
+    Result.capacity says when it is not the buffers' real size.  -> (ids, dists), the `size` elements the call reports"""
+    q, qsz, ne = idx._query(query)
+    ids = np.full(capacity + _GUARD, ID_SENTINEL, np.int32)
+    ds = np.full(capacity + _GUARD, np.nan, np.float32)
+    r = nz.Result(ids.ctypes.data_as(C.POINTER(C.c_int32)), ds.ctypes.data_as(C.POINTER(C.c_float)), 0,
+                  capacity if declared is None else declared)
+    nz._check(nz.lib().nmslib_range_query_fill(idx.h, q.ctypes.data, qsz, float(radius), C.byref(r), ne), idx.alloc)
+    assert r.size <= capacity, f"size {r.size} beyond the buffer's {capacity} elements"
+    assert (ids[capacity:] == ID_SENTINEL).all(), "ids were written outside the output buffer"
+    assert np.isnan(ds[capacity:]).all(), "distances were written outside the output buffer"
+    return ids[:r.size].copy(), ds[:r.size].copy()
 
 
 def expect_path(idx, code, **more):
