@@ -1095,20 +1095,22 @@ void Engine::knn_device(const void* d_queries, size_t nq, size_t elem_count, siz
     // stay bounded and every slice still fills the chip (the work counters then describe the last slice)
     const size_t slice = method_ == Method::Brute ? 32768 : 65536;
     const size_t qbytes = elem_count * elem_bytes();
-    if (method_ == Method::Hnsw) {  // work counters for the WHOLE batch (slices write at their offset)
-        ws_ndc_.ensure(nq * 4);
-        ws_hops_.ensure(nq * 4);
-        ws_hops_up_.ensure(nq * 4);
-        ws_status_.ensure(nq * 4);
+    HnswOut out{};
+    if (method_ == Method::Hnsw) {  // results and work counters of the WHOLE batch (a slice gets out.at(q0, k))
+        for (DevBuf* b : {&ws_ndc_, &ws_hops_, &ws_hops_up_, &sw_.status}) b->ensure(nq * 4);
+        if (!d_cnt) sw_.outcnt.ensure(nq * 4);  // the counts go to a workspace when the caller asks for none
+        out = {d_ids, d_dists, d_cnt ? d_cnt : sw_.outcnt.as<int32_t>(), ws_ndc_.as<int32_t>(), ws_hops_.as<int32_t>(),
+               ws_hops_up_.as<int32_t>(), sw_.status.as<int32_t>()};
     }
     for (size_t q0 = 0; q0 < nq; q0 += slice) {
         const size_t m = std::min(slice, nq - q0);
-        ctr_off_ = q0;
         const void* qs = static_cast<const char*>(d_queries) + q0 * qbytes;
         int32_t* cnt = d_cnt ? d_cnt + q0 : nullptr;
-        if (f) knn_filtered_slice(*f, qs, m, k, d_ids + q0 * k, d_dists + q0 * k, cnt, stream);
-        else if (method_ == Method::Brute) knn_brute(qs, m, k, d_ids + q0 * k, d_dists + q0 * k, cnt, stream);
-        else knn_hnsw(qs, m, k, d_ids + q0 * k, d_dists + q0 * k, cnt, stream);
+        if (method_ == Method::Hnsw) {
+            if (f) knn_hnsw_filtered(*f, qs, m, k, out.at(q0, k), stream);
+            else knn_hnsw(qs, m, k, out.at(q0, k), stream);
+        } else if (f) knn_filtered_slice(*f, qs, m, k, d_ids + q0 * k, d_dists + q0 * k, cnt, stream);
+        else knn_brute(qs, m, k, d_ids + q0 * k, d_dists + q0 * k, cnt, stream);
     }
 }
 
@@ -1129,217 +1131,6 @@ void Engine::fast_tile_counts(size_t* tiles, size_t* precise, size_t* fallback) 
         *fallback += h[i] != 0;
         if (fast_has_precise_) *precise += h[(size_t)fast_nqt_ + i] != 0;
     }
-}
-
-size_t Engine::hnsw_redone() {
-    if (!shards_.empty()) return shards_[0]->hnsw_redone();
-    if ((last_path != 4 && last_path != 5) || !hnsw_fix_valid_) return 0;
-    int32_t v = 0;
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    hip_check(hipStreamSynchronize(last_stream_ ? last_stream_ : stream_), "stats");
-    hip_check(hipMemcpy(&v, ws_fix_.ptr(), 4, hipMemcpyDeviceToHost), "stats redo count");
-    return (size_t)v;
-}
-
-// The results and work counters of the current slice of a batch (knn_device sets ctr_off_): nq queries from d_ids /
-// d_dists / d_cnt on; the counts go to a workspace when the caller asks for none.
-HnswOut Engine::hnsw_out(int32_t* d_ids, float* d_dists, int32_t* d_cnt, size_t nq) {
-    if (!d_cnt) {
-        ws_outcnt_.ensure(nq * 4);
-        d_cnt = ws_outcnt_.as<int32_t>();
-    }
-    return {d_ids, d_dists, d_cnt, ws_ndc_.as<int32_t>() + ctr_off_, ws_hops_.as<int32_t>() + ctr_off_,
-            ws_hops_up_.as<int32_t>() + ctr_off_, ws_status_.as<int32_t>() + ctr_off_};
-}
-
-// m visited bitsets of `words` words each in ws_bitset_, cleared on the stream
-uint32_t* Engine::cleared_bitset(size_t m, size_t words, hipStream_t stream) {
-    ws_bitset_.ensure(m * words * 4);
-    hip_check(hipMemsetAsync(ws_bitset_.ptr(), 0, m * words * 4, stream), "clear visited bitset");
-    return ws_bitset_.as<uint32_t>();
-}
-
-void Engine::knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
-                      hipStream_t stream) {
-    if (n_dead_ > 0) knn_hnsw_live(d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
-    else hnsw_walk(false, d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
-}
-
-// Deleted rows.  Stage 1: the search as it would run anyway, asked for cap = max(ef, k) results as positions,
-// into a workspace.  Stage 2: hnsw_live_topk_kernel writes the first k live ones of them to the caller's buffers.  The
-// counters are the walk's; the timed interval ends behind the filter.
-void Engine::knn_hnsw_live(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
-                           hipStream_t stream) {
-    const size_t cap = std::max<size_t>((size_t)ef_, k);
-    // cap is unbounded on the SearchOld path: the slices of the batch are cut further where their results would not fit the
-    // budget its own workspaces keep to
-    const size_t slice = std::max<size_t>(1, std::min<size_t>(nq, ((size_t)4 << 30) / (cap * 8)));
-    const size_t qbytes = dim_ * elem_bytes(), off0 = ctr_off_;
-    const HnswOut out = hnsw_out(d_ids, d_dists, d_cnt, nq);
-    ws_live_ids_.ensure(slice * cap * 4);
-    ws_live_d_.ensure(slice * cap * 4);
-    ws_live_cnt_.ensure(slice * 4);
-    for (size_t q0 = 0; q0 < nq; q0 += slice) {
-        const size_t m = std::min(slice, nq - q0);
-        ctr_off_ = off0 + q0;  // the walk's counters go to this slice's place in the batch's arrays
-        hnsw_walk(true, static_cast<const char*>(d_queries) + q0 * qbytes, m, cap, ws_live_ids_.as<int32_t>(),
-                  ws_live_d_.as<float>(), ws_live_cnt_.as<int32_t>(), stream);
-        hip_check(launch_hnsw_live_topk(ws_live_ids_.as<int32_t>(), ws_live_d_.as<float>(), ws_live_cnt_.as<int32_t>(), (int)m,
-                                        (int)cap, d_tomb_.as<uint32_t>(), (int)d_n_, dg_.ext_ids, (int)k, out.at(q0, k),
-                                        stream),
-                  "hnsw_live_topk");
-        prof_end(stream);  // (the interval the walk opened: its end moves behind the filter)
-    }
-    ctr_off_ = off0;
-}
-
-// positions: the launches get the graph without ext_ids, so that every kernel emits internal positions (the builder and the
-// fp16 walk rely on the same)
-void Engine::hnsw_walk(bool positions, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
-                       int32_t* d_cnt, hipStream_t stream) {
-    const int ef = ef_;
-    last_path = 4;
-    hnsw_fix_valid_ = false;
-    auto graph = [&] {  // (read where a path is taken: ensure_rows16 below names the fp16 copy in dg_)
-        HnswDeviceGraph g = dg_;
-        if (positions) g.ext_ids = nullptr;
-        return g;
-    };
-    if (search_old()) {
-        knn_hnsw_old(graph(), d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
-        return;
-    }
-    const HnswOut out = hnsw_out(d_ids, d_dists, d_cnt, nq);
-    if (std::max<size_t>(ef, k) > 1024 || hnsw_nbcap(dg_) > HNSW_NBCAP_LDS) {
-        const HnswDeviceGraph g = graph();
-        // beyond the LDS kernels' sorted array, or adjacency lists longer than their frontier arrays (maxM0 > 254): the
-        // same algorithm with the array in HBM and lists walked in chunks (slices of bounded workspace)
-        const size_t cap = std::max<size_t>(ef, k), words = (d_n_ + 31) / 32;
-        const size_t per_q = cap * 8 + words * 4;
-        const size_t slice = std::max<size_t>(1, std::min<size_t>(nq, ((size_t)4 << 30) / per_q));
-        const size_t qbytes = dim_ * elem_bytes();
-        have_counters_ = true;
-        for (size_t q0 = 0; q0 < nq; q0 += slice) {
-            const size_t m = std::min(slice, nq - q0);
-            ws_old_a_.ensure(m * cap * 4);
-            ws_old_r_.ensure(m * cap * 4);
-            uint32_t* bitset = cleared_bitset(m, words, stream);
-            if (q0 == 0) prof_begin(stream);
-            hip_check(launch_hnsw_search_big(g, (int)m, (int)k, ef, static_cast<const char*>(d_queries) + q0 * qbytes,
-                                             bitset, ws_old_a_.as<float>(), ws_old_r_.as<int32_t>(), out.at(q0, k), stream),
-                      "hnsw_search(big)");
-            if (q0 + slice >= nq) prof_end(stream);
-        }
-        return;
-    }
-    // (SearchOld and the HBM-array kernel above stay on the f32 rows whatever gpu_rows says)
-    if (rows_f16_ && ensure_rows16()) {
-        knn_hnsw_f16(graph(), d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
-        return;
-    }
-    hnsw_search_lds(graph(), false, d_queries, nq, k, ef, out, true, stream);
-}
-
-void Engine::hnsw_search_lds(const HnswDeviceGraph& g, bool rows_f16, const void* d_queries, size_t nq, size_t k, int ef,
-                             const HnswOut& out, bool timed, hipStream_t stream) {
-    const HnswQueries queries = HnswQueries::external(d_queries);
-    HnswSearchPlan p = hnsw_make_plan(g, (int)nq, (int)k, ef, false);
-    p.rows_f16 = rows_f16 ? 1 : 0;
-    have_counters_ = true;
-    if (p.table_size == 0) {
-        uint32_t* bitset = cleared_bitset(nq, p.bitset_words, stream);
-        prof_begin(stream);
-        hip_check(launch_hnsw_search(g, p, queries, bitset, HnswOverflow{}, out, stream), "hnsw_search");
-        if (timed) prof_end(stream);
-        return;
-    }
-    // The LDS visited table is exact but finite.  Queries that fill it append themselves to a list on the device and
-    // are re-run by a second, small launch of the bitset variant that walks that list -- the host never looks at it,
-    // so the call only enqueues work (include/nmslib_gpu.h).
-    const int fix_slots = (int)std::min<size_t>(nq, 128);
-    HnswSearchPlan pb = hnsw_make_plan(g, (int)nq, (int)k, ef, true);
-    pb.rows_f16 = p.rows_f16;
-    ws_fix_.ensure((nq + 16) * 4);
-    // (not cleared_bitset: the workgroups that walk the list clear their own slot on the device)
-    ws_bitset_.ensure((size_t)fix_slots * pb.bitset_words * 4);
-    int32_t* fix_count = ws_fix_.as<int32_t>();
-    int32_t* fix_list = fix_count + 16;
-    hip_check(hipMemsetAsync(fix_count, 0, 4, stream), "clear overflow count");
-    hnsw_fix_valid_ = true;
-    prof_begin(stream);
-    hip_check(launch_hnsw_search(g, p, queries, nullptr, HnswOverflow{0, fix_list, fix_count}, out, stream), "hnsw_search");
-    if (timed) prof_end(stream);
-    hip_check(launch_hnsw_search(g, pb, queries, ws_bitset_.as<uint32_t>(), HnswOverflow{fix_slots, fix_list, fix_count},
-                                 out, stream),
-              "hnsw_search(bitset)");
-}
-
-// The walk reads the fp16 copy; what it ends with is re-ranked against the f32 rows, so every distance returned is the f32
-// distance.  The walk is the search launch asked for cap = max(ef, k) results: the fp16 kernels then write their whole sorted
-// array, in array order and as internal positions.  ndc / hops / hops_up describe the walk; the timed interval is walk +
-// overflow launch + re-rank.
-void Engine::knn_hnsw_f16(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, int32_t* d_ids,
-                          float* d_dists, int32_t* d_cnt, hipStream_t stream) {
-    const int ef = ef_;
-    const size_t cap = std::max<size_t>(ef, k);
-    last_path = 5;
-    const HnswOut fin = hnsw_out(d_ids, d_dists, d_cnt, nq);
-    ws_rr_ids_.ensure(nq * cap * 4);
-    ws_rr_d_.ensure(nq * cap * 4);
-    ws_rr_cnt_.ensure(nq * 4);
-    HnswOut walk = fin;
-    walk.ids = ws_rr_ids_.as<int32_t>();
-    walk.dists = ws_rr_d_.as<float>();
-    walk.cnt = ws_rr_cnt_.as<int32_t>();
-    hnsw_search_lds(g, true, d_queries, nq, cap, ef, walk, false, stream);
-    const size_t rerank = rerank_ > 0 ? std::min(cap, std::max<size_t>(k, (size_t)rerank_)) : cap;
-    hip_check(launch_hnsw_rerank(g, (int)nq, (int)k, (int)cap, (int)rerank, d_queries, walk.ids, walk.cnt, fin, stream),
-              "hnsw_rerank");
-    prof_end(stream);
-}
-
-// Hnsw::SearchOld (hnsw_distfunc_opt.cc:46-150) on the GPU: no limit on ef or k.  Queues that outgrow LDS live in
-// per-query HBM workspaces, so very large batches go through in slices of bounded workspace.
-void Engine::knn_hnsw_old(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, int32_t* d_ids,
-                          float* d_dists, int32_t* d_cnt, hipStream_t stream) {
-    const int ef = ef_;
-    const HnswOut out = hnsw_out(d_ids, d_dists, d_cnt, nq);
-    const size_t qbytes = dim_ * elem_bytes();
-    bool force_bitset = false;
-    int heap_cap = 0;
-    std::vector<int32_t> status(nq);
-    for (int attempt = 0; attempt < 3; ++attempt) {
-        HnswSearchPlan p0 = hnsw_make_plan_old(g, 1, (int)k, ef, force_bitset, heap_cap);
-        const size_t per_q = hnsw_old_ws_a(p0) + hnsw_old_ws_r(p0) + hnsw_old_ws_heap(p0) + p0.bitset_words * 4;
-        const size_t budget = (size_t)4 << 30;
-        const size_t slice = std::max<size_t>(1, std::min<size_t>(nq, per_q ? budget / per_q : nq));
-        for (size_t q0 = 0; q0 < nq; q0 += slice) {
-            const size_t m = std::min(slice, nq - q0);
-            HnswSearchPlan p = hnsw_make_plan_old(g, (int)m, (int)k, ef, force_bitset, heap_cap);
-            uint32_t* bitset = p.table_size == 0 ? cleared_bitset(m, p.bitset_words, stream) : nullptr;
-            ws_old_a_.ensure(std::max<size_t>(16, m * hnsw_old_ws_a(p)));
-            ws_old_r_.ensure(std::max<size_t>(16, m * hnsw_old_ws_r(p)));
-            ws_old_heap_.ensure(std::max<size_t>(16, m * hnsw_old_ws_heap(p)));
-            if (q0 == 0) prof_begin(stream);  // all slices of one attempt are one timed interval
-            hip_check(launch_hnsw_search_old(g, p, static_cast<const char*>(d_queries) + q0 * qbytes, bitset,
-                                             ws_old_a_.ptr(), ws_old_r_.ptr(), ws_old_heap_.ptr(), out.at(q0, k), stream),
-                      "hnsw_search_old");
-            if (q0 + slice >= nq) prof_end(stream);
-        }
-        have_counters_ = true;
-        // status 1: the LDS visited table filled up -> HBM bitsets; status 2: the candidate heap outgrew its bound
-        hip_check(hipMemcpyAsync(status.data(), out.status, nq * 4, hipMemcpyDeviceToHost, stream), "status");
-        hip_check(hipStreamSynchronize(stream), "hnsw_search_old");
-        bool any1 = false, any2 = false;
-        for (int32_t v : status) {
-            any1 |= v == 1;
-            any2 |= v == 2;
-        }
-        if (!any1 && !any2) return;
-        if (any1) force_bitset = true;
-        if (any2) heap_cap = (int)std::min<size_t>(d_n_ + 1, (size_t)INT32_MAX);
-    }
-    throw EngineError(Err::QueryExecutionFailed, "SearchOld: queue workspaces exhausted");
 }
 
 // Pinned host staging buffer (grow-only): PCIe copies from/to pageable memory are staged by the runtime in small

@@ -178,6 +178,20 @@ struct HnswBuildWs {
     void reserve_pairs(size_t npairs, int efC);            // one batch's pairs
 };
 
+// ---- dense HNSW search (hnsw_search.cpp): per-batch workspaces (grow-only, not resident data) ----
+struct HnswSearchWs {
+    // per query of the whole batch: the counts when the caller asks for none, SearchOld's status
+    DevBuf outcnt, status;
+    // visited bitsets of the HBM-visited plans; the visited-overflow list of the LDS-table plans (count + query ids)
+    DevBuf bitset, fix;
+    // fp16 walk: its sorted arrays (positions, fp16-row distances) and their lengths
+    DevBuf rr_ids, rr_d, rr_cnt;
+    // two stages (tombstones, filters): the walk's max(ef, k) results per query of a slice, their counts
+    DevBuf live_ids, live_d, live_cnt;
+    // SearchOld's per-query queues; the HBM-array kernel's sorted array (old_a keys, old_r positions)
+    DevBuf old_a, old_r, old_heap;
+};
+
 // ---- the index ---------------------------------------------------------------------------------
 enum class Method { Brute, Hnsw };
 
@@ -315,6 +329,8 @@ class Engine {
     // Called under `mu` before anything is enqueued on `next`: when the last work went to another stream, `next` waits
     // for an event recorded there.  The same stream again is a pointer compare.
     void order_after_last(hipStream_t next);
+    // sw_.fix holds the last batch's count: set by hnsw_search_lds with an LDS-table plan; cleared by every other search path,
+    // reset, the consolidate and the builder
     bool hnsw_fix_valid_ = false;
     size_t hbm_bytes() const;
 
@@ -388,13 +404,12 @@ class Engine {
                         size_t& count);
     void filter_gather(Filter& f);                // exact scan: f.sub = the index of the allowed live rows
     // a filtered batch, from knn_device: what has to happen before anything is enqueued (refusals; the exact scan's gather
-    // when the index was prepared again: may block), and one slice of the batch
+    // when the index was prepared again: may block), and one slice of the batch (exact scan; HNSW)
     void filter_begin_batch(Filter& f);
     void knn_filtered_slice(Filter& f, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
                             hipStream_t stream);
     void filter_forget_flags(const Filter& f);    // the statistics' pointer into f's child, before its workspaces go
-    void knn_hnsw_filtered(Filter& f, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
-                           int32_t* d_cnt, hipStream_t stream);
+    void knn_hnsw_filtered(Filter& f, const void* d_queries, size_t nq, size_t k, const HnswOut& out, hipStream_t stream);
     std::vector<std::unique_ptr<Filter>> filters_;
     uint64_t pos_epoch_ = 0;     // counts what moves positions: a consolidate that removed a row, a reset
     uint64_t prepared_ = 0;      // counts upload_rows: an exact-scan filter gathered at another count gathers again
@@ -431,16 +446,16 @@ class Engine {
     void make_l1_copy();   // the l1 fast path's resident side; leaves have_l1 = false when declined or out of memory
     void knn_brute(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
                    int32_t* d_cnt, hipStream_t stream);
-    void knn_hnsw(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
-                  int32_t* d_cnt, hipStream_t stream);
+    // dense HNSW search (hnsw_search.cpp).  out: the results and work counters of the slice (knn_device: out.at(q0, k))
+    void knn_hnsw(const void* d_queries, size_t nq, size_t k, const HnswOut& out, hipStream_t stream);
     // the search of one slice on whichever path it takes; positions: on dg_ without ext_ids, so that positions come out
-    void hnsw_walk(bool positions, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
-                   int32_t* d_cnt, hipStream_t stream);
-    // an index with tombstones: the walk for max(ef, k) positions into a workspace, then the first k live ones
-    void knn_hnsw_live(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
-                       hipStream_t stream);
-    void knn_hnsw_old(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
-                      int32_t* d_cnt, hipStream_t stream);
+    void hnsw_walk(bool positions, const void* d_queries, size_t nq, size_t k, const HnswOut& out, hipStream_t stream);
+    // the walk for max(ef, k) positions into a workspace, then the first k of them that are live (an index with tombstones) and
+    // allowed (allow: a filter's bits over n_allow positions, or nullptr)
+    void knn_hnsw_two_stage(const void* d_queries, size_t nq, size_t k, const uint32_t* allow, size_t n_allow,
+                            const HnswOut& out, hipStream_t stream);
+    void knn_hnsw_old(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, const HnswOut& out,
+                      hipStream_t stream);
     // Hnsw::Search, hnsw.cc:724: algoType=old, or hybrid with ef >= 1000, runs SearchOld
     bool search_old() const { return algo_ == "old" || (algo_ == "hybrid" && ef_ >= 1000); }
     // SearchV1Merge on the LDS kernels: the launch, and behind it the bitset launch for queries whose visited table
@@ -448,12 +463,11 @@ class Engine {
     void hnsw_search_lds(const HnswDeviceGraph& g, bool rows_f16, const void* d_queries, size_t nq, size_t k, int ef,
                          const HnswOut& out, bool timed, hipStream_t stream);
     // gpu_rows=f16: the walk over the fp16 copy, then the f32 re-rank of its sorted array
-    void knn_hnsw_f16(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
-                      int32_t* d_cnt, hipStream_t stream);
+    void knn_hnsw_f16(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, const HnswOut& fin,
+                      hipStream_t stream);
     bool ensure_rows16();  // makes the copy if there is none; false: no copy (allocation failed, no rows): stay on f32
     static bool parse_gpu_rows(const std::string& v);  // "f32" -> false, "f16" -> true, else InvalidArgument
     void check_rows16_served() const;                  // InvalidArgument for indexes without float rows
-    HnswOut hnsw_out(int32_t* d_ids, float* d_dists, int32_t* d_cnt, size_t nq);
     uint32_t* cleared_bitset(size_t m, size_t words, hipStream_t stream);
 
     std::string space_name_, method_name_;
@@ -523,14 +537,13 @@ class Engine {
     HnswDeviceGraph dg_{};
 
     // workspaces
-    DevBuf ws_q_, ws_qpad_, ws_qsel_, ws_qaux_, ws_cand_, ws_cnt_, ws_ids_, ws_dists_, ws_outcnt_, ws_status_, ws_bitset_;
-    DevBuf ws_ndc_, ws_hops_, ws_hops_up_, ws_pair_, ws_rdist_, ws_rcnt_, ws_old_a_, ws_old_r_, ws_old_heap_;
+    DevBuf ws_q_, ws_qpad_, ws_qsel_, ws_qaux_, ws_cand_, ws_cnt_, ws_ids_, ws_dists_;
+    DevBuf ws_ndc_, ws_hops_, ws_hops_up_, ws_pair_, ws_rdist_, ws_rcnt_;  // (the counters: dense and string HNSW, the builder)
+    HnswSearchWs sw_;
     HnswBuildWs bw_;
     DevBuf ws_bq_, ws_split_;  // sparse / string batches: the packed queries; per-split lists (string HNSW: per-query state)
-    DevBuf ws_fix_;       // visited-overflow list of the HNSW search (count + query ids), device only
-    DevBuf ws_rr_ids_, ws_rr_d_, ws_rr_cnt_;  // fp16 walk: its sorted arrays (positions, fp16-row distances) and their lengths
-    DevBuf ws_live_ids_, ws_live_d_, ws_live_cnt_;  // tombstones: the walk's max(ef, k) results per query of a slice, their counts
-    size_t ctr_off_ = 0;  // offset of the current slice inside the per-batch counter arrays
+    // the last batch left work counters: set by the dense HNSW search (hnsw_search.cpp, filter.cpp's subset route) and the string
+    // HNSW; cleared by the exact scans, knn_sharded, reset and the consolidate
     bool have_counters_ = false;
     bool prof_ = false;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events_;

@@ -162,14 +162,10 @@ void Engine::filter_begin_batch(Filter& f) {
     if (method_ == Method::Brute && f.gathered_at != prepared_) filter_gather(f);
 }
 
-// One slice of a filtered batch (knn_device's slices and counter workspaces).  Exact scan: knn_brute on the filter's child; the
-// batch is this index's, so its timed intervals, path and fast-path flags are read here.
+// One slice of a filtered exact-scan batch (knn_device's slices): knn_brute on the filter's child; the batch is this index's,
+// so its timed intervals, path and fast-path flags are read here.
 void Engine::knn_filtered_slice(Filter& f, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
                                 int32_t* d_cnt, hipStream_t stream) {
-    if (method_ == Method::Hnsw) {
-        knn_hnsw_filtered(f, d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
-        return;
-    }
     Engine& c = *f.sub;
     c.prof_ = prof_;
     c.knn_brute(d_queries, nq, k, d_ids, d_dists, d_cnt, stream);
@@ -191,42 +187,22 @@ void Engine::filter_forget_flags(const Filter& f) {
 }
 
 // One slice of a filtered HNSW batch.  Subset route: hnsw_subset_knn_kernel over the filter's list (last_path 7).  Walk route:
-// knn_hnsw_live's two stages with the two-bitset filter behind the walk; the counters are the walk's.
-void Engine::knn_hnsw_filtered(Filter& f, const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
-                               int32_t* d_cnt, hipStream_t stream) {
-    const uint32_t* tomb = n_dead_ > 0 ? d_tomb_.as<uint32_t>() : nullptr;
+// the two stages of hnsw_search.cpp with the filter's bits; the counters are the walk's.
+void Engine::knn_hnsw_filtered(Filter& f, const void* d_queries, size_t nq, size_t k, const HnswOut& out, hipStream_t stream) {
     if (filter_route(f.m, (size_t)ef_, k, f.scan_rows, hnsw_subset_query_bytes(dg_)) == FilterRoute::Subset) {
+        const uint32_t* tomb = n_dead_ > 0 ? d_tomb_.as<uint32_t>() : nullptr;
         HnswDeviceGraph g = dg_;
         g.rows16 = nullptr;  // always the f32 rows: the bits of the f32 walk
         have_counters_ = true;
         hnsw_fix_valid_ = false;
         last_path = 7;
         prof_begin(stream);
-        hip_check(launch_hnsw_subset_knn(g, (int)nq, (int)k, d_queries, f.d_list.as<int32_t>(), (int)f.m, tomb,
-                                         hnsw_out(d_ids, d_dists, d_cnt, nq), stream),
+        hip_check(launch_hnsw_subset_knn(g, (int)nq, (int)k, d_queries, f.d_list.as<int32_t>(), (int)f.m, tomb, out, stream),
                   "hnsw_subset_knn");
         prof_end(stream);
         return;
     }
-    const size_t cap = filter_walk_results((size_t)ef_, k);
-    const size_t slice = std::max<size_t>(1, std::min<size_t>(nq, ((size_t)4 << 30) / (cap * 8)));  // (knn_hnsw_live's budget)
-    const size_t qbytes = dim_ * elem_bytes(), off0 = ctr_off_;
-    const HnswOut out = hnsw_out(d_ids, d_dists, d_cnt, nq);
-    ws_live_ids_.ensure(slice * cap * 4);
-    ws_live_d_.ensure(slice * cap * 4);
-    ws_live_cnt_.ensure(slice * 4);
-    for (size_t q0 = 0; q0 < nq; q0 += slice) {
-        const size_t m = std::min(slice, nq - q0);
-        ctr_off_ = off0 + q0;
-        hnsw_walk(true, static_cast<const char*>(d_queries) + q0 * qbytes, m, cap, ws_live_ids_.as<int32_t>(),
-                  ws_live_d_.as<float>(), ws_live_cnt_.as<int32_t>(), stream);
-        hip_check(launch_hnsw_filter_topk(ws_live_ids_.as<int32_t>(), ws_live_d_.as<float>(), ws_live_cnt_.as<int32_t>(), (int)m,
-                                          (int)cap, f.d_allow.as<uint32_t>(), (int)f.n, tomb, (int)d_n_, dg_.ext_ids, (int)k,
-                                          out.at(q0, k), stream),
-                  "hnsw_filter_topk");
-        prof_end(stream);
-    }
-    ctr_off_ = off0;
+    knn_hnsw_two_stage(d_queries, nq, k, f.d_allow.as<uint32_t>(), f.n, out, stream);
 }
 
 }  // namespace gfxknn

@@ -1,8 +1,8 @@
 // Filtered search: a bitset of allowed positions becomes what the two index kinds need.
 //   exact scan: the ascending list of allowed device rows (filter_count / filter_write), then the rows and ids gathered into
 //               an index of their own (filter_gather_rows / filter_gather_ids);
-//   HNSW:       the walk's results filtered through the allow bitset and the tombstones (hnsw_filter_topk_kernel), or, for a
-//               subset no larger than the walk's own result array, an exact scan of the listed rows (hnsw_subset_knn_kernel).
+//   HNSW:       the walk's results filtered through the allow bitset and the tombstones (hnsw_keep_topk_kernel in
+//               hnsw_live_kernels.hip), or, for a subset no larger than the walk's own result array, an exact scan of the listed rows (hnsw_subset_knn_kernel).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -147,60 +147,6 @@ hipError_t launch_filter_gather_ids(const int32_t* src, const int32_t* list, int
     if (!src || !list || !dst) return hipErrorInvalidValue;
     const int blocks = (int)std::min<size_t>(((size_t)m + 255) / 256, 65536);
     hipLaunchKernelGGL(filter_gather_ids_kernel, dim3(blocks), dim3(256), 0, s, src, list, m, dst);
-    return hipGetLastError();
-}
-
-// ---- HNSW, walk route: the result filter with two bitsets ---------------------------------------------------------------
-// hnsw_live_topk_kernel's scheme (one wave per query, a ballot per chunk of 64 entries keeps the search's order) with
-// "allowed and not deleted" in the place of "not deleted".
-__global__ __launch_bounds__(64) void hnsw_filter_topk_kernel(const int32_t* __restrict__ cand, const float* __restrict__ cand_d,
-                                                              const int32_t* __restrict__ cand_n, int cap,
-                                                              const uint32_t* __restrict__ allow, int n_allow,
-                                                              const uint32_t* __restrict__ tomb, int n,
-                                                              const int32_t* __restrict__ ext_ids, int k, int32_t* out_ids,
-                                                              float* out_dists, int32_t* out_cnt) {
-    using u64 = unsigned long long;
-    const int q = blockIdx.x, lane = threadIdx.x;
-    int cnt = cand_n[q];
-    cnt = cnt < 0 ? 0 : (cnt < cap ? cnt : cap);
-    const int32_t* c = cand + (size_t)q * cap;
-    const float* cd = cand_d + (size_t)q * cap;
-    int taken = 0;  // entries kept so far (wave-uniform)
-    for (int base = 0; base < cnt && taken < k; base += 64) {
-        const int i = base + lane;
-        int pos = -1;
-        float d = INFINITY;
-        bool keep = false;
-        if (i < cnt) {
-            pos = c[i];
-            d = cd[i];
-            // (a row added after the filter was made stands at or beyond n_allow: no word outside either bitset is read)
-            keep = (unsigned)pos < (unsigned)n_allow && ((allow[pos >> 5] >> (pos & 31)) & 1u) != 0;
-            if (keep && tomb) keep = (unsigned)pos < (unsigned)n && ((tomb[pos >> 5] >> (pos & 31)) & 1u) == 0;
-        }
-        const u64 mask = __ballot(keep);
-        const int at = taken + __popcll(mask & ((1ull << lane) - 1ull));
-        if (keep && at < k) {
-            out_ids[(size_t)q * k + at] = ext_ids ? ext_ids[pos] : pos;
-            out_dists[(size_t)q * k + at] = d;
-        }
-        taken += __popcll(mask);
-    }
-    if (taken > k) taken = k;
-    for (int i = taken + lane; i < k; i += 64) {
-        out_ids[(size_t)q * k + i] = -1;
-        out_dists[(size_t)q * k + i] = INFINITY;
-    }
-    if (lane == 0) out_cnt[q] = taken;
-}
-
-hipError_t launch_hnsw_filter_topk(const int32_t* cand, const float* cand_d, const int32_t* cand_n, int nq, int cap,
-                                   const uint32_t* allow, int n_allow, const uint32_t* tomb, int n, const int32_t* ext_ids,
-                                   int k, const HnswOut& out, hipStream_t s) {
-    if (nq == 0) return hipSuccess;
-    if (k < 1 || cap < 1 || n_allow < 0 || (n_allow > 0 && !allow) || !out.cnt) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(hnsw_filter_topk_kernel, dim3(nq), dim3(64), 0, s, cand, cand_d, cand_n, cap, allow, n_allow, tomb, n,
-                       ext_ids, k, out.ids, out.dists, out.cnt);
     return hipGetLastError();
 }
 

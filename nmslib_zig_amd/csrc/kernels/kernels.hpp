@@ -425,13 +425,14 @@ hipError_t launch_hnsw_pack_rows16(const float* rows, int n, int ldv, int dim, f
 // position); k results with external ids, -1 / +inf padding and the count go to out.
 hipError_t launch_hnsw_rerank(const HnswDeviceGraph& g, int nq, int k, int cap, int rerank, const void* queries,
                               const int32_t* cand, const int32_t* cand_n, const HnswOut& out, hipStream_t s);
-// Deleted rows (hnsw_live_kernels.hip): cand / cand_d [nq][cap] are the results of a search launched for cap results
-// without ext_ids (internal positions, in the search's order), cand_n [nq] their counts.  One wave per query: the first k
-// entries whose bit in tomb ([ceil(n / 32)] words, bit = position) is clear, in their order, with external ids; -1 / +inf
-// padding and the count go to out (out.cnt is required).  Nothing beyond cand_n[q] entries is read.
-hipError_t launch_hnsw_live_topk(const int32_t* cand, const float* cand_d, const int32_t* cand_n, int nq, int cap,
-                                 const uint32_t* tomb, int n, const int32_t* ext_ids, int k, const HnswOut& out,
-                                 hipStream_t s);
+// Deleted rows and filtered batches (hnsw_live_kernels.hip): cand / cand_d [nq][cap] are the results of a search launched for
+// cap results without ext_ids (internal positions, in the search's order), cand_n [nq] their counts.  One wave per query: the
+// first k entries whose position is below n_allow with its bit in allow set (allow optional) and whose bit in tomb ([ceil(n /
+// 32)] words, bit = position; optional; at least one of the two is given) is clear, in their order, with external ids; -1 /
+// +inf padding and the count go to out (out.cnt is required).  Nothing beyond cand_n[q] entries is read.
+hipError_t launch_hnsw_keep_topk(const int32_t* cand, const float* cand_d, const int32_t* cand_n, int nq, int cap,
+                                 const uint32_t* allow, int n_allow, const uint32_t* tomb, int n, const int32_t* ext_ids,
+                                 int k, const HnswOut& out, hipStream_t s);
 // SearchOld; ws_a / ws_r / ws_heap: the per-query HBM workspaces above (may be unused)
 hipError_t launch_hnsw_search_old(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries, uint32_t* bitset,
                                   void* ws_a, void* ws_r, void* ws_heap, const HnswOut& out, hipStream_t s);
@@ -456,11 +457,7 @@ hipError_t launch_filter_write(const uint32_t* mask, const int32_t* prefix, int 
 hipError_t launch_filter_gather_rows(const void* src, const int32_t* list, int m, size_t row_bytes, void* dst, hipStream_t s);
 // dst[i] = src[list[i]]
 hipError_t launch_filter_gather_ids(const int32_t* src, const int32_t* list, int m, int32_t* dst, hipStream_t s);
-// The result filter of hnsw_live_topk with two bitsets: the first k entries whose position is below n_allow with its bit in
-// allow set and whose bit in tomb (optional, n positions) is clear.
-hipError_t launch_hnsw_filter_topk(const int32_t* cand, const float* cand_d, const int32_t* cand_n, int nq, int cap,
-                                   const uint32_t* allow, int n_allow, const uint32_t* tomb, int n, const int32_t* ext_ids,
-                                   int k, const HnswOut& out, hipStream_t s);
+// (the walk route's result filter is launch_hnsw_keep_topk above)
 // Exact k-NN over the m <= HNSW_SUBSET_MAX positions of list (ascending), one workgroup per query: the distances of the f32
 // walk on g.rows (u8 rows: the integer distance), rows with their bit in tomb (optional) set left out, order (distance,
 // position).  out: k results with external ids, -1 / +inf padding, the count; ndc = m, hops = hops_up = 0.

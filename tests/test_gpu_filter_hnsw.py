@@ -141,6 +141,36 @@ def test_slices_of_a_large_batch():
     idx.close()
 
 
+@pytest.mark.parametrize("deleted", [False, True])
+def test_inner_slices_of_the_walk_route(monkeypatch, deleted):
+    """250 queries cut at 100 through NMSLIB_HNSW_SLICE_MAXQ (two slices and a tail of 50) answer as the uncut batch does:
+    results, counts and the walk's counters at their offsets"""
+    n, nq, ef = 1500, 250, 32
+    X, Q = refio.s_lowrank(n, D, 1109), refio.s_lowrank(nq, D, 1110)
+    ids = ext_ids(n)
+    rng = np.random.default_rng(1111)
+    mask = rng.random(n) < 0.5
+    idx = make_index("l2", "hnsw", X, ids, M=8, efConstruction=40, indexThreadQty=1)
+    idx.setQueryTimeParams(efSearch=ef)
+    if deleted:
+        dead = ids[rng.permutation(n)[:n // 5]]
+        assert idx.deleteIds(dead) == len(dead)
+    flt = idx.makeFilter(mask)
+    assert flt.allowed > ef                                       # (the walk route)
+    monkeypatch.delenv("NMSLIB_HNSW_SLICE_MAXQ", raising=False)
+    want, wctr = run(idx, Q, K, flt)
+    assert idx.stats()["last_path"] == 4
+    monkeypatch.setenv("NMSLIB_HNSW_SLICE_MAXQ", "100")
+    got, gctr = run(idx, Q, K, flt)
+    assert idx.stats()["last_path"] == 4
+    same_bits(got, want)
+    for nm, g, w in zip(("ndc", "hops", "hops_up"), gctr, wctr):
+        assert g.shape == (nq,)
+        np.testing.assert_array_equal(g, w, err_msg=nm)
+    flt.close()
+    idx.close()
+
+
 # ---- subset route -----------------------------------------------------------------------------------------------------
 NS = 4200
 MS = (0, 1, 7, 8, 9, 31, 32, 33, 64, 65, 1000, 4096)

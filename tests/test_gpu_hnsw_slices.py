@@ -39,3 +39,48 @@ def test_sliced_batch_equals_the_small_batch(index_and_queries, ef, algo):
     for name, got, want in zip(("ndc", "hops", "hops_up"), bcounters, counters):
         assert got.shape == (NQ_BIG,)
         np.testing.assert_array_equal(got, want[src], err_msg=name)
+
+
+# ---- the inner slices (hnsw_search.cpp's workspace budget), cut at 100 queries through NMSLIB_HNSW_SLICE_MAXQ ----
+@pytest.fixture(scope="module")
+def index_with_deleted_rows():
+    idx = make_index("l2", "hnsw", refio.s_lowrank(N, D, 501), M=8, efConstruction=40, indexThreadQty=1)
+    dead = np.random.default_rng(503).permutation(N)[:N * 3 // 10].astype(np.int32)
+    assert idx.deleteIds(dead) == len(dead)
+    yield idx
+    idx.close()
+
+
+def answer(idx, Q):
+    ids, ds, cnt = idx.knnQueryBatch(Q, K)
+    return (ids, np.ascontiguousarray(ds).view(np.uint32), cnt) + tuple(c.copy() for c in idx.read_counters(len(Q)))
+
+
+INNER = [
+    # (deleted rows, ef, algo, gpu_rows)
+    (False, 32, "old", "f32"),        # SearchOld's slices
+    (False, 1100, "v1merge", "f32"),  # the HBM-array kernel's slices
+    (True, 32, "v1merge", "f32"),     # two stages over the LDS kernels
+    (True, 32, "old", "f32"),         # two stages over SearchOld, sliced again
+    (True, 1100, "v1merge", "f32"),   # two stages over the HBM-array kernel, sliced again
+    (True, 32, "v1merge", "f16"),     # two stages over the fp16 walk and its re-rank
+]
+
+
+@pytest.mark.parametrize("nq", [100, 101, 250])  # one full slice; a tail of one; two slices and a tail of 50
+@pytest.mark.parametrize("deleted,ef,algo,rows", INNER)
+def test_inner_slices_equal_the_uncut_batch(index_and_queries, index_with_deleted_rows, monkeypatch, deleted, ef, algo, rows,
+                                            nq):
+    idx, Q = (index_with_deleted_rows if deleted else index_and_queries[0]), index_and_queries[1][:nq]
+    idx.setQueryTimeParams(efSearch=ef, algoType=algo, gpu_rows=rows)
+    try:
+        monkeypatch.delenv("NMSLIB_HNSW_SLICE_MAXQ", raising=False)
+        want = answer(idx, Q)
+        assert idx.stats()["last_path"] == (5 if rows == "f16" else 4)
+        monkeypatch.setenv("NMSLIB_HNSW_SLICE_MAXQ", "100")
+        got = answer(idx, Q)
+    finally:
+        idx.setQueryTimeParams(gpu_rows="f32")
+    for name, g, w in zip(("ids", "distance bits", "counts", "ndc", "hops", "hops_up"), got, want):
+        assert g.shape[0] == nq
+        np.testing.assert_array_equal(g, w, err_msg=name)
