@@ -950,3 +950,509 @@ void orc_hnsw_search(const orc_hnsw_t* g, int optimized, int algo, const void* q
     free(qbuf);
     free(visited);
 }
+
+/* ======================================================================== */
+/* The batched GPU builder, restated sequentially                           */
+/* (nmslib_zig_amd/csrc/hnsw_gpu_build.cpp and        */
+/* kernels/hnsw_build_kernels.hip are what is CHECKED against this, nothing */
+/* here is taken from them but the rule).  Insertion order, level stream,   */
+/* selection and addFriendlevel are the reference's (hnsw.cc:534-609,       */
+/* hnsw.h:82-169,258-314); what differs is visibility: a batch of nodes is  */
+/* searched against the graph before the batch and then linked, level by    */
+/* level from the top down.                                                 */
+/* ======================================================================== */
+typedef struct {
+    double d;
+    int32_t id;
+} bcand;
+
+/* the distance of the flat index (hnsw.cc:70-102): squared l2, 1 - dot over rows normalised once, the space's own
+ * otherwise; integer for l2sqr_sift */
+static double bdist(const orc_hnsw_t* g, int a, int b) {
+    if (g->sift_norms)
+        return orc_l2sqr_sift((const uint8_t*)g->base + (size_t)a * g->rb, g->sift_norms[a],
+                              (const uint8_t*)g->base + (size_t)b * g->rb, g->sift_norms[b]);
+    if (g->space == ORC_ANGULAR) return orc_space_distance(g->space, g->base + (size_t)a * g->rb, g->base + (size_t)b * g->rb, g->dim);
+    const float* rows = g->norm_base ? g->norm_base : (const float*)g->base;
+    return orc_hnsw_opt_distance(g->space, rows + (size_t)a * g->dim, rows + (size_t)b * g->dim, g->dim);
+}
+
+double orc_hnsw_build_distance(const orc_hnsw_t* g, int a, int b) { return bdist(g, a, b); }
+int orc_hnsw_maxM0(const orc_hnsw_t* g) { return g->maxM0; }
+
+/* One construction search: SearchV1Merge (hnsw_distfunc_opt.cc:200-274) over the lists of `level`, ef = k = cap, with node
+ * q's row as the query.  start < 0: greedy descent from the entry point down to level + 1 (hnsw.cc:553-575: strict <, the
+ * first index attaining the minimum of a list).  The unvisited neighbours of one expansion are taken in list order, 64 at
+ * a time; each group is sorted by distance keeping list order among equal keys and pushed item by item
+ * (SortArrBI::push_or_replace_non_empty_exp).  Returns the array's items, equal keys in ascending id. */
+static int batched_search(const orc_hnsw_t* g, int q, int level, int start, int ef, bcand* out, uint32_t* visited,
+                          uint32_t epoch) {
+    int cur;
+    double curdist;
+    if (start >= 0) {
+        cur = start;
+        curdist = bdist(g, q, cur);
+    } else {
+        cur = g->enterpoint;
+        curdist = bdist(g, q, cur);
+        for (int lvl = g->maxlevel; lvl > level; --lvl) {
+            int changed = 1;
+            while (changed) {
+                changed = 0;
+                const int32_t* L = node_links(g, cur, lvl);
+                int best = -1;
+                double bd = 0;
+                for (int j = 1; j <= L[0]; ++j) {
+                    double d = bdist(g, q, L[j]);
+                    if (best < 0 || d < bd) {
+                        bd = d;
+                        best = L[j];
+                    }
+                }
+                if (best >= 0 && bd < curdist) {
+                    curdist = bd;
+                    cur = best;
+                    changed = 1;
+                }
+            }
+        }
+    }
+    sortarr s;
+    s.cap = (size_t)ef;
+    s.v = (sa_item*)calloc(s.cap + 1, sizeof(sa_item));
+    s.v[0].used = 0;
+    s.v[0].key = curdist;
+    s.v[0].data = cur;
+    s.n = 1;
+    size_t buffcap = 1 + (size_t)(g->maxM > g->maxM0 ? g->maxM : g->maxM0);
+    sa_item* buff = (sa_item*)malloc(buffcap * sizeof(sa_item));
+    long currElem = 0;
+    visited[cur] = epoch;
+    while (currElem < (long)(s.n < (size_t)ef ? s.n : (size_t)ef)) {
+        sa_item* e = &s.v[currElem];
+        e->used = 1;
+        cur = e->data;
+        ++currElem;
+        const double topKey = s.v[s.n - 1].key;
+        const size_t size0 = s.n;
+        const int32_t* L = node_links(g, cur, level);
+        size_t m = 0;
+        for (int j = 1; j <= L[0]; ++j) {
+            int t = L[j];
+            if (visited[t] == epoch) continue;
+            visited[t] = epoch;
+            buff[m].key = bdist(g, q, t);
+            buff[m].used = 0;
+            buff[m].data = t;
+            m++;
+        }
+        for (size_t r0 = 0; r0 < m; r0 += 64) {
+            sa_item acc[64];
+            size_t qty = 0;
+            for (size_t j = r0; j < m && j < r0 + 64; ++j)
+                if (buff[j].key < topKey || size0 < (size_t)ef) { /* :240 */
+                    size_t p = qty++;
+                    while (p > 0 && acc[p - 1].key > buff[j].key) { /* stable */
+                        acc[p] = acc[p - 1];
+                        --p;
+                    }
+                    acc[p] = buff[j];
+                }
+            for (size_t ii = 0; ii < qty; ++ii) {
+                size_t ins = sa_push(&s, acc[ii].key, acc[ii].data);
+                if ((long)ins < currElem) currElem = (long)ins;
+            }
+        }
+        while (currElem < (long)s.n && s.v[currElem].used) ++currElem;
+    }
+    int cnt = (int)s.n;
+    for (int i = 0; i < cnt; ++i) {
+        out[i].d = s.v[i].key;
+        out[i].id = s.v[i].data;
+    }
+    for (int i = 1; i < cnt; ++i) { /* equal keys: ascending id */
+        bcand x = out[i];
+        int p = i;
+        while (p > 0 && out[p - 1].d == x.d && out[p - 1].id > x.id) {
+            out[p] = out[p - 1];
+            --p;
+        }
+        out[p] = x;
+    }
+    free(buff);
+    free(s.v);
+    return cnt;
+}
+
+/* Selection of Hnsw::add (hnsw.cc:582-597) and of addFriendlevel's shrink (hnsw.h:283-289) over candidates ascending by
+ * distance.  delaunay 0: the NN closest.  2: getNeighborsByHeuristic2 (hnsw.h:129-169).  1: getNeighborsByHeuristic1
+ * (hnsw.h:82-127) = heuristic 2, then, if every candidate was examined and fewer than NN kept, the first rejected ones in
+ * candidate order; the result is in candidate order.  *topup is set when rejected ones were added. */
+static int batched_select(const orc_hnsw_t* g, const bcand* c, int nc, int NN, int delaunay, bcand* kept, int* topup) {
+    if (nc < NN || delaunay == 0) {
+        int n = nc < NN ? nc : NN;
+        memcpy(kept, c, (size_t)n * sizeof(bcand));
+        return n;
+    }
+    char* isk = (char*)calloc((size_t)nc + 1, 1);
+    int nk = 0, i = 0;
+    for (; i < nc && nk < NN; ++i) {
+        int good = 1;
+        for (int j = 0; j < nk && good; ++j)
+            if (bdist(g, c[i].id, kept[j].id) < c[i].d) good = 0;
+        if (good) {
+            kept[nk++] = c[i];
+            isk[i] = 1;
+        }
+    }
+    if (delaunay == 1 && nk < NN) { /* (the scan ended at i == nc) */
+        int need = NN - nk, out = 0;
+        for (int j = 0; j < nc; ++j)
+            if (isk[j]) kept[out++] = c[j];
+            else if (need > 0) {
+                kept[out++] = c[j];
+                --need;
+            }
+        nk = out;
+        if (topup) *topup = 1;
+    }
+    free(isk);
+    return nk;
+}
+
+typedef struct {
+    uint32_t target, node;
+    double d;
+} breq;
+static int breq_cmp(const void* a, const void* b) {
+    const breq *x = (const breq*)a, *y = (const breq*)b;
+    if (x->target != y->target) return x->target < y->target ? -1 : 1;
+    return (x->node > y->node) - (x->node < y->node);
+}
+static int bcand_cmp_stable(const void* a, const void* b) { /* (distance, id): id holds the original position */
+    const bcand *x = (const bcand*)a, *y = (const bcand*)b;
+    if (x->d != y->d) return x->d < y->d ? -1 : 1;
+    return (x->id > y->id) - (x->id < y->id);
+}
+
+typedef struct {
+    int M, efC, delaunay, batch_div, max_batch;
+    size_t cut, stop; /* stop != 0: no batch starts at or behind this position */
+} bparams;
+
+/* One insertion pass.  Every node of g is allocated (empty lists) with its level; position 0 is node 0, position i > 0 is
+ * node i, or node n - i in reverse order. */
+static void batched_pass(orc_hnsw_t* g, const bparams* P, int reverse, orc_batched_stats* st, int32_t* out_batch) {
+    const size_t n = g->n;
+    const int efC = P->efC, M = P->M;
+    g->maxlevel = g->level[0];
+    g->enterpoint = 0;
+    if (out_batch) out_batch[0] = out_batch[1] = 0;
+    size_t maxb = (size_t)P->max_batch < n ? (size_t)P->max_batch : n;
+    int32_t* nodes = (int32_t*)malloc((maxb + 1) * sizeof(int32_t));
+    int32_t* slice = (int32_t*)malloc((maxb + 1) * sizeof(int32_t)); /* batch index of the slice's q-th node */
+    bcand* merged = (bcand*)malloc(((size_t)efC + 64 + 1) * sizeof(bcand));
+    bcand* mates = (bcand*)malloc((maxb + 1) * sizeof(bcand));
+    int wide = (g->maxM0 > g->maxM ? g->maxM0 : g->maxM) + 2;
+    bcand* kept = (bcand*)malloc(((size_t)(efC > wide ? efC : wide) + 1) * sizeof(bcand));
+    bcand* ranked = (bcand*)malloc(((size_t)wide + 1) * sizeof(bcand));
+    breq* reqs = (breq*)malloc((maxb * (size_t)M + 1) * sizeof(breq));
+    int32_t batch_no = 0;
+    for (size_t next = 1, end; next < n && (P->stop == 0 || next < P->stop); next = end, ++batch_no) {
+        /* ---- the batch: at most 1/div of the positions before it, at most max_batch, at least one; never across the
+         * cut; closed by the first node that rises above the top level */
+        size_t want = next / (size_t)P->batch_div;
+        if (want < 1) want = 1;
+        int capped = 0, at_cut = 0;
+        if (want >= (size_t)P->max_batch) {
+            want = (size_t)P->max_batch;
+            capped = 1;
+        }
+        end = next + want < n ? next + want : n;
+        if (next < P->cut && P->cut < end) {
+            end = P->cut;
+            at_cut = 1;
+        }
+        const int top = g->maxlevel;
+        int promoted = 0;
+        for (size_t i = next; i < end; ++i) {
+            size_t node = reverse ? n - i : i;
+            if (g->level[node] > top) {
+                promoted = 1;
+                if (i + 1 < end) at_cut = 0;
+                end = i + 1;
+                break;
+            }
+        }
+        const size_t nb = end - next;
+        for (size_t i = 0; i < nb; ++i) {
+            nodes[i] = (int32_t)(reverse ? n - (next + i) : next + i);
+            if (out_batch) {
+                out_batch[2 * (size_t)nodes[i]] = batch_no + 1;
+                out_batch[2 * (size_t)nodes[i] + 1] = (int32_t)i;
+            }
+        }
+        if (st) {
+            st->batches++;
+            if ((int64_t)nb > st->largest_batch) st->largest_batch = (int64_t)nb;
+            if (capped && nb == (size_t)P->max_batch) st->batches_at_cap++;
+            if (at_cut && end == P->cut) st->batches_at_cut++;
+            if (promoted && nb >= 2) st->promotions_in_batch++;
+        }
+        /* ---- searches: every (node, level) pair against the graph as it is now */
+        size_t npairs = 0;
+        for (size_t i = 0; i < nb; ++i) npairs += (size_t)(g->level[nodes[i]] < top ? g->level[nodes[i]] : top) + 1;
+        bcand* cand = (bcand*)malloc(npairs * (size_t)efC * sizeof(bcand));
+        int32_t* cand_n = (int32_t*)malloc(npairs * sizeof(int32_t));
+        size_t* pair0 = (size_t*)malloc(nb * sizeof(size_t)); /* node i's level-l pair is pair0[i] + l */
+        for (size_t i = 0, o = 0; i < nb; ++i) {
+            const int p = nodes[i], nl = g->level[p] < top ? g->level[p] : top;
+            pair0[i] = o;
+            for (int l = nl; l >= 0; --l) {
+                const int start = l == nl ? -1 : cand[(o + (size_t)l + 1) * efC].id;
+                g->epoch++;
+                cand_n[o + l] = batched_search(g, p, l, start, efC, cand + (o + (size_t)l) * efC, g->visited, g->epoch);
+            }
+            o += (size_t)nl + 1;
+        }
+        /* ---- links, level by level from the top */
+        for (int l = top; l >= 0; --l) {
+            size_t m = 0;
+            for (size_t i = 0; i < nb; ++i)
+                if ((g->level[nodes[i]] < top ? g->level[nodes[i]] : top) >= l) slice[m++] = (int32_t)i;
+            if (m == 0) continue;
+            if (st && l > 0 && m >= 2) st->upper_slices_ge2++;
+            size_t nreq = 0;
+            for (size_t q = 0; q < m; ++q) {
+                const int p = nodes[slice[q]];
+                const bcand* c = cand + (pair0[slice[q]] + (size_t)l) * efC;
+                const int nc = cand_n[pair0[slice[q]] + l];
+                /* (a) earlier nodes of the slice closer than the worst candidate of a full list: the 64 closest */
+                const double thr = nc >= efC ? c[nc - 1].d : INFINITY;
+                int nx = 0;
+                for (size_t j = 0; j < q; ++j) {
+                    double d = bdist(g, p, nodes[slice[j]]);
+                    if (d < thr) {
+                        mates[nx].d = d;
+                        mates[nx].id = (int32_t)j; /* slice order, for the sort */
+                        nx++;
+                    }
+                }
+                qsort(mates, (size_t)nx, sizeof(bcand), bcand_cmp_stable);
+                if (nx > 64) {
+                    nx = 64;
+                    if (st) st->mates_truncated++;
+                }
+                for (int j = 0; j < nx; ++j) mates[j].id = nodes[slice[mates[j].id]];
+                if (st) {
+                    if (nc > 64) st->cand_lists_gt64++;
+                    if (l > 0) st->upper_mates += nx;
+                    st->mates += nx;
+                }
+                /* (b) stable merge, graph candidates first among equal distances, cut at efConstruction */
+                int nm = 0, a = 0, b = 0;
+                while ((a < nc || b < nx) && nm < efC) {
+                    if (st && a < nc && b < nx && c[a].d == mates[b].d) st->ties_merge++;
+                    if (b >= nx || (a < nc && c[a].d <= mates[b].d)) merged[nm++] = c[a++];
+                    else merged[nm++] = mates[b++];
+                }
+                if (st && nx > 0 && nc + nx > efC) st->merged_cut++;
+                /* (c) the new node's neighbours; its list farthest first (hnsw.cc:597-601), one request each */
+                int topup = 0;
+                const int nk = batched_select(g, merged, nm, M, P->delaunay, kept, &topup);
+                if (st) {
+                    if (nm < M) st->short_lists_kept++;
+                    if (topup) st->h1_topups_select++;
+                }
+                int32_t* L = node_links(g, p, l);
+                L[0] = nk;
+                for (int i = 0; i < nk; ++i) {
+                    L[1 + i] = kept[nk - 1 - i].id;
+                    reqs[nreq].target = (uint32_t)kept[i].id;
+                    reqs[nreq].node = (uint32_t)p;
+                    reqs[nreq].d = kept[i].d;
+                    nreq++;
+                }
+            }
+            /* (d) requests by (target, new node); addFriendlevel per request (hnsw.h:258-314) */
+            qsort(reqs, nreq, sizeof(breq), breq_cmp);
+            const int maxsz = l > 0 ? g->maxM : g->maxM0;
+            int64_t ntargets = 0;
+            for (size_t r = 0; r < nreq;) {
+                const int t = (int)reqs[r].target;
+                size_t r1 = r;
+                while (r1 < nreq && (int)reqs[r1].target == t) ++r1;
+                ntargets++;
+                if (st) {
+                    if ((int64_t)(r1 - r) > st->most_requests_one_target) st->most_requests_one_target = (int64_t)(r1 - r);
+                    if (r1 - r >= 2) st->targets_ge2_requests++;
+                }
+                int32_t* L = node_links(g, t, l);
+                for (; r < r1; ++r) {
+                    const int p = (int)reqs[r].node;
+                    if (L[0] < maxsz) {
+                        L[1 + L[0]] = p;
+                        L[0]++;
+                        continue;
+                    }
+                    const int cnt = L[0], n1 = cnt + 1;
+                    for (int i = 0; i < cnt; ++i) {
+                        ranked[i].d = bdist(g, t, L[1 + i]);
+                        ranked[i].id = i;
+                    }
+                    ranked[cnt].d = reqs[r].d; /* the carried distance */
+                    ranked[cnt].id = cnt;
+                    qsort(ranked, (size_t)n1, sizeof(bcand), bcand_cmp_stable);
+                    L[1 + cnt] = p;
+                    for (int i = 0; i < n1; ++i) {
+                        if (st && i > 0 && ranked[i].d == ranked[i - 1].d) st->ties_link++;
+                        ranked[i].id = L[1 + ranked[i].id];
+                    }
+                    int topup = 0;
+                    const int nk = batched_select(g, ranked, n1, n1 - 1, P->delaunay, kept, &topup);
+                    for (int i = 0; i < nk; ++i) L[1 + i] = kept[nk - 1 - i].id; /* hnsw.h:295-300 */
+                    for (int i = nk; i <= cnt; ++i) L[1 + i] = 0;
+                    L[0] = nk;
+                    if (st) {
+                        st->shrinks++;
+                        if (cnt > st->longest_list_shrunk) st->longest_list_shrunk = cnt;
+                        if (topup) st->h1_topups_shrink++;
+                    }
+                }
+            }
+            if (st && ntargets > (int64_t)next) st->targets_gt_nodes_before++;
+        }
+        free(cand);
+        free(cand_n);
+        free(pair0);
+        /* ---- the tallest node above the top level becomes the entry point */
+        for (size_t i = 0; i < nb; ++i)
+            if (g->level[nodes[i]] > g->maxlevel) {
+                g->maxlevel = g->level[nodes[i]];
+                g->enterpoint = nodes[i];
+            }
+    }
+    free(nodes);
+    free(slice);
+    free(merged);
+    free(mates);
+    free(kept);
+    free(ranked);
+    free(reqs);
+}
+
+static orc_hnsw_t* batched_graph(int space, const void* base, size_t n, size_t dim, int maxM, int maxM0,
+                                 const int32_t* levels) {
+    orc_hnsw_t* g = graph_new(space, base, n, dim, maxM, maxM0);
+    for (size_t i = 0; i < n; ++i) node_alloc(g, (int)i, levels[i]);
+    return g;
+}
+
+orc_hnsw_t* orc_hnsw_build_batched_state(int space, const void* base, size_t n, size_t dim, int M, int maxM, int maxM0,
+                                         int efConstruction, int delaunay_type, int batch_div, int max_batch,
+                                         size_t cut) {
+    if (n == 0) return graph_new(space, base, 0, dim, maxM, maxM0);
+    const bparams P = {M, efConstruction, delaunay_type, batch_div > 0 ? batch_div : 16, max_batch > 0 ? max_batch : 4096,
+                       cut, cut};
+    int32_t* draws = (int32_t*)malloc(n * sizeof(int32_t));
+    orc_random_levels(0, 1.0 / log(1.0 * M), 0, n, draws);
+    orc_hnsw_t* g = batched_graph(space, base, n, dim, maxM, maxM0, draws);
+    free(draws);
+    batched_pass(g, &P, 0, NULL, NULL);
+    return g;
+}
+
+orc_hnsw_t* orc_hnsw_build_batched(int space, const void* base, size_t n, size_t dim, int M, int maxM, int maxM0,
+                                   int efConstruction, int delaunay_type, int post, int batch_div, int max_batch,
+                                   size_t cut, orc_batched_stats* st, int32_t* out_batch) {
+    if (st) memset(st, 0, sizeof(*st));
+    if (n == 0) return graph_new(space, base, 0, dim, maxM, maxM0);
+    const bparams P = {M, efConstruction, delaunay_type, batch_div > 0 ? batch_div : 16, max_batch > 0 ? max_batch : 4096,
+                       cut, 0};
+    const int two = post != 0 && n > 1;
+    int32_t* draws = (int32_t*)malloc((two ? 2 * n : n) * sizeof(int32_t));
+    orc_random_levels(0, 1.0 / log(1.0 * M), 0, two ? 2 * n : n, draws); /* hnsw.cc:203, init.cc:34-38 */
+    orc_hnsw_t* g = batched_graph(space, base, n, dim, maxM, maxM0, draws);
+    g->M = M;
+    g->efC = efConstruction;
+    g->delaunay = delaunay_type;
+    batched_pass(g, &P, 0, st, two ? NULL : out_batch);
+    if (!two) {
+        free(draws);
+        return g;
+    }
+    /* post = 1, 2 (hnsw.cc:251-330): once more in the order 0, n-1, ..., 1 with the stream's next n levels */
+    int32_t* levels2 = (int32_t*)malloc(n * sizeof(int32_t));
+    levels2[0] = draws[n];
+    for (size_t pos = 1; pos < n; ++pos) levels2[n - pos] = draws[n + pos];
+    orc_hnsw_t* g2 = batched_graph(space, base, n, dim, maxM, maxM0, levels2);
+    g2->M = M;
+    g2->efC = efConstruction;
+    g2->delaunay = delaunay_type;
+    orc_batched_stats st2;
+    memset(&st2, 0, sizeof(st2));
+    batched_pass(g2, &P, 1, &st2, out_batch);
+    if (st) {
+        st->second_pass_batches = st2.batches;
+        st->second_pass_largest_batch = st2.largest_batch;
+    }
+    /* new level-0 lists: the second graph's entries, then the first graph's that are not among them */
+    const size_t uw = 2 * (size_t)maxM0 + 2;
+    int32_t* un = (int32_t*)calloc(n * uw, sizeof(int32_t));
+    bcand* ranked = (bcand*)malloc(uw * sizeof(bcand));
+    bcand* kept = (bcand*)malloc(uw * sizeof(bcand));
+    int longest = 0;
+    for (size_t i = 0; i < n; ++i) {
+        int32_t* U = un + i * uw;
+        const int32_t *A = g2->links[i], *B = g->links[i];
+        int nu = A[0];
+        memcpy(U + 1, A + 1, (size_t)nu * sizeof(int32_t));
+        if (i != 0) /* hnsw.cc:281 */
+            for (int j = 1; j <= B[0]; ++j) {
+                int fresh = 1;
+                for (int k = 1; k <= A[0]; ++k) fresh &= A[k] != B[j];
+                if (fresh) U[1 + nu++] = B[j];
+            }
+        if (post == 2 && i != 0 && nu > 0) {
+            for (int j = 0; j < nu; ++j) {
+                ranked[j].d = bdist(g, (int)i, U[1 + j]);
+                ranked[j].id = j;
+            }
+            qsort(ranked, (size_t)nu, sizeof(bcand), bcand_cmp_stable);
+            for (int j = 0; j < nu; ++j) ranked[j].id = U[1 + ranked[j].id];
+            int nk;
+            const bcand* res = ranked;
+            if (delaunay_type == 0 || nu < maxM0) nk = nu < maxM0 ? nu : maxM0;
+            else {
+                nk = batched_select(g, ranked, nu, maxM0, 1, kept, NULL);
+                res = kept;
+            }
+            for (int j = 0; j < nk; ++j) U[1 + j] = res[nk - 1 - j].id;
+            for (int j = nk; j < nu; ++j) U[1 + j] = 0;
+            nu = nk;
+        }
+        U[0] = nu;
+        if (nu > longest) longest = nu;
+    }
+    const int newM0 = post == 1 ? (longest > 1 ? longest : 1) : maxM0;
+    if (st && post == 1 && newM0 > maxM0) st->post1_widened = newM0;
+    orc_hnsw_t* gr = batched_graph(space, base, n, dim, maxM, newM0, levels2);
+    gr->M = M;
+    gr->efC = efConstruction;
+    gr->delaunay = delaunay_type;
+    gr->maxlevel = g2->maxlevel;
+    gr->enterpoint = g2->enterpoint;
+    for (size_t i = 0; i < n; ++i) {
+        memcpy(gr->links[i], un + i * uw, (size_t)(un[i * uw] + 1) * sizeof(int32_t));
+        for (int l = 1; l <= levels2[i]; ++l)
+            memcpy(node_links(gr, (int)i, l), node_links(g2, (int)i, l), (size_t)(maxM + 1) * sizeof(int32_t));
+    }
+    free(un);
+    free(ranked);
+    free(kept);
+    free(levels2);
+    free(draws);
+    orc_hnsw_free(g);
+    orc_hnsw_free(g2);
+    return gr;
+}

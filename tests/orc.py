@@ -73,8 +73,31 @@ def lib():
                                   vp, vp, vp, vp, vp]
     L.orc_random_levels.restype = None
     L.orc_random_levels.argtypes = [C.c_uint32, C.c_double, C.c_int, C.c_size_t, vp]
+    L.orc_hnsw_build_batched.restype = vp
+    L.orc_hnsw_build_batched.argtypes = [C.c_int, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp]
+    L.orc_hnsw_build_batched_state.restype = vp
+    L.orc_hnsw_build_batched_state.argtypes = [C.c_int, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]
+    L.orc_hnsw_maxM0.restype = C.c_int
+    L.orc_hnsw_maxM0.argtypes = [vp]
+    L.orc_hnsw_build_distance.restype = C.c_double
+    L.orc_hnsw_build_distance.argtypes = [vp, C.c_int, C.c_int]
     _lib = L
     return L
+
+
+class BatchedStats(C.Structure):
+    """orc_batched_stats: the witness counters of orc_hnsw_build_batched (oracle/knn_oracle.h)"""
+    _fields_ = [(name, C.c_int64) for name in (
+        "batches", "largest_batch", "batches_at_cap", "batches_at_cut", "promotions_in_batch", "upper_slices_ge2",
+        "mates", "upper_mates", "mates_truncated", "merged_cut", "cand_lists_gt64", "short_lists_kept",
+        "most_requests_one_target", "targets_ge2_requests", "shrinks", "longest_list_shrunk", "h1_topups_select",
+        "h1_topups_shrink", "targets_gt_nodes_before", "ties_merge", "ties_link", "second_pass_batches",
+        "second_pass_largest_batch", "post1_widened")]
+
+    def as_dict(self):
+        return {name: int(getattr(self, name)) for name, _ in self._fields_}
 
 
 def _ptr(a):
@@ -124,6 +147,39 @@ class HnswGraph:
         h = lib().orc_hnsw_build(SPACES[space], _ptr(base), base.shape[0], base.shape[1], M, maxM,
                                  maxM0, efConstruction, delaunay_type, seed, log_variant)
         return cls(h, space, base, maxM, maxM0)
+
+    @classmethod
+    def build_batched(cls, space, base, M=16, efConstruction=200, maxM=None, maxM0=None, delaunay_type=2, post=0,
+                      batch_div=0, max_batch=0, cut=0):
+        """The batched GPU builder's graph, restated sequentially (orc_hnsw_build_batched).  The graph carries
+        .stats (dict of witness counters) and .batch ([n, 2]: batch number and index in the batch of every node, last
+        pass); .maxM0 is the graph's own (post = 1 changes it)."""
+        base = _rows(space, base)
+        maxM = M if maxM is None else maxM
+        maxM0 = 2 * M if maxM0 is None else maxM0
+        st = BatchedStats()
+        batch = np.zeros((max(base.shape[0], 1), 2), np.int32)
+        h = lib().orc_hnsw_build_batched(SPACES[space], _ptr(base), base.shape[0], base.shape[1], M, maxM, maxM0,
+                                         efConstruction, delaunay_type, post, batch_div, max_batch, cut,
+                                         C.byref(st), _ptr(batch))
+        g = cls(h, space, base, maxM, lib().orc_hnsw_maxM0(h))
+        g.stats, g.batch = st.as_dict(), batch[:base.shape[0]]
+        return g
+
+    @classmethod
+    def batched_state_at(cls, space, base, cut, M=16, efConstruction=200, maxM=None, maxM0=None, delaunay_type=2,
+                         batch_div=0, max_batch=0):
+        """what the first pass of build_batched(..., cut=cut) has built when it reaches position `cut`: all rows are
+        there, positions >= cut with empty lists"""
+        base = _rows(space, base)
+        maxM = M if maxM is None else maxM
+        maxM0 = 2 * M if maxM0 is None else maxM0
+        h = lib().orc_hnsw_build_batched_state(SPACES[space], _ptr(base), base.shape[0], base.shape[1], M, maxM,
+                                               maxM0, efConstruction, delaunay_type, batch_div, max_batch, cut)
+        return cls(h, space, base, maxM, maxM0)
+
+    def build_distance(self, a, b):
+        return lib().orc_hnsw_build_distance(self.h, int(a), int(b))
 
     @classmethod
     def from_arrays(cls, space, base, maxM, maxM0, maxlevel, enterpoint, levels, links0, up_off,

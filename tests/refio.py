@@ -37,7 +37,7 @@ def parse_optimized_index(path):
     pos = hdr + n * mem_per_obj
     levels = np.zeros(n, np.int32)
     up_off = np.full(n, -1, np.int64)
-    chunks, cur = [], 0
+    chunks, raw_chunks, cur = [], [], 0
     for i in range(n):
         (nbytes,) = struct.unpack_from("<I", raw, pos)
         pos += 4
@@ -45,6 +45,7 @@ def parse_optimized_index(path):
             lv = nbytes // ((maxM + 1) * 4)
             levels[i] = lv
             arr = np.frombuffer(raw, np.int32, nbytes // 4, pos).reshape(lv, maxM + 1).copy()
+            raw_chunks.append(arr.ravel())
             c = np.arange(maxM + 1)[None, :]
             arr = np.where(c <= arr[:, :1], arr, 0).astype(np.int32)
             up_off[i] = cur
@@ -53,11 +54,113 @@ def parse_optimized_index(path):
             pos += nbytes
     # this repo's library appends a 32-byte trailer naming the space (ignored by the reference)
     assert pos == len(raw) or (pos + 32 == len(raw) and raw[pos:pos + 8] == b"GFXKNNv1")
+    # (links0_raw / up_links_raw: the lists as the file has them, padding behind the counts included)
+    links0_raw = blk[:, off_l0:off_l0 + 4 * (maxM0 + 1)].copy().view(np.int32).reshape(n, maxM0 + 1)
     return dict(n=n, mem_per_obj=mem_per_obj, off_level0=off_l0, off_data=off_data,
                 maxlevel=maxlevel, enterpoint=enterpoint, maxM=maxM, maxM0=maxM0,
                 dist_func=dist_func, search_method=search_method, ids=ids, datalen=datalen,
-                payload=payload, links0=links0, levels=levels, up_off=up_off,
+                payload=payload, links0=links0, levels=levels, up_off=up_off, links0_raw=links0_raw,
+                up_links_raw=(np.concatenate(raw_chunks) if raw_chunks else np.zeros(0, np.int32)),
                 up_links=(np.concatenate(chunks) if chunks else np.zeros(0, np.int32)))
+
+
+def parse_regular_index(path):
+    """Parse the regular (non-optimized) index file, src/method/hnsw.cc:808-840: u32 0, u32 n, i32 maxlevel,
+    u32 enterpoint, u64 M, u64 maxM, u64 maxM0; per node u32 level, then per level u32 count and the ids.  -> the keys
+    of parse_optimized_index that a graph needs (the file has no padding: the slots behind a count are zero here)."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    flag, n, maxlevel, enterpoint, M, maxM, maxM0 = struct.unpack_from("<IIiIQQQ", raw, 0)
+    assert flag == 0, "not a regular index"
+    pos = 40
+    links0 = np.zeros((n, maxM0 + 1), np.int32)
+    levels = np.zeros(n, np.int32)
+    up_off = np.full(n, -1, np.int64)
+    chunks, cur = [], 0
+    for i in range(n):
+        (lv,) = struct.unpack_from("<I", raw, pos)
+        pos += 4
+        levels[i] = lv
+        if lv:
+            up_off[i] = cur
+        for l in range(lv + 1):
+            (c,) = struct.unpack_from("<I", raw, pos)
+            pos += 4
+            assert c <= (maxM0 if l == 0 else maxM), (i, l, c)
+            ids = np.frombuffer(raw, np.int32, c, pos)
+            pos += 4 * c
+            if l == 0:
+                links0[i, 0] = c
+                links0[i, 1:1 + c] = ids
+            else:
+                blk = np.zeros(maxM + 1, np.int32)
+                blk[0] = c
+                blk[1:1 + c] = ids
+                chunks.append(blk)
+                cur += maxM + 1
+    assert pos == len(raw) or (pos + 32 == len(raw) and raw[pos:pos + 8] == b"GFXKNNv1")
+    return dict(n=n, M=M, maxlevel=maxlevel, enterpoint=enterpoint, maxM=maxM, maxM0=maxM0, links0=links0,
+                levels=levels, up_off=up_off,
+                up_links=(np.concatenate(chunks) if chunks else np.zeros(0, np.int32)))
+
+
+def parse_index(path):
+    """either file format, by its first word"""
+    with open(path, "rb") as f:
+        (flag,) = struct.unpack("<I", f.read(4))
+    return parse_optimized_index(path) if flag == 1 else parse_regular_index(path)
+
+
+def _list_of(g, i, l):
+    """adjacency block [count, ids..., padding] of node i on level l in a parsed graph"""
+    if l == 0:
+        return g["links0"][i]
+    o = g["up_off"][i] + (l - 1) * (g["maxM"] + 1)
+    return g["up_links"][o:o + g["maxM"] + 1]
+
+
+def assert_graph_equals_restatement(got, want):
+    """`got`: a parsed index file (parse_index); `want`: the orc.HnswGraph of orc.HnswGraph.build_batched.  Levels, top
+    level, entry point, maxM0 and every list of every node on every level must be equal, entry by entry in list order,
+    and where the file carries padding behind a count it must be zeros.  On a difference the message names the
+    differing node that was inserted first, with its level, its batch and index in the batch, and both lists with the
+    distances to the node."""
+    n = want.n
+    assert got["n"] == n
+    wl = want.levels()
+    np.testing.assert_array_equal(got["levels"], wl, err_msg="levels")
+    assert (got["maxlevel"], got["enterpoint"], got["maxM0"], got["maxM"]) == \
+        (want.maxlevel, want.enterpoint, want.maxM0, want.maxM), "maxlevel / enterpoint / maxM0 / maxM"
+    wup_off, wup = want.flat_upper()
+    w = dict(links0=want.links0(), up_off=wup_off, up_links=wup, maxM=want.maxM)
+    if "links0_raw" in got:
+        raw = got["links0_raw"]
+        behind = np.arange(raw.shape[1])[None, :] > raw[:, :1]
+        assert not (raw * behind).any(), "level-0 padding behind the count is not zero"
+        rawu = got["up_links_raw"].reshape(-1, got["maxM"] + 1)
+        behind = np.arange(rawu.shape[1])[None, :] > rawu[:, :1]
+        assert not (rawu * behind).any(), "upper-level padding behind the count is not zero"
+    same0 = (got["links0"] == w["links0"]).all(axis=1)
+    same_up = np.array_equal(got["up_off"], wup_off) and np.array_equal(got["up_links"], wup)
+    if same0.all() and same_up:
+        return
+    bad = []
+    for i in range(n):
+        for l in range(int(wl[i]) + 1):
+            if not np.array_equal(_list_of(got, i, l), _list_of(w, i, l)):
+                bad.append((i, l))
+    assert bad, "upper-level offsets differ although every list is equal"
+    order = want.batch[:, 0].astype(np.int64) * (n + 1) + want.batch[:, 1]
+    i, l = min(bad, key=lambda t: (order[t[0]], -t[1]))
+
+    def show(L):
+        ids = L[1:1 + L[0]].tolist()
+        return "[" + ", ".join(f"{j}:{want.build_distance(i, j):.9g}" for j in ids) + "]" + \
+            ("" if not L[1 + L[0]:].any() else f" padding {L[1 + L[0]:].tolist()}")
+    raise AssertionError(
+        f"{len(bad)} lists differ from the restatement; first inserted: node {i} (level {int(wl[i])}) on level {l}, "
+        f"batch {int(want.batch[i, 0])}, index {int(want.batch[i, 1])} in the batch\n"
+        f"  built:       {show(_list_of(got, i, l))}\n  restatement: {show(_list_of(w, i, l))}")
 
 
 def run_ref_driver(space, method, base, queries, k, index_params="", query_params="", threads=1,

@@ -1,9 +1,13 @@
 """-m gpu: batched HNSW construction on the GPU (index parameter gpu_build=1).
 
 The batched build is not the reference's insertion schedule (a batch is searched against the graph
-before the batch), so it is held to structural invariants of Hnsw::add / addFriendlevel and to
-search quality: recall of the GPU-built graph must be on par with the reference-order host build
-(which test_cabi_cpu.py proves equal to the reference's graph) at the same parameters."""
+before the batch), so the reference's graph is no yardstick for it.  Its own rule is: the exact check is
+tests/test_gpu_hnsw_build_exact.py, which compares the built graph list for list with a sequential
+restatement of the batched rule on inputs whose f32 arithmetic is exact.  This file holds what that
+check does not reach -- production-like float data, large graphs, angulardist -- to the structural
+invariants of Hnsw::add / addFriendlevel, to determinism and to search quality: recall of the GPU-built
+graph must be on par with the reference-order host build (which test_cabi_cpu.py proves equal to the
+reference's graph) at the same parameters."""
 import numpy as np
 import pytest
 

@@ -2,10 +2,12 @@
 maxM0 <= 254), selection heuristic 1 (delaunay_type=1) and the post-processing (post=1, 2) -- and
 Index.graphBuilder(), which tells which builder made the graph.
 
-Like tests/test_gpu_hnsw_build.py: the batched build is not the reference's insertion schedule, so it is held to the
-structural invariants of Hnsw::add / addFriendlevel, to determinism and to search quality on par with the host
-one-thread build (the reference's own graph, tests/test_golden_v4.py).  Where the schedule IS the reference's (batches
-of one node, efConstruction >= n, no distance ties) the graphs must be equal.
+Like tests/test_gpu_hnsw_build.py: the batched build is not the reference's insertion schedule, so here, on Gaussian
+float rows at 8000 nodes, it is held to the structural invariants of Hnsw::add / addFriendlevel, to determinism and to
+search quality on par with the host one-thread build (the reference's own graph, tests/test_golden_v4.py).  Where the
+schedule IS the reference's (batches of one node, efConstruction >= n, no distance ties) the graphs must be equal.  The
+exact check of the batched rule itself -- wide lists, heuristic 1 and both post modes with batches of many nodes, list
+order included -- is tests/test_gpu_hnsw_build_exact.py.
 
 One data set (iid Gaussian, D = 32: lists fill up to maxM0) and one build per configuration, shared by the tests."""
 import numpy as np
