@@ -96,8 +96,9 @@ typedef struct {
                               2 adaptive int8, 3 int8 fast path; 4 = HNSW; 5 = HNSW with the walk on the fp16 copy
                               of the rows and an f32 re-rank (gpu_rows=f16), and the brute-force scan for k > 512;
                               6 = l1 fast path (8-bit SAD filter, exact f32 re-rank); 7 = HNSW under a filter whose rows
-                              were scanned exactly instead of walked (nmslib_gpu_filter_create).  A filtered batch on an
-                              exact-scan index reports the path it took over the allowed rows */
+                              were scanned exactly instead of walked (nmslib_gpu_filter_create); 8 = HNSW with the filter and
+                              the tombstones tested inside the walk (query-time parameter gpu_inwalk=1).  A filtered batch
+                              on an exact-scan index reports the path it took over the allowed rows */
     /* fast paths, last slice of the last batch (reading them waits for the stream): query tiles in the slice, tiles the
        threshold kernel sent through the split-bf16-product scan instead of the one-product scan (float rows only), and
        tiles whose verification failed and were redone by the adaptive kernel */
@@ -141,6 +142,14 @@ nmslib_error_t nmslib_gpu_string_hnsw_links(nmslib_index_handle_t index, size_t 
  * hnsw: marked rows stay in the graph as stepping stones; a batch asked for k results is the first k unmarked entries of the
  * search for max(efSearch, k) results, so a count can fall below k when most of what the search finds is marked.  The call
  * is ordered with the index's other work like every host entry: a batch enqueued before it sees the old state.
+ * hnsw with the query-time parameter gpu_inwalk=1 (nmslib_set_query_time_params; 0 or 1, default 0, stays as set; any other
+ *   value -> NMSLIB_ERROR_INVALID_ARGUMENT; an unknown parameter for brute_force, seq_search and string or sparse graphs):
+ *   a marked row does not count against efSearch.  The walk keeps two sets: the max(efSearch, k) closest unmarked rows found
+ *   and the closest rows not yet expanded (at most 1024), marked ones among them; it goes on until no row left to expand is
+ *   closer than the farthest result, so counts stay at k while the graph around the query holds k unmarked rows.  Served
+ *   for max(efSearch, k) <= 1024 and maxM0 <= 254 on the f32 rows (also under gpu_rows=f16 and algoType=old: the rule is
+ *   its own algorithm), last_path 8; any other batch runs the two stages above.  An index without marked rows, searched
+ *   without a filter, runs what it runs without the parameter.
  * brute_force / seq_search: the index is prepared again at its next use, over the unmarked rows only. */
 nmslib_error_t nmslib_gpu_delete_ids(nmslib_index_handle_t index, const int32_t* ids, size_t count, size_t* marked);
 /* Rows of this index that are marked deleted. */
@@ -197,6 +206,11 @@ nmslib_error_t nmslib_gpu_consolidate(nmslib_index_handle_t index, size_t* remov
  *   raises the bound for a caller who has measured.  A scan whose keys and query would not fit into the 160 KB of LDS of a
  *   workgroup (4096 rows of more than 32 252 dimensions) is left to the walk.  The scan reports ndc = m, hops = hops_up = 0 through
  *   nmslib_gpu_last_batch_counters, and last_path 7.
+ *   With the query-time parameter gpu_inwalk=1 (see nmslib_gpu_delete_ids) a batch that would walk tests the filter and the
+ *   tombstones inside the walk instead: rows that are not allowed are stepping stones and do not count against efSearch, the
+ *   results are the walk's max(efSearch, k) closest allowed live rows cut to k, ordered by (distance, position), and
+ *   last_path is 8.  The exact scan keeps precedence where the rule above chooses it.  Selective filters then return k
+ *   results at the price of a longer walk (DESIGN.md 6 has the measurements); the choice is the caller's switch.
  * brute_force / seq_search: the filter is the index of the allowed live rows alone, gathered and prepared in HBM (no row
  *   crosses PCIe); a batch takes every path such an index would take.  When the index has been prepared again since (rows
  *   added or deleted), the next filtered batch gathers and prepares again before it runs and may block; every other batch

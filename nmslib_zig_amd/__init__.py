@@ -368,7 +368,10 @@ class Index:
     def setQueryTimeParams(self, **params):
         """hnsw: efSearch / ef, algoType; engine extensions gpu_rows="f32"|"f16" (the walk reads an fp16 copy of the rows,
         the result is re-ranked in f32; also an index parameter of buildIndex) and gpu_rerank=R (how many entries of the
-        final array are re-ranked).  The two extensions stay as set until set again."""
+        final array are re-ranked); gpu_inwalk=0|1 (1: an index with deleted rows and a filtered batch test eligibility inside
+        the walk, so that deleted and disallowed rows do not count against efSearch and selective filters return k results;
+        served for max(efSearch, k) <= 1024 and maxM0 <= 254, on the f32 rows; stats()["last_path"] == 8).  The extensions
+        stay as set until set again."""
         p = Params(self.alloc, **params)
         try:
             _check(lib().nmslib_set_query_time_params(self.h, p.h), self.alloc)
@@ -539,8 +542,9 @@ class Index:
         """nmslib_gpu_delete_ids: marks every stored row that carries one of `ids` as deleted -> rows newly marked.  Later
         k-NN and range results never contain them; positions do not move, and a row added later under a deleted id is live
         (update = deleteIds([id]), then add the new row under it).  hnsw: results are the first k live entries of the search
-        for max(efSearch, k), so counts can fall below k under heavy deletion; brute_force / seq_search: the index is
-        prepared again at its next use."""
+        for max(efSearch, k), so counts can fall below k under heavy deletion -- unless setQueryTimeParams(gpu_inwalk=1),
+        under which a deleted row does not count against efSearch; brute_force / seq_search: the index is prepared again at
+        its next use."""
         a = np.ascontiguousarray(ids, np.int32).reshape(-1)
         m = C.c_size_t()
         _check(lib().nmslib_gpu_delete_ids(self.h, a.ctypes.data if a.size else None, a.size, C.byref(m)), self.alloc)
@@ -583,7 +587,8 @@ class Index:
     def knnQueryBatchFiltered(self, flt, queries, k):
         """nmslib_gpu_knn_query_batch_filtered: knnQueryBatch over the rows the filter allows -> ids [Q,k], dists [Q,k],
         counts [Q].  hnsw: counts can fall below k when few of the rows the search finds are allowed; a filter of at most
-        max(efSearch, k, scan_rows) rows is answered exactly."""
+        max(efSearch, k, scan_rows) rows is answered exactly; setQueryTimeParams(gpu_inwalk=1) filters inside the walk
+        instead, which keeps counts at k under selective filters."""
         q = np.ascontiguousarray(queries, np.uint8 if self.data_type == "DenseUInt8Vector" else np.float32)
         nq = q.shape[0]
         ids = np.full((nq, k), -1, np.int32)

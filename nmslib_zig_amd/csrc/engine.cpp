@@ -443,6 +443,7 @@ void Engine::reset() {
     rows16_failed_ = false;
     rows_f16_index_ = rows_f16_ = false;
     rerank_ = 0;
+    inwalk_ = false;
 }
 
 size_t Engine::memory_usage() const {
@@ -517,6 +518,7 @@ void Engine::create_index(const std::vector<std::string>& params) {
                                                          std::to_string(bp.gpu_build_cut));
         rows_f16_index_ = rows_f16_ = f16;
         rerank_ = 0;
+        inwalk_ = false;
         if (defer && bp.gpu_build < 0) bp.gpu_build = 0;  // deferred upload = no device work now
         bp_ = bp;
         ef_ = 200;  // the shim forces efSearch=200 per query (nmslib_c.cpp:330,986)
@@ -578,7 +580,13 @@ void Engine::set_query_params(const std::vector<std::string>& params) {
         long long rerank = 0;
         ps.get("gpu_rows", gpu_rows);
         ps.get("gpu_rerank", rerank);
+        // (the dense spaces' in-walk kernel: an unknown parameter on a string or a sparse graph)
+        const bool has_inwalk = !str_space_ && !sparse_ && ps.has("gpu_inwalk");
+        std::string inwalk = "0";
+        if (has_inwalk) ps.get("gpu_inwalk", inwalk);
         ps.check_unused();
+        if (has_inwalk && inwalk != "0" && inwalk != "1")
+            throw EngineError(Err::InvalidArgument, "gpu_inwalk must be 0 or 1, got '" + inwalk + "'");
         if (ef < 1) throw std::runtime_error("ef must be positive");
         const bool f16 = has_rows && parse_gpu_rows(gpu_rows);
         if (f16) check_rows16_served();
@@ -589,6 +597,7 @@ void Engine::set_query_params(const std::vector<std::string>& params) {
         algo_ = algo;
         if (has_rows) rows_f16_ = f16;
         if (has_rerank) rerank_ = (int)std::min<long long>(rerank, INT32_MAX);
+        if (has_inwalk) inwalk_ = inwalk == "1";
     } else {
         ps.check_unused();  // SeqSearch has no query-time parameters
     }
@@ -1033,6 +1042,7 @@ void Engine::knn_sharded(const void* d_queries, size_t nq, size_t elem_count, si
         c.algo_ = algo_;
         c.rows_f16_ = rows_f16_;
         c.rerank_ = rerank_;
+        c.inwalk_ = inwalk_;
         hip_check(hipStreamWaitEvent(c.stream_, shard_ready_, 0), "hipStreamWaitEvent");
         const void* q = d_queries;
         if (c.device_ != device_) {

@@ -454,6 +454,11 @@ class Engine {
     // allowed (allow: a filter's bits over n_allow positions, or nullptr)
     void knn_hnsw_two_stage(const void* d_queries, size_t nq, size_t k, const uint32_t* allow, size_t n_allow,
                             const HnswOut& out, hipStream_t stream);
+    // gpu_inwalk=1: the same two tests inside the walk, in place of the two stages, where the kernel serves
+    // the batch (hnsw_inwalk_plan.hpp); last_path 8
+    bool inwalk_serves(size_t k) const;
+    void knn_hnsw_inwalk(const void* d_queries, size_t nq, size_t k, const uint32_t* allow, size_t n_allow, const HnswOut& out,
+                         hipStream_t stream);
     void knn_hnsw_old(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, const HnswOut& out,
                       hipStream_t stream);
     // Hnsw::Search, hnsw.cc:724: algoType=old, or hybrid with ef >= 1000, runs SearchOld
@@ -518,10 +523,11 @@ class Engine {
     std::vector<float> graph_rows_;  // rows as stored inside a loaded index (cosine: normalised)
     int ef_ = 200;                   // the shim's default (nmslib_c.cpp:330)
     std::string algo_ = "hybrid";
-    // engine extensions, index-time gpu_rows and query-time gpu_rows / gpu_rerank: they stay as set until set again
+    // engine extensions, index-time gpu_rows and query-time gpu_rows / gpu_rerank / gpu_inwalk: they stay as set until set again
     bool rows_f16_index_ = false;    // make the fp16 copy at finalize
     bool rows_f16_ = false;          // walk the fp16 copy (made at the next batch if there is none)
     int rerank_ = 0;                 // entries of the walk's sorted array that are re-ranked in f32; 0 = all
+    bool inwalk_ = false;            // deleted rows and filters are tested inside the walk (hnsw_inwalk_kernels.hip)
     bool rows16_failed_ = false;     // the copy did not fit into HBM: f32 until the rows change
     int rows16_exp_ = 0;             // the copy's scale is 2^rows16_exp_, chosen for rows16_max_ = the largest |element|
     float rows16_max_ = 0;

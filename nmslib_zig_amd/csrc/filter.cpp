@@ -187,7 +187,8 @@ void Engine::filter_forget_flags(const Filter& f) {
 }
 
 // One slice of a filtered HNSW batch.  Subset route: hnsw_subset_knn_kernel over the filter's list (last_path 7).  Walk route:
-// the two stages of hnsw_search.cpp with the filter's bits; the counters are the walk's.
+// the two stages of hnsw_search.cpp with the filter's bits, or under gpu_inwalk=1 its in-walk search (last_path 8); the counters
+// are the walk's.
 void Engine::knn_hnsw_filtered(Filter& f, const void* d_queries, size_t nq, size_t k, const HnswOut& out, hipStream_t stream) {
     if (filter_route(f.m, (size_t)ef_, k, f.scan_rows, hnsw_subset_query_bytes(dg_)) == FilterRoute::Subset) {
         const uint32_t* tomb = n_dead_ > 0 ? d_tomb_.as<uint32_t>() : nullptr;
@@ -202,7 +203,8 @@ void Engine::knn_hnsw_filtered(Filter& f, const void* d_queries, size_t nq, size
         prof_end(stream);
         return;
     }
-    knn_hnsw_two_stage(d_queries, nq, k, f.d_allow.as<uint32_t>(), f.n, out, stream);
+    if (inwalk_serves(k)) knn_hnsw_inwalk(d_queries, nq, k, f.d_allow.as<uint32_t>(), f.n, out, stream);
+    else knn_hnsw_two_stage(d_queries, nq, k, f.d_allow.as<uint32_t>(), f.n, out, stream);
 }
 
 }  // namespace gfxknn

@@ -1,13 +1,14 @@
 // The dense HNSW search of one slice of a batch (knn_device cuts the batch and owns its HnswOut): which kernels answer it --
 // the LDS kernels, the fp16 walk with its f32 re-rank, the HBM-array kernel, SearchOld -- and, for an index with deleted rows
-// or a filtered batch, the two stages around them.  The workspaces are HnswSearchWs; the resident side
-// of the graph stays in engine.cpp.
+// or a filtered batch, the two stages around them or, under gpu_inwalk=1, the search that filters
+// inside the walk (4.6e).  The workspaces are HnswSearchWs; the resident side of the graph stays in engine.cpp.
 #include <algorithm>
 #include <climits>
 #include <cstdlib>
 
 #include "engine.hpp"
 #include "filter_plan.hpp"
+#include "hnsw_inwalk_plan.hpp"
 
 namespace gfxknn {
 
@@ -43,8 +44,34 @@ uint32_t* Engine::cleared_bitset(size_t m, size_t words, hipStream_t stream) {
 }
 
 void Engine::knn_hnsw(const void* d_queries, size_t nq, size_t k, const HnswOut& out, hipStream_t stream) {
-    if (n_dead_ > 0) knn_hnsw_two_stage(d_queries, nq, k, nullptr, 0, out, stream);
+    if (n_dead_ > 0 && inwalk_serves(k)) knn_hnsw_inwalk(d_queries, nq, k, nullptr, 0, out, stream);
+    else if (n_dead_ > 0) knn_hnsw_two_stage(d_queries, nq, k, nullptr, 0, out, stream);
     else hnsw_walk(false, d_queries, nq, k, out, stream);
+}
+
+// gpu_inwalk=1 and a batch the kernel serves; any other takes the two stages below
+bool Engine::inwalk_serves(size_t k) const {
+    return inwalk_ && inwalk_served((size_t)ef_, k, (size_t)hnsw_nbcap(dg_), hnsw_subset_query_bytes(dg_));
+}
+
+// Deleted rows and the walk route of a filtered batch with the tests inside the walk: one launch per slice on
+// the f32 rows, whatever algoType and gpu_rows say.  The visited sets are HBM bitsets, so the batch is cut where they would
+// outgrow the budget; all slices are one timed interval.
+void Engine::knn_hnsw_inwalk(const void* d_queries, size_t nq, size_t k, const uint32_t* allow, size_t n_allow,
+                             const HnswOut& out, hipStream_t stream) {
+    const uint32_t* tomb = n_dead_ > 0 ? d_tomb_.as<uint32_t>() : nullptr;
+    const size_t words = (d_n_ + 31) / 32, qbytes = dim_ * elem_bytes();
+    last_path = 8;
+    have_counters_ = true;
+    hnsw_fix_valid_ = false;
+    hnsw_for_slices(nq, words * 4, [&](size_t q0, size_t m) {
+        uint32_t* bitset = cleared_bitset(m, words, stream);
+        if (q0 == 0) prof_begin(stream);
+        hip_check(launch_hnsw_inwalk(dg_, (int)m, (int)k, ef_, static_cast<const char*>(d_queries) + q0 * qbytes, bitset, words,
+                                     allow, (int)n_allow, tomb, out.at(q0, k), stream),
+                  "hnsw_inwalk");
+        if (q0 + m == nq) prof_end(stream);
+    });
 }
 
 // Deleted rows and the walk route of a filtered batch (4.6d; allow: the filter's bits over n_allow positions).

@@ -350,4 +350,60 @@ __device__ __forceinline__ void frontier_finish(FrontierLoads<SPACE, ROW>& L, co
     if (m > 32) frontier_distances<SPACE, ROW>(g, qv, qb, qnorm, nbr + 32, nd + 32, m - 32, lane);
 }
 
+// ---- adjacency lists of any length (round 3: M / maxM > 62, maxM0 > 126 -- hnsw.cc:189-208 takes any M) -------------
+// The LDS search kernels give a list one or two words per lane.  SearchOld, the HBM-array SearchV1Merge and the in-walk kernel
+// walk longer lists in chunks of 64 neighbours (list order kept: neighbour i is list word i + 1); their frontier arrays hold
+// hnsw_nbcap(g) entries.
+// unvisited neighbours of list[] -> nbr[0 .. m), returns m
+template <class Visit>
+__device__ __forceinline__ int collect_unvisited_any(const int* list, int* nbr, int lane, Visit&& visit) {
+    const int cnt = __builtin_amdgcn_readfirstlane(list[0]);
+    int m = 0;
+    for (int c0 = 0; c0 < cnt; c0 += 64) {
+        const int i = c0 + lane;
+        const int nb = i < cnt ? list[i + 1] : 0;
+        bool isn = false;
+        if (i < cnt) isn = visit((uint32_t)nb);
+        const u64 mask = __ballot(isn);
+        if (isn) nbr[m + __popcll(mask & ((1ull << lane) - 1ull))] = nb;
+        m += __popcll(mask);
+    }
+    return m;
+}
+// one greedy step on an upper level over a list of any length: the FIRST neighbour attaining the minimum, if it is closer
+// than curdist (the sequential "if (d < curdist)" scan of hnsw.cc / hnsw_distfunc_opt.cc:176-196).  Returns the list length.
+template <int SPACE, class ROW = float>
+__device__ __forceinline__ int greedy_step_any(const HnswDeviceGraph& g, const int* list, const float* qv, const uint8_t* qb,
+                                               int qnorm, int* nbr, float* nd, int lane, int& cur, float& curdist,
+                                               bool& changed) {
+    const int cnt = __builtin_amdgcn_readfirstlane(list[0]);
+    for (int c0 = 0; c0 < cnt; c0 += 64)
+        if (c0 + lane < cnt) nbr[c0 + lane] = list[c0 + lane + 1];
+    __builtin_amdgcn_wave_barrier();
+    if (cnt > 0) {
+        frontier_distances<SPACE, ROW>(g, qv, qb, qnorm, nbr, nd, cnt, lane);
+        u64 key = ~0ull;
+        for (int c0 = 0; c0 < cnt; c0 += 64) {
+            const int i = c0 + lane;
+            if (i < cnt) {
+                const u64 k2 = ((u64)f32_ord(nd[i]) << 32) | (uint32_t)i;
+                key = k2 < key ? k2 : key;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const u64 other = __shfl_xor(key, o, 64);
+            key = other < key ? other : key;
+        }
+        const float dmin = ord_f32((uint32_t)(key >> 32));
+        if (dmin < curdist) {
+            curdist = dmin;
+            cur = nbr[(uint32_t)key];
+            changed = true;
+        }
+    }
+    __builtin_amdgcn_wave_barrier();
+    return cnt;
+}
+
 }  // namespace gfxknn

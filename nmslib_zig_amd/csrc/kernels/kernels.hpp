@@ -433,6 +433,15 @@ hipError_t launch_hnsw_rerank(const HnswDeviceGraph& g, int nq, int k, int cap, 
 hipError_t launch_hnsw_keep_topk(const int32_t* cand, const float* cand_d, const int32_t* cand_n, int nq, int cap,
                                  const uint32_t* allow, int n_allow, const uint32_t* tomb, int n, const int32_t* ext_ids,
                                  int k, const HnswOut& out, hipStream_t s);
+// The same two tests inside the walk (hnsw_inwalk_kernels.hip): disallowed and deleted nodes are stepping
+// stones, only eligible ones enter the result set of cap = max(ef, k) entries, and the walk goes on until that set is full.
+// One wave per query on the f32 rows (u8 rows: the integer distance); bitset [nq][bitset_words >= ceil(n / 32)], cleared by
+// the caller; allow / tomb as above (both optional).  k results with external ids in (distance, position) order, -1 / +inf
+// padding, the count and the walk's counters go to out.  Served shapes: inwalk_served (hnsw_inwalk_plan.hpp); any other is
+// hipErrorInvalidValue.
+hipError_t launch_hnsw_inwalk(const HnswDeviceGraph& g, int nq, int k, int ef, const void* queries, uint32_t* bitset,
+                              size_t bitset_words, const uint32_t* allow, int n_allow, const uint32_t* tomb, const HnswOut& out,
+                              hipStream_t s);
 // SearchOld; ws_a / ws_r / ws_heap: the per-query HBM workspaces above (may be unused)
 hipError_t launch_hnsw_search_old(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries, uint32_t* bitset,
                                   void* ws_a, void* ws_r, void* ws_heap, const HnswOut& out, hipStream_t s);

@@ -113,7 +113,8 @@ class Index {
         check(nmslib_create_index(h_, p ? p->handle() : nullptr, print_progress ? 1 : 0), alloc_, "buildIndex");
     }
     // hnsw: efSearch / ef, algoType; engine extensions gpu_rows=f32|f16 (walk an fp16 copy of the rows, f32 re-rank) and
-    // gpu_rerank=R (entries of the final array that are re-ranked), both staying as set until set again
+    // gpu_rerank=R (entries of the final array that are re-ranked); gpu_inwalk=0|1 (1: deleted rows and filters are tested
+    // inside the walk and do not count against efSearch); all staying as set until set again
     void setQueryTimeParams(const Params& p) { check(nmslib_set_query_time_params(h_, p.handle()), alloc_, "setQueryTimeParams"); }
 
     QueryResult knnQuery(const void* query, size_t elem_count, size_t k) {
