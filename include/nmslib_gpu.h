@@ -97,8 +97,9 @@ typedef struct {
                               of the rows and an f32 re-rank (gpu_rows=f16), and the brute-force scan for k > 512;
                               6 = l1 fast path (8-bit SAD filter, exact f32 re-rank); 7 = HNSW under a filter whose rows
                               were scanned exactly instead of walked (nmslib_gpu_filter_create); 8 = HNSW with the filter and
-                              the tombstones tested inside the walk (query-time parameter gpu_inwalk=1).  A filtered batch
-                              on an exact-scan index reports the path it took over the allowed rows */
+                              the tombstones tested inside the walk (query-time parameter gpu_inwalk=1); 9 = a batch with one
+                              filter per query (nmslib_gpu_knn_query_batch_filtered_each: its `routes` has the paths).  A filtered
+                              batch on an exact-scan index reports the path it took over the allowed rows */
     /* fast paths, last slice of the last batch (reading them waits for the stream): query tiles in the slice, tiles the
        threshold kernel sent through the split-bf16-product scan instead of the one-product scan (float rows only), and
        tiles whose verification failed and were redone by the adaptive kernel */
@@ -234,6 +235,40 @@ nmslib_error_t nmslib_gpu_knn_query_batch_filtered_device(nmslib_index_handle_t 
                                                           const void* d_queries, size_t query_count, size_t elem_count,
                                                           size_t k, int32_t* d_ids, float* d_dists, int32_t* d_counts,
                                                           void* stream);
+
+/* One filter per query: a batch whose queries belong to different filters
+ * of the same index -- tenants, categories, access lists -- in one call.  filter_of_query[q] is an index into filters
+ * [n_filters], or -1 = query q is unfiltered; the same filter may stand at several indices.  Row q of the results is what
+ * nmslib_gpu_knn_query_batch_filtered returns for query q under its filter (the unfiltered entries for -1), bit for bit, and
+ * on hnsw nmslib_gpu_last_batch_counters describes the batch in the caller's order.
+ *   filters and filter_of_query are host memory in both entries and are read before the call returns: the caller may free
+ *   them at once.  The device entry otherwise keeps the contract of nmslib_gpu_knn_query_batch_filtered_device (it only
+ *   enqueues; d_counts may be NULL); the host entry takes host pointers, counts may be NULL.
+ *   routes (host, [query_count], optional): per query the last_path the single-filter entry reports for the batch formed by
+ *   the queries of its filter -- hnsw: 4, 5, 7 or 8; exact scan: the path over the allowed rows; -1 queries: the unfiltered
+ *   entry's.  The routing is host arithmetic: every value is there when the call returns, in both entries.  last_path is 9
+ *   afterwards; the fast_tiles* and hnsw_redone statistics describe the part of the batch that ran last.
+ * hnsw: the batch is run in plan order -- unfiltered queries, then those of the filters that walk, then those of the filters
+ *   that are scanned exactly -- and costs one launch chain per such segment, whatever the number of filters: the kernels read
+ *   each query's filter from a table that is uploaded with the batch.  A batch that is not in that order already is gathered
+ *   into a workspace and its results gathered back (five small launches more).
+ * brute_force / seq_search: one exact scan per filter that has queries, over that filter's queries, on the index of its
+ *   allowed rows: the launch count grows with the number of distinct filters in the batch, and groups of fewer than 256
+ *   queries stay off the fast paths.  A filter whose index was prepared again gathers again first (may block).
+ * Checked before any device work: a NULL index, filter_of_query, queries or output, or filters with n_filters > 0 ->
+ * NMSLIB_ERROR_NULL_POINTER; an entry of filter_of_query outside [-1, n_filters) -> NMSLIB_ERROR_INVALID_ARGUMENT (the
+ * message names the query and the value); a stale filter or one of another index -> NMSLIB_ERROR_INVALID_ARGUMENT (the
+ * message names its index in filters); the index kinds nmslib_gpu_filter_create refuses -> its refusal.  query_count == 0 ->
+ * NMSLIB_SUCCESS, nothing is written.  On an error the outputs are untouched. */
+nmslib_error_t nmslib_gpu_knn_query_batch_filtered_each(nmslib_index_handle_t index, const nmslib_gpu_filter_t* filters,
+                                                        size_t n_filters, const int32_t* filter_of_query, const void* queries,
+                                                        size_t query_count, size_t elem_count, size_t k, int32_t* ids,
+                                                        float* dists, int32_t* counts, int32_t* routes);
+nmslib_error_t nmslib_gpu_knn_query_batch_filtered_each_device(nmslib_index_handle_t index, const nmslib_gpu_filter_t* filters,
+                                                               size_t n_filters, const int32_t* filter_of_query,
+                                                               const void* d_queries, size_t query_count, size_t elem_count,
+                                                               size_t k, int32_t* d_ids, float* d_dists, int32_t* d_counts,
+                                                               int32_t* routes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -184,6 +184,8 @@ def lib():
         "nmslib_gpu_filter_info": (C.c_int, [vp, C.POINTER(sz), C.POINTER(sz)]),
         "nmslib_gpu_knn_query_batch_filtered": (C.c_int, [vp, vp, vp, sz, sz, sz, vp, vp, vp]),
         "nmslib_gpu_knn_query_batch_filtered_device": (C.c_int, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp]),
+        "nmslib_gpu_knn_query_batch_filtered_each": (C.c_int, [vp, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp, vp]),
+        "nmslib_gpu_knn_query_batch_filtered_each_device": (C.c_int, [vp, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)   # AttributeError here = a declared symbol is not exported
@@ -213,7 +215,8 @@ ABI_SYMBOLS_GPU = ["nmslib_gpu_device_count", "nmslib_gpu_finalize",
                    "nmslib_gpu_string_hnsw_links", "nmslib_gpu_graph_builder", "nmslib_gpu_delete_ids",
                    "nmslib_gpu_deleted_rows", "nmslib_gpu_consolidate", "nmslib_gpu_filter_create",
                    "nmslib_gpu_filter_destroy", "nmslib_gpu_filter_info", "nmslib_gpu_knn_query_batch_filtered",
-                   "nmslib_gpu_knn_query_batch_filtered_device"]
+                   "nmslib_gpu_knn_query_batch_filtered_device", "nmslib_gpu_knn_query_batch_filtered_each",
+                   "nmslib_gpu_knn_query_batch_filtered_each_device"]
 
 
 class TrackingAllocator:
@@ -601,6 +604,41 @@ class Index:
     def knn_device_filtered(self, flt, d_queries_ptr, nq, dim, k, d_ids_ptr, d_dists_ptr, d_cnt_ptr=None, stream=None):
         _check(lib().nmslib_gpu_knn_query_batch_filtered_device(self.h, flt.h, d_queries_ptr, nq, dim, k, d_ids_ptr,
                                                                 d_dists_ptr, d_cnt_ptr, stream), self.alloc)
+
+    @staticmethod
+    def _filter_table(filters, filter_of_query, nq):
+        """The host arrays of a batch with one filter per query: the handles, the int32 entries."""
+        hs = (C.c_void_p * max(len(filters), 1))(*[f.h.value if isinstance(f.h, C.c_void_p) else f.h for f in filters])
+        fq = np.ascontiguousarray(filter_of_query, np.int32).reshape(-1)
+        if fq.size != nq:
+            raise ValueError("filter_of_query: one entry per query")
+        return hs, fq
+
+    def knnQueryBatchEachFiltered(self, filters, filter_of_query, queries, k, return_routes=False):
+        """nmslib_gpu_knn_query_batch_filtered_each: one batch whose query q runs under filters[filter_of_query[q]] (-1:
+        unfiltered) -> ids [Q,k], dists [Q,k], counts [Q] and, with return_routes, routes [Q]: per query the last_path
+        knnQueryBatchFiltered reports for its filter's queries.  Every row is what that call returns for the query.  hnsw: one
+        launch chain per route, whatever the number of filters; brute_force / seq_search: one scan per filter with queries."""
+        q = np.ascontiguousarray(queries, np.uint8 if self.data_type == "DenseUInt8Vector" else np.float32)
+        nq = q.shape[0]
+        hs, fq = self._filter_table(filters, filter_of_query, nq)
+        ids = np.full((nq, k), -1, np.int32)
+        ds = np.full((nq, k), np.inf, np.float32)
+        cnt = np.zeros(nq, np.int32)
+        routes = np.full(nq, -1, np.int32)
+        _check(lib().nmslib_gpu_knn_query_batch_filtered_each(self.h, hs if len(filters) else None, len(filters),
+                                                              fq.ctypes.data, q.ctypes.data, nq, q.shape[1], k, ids.ctypes.data,
+                                                              ds.ctypes.data, cnt.ctypes.data, routes.ctypes.data), self.alloc)
+        return (ids, ds, cnt, routes) if return_routes else (ids, ds, cnt)
+
+    def knn_device_each_filtered(self, filters, filter_of_query, d_queries_ptr, nq, dim, k, d_ids_ptr, d_dists_ptr,
+                                 d_cnt_ptr=None, stream=None, routes=None):
+        """nmslib_gpu_knn_query_batch_filtered_each_device: queries and results in device memory, filter_of_query (and
+        routes: an int32 array of nq entries, optional) on the host; both host arrays are read before the call returns."""
+        hs, fq = self._filter_table(filters, filter_of_query, nq)
+        _check(lib().nmslib_gpu_knn_query_batch_filtered_each_device(
+            self.h, hs if len(filters) else None, len(filters), fq.ctypes.data, d_queries_ptr, nq, dim, k, d_ids_ptr,
+            d_dists_ptr, d_cnt_ptr, routes.ctypes.data if routes is not None else None, stream), self.alloc)
 
     # -- metadata / stored data -------------------------------------------------------------------
     def getDistance(self, a, b):

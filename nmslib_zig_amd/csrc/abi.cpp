@@ -977,6 +977,53 @@ nmslib_error_t nmslib_gpu_knn_query_batch_filtered_device(nmslib_index_handle_t 
     });
 }
 
+// one filter per query: every check that needs no device comes first, in the engine
+static nmslib_error_t each_null_check(nmslib_index_handle_t handle, const nmslib_gpu_filter_t* filters, size_t n_filters,
+                                      const int32_t* filter_of_query, const void* queries, const int32_t* ids,
+                                      const float* dists, size_t elem_count, size_t k) {
+    if (!handle) FAIL(NMSLIB_ERROR_NULL_POINTER, "Invalid index");
+    if (!filters && n_filters > 0) FAIL(NMSLIB_ERROR_NULL_POINTER, "filters is NULL with a positive n_filters");
+    if (!filter_of_query || !queries || !ids || !dists)
+        FAIL(NMSLIB_ERROR_NULL_POINTER, "filter_of_query, queries, ids or dists is NULL");
+    if (k == 0 || elem_count == 0) FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "Invalid per-query filtered batch inputs");
+    return NMSLIB_SUCCESS;
+}
+
+nmslib_error_t nmslib_gpu_knn_query_batch_filtered_each(nmslib_index_handle_t handle, const nmslib_gpu_filter_t* filters,
+                                                        size_t n_filters, const int32_t* filter_of_query, const void* queries,
+                                                        size_t query_count, size_t elem_count, size_t k, int32_t* ids,
+                                                        float* dists, int32_t* counts, int32_t* routes) {
+    const nmslib_error_t rc = each_null_check(handle, filters, n_filters, filter_of_query, queries, ids, dists, elem_count, k);
+    if (rc != NMSLIB_SUCCESS) return rc;
+    Engine* e = H(handle)->engine;
+    return guarded(NMSLIB_ERROR_QUERY_EXECUTION_FAILED, "Per-query filtered KNN batch failed", [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        const int32_t *rid = nullptr, *rcnt = nullptr;
+        const float* rd = nullptr;
+        e->knn_host_each(reinterpret_cast<gfxknn::Filter* const*>(filters), n_filters, filter_of_query, queries, query_count,
+                         elem_count, k, &rid, &rd, &rcnt, routes);
+        if (query_count == 0) return;
+        std::memcpy(ids, rid, query_count * k * sizeof(int32_t));
+        std::memcpy(dists, rd, query_count * k * sizeof(float));
+        if (counts) std::memcpy(counts, rcnt, query_count * sizeof(int32_t));
+    });
+}
+
+nmslib_error_t nmslib_gpu_knn_query_batch_filtered_each_device(nmslib_index_handle_t handle, const nmslib_gpu_filter_t* filters,
+                                                               size_t n_filters, const int32_t* filter_of_query,
+                                                               const void* d_queries, size_t query_count, size_t elem_count,
+                                                               size_t k, int32_t* d_ids, float* d_dists, int32_t* d_counts,
+                                                               int32_t* routes, void* stream) {
+    const nmslib_error_t rc = each_null_check(handle, filters, n_filters, filter_of_query, d_queries, d_ids, d_dists, elem_count, k);
+    if (rc != NMSLIB_SUCCESS) return rc;
+    Engine* e = H(handle)->engine;
+    return guarded(NMSLIB_ERROR_QUERY_EXECUTION_FAILED, "Per-query filtered KNN device batch failed", [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        e->knn_device_each(reinterpret_cast<gfxknn::Filter* const*>(filters), n_filters, filter_of_query, d_queries, query_count,
+                           elem_count, k, d_ids, d_dists, d_counts, static_cast<hipStream_t>(stream), routes);
+    });
+}
+
 nmslib_error_t nmslib_gpu_string_hnsw_links(nmslib_index_handle_t index, size_t node, int level, int32_t* out,
                                             size_t capacity, size_t* count, int* enterpoint, int* maxlevel) {
     if (!index || !count || !enterpoint || !maxlevel || node >= nmslib_data_qty(index) || level < 0)

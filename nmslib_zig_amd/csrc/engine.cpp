@@ -265,6 +265,8 @@ Engine::~Engine() {
     if (pinned_) (void)hipHostFree(pinned_);
     if (tomb_event_) (void)hipEventDestroy(tomb_event_);
     if (tomb_pinned_) (void)hipHostFree(tomb_pinned_);
+    if (each_.event) (void)hipEventDestroy(each_.event);
+    if (each_.pinned) (void)hipHostFree(each_.pinned);
     if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -1130,7 +1132,8 @@ void Engine::fast_tile_counts(size_t* tiles, size_t* precise, size_t* fallback) 
         shards_[0]->fast_tile_counts(tiles, precise, fallback);
         return;
     }
-    if ((last_path != 1 && last_path != 3 && last_path != 6) || !fast_flags_ || fast_nqt_ <= 0) return;
+    const int path = stats_path();
+    if ((path != 1 && path != 3 && path != 6) || !fast_flags_ || fast_nqt_ <= 0) return;
     std::vector<int> h((size_t)fast_nqt_ * 2, 0);
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hip_check(hipStreamSynchronize(last_stream_ ? last_stream_ : stream_), "stats");

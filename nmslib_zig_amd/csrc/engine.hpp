@@ -292,6 +292,16 @@ class Engine {
     // host buffers in, results in this engine's pinned staging block (valid until the next call; the caller holds `mu`)
     void knn_host(const void* queries, size_t nq, size_t elem_count, size_t k, const int32_t** ids, const float** dists,
                   const int32_t** cnt, Filter* f = nullptr);
+    // ... with one filter per query (filter.cpp): filter_of_query [nq] (host) names an entry of filters
+    // [n_filters] (host), or -1 = unfiltered; both are read before the call returns.  routes [nq] (host, optional): per query
+    // the last_path of the single-filter batch its filter's queries would form.  last_path is 9 afterwards.  HNSW: one launch
+    // chain per route segment of the batch (filter_batch_plan.hpp); exact scan: one knn_brute per filter that has queries.
+    void knn_device_each(Filter* const* filters, size_t n_filters, const int32_t* filter_of_query, const void* d_queries,
+                         size_t nq, size_t elem_count, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
+                         hipStream_t stream, int32_t* routes);
+    void knn_host_each(Filter* const* filters, size_t n_filters, const int32_t* filter_of_query, const void* queries, size_t nq,
+                       size_t elem_count, size_t k, const int32_t** ids, const float** dists, const int32_t** cnt,
+                       int32_t* routes);
     float pair_distance(size_t p1, size_t p2);
     // RangeQuery on the brute-force index: matches in insertion order, the first `capacity`; returns how many were written
     size_t range_host(const void* query, size_t elem_count, double radius, size_t capacity, int32_t* ids, float* dists);
@@ -316,6 +326,8 @@ class Engine {
     // the last finalize: rows it inserted into an existing graph (0: a full build), rows it copied to HBM
     size_t rows_appended = 0, rows_uploaded = 0;
     int last_path = 0;  // see nmslib_gpu_stats_t
+    int each_path_ = 0;  // last_path 9: the path of the last part of that batch (what the fast-path statistics describe)
+    int stats_path() const { return last_path == 9 ? each_path_ : last_path; }
     size_t rows16_bytes() const;  // the fp16 traversal copy (gpu_rows=f16), shards included
     // flags of the last fast-path slice (device): [fast_nqt_] fallback flags, then (float rows) [fast_nqt_] precise flags
     const int* fast_flags_ = nullptr;
@@ -410,6 +422,18 @@ class Engine {
                             hipStream_t stream);
     void filter_forget_flags(const Filter& f);    // the statistics' pointer into f's child, before its workspaces go
     void knn_hnsw_filtered(Filter& f, const void* d_queries, size_t nq, size_t k, const HnswOut& out, hipStream_t stream);
+    // one filter per query: every check that needs no device (served index kinds, the entries' range, each filter)
+    void check_filters_each(Filter* const* filters, size_t n_filters, const int32_t* filter_of_query, size_t nq) const;
+    // dst row i = src row list[i] (rows of a multiple of 4 bytes): the 16-byte gather where its rule holds, else word by word
+    void gather_rows(const void* src, const int32_t* list, size_t m, size_t row_bytes, void* dst, hipStream_t stream);
+    // what a batch with one filter per query uploads and works in (grow-only): the filter table, slots and permutations (one
+    // block, staged in `pinned`; `event` stands behind the last copy out of it), the batch in plan order and its results
+    struct FilterEachWs {
+        DevBuf tab, q, res;
+        void* pinned = nullptr;
+        size_t pinned_bytes = 0;
+        hipEvent_t event = nullptr;
+    } each_;
     std::vector<std::unique_ptr<Filter>> filters_;
     uint64_t pos_epoch_ = 0;     // counts what moves positions: a consolidate that removed a row, a reset
     uint64_t prepared_ = 0;      // counts upload_rows: an exact-scan filter gathered at another count gathers again
@@ -452,13 +476,14 @@ class Engine {
     void hnsw_walk(bool positions, const void* d_queries, size_t nq, size_t k, const HnswOut& out, hipStream_t stream);
     // the walk for max(ef, k) positions into a workspace, then the first k of them that are live (an index with tombstones) and
     // allowed (allow: a filter's bits over n_allow positions, or nullptr)
+    // each (optional, in place of allow): every query's own filter (slot[0] is the first query's)
     void knn_hnsw_two_stage(const void* d_queries, size_t nq, size_t k, const uint32_t* allow, size_t n_allow,
-                            const HnswOut& out, hipStream_t stream);
+                            const HnswOut& out, hipStream_t stream, const FilterEach* each = nullptr);
     // gpu_inwalk=1: the same two tests inside the walk, in place of the two stages, where the kernel serves
     // the batch (hnsw_inwalk_plan.hpp); last_path 8
     bool inwalk_serves(size_t k) const;
     void knn_hnsw_inwalk(const void* d_queries, size_t nq, size_t k, const uint32_t* allow, size_t n_allow, const HnswOut& out,
-                         hipStream_t stream);
+                         hipStream_t stream, const FilterEach* each = nullptr);
     void knn_hnsw_old(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, const HnswOut& out,
                       hipStream_t stream);
     // Hnsw::Search, hnsw.cc:724: algoType=old, or hybrid with ef >= 1000, runs SearchOld

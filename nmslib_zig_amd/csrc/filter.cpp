@@ -4,9 +4,13 @@
 //               prepared by prepare_brute, so that a filtered batch is knn_brute on it, every path included;
 //   HNSW:       the walk for max(ef, k) results filtered through the bitset and the tombstones, or (filter_plan.hpp) an exact
 //               scan of the listed rows when the subset is no larger than that result array.
+// A batch in which every query names its own filter (knn_device_each) is put into plan order
+// (filter_batch_plan.hpp) and run there: HNSW one launch chain per route segment, the exact scan one knn_brute per filter.
 #include <algorithm>
+#include <cstring>
 
 #include "engine.hpp"
+#include "filter_batch_plan.hpp"
 #include "filter_plan.hpp"
 
 namespace gfxknn {
@@ -205,6 +209,230 @@ void Engine::knn_hnsw_filtered(Filter& f, const void* d_queries, size_t nq, size
     }
     if (inwalk_serves(k)) knn_hnsw_inwalk(d_queries, nq, k, f.d_allow.as<uint32_t>(), f.n, out, stream);
     else knn_hnsw_two_stage(d_queries, nq, k, f.d_allow.as<uint32_t>(), f.n, out, stream);
+}
+
+// ---- one filter per query (nmslib_gpu_knn_query_batch_filtered_each) ----------------------------------------
+
+static const char* const kEachSharded = " devices takes no filter: ";
+
+void Engine::check_filters_each(Filter* const* filters, size_t n_filters, const int32_t* filter_of_query, size_t nq) const {
+    check_filter_served();
+    const size_t bad = filter_batch_first_bad(filter_of_query, nq, n_filters);
+    if (bad < nq)
+        throw EngineError(Err::InvalidArgument, "filter_of_query[" + std::to_string(bad) + "] = " +
+                                                    std::to_string(filter_of_query[bad]) + " is outside [-1, " +
+                                                    std::to_string(n_filters) + ")");
+    for (size_t j = 0; j < n_filters; ++j) {
+        try {
+            check_filter(filters[j]);
+        } catch (const EngineError& x) {
+            throw EngineError(x.code, "filters[" + std::to_string(j) + "]: " + x.what());
+        }
+    }
+}
+
+void Engine::gather_rows(const void* src, const int32_t* list, size_t m, size_t row_bytes, void* dst, hipStream_t stream) {
+    const bool wide = row_bytes % 16 == 0 && (reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst)) % 16 == 0;
+    hip_check(wide ? launch_filter_gather_rows(src, list, (int)m, row_bytes, dst, stream)
+                   : launch_filter_gather_words(src, list, (int)m, row_bytes, dst, stream),
+              "filter batch gather");
+}
+
+void Engine::knn_device_each(Filter* const* filters, size_t n_filters, const int32_t* filter_of_query, const void* d_queries,
+                             size_t nq, size_t elem_count, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
+                             hipStream_t stream, int32_t* routes) {
+    check_filters_each(filters, n_filters, filter_of_query, nq);
+    if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
+    if (nq == 0) return;
+    if (k == 0) throw EngineError(Err::InvalidArgument, "k must be positive");
+    if (nq > (size_t)INT32_MAX) throw EngineError(Err::QueryTooLarge, "a batch takes at most 2^31 - 1 queries");
+    if (dirty_) finalize();
+    check_device();
+    const bool hnsw = method_ == Method::Hnsw;
+    // the route of every filter, then the batch's order; both host arithmetic
+    std::vector<int> segment(n_filters, kSegWalk);
+    if (hnsw)
+        for (size_t j = 0; j < n_filters; ++j)
+            if (filter_route(filters[j]->m, (size_t)ef_, k, filters[j]->scan_rows, hnsw_subset_query_bytes(dg_)) ==
+                FilterRoute::Subset)
+                segment[j] = kSegSubset;
+    const FilterBatchPlan plan = filter_batch_plan(filter_of_query, nq, segment.data(), n_filters);
+    if (!shards_.empty()) {  // (automatic sharding of an exact-scan index: only the unfiltered batch is served)
+        if (!plan.groups.empty())
+            throw EngineError(Err::SpaceIncompatible, "an index spread over " + std::to_string(shards_.size()) + kEachSharded +
+                                                          kFilterServed);
+        knn_device(d_queries, nq, elem_count, k, d_ids, d_dists, d_cnt, stream);
+        if (routes) std::fill(routes, routes + nq, last_path);
+        each_path_ = last_path;
+        last_path = 9;
+        return;
+    }
+    if (d_n_ > 0 && elem_count != dim_) throw EngineError(Err::QueryExecutionFailed, "query dimension does not match the index");
+    // before anything is enqueued: an exact-scan filter whose index was prepared again gathers again (and waits)
+    for (const FilterBatchGroup& g : plan.groups) filter_begin_batch(*filters[g.filter]);
+
+    // ---- what the device reads of the plan: one block, staged in pinned memory of our own (the caller's arrays are free
+    // when the call returns) ----
+    const bool permute = !plan.identity, table = hnsw && !plan.groups.empty();
+    const size_t tab_bytes = table ? (n_filters * sizeof(FilterSlot) + 15) & ~(size_t)15 : 0;
+    const size_t up_bytes = tab_bytes + (table ? nq * 4 : 0) + (permute ? 2 * nq * 4 : 0);
+    const FilterSlot* d_table = nullptr;
+    const int32_t *d_slot = nullptr, *d_perm = nullptr, *d_inv = nullptr;
+    if (up_bytes > 0) {
+        if (each_.event) hip_check(hipEventSynchronize(each_.event), "filter batch");  // the last copy has left the block
+        else hip_check(hipEventCreateWithFlags(&each_.event, hipEventDisableTiming), "hipEventCreate");
+        if (each_.pinned_bytes < up_bytes) {
+            if (each_.pinned) (void)hipHostFree(each_.pinned);
+            each_.pinned = nullptr;
+            each_.pinned_bytes = 0;
+            hip_check(hipHostMalloc(&each_.pinned, up_bytes + up_bytes / 4, hipHostMallocDefault), "hipHostMalloc");
+            each_.pinned_bytes = up_bytes + up_bytes / 4;
+        }
+        char* hp = static_cast<char*>(each_.pinned);
+        each_.tab.ensure(up_bytes);
+        const char* dp = static_cast<const char*>(each_.tab.ptr());
+        size_t at = 0;
+        if (table) {
+            FilterSlot* t = reinterpret_cast<FilterSlot*>(hp);
+            for (size_t j = 0; j < n_filters; ++j) {
+                const Filter& f = *filters[j];
+                const bool subset = segment[j] == kSegSubset;
+                t[j] = {f.d_allow.as<uint32_t>(), subset && f.m > 0 ? f.d_list.as<int32_t>() : nullptr, (int)f.n,
+                        subset ? (int)f.m : 0};
+            }
+            int32_t* slot = reinterpret_cast<int32_t*>(hp + tab_bytes);
+            for (size_t p = 0; p < nq; ++p) slot[p] = std::max(filter_of_query[plan.perm[p]], 0);  // (unfiltered: not read)
+            d_table = reinterpret_cast<const FilterSlot*>(dp);
+            d_slot = reinterpret_cast<const int32_t*>(dp + tab_bytes);
+            at = tab_bytes + nq * 4;
+        }
+        if (permute) {
+            std::memcpy(hp + at, plan.perm.data(), nq * 4);
+            std::memcpy(hp + at + nq * 4, plan.inv.data(), nq * 4);
+            d_perm = reinterpret_cast<const int32_t*>(dp + at);
+            d_inv = d_perm + nq;
+        }
+    }
+    order_after_last(stream);
+    if (up_bytes > 0) {
+        hip_check(hipMemcpyAsync(each_.tab.ptr(), each_.pinned, up_bytes, hipMemcpyHostToDevice, stream), "filter batch H2D");
+        hip_check(hipEventRecord(each_.event, stream), "hipEventRecord");
+    }
+
+    // ---- the batch in plan order: the caller's arrays when it is in that order already, else workspaces ----
+    const size_t qbytes = elem_count * elem_bytes(), rb = k * 4;
+    const char* q = static_cast<const char*>(d_queries);
+    int32_t* ids = d_ids;
+    float* dists = d_dists;
+    int32_t* cnt = d_cnt;
+    if (hnsw) {  // results and work counters of the whole batch, as knn_device keeps them
+        for (DevBuf* b : {&ws_ndc_, &ws_hops_, &ws_hops_up_, &sw_.status}) b->ensure(nq * 4);
+        if (!d_cnt) sw_.outcnt.ensure(nq * 4);
+        if (!cnt) cnt = sw_.outcnt.as<int32_t>();
+    }
+    int32_t *ndc = ws_ndc_.as<int32_t>(), *hops = ws_hops_.as<int32_t>(), *hops_up = ws_hops_up_.as<int32_t>();
+    if (permute) {
+        each_.q.ensure(nq * qbytes);
+        each_.res.ensure(2 * nq * rb + 4 * nq * 4);
+        gather_rows(d_queries, d_perm, nq, qbytes, each_.q.ptr(), stream);
+        q = static_cast<const char*>(each_.q.ptr());
+        ids = each_.res.as<int32_t>();
+        dists = reinterpret_cast<float*>(ids + nq * k);
+        cnt = ids + 2 * nq * k;
+        ndc = cnt + nq;
+        hops = ndc + nq;
+        hops_up = hops + nq;
+    }
+    auto route_of = [&](size_t a, size_t b) {  // plan positions [a, b) took the path last_path names
+        if (routes)
+            for (size_t p = a; p < b; ++p) routes[plan.perm[p]] = last_path;
+    };
+
+    if (hnsw) {
+        const HnswOut out{ids, dists, cnt, ndc, hops, hops_up, sw_.status.as<int32_t>()};
+        const uint32_t* tomb = n_dead_ > 0 ? d_tomb_.as<uint32_t>() : nullptr;
+        // knn_device's slices of the batch, in plan order; a slice runs the part of every segment that lies in it
+        for (size_t s0 = 0; s0 < nq; s0 += 65536) {
+            const size_t s1 = std::min(nq, s0 + 65536);
+            for (int sg = 0; sg < kSegCount; ++sg) {
+                const size_t a = std::max(s0, plan.seg[sg]), b = std::min(s1, plan.seg[sg + 1]);
+                if (a >= b) continue;
+                const void* qs = q + a * qbytes;
+                const FilterEach ea{d_table, d_slot ? d_slot + a : nullptr};
+                if (sg == kSegUnfiltered) {
+                    knn_hnsw(qs, b - a, k, out.at(a, k), stream);
+                } else if (sg == kSegWalk) {
+                    if (inwalk_serves(k)) knn_hnsw_inwalk(qs, b - a, k, nullptr, 0, out.at(a, k), stream, &ea);
+                    else knn_hnsw_two_stage(qs, b - a, k, nullptr, 0, out.at(a, k), stream, &ea);
+                } else {
+                    size_t m_max = 0;  // the launch's LDS: the largest list among the filters with queries in [a, b)
+                    for (const FilterBatchGroup& g : plan.groups)
+                        if (g.begin < b && g.end > a && segment[g.filter] == kSegSubset) m_max = std::max(m_max, filters[g.filter]->m);
+                    HnswDeviceGraph g = dg_;
+                    g.rows16 = nullptr;  // always the f32 rows: the bits of the f32 walk
+                    have_counters_ = true;
+                    hnsw_fix_valid_ = false;
+                    last_path = 7;
+                    prof_begin(stream);
+                    hip_check(launch_hnsw_subset_knn_each(g, (int)(b - a), (int)k, qs, ea, (int)m_max, tomb, out.at(a, k), stream),
+                              "hnsw_subset_knn");
+                    prof_end(stream);
+                }
+                route_of(a, b);
+            }
+        }
+    } else {
+        // one knn_brute per part: the index itself for the unfiltered queries, then every filter's child over its group;
+        // parts beyond 32768 queries are cut as knn_device cuts them
+        auto run = [&](Filter* f, size_t a, size_t b) {
+            for (size_t q0 = a; q0 < b; q0 += 32768) {
+                const size_t m = std::min<size_t>(32768, b - q0);
+                int32_t* c = cnt ? cnt + q0 : nullptr;
+                if (f) knn_filtered_slice(*f, q + q0 * qbytes, m, k, ids + q0 * k, dists + q0 * k, c, stream);
+                else knn_brute(q + q0 * qbytes, m, k, ids + q0 * k, dists + q0 * k, c, stream);
+            }
+            route_of(a, b);
+        };
+        if (plan.seg[kSegWalk] > 0) run(nullptr, 0, plan.seg[kSegWalk]);
+        for (const FilterBatchGroup& g : plan.groups) run(filters[g.filter], g.begin, g.end);
+        have_counters_ = false;
+    }
+
+    if (permute) {  // back to the caller's order: row q of the results is plan row inv[q]
+        gather_rows(ids, d_inv, nq, rb, d_ids, stream);
+        gather_rows(dists, d_inv, nq, rb, d_dists, stream);
+        if (d_cnt) gather_rows(cnt, d_inv, nq, 4, d_cnt, stream);
+        if (hnsw) {
+            gather_rows(ndc, d_inv, nq, 4, ws_ndc_.ptr(), stream);
+            gather_rows(hops, d_inv, nq, 4, ws_hops_.ptr(), stream);
+            gather_rows(hops_up, d_inv, nq, 4, ws_hops_up_.ptr(), stream);
+        }
+    }
+    each_path_ = last_path;
+    last_path = 9;
+}
+
+void Engine::knn_host_each(Filter* const* filters, size_t n_filters, const int32_t* filter_of_query, const void* queries,
+                           size_t nq, size_t elem_count, size_t k, const int32_t** ids, const float** dists,
+                           const int32_t** cnt, int32_t* routes) {
+    check_filters_each(filters, n_filters, filter_of_query, nq);  // (refused before the index is finalized for it)
+    if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
+    *ids = nullptr;
+    *dists = nullptr;
+    *cnt = nullptr;
+    if (nq == 0) return;
+    if (dirty_) finalize();
+    check_device();
+    const size_t qbytes = nq * elem_count * elem_bytes();
+    ws_q_.ensure(qbytes);
+    const ResultBlock out = result_block(nq, k);
+    char* hp = static_cast<char*>(pinned(std::max(qbytes, 2 * nq * k * 4 + nq * 4)));
+    std::memcpy(hp, queries, qbytes);
+    order_after_last(stream_);
+    hip_check(hipMemcpyAsync(ws_q_.ptr(), hp, qbytes, hipMemcpyHostToDevice, stream_), "queries H2D");
+    knn_device_each(filters, n_filters, filter_of_query, ws_q_.ptr(), nq, elem_count, k, out.ids, out.dists, out.cnt, stream_,
+                    routes);
+    fetch_results(nq, k, "knn", ids, dists, cnt);
 }
 
 }  // namespace gfxknn

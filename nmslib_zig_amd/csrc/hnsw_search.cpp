@@ -28,7 +28,7 @@ static void hnsw_for_slices(size_t nq, size_t per_q, Body body) {
 
 size_t Engine::hnsw_redone() {
     if (!shards_.empty()) return shards_[0]->hnsw_redone();
-    if ((last_path != 4 && last_path != 5) || !hnsw_fix_valid_) return 0;
+    if ((stats_path() != 4 && stats_path() != 5) || !hnsw_fix_valid_) return 0;
     int32_t v = 0;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hip_check(hipStreamSynchronize(last_stream_ ? last_stream_ : stream_), "stats");
@@ -58,7 +58,7 @@ bool Engine::inwalk_serves(size_t k) const {
 // the f32 rows, whatever algoType and gpu_rows say.  The visited sets are HBM bitsets, so the batch is cut where they would
 // outgrow the budget; all slices are one timed interval.
 void Engine::knn_hnsw_inwalk(const void* d_queries, size_t nq, size_t k, const uint32_t* allow, size_t n_allow,
-                             const HnswOut& out, hipStream_t stream) {
+                             const HnswOut& out, hipStream_t stream, const FilterEach* each) {
     const uint32_t* tomb = n_dead_ > 0 ? d_tomb_.as<uint32_t>() : nullptr;
     const size_t words = (d_n_ + 31) / 32, qbytes = dim_ * elem_bytes();
     last_path = 8;
@@ -67,8 +67,12 @@ void Engine::knn_hnsw_inwalk(const void* d_queries, size_t nq, size_t k, const u
     hnsw_for_slices(nq, words * 4, [&](size_t q0, size_t m) {
         uint32_t* bitset = cleared_bitset(m, words, stream);
         if (q0 == 0) prof_begin(stream);
-        hip_check(launch_hnsw_inwalk(dg_, (int)m, (int)k, ef_, static_cast<const char*>(d_queries) + q0 * qbytes, bitset, words,
-                                     allow, (int)n_allow, tomb, out.at(q0, k), stream),
+        const void* qs = static_cast<const char*>(d_queries) + q0 * qbytes;
+        // (a slice's queries start at q0: so do their slots)
+        hip_check(each ? launch_hnsw_inwalk_each(dg_, (int)m, (int)k, ef_, qs, bitset, words, {each->table, each->slot + q0}, tomb,
+                                                 out.at(q0, k), stream)
+                       : launch_hnsw_inwalk(dg_, (int)m, (int)k, ef_, qs, bitset, words, allow, (int)n_allow, tomb, out.at(q0, k),
+                                            stream),
                   "hnsw_inwalk");
         if (q0 + m == nq) prof_end(stream);
     });
@@ -79,7 +83,7 @@ void Engine::knn_hnsw_inwalk(const void* d_queries, size_t nq, size_t k, const u
 // hnsw_keep_topk_kernel writes the first k allowed live ones of them to the caller's buffers.  The counters are the walk's,
 // at the slice's place in the batch's arrays; the timed interval ends behind the filter.
 void Engine::knn_hnsw_two_stage(const void* d_queries, size_t nq, size_t k, const uint32_t* allow, size_t n_allow,
-                                const HnswOut& out, hipStream_t stream) {
+                                const HnswOut& out, hipStream_t stream, const FilterEach* each) {
     const size_t cap = filter_walk_results((size_t)ef_, k);
     const uint32_t* tomb = n_dead_ > 0 ? d_tomb_.as<uint32_t>() : nullptr;
     const size_t qbytes = dim_ * elem_bytes();
@@ -95,8 +99,10 @@ void Engine::knn_hnsw_two_stage(const void* d_queries, size_t nq, size_t k, cons
         walk.dists = sw_.live_d.as<float>();
         walk.cnt = sw_.live_cnt.as<int32_t>();
         hnsw_walk(true, static_cast<const char*>(d_queries) + q0 * qbytes, m, cap, walk, stream);
-        hip_check(launch_hnsw_keep_topk(walk.ids, walk.dists, walk.cnt, (int)m, (int)cap, allow, (int)n_allow, tomb, (int)d_n_,
-                                        dg_.ext_ids, (int)k, fin, stream),
+        hip_check(each ? launch_hnsw_keep_topk_each(walk.ids, walk.dists, walk.cnt, (int)m, (int)cap,
+                                                    {each->table, each->slot + q0}, tomb, (int)d_n_, dg_.ext_ids, (int)k, fin, stream)
+                       : launch_hnsw_keep_topk(walk.ids, walk.dists, walk.cnt, (int)m, (int)cap, allow, (int)n_allow, tomb,
+                                               (int)d_n_, dg_.ext_ids, (int)k, fin, stream),
                   "hnsw_keep_topk");
         prof_end(stream);  // (the interval the walk opened: its end moves behind the filter)
     });

@@ -6,7 +6,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <climits>
 #include <cmath>
+#include <type_traits>
 
 #include "../filter_plan.hpp"
 #include "hnsw_common_dev.hpp"
@@ -167,9 +169,12 @@ constexpr int SUBSET_WAVES = 4;
 // Wave 0 stages the query as the search kernels do (same operations in the same order: the same bits).  The waves then take
 // chunks of 64 list entries through frontier_distances on the f32 rows; a deleted row's key stays "no entry".  A bitonic
 // sort of the padded keys orders the entries by (distance, position).
-template <int SPACE>
+// FILTER: FilterOne (one list of m rows for the launch, mpad its keys) or FilterPerQuery (the query's own list;
+// mpad, the keys of the launch's largest list, places what stands behind the keys in LDS, and the workgroup fills and sorts
+// only the keys of its own m).
+template <int SPACE, class FILTER>
 __global__ __launch_bounds__(64 * SUBSET_WAVES) void hnsw_subset_knn_kernel(HnswDeviceGraph g, const void* __restrict__ queries,
-                                                                            const int32_t* __restrict__ list, int m, int mpad,
+                                                                            FILTER flt, int mpad,
                                                                             const uint32_t* __restrict__ tomb, int k,
                                                                             int32_t* out_ids, float* out_dists, int32_t* out_cnt,
                                                                             int32_t* out_ndc, int32_t* out_hops,
@@ -185,8 +190,16 @@ __global__ __launch_bounds__(64 * SUBSET_WAVES) void hnsw_subset_knn_kernel(Hnsw
     float* nd_all = reinterpret_cast<float*>(nbr_all + 64 * SUBSET_WAVES);      // [waves][64]
     int* shared_i = reinterpret_cast<int*>(nd_all + 64 * SUBSET_WAVES);         // [0] u8 query norm, [1] entries
     const int q = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const FilterSlot fs = flt.at(q);
+    const int32_t* __restrict__ list = fs.list;
+    const int m = fs.m < mpad ? fs.m : mpad;  // (a list never outgrows the launch's keys)
+    int msort = mpad;
+    if constexpr (std::is_same<FILTER, FilterPerQuery>::value) {
+        msort = 64;
+        while (msort < m) msort <<= 1;
+    }
 
-    for (int i = tid; i < mpad; i += 64 * SUBSET_WAVES) keys[i] = kNone;
+    for (int i = tid; i < msort; i += 64 * SUBSET_WAVES) keys[i] = kNone;
     if (tid == 0) shared_i[1] = 0;
     if (wave == 0) {
         int qnorm = 0;
@@ -237,9 +250,9 @@ __global__ __launch_bounds__(64 * SUBSET_WAVES) void hnsw_subset_knn_kernel(Hnsw
         __builtin_amdgcn_wave_barrier();
     }
     __syncthreads();
-    for (int size = 2; size <= mpad; size <<= 1) {
+    for (int size = 2; size <= msort; size <<= 1) {
         for (int j = size >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < mpad; i += 64 * SUBSET_WAVES) {
+            for (int i = tid; i < msort; i += 64 * SUBSET_WAVES) {
                 const int o = i ^ j;
                 if (o > i) {
                     const u64 a = keys[i], b = keys[o];
@@ -254,8 +267,8 @@ __global__ __launch_bounds__(64 * SUBSET_WAVES) void hnsw_subset_knn_kernel(Hnsw
         }
     }
     // the entries stand in front of the "no entry" keys
-    for (int i = tid; i < mpad; i += 64 * SUBSET_WAVES)
-        if (keys[i] != kNone && (i + 1 == mpad || keys[i + 1] == kNone)) shared_i[1] = i + 1;
+    for (int i = tid; i < msort; i += 64 * SUBSET_WAVES)
+        if (keys[i] != kNone && (i + 1 == msort || keys[i + 1] == kNone)) shared_i[1] = i + 1;
     __syncthreads();
     const int live = shared_i[1];
     const int kk = k < live ? k : live;
@@ -278,23 +291,67 @@ __global__ __launch_bounds__(64 * SUBSET_WAVES) void hnsw_subset_knn_kernel(Hnsw
     }
 }
 
-hipError_t launch_hnsw_subset_knn(const HnswDeviceGraph& g, int nq, int k, const void* queries, const int32_t* list, int m,
-                                  const uint32_t* tomb, const HnswOut& out, hipStream_t s) {
-    if (nq == 0) return hipSuccess;
-    if (k < 1 || m < 0 || m > HNSW_SUBSET_MAX || (m > 0 && (!list || g.n <= 0)) || !out.cnt) return hipErrorInvalidValue;
+template <class FILTER>
+static hipError_t subset_launch(const HnswDeviceGraph& g, int nq, int k, const void* queries, const FILTER& flt, int m,
+                                const uint32_t* tomb, const HnswOut& out, hipStream_t s) {
     static_assert(SUBSET_WAVES == 4, "filter_subset_lds_bytes counts four waves' scratch");
     const int mpad = (int)filter_subset_keys((size_t)m);
     return hnsw_dispatch_space(g.space, [&](auto sp) -> hipError_t {
         const size_t lds = filter_subset_lds_bytes((size_t)m, hnsw_subset_query_bytes(g));
         if (lds > kFilterLdsMax) return hipErrorInvalidValue;  // (filter_route sends such a batch to the walk)
-        auto kern = hnsw_subset_knn_kernel<sp.value>;
+        auto kern = hnsw_subset_knn_kernel<sp.value, FILTER>;
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)lds);
         if (e != hipSuccess) return e;
-        hipLaunchKernelGGL(kern, dim3(nq), dim3(64 * SUBSET_WAVES), lds, s, g, queries, list, m, mpad, tomb, k, out.ids,
+        hipLaunchKernelGGL(kern, dim3(nq), dim3(64 * SUBSET_WAVES), lds, s, g, queries, flt, mpad, tomb, k, out.ids,
                            out.dists, out.cnt, out.ndc, out.hops, out.hops_up);
         return hipGetLastError();
     });
+}
+
+hipError_t launch_hnsw_subset_knn(const HnswDeviceGraph& g, int nq, int k, const void* queries, const int32_t* list, int m,
+                                  const uint32_t* tomb, const HnswOut& out, hipStream_t s) {
+    if (nq == 0) return hipSuccess;
+    if (k < 1 || m < 0 || m > HNSW_SUBSET_MAX || (m > 0 && (!list || g.n <= 0)) || !out.cnt) return hipErrorInvalidValue;
+    return subset_launch(g, nq, k, queries, FilterOne{{nullptr, list, 0, m}}, m, tomb, out, s);
+}
+
+// m_max: the largest m among the launch's entries (the host knows every filter's m)
+hipError_t launch_hnsw_subset_knn_each(const HnswDeviceGraph& g, int nq, int k, const void* queries, const FilterEach& each,
+                                       int m_max, const uint32_t* tomb, const HnswOut& out, hipStream_t s) {
+    if (nq == 0) return hipSuccess;
+    if (k < 1 || m_max < 0 || m_max > HNSW_SUBSET_MAX || (m_max > 0 && g.n <= 0) || !each.table || !each.slot || !out.cnt)
+        return hipErrorInvalidValue;
+    return subset_launch(g, nq, k, queries, FilterPerQuery{each}, m_max, tomb, out, s);
+}
+
+// ---- rows of any multiple of four bytes ---------------------------------------------------------------------------------
+// The results of a per-query-filter batch go back to the caller's order row by row: k entries, or one counter, are rows that
+// the 16-byte gather above does not take.  One word per lane and step; the same in-bounds reload for the lanes past the end.
+__global__ __launch_bounds__(256) void filter_gather_words_kernel(const uint32_t* __restrict__ src,
+                                                                  const int32_t* __restrict__ list, int m, int wpr,
+                                                                  uint32_t* __restrict__ dst) {
+    const size_t total = (size_t)m * wpr;
+    for (size_t t0 = (size_t)blockIdx.x * 256; t0 < total; t0 += (size_t)gridDim.x * 256) {
+        const size_t t = t0 + threadIdx.x;
+        const bool ok = t < total;
+        const size_t tc = ok ? t : total - 1;
+        const size_t i = tc / wpr;
+        const size_t c = tc - i * wpr;
+        const uint32_t v = src[(size_t)list[i] * wpr + c];
+        if (ok) dst[tc] = v;
+    }
+}
+
+hipError_t launch_filter_gather_words(const void* src, const int32_t* list, int m, size_t row_bytes, void* dst, hipStream_t s) {
+    if (m <= 0) return hipSuccess;
+    if (!src || !list || !dst || row_bytes == 0 || row_bytes % 4 != 0 || row_bytes / 4 > (size_t)INT32_MAX)
+        return hipErrorInvalidValue;
+    const size_t total = (size_t)m * (row_bytes / 4);
+    const int blocks = (int)std::min<size_t>((total + 255) / 256, 65536);
+    hipLaunchKernelGGL(filter_gather_words_kernel, dim3(blocks), dim3(256), 0, s, static_cast<const uint32_t*>(src), list, m,
+                       (int)(row_bytes / 4), static_cast<uint32_t*>(dst));
+    return hipGetLastError();
 }
 
 }  // namespace gfxknn

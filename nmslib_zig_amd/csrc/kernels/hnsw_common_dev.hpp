@@ -406,4 +406,28 @@ __device__ __forceinline__ int greedy_step_any(const HnswDeviceGraph& g, const i
     return cnt;
 }
 
+// ---- the filter of a query ----
+// What a filter kernel is launched with: one filter for the whole launch, or a table and each query's entry.  at(q) is the
+// entry of the workgroup's query as wave-uniform values: the per-query form reads the slot and the entry once, and every
+// field goes through readfirstlane, so that the bitset tests behind it address from scalars as the one-filter form does.
+struct FilterOne {
+    FilterSlot f;
+    __device__ __forceinline__ FilterSlot at(int) const { return f; }
+};
+__device__ __forceinline__ int uniform_i(int v) { return __builtin_amdgcn_readfirstlane(v); }
+template <class T>
+__device__ __forceinline__ const T* uniform_ptr(const T* p) {
+    const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+    const unsigned lo = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)v);
+    const unsigned hi = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(v >> 32));
+    return reinterpret_cast<const T*>(((unsigned long long)hi << 32) | lo);
+}
+struct FilterPerQuery {
+    FilterEach e;
+    __device__ __forceinline__ FilterSlot at(int q) const {
+        const FilterSlot s = e.table[uniform_i(e.slot[q])];
+        return {uniform_ptr(s.allow), uniform_ptr(s.list), uniform_i(s.n_allow), uniform_i(s.m)};
+    }
+};
+
 }  // namespace gfxknn

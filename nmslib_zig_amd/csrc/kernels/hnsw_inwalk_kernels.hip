@@ -29,13 +29,13 @@
 
 namespace gfxknn {
 
+template <class FILTER>
 struct InwalkArgs {
     HnswDeviceGraph g;
     const void* queries;
     uint32_t* bitset;        // [nq][bitset_words], cleared
     size_t bitset_words;
-    const uint32_t* allow;   // bit = position, n_allow positions; or null
-    int n_allow;
+    FILTER flt;              // allow: bit = position, n_allow positions; or null (FilterPerQuery: the query's own entry)
     const uint32_t* tomb;    // bit = position, every position of the graph; or null
     int32_t* out_ids;
     float* out_dists;
@@ -50,8 +50,8 @@ __device__ __forceinline__ void inwalk_sync() {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
 }
 
-template <int SPACE>
-__global__ __launch_bounds__(64) void hnsw_inwalk_kernel(InwalkArgs a) {
+template <int SPACE, class FILTER>
+__global__ __launch_bounds__(64) void hnsw_inwalk_kernel(InwalkArgs<FILTER> a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const HnswDeviceGraph& g = a.g;
     const int q = blockIdx.x, lane = threadIdx.x;
@@ -68,6 +68,10 @@ __global__ __launch_bounds__(64) void hnsw_inwalk_kernel(InwalkArgs a) {
     u64* W = sk + kInwalkSortKeys;                                     // [cap]
     u64* Cq = W + ((a.cap + 1) & ~1);                                  // [CAPC], entry i at (head + i) % CAPC
     uint32_t* bits = a.bitset + (size_t)q * a.bitset_words;
+    // the query's filter, once and in scalars: `eligible` below runs per lane and per neighbour
+    const FilterSlot fs = a.flt.at(q);
+    const uint32_t* __restrict__ allow = fs.allow;
+    const int n_allow = fs.n_allow;
 
     // ---- stage the query (as the other search kernels: the same operations in the same order) ----
     int qnorm = 0;
@@ -104,7 +108,7 @@ __global__ __launch_bounds__(64) void hnsw_inwalk_kernel(InwalkArgs a) {
     // the two tests of hnsw_keep_topk_kernel (a row added after the filter was made stands at or beyond n_allow)
     auto eligible = [&](int p) -> bool {
         bool ok = true;
-        if (a.allow) ok = (unsigned)p < (unsigned)a.n_allow && ((a.allow[p >> 5] >> (p & 31)) & 1u) != 0;
+        if (allow) ok = (unsigned)p < (unsigned)n_allow && ((allow[p >> 5] >> (p & 31)) & 1u) != 0;
         if (ok && a.tomb) ok = ((a.tomb[p >> 5] >> (p & 31)) & 1u) == 0;
         return ok;
     };
@@ -241,23 +245,22 @@ __global__ __launch_bounds__(64) void hnsw_inwalk_kernel(InwalkArgs a) {
     }
 }
 
-hipError_t launch_hnsw_inwalk(const HnswDeviceGraph& g, int nq, int k, int ef, const void* queries, uint32_t* bitset,
-                              size_t bitset_words, const uint32_t* allow, int n_allow, const uint32_t* tomb, const HnswOut& out,
-                              hipStream_t s) {
+template <class FILTER>
+static hipError_t inwalk_launch(const HnswDeviceGraph& g, int nq, int k, int ef, const void* queries, uint32_t* bitset,
+                                size_t bitset_words, const FILTER& flt, const uint32_t* tomb, const HnswOut& out, hipStream_t s) {
     if (nq == 0) return hipSuccess;
     const size_t qbytes = hnsw_subset_query_bytes(g);
     const int nbcap = hnsw_nbcap(g);
     static_assert(kInwalkNbcapMax == (size_t)HNSW_NBCAP_LDS, "the routing rule and the LDS kernels name one list length");
-    if (k < 1 || ef < 1 || n_allow < 0 || !bitset || bitset_words < ((size_t)(g.n > 0 ? g.n : 0) + 31) / 32 ||
+    if (k < 1 || ef < 1 || !bitset || bitset_words < ((size_t)(g.n > 0 ? g.n : 0) + 31) / 32 ||
         !inwalk_served((size_t)ef, (size_t)k, (size_t)nbcap, qbytes))
         return hipErrorInvalidValue;
-    InwalkArgs a{};
+    InwalkArgs<FILTER> a{};
     a.g = g;
     a.queries = queries;
     a.bitset = bitset;
     a.bitset_words = bitset_words;
-    a.allow = allow;
-    a.n_allow = n_allow;
+    a.flt = flt;
     a.tomb = tomb;
     a.out_ids = out.ids;
     a.out_dists = out.dists;
@@ -270,13 +273,27 @@ hipError_t launch_hnsw_inwalk(const HnswDeviceGraph& g, int nq, int k, int ef, c
     a.nbcap = nbcap;
     return hnsw_dispatch_space(g.space, [&](auto sp) -> hipError_t {
         const size_t lds = inwalk_lds_bytes((size_t)a.cap, (size_t)nbcap, qbytes);
-        auto kern = hnsw_inwalk_kernel<sp.value>;
+        auto kern = hnsw_inwalk_kernel<sp.value, FILTER>;
         const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)lds);
         if (e != hipSuccess) return e;
         hipLaunchKernelGGL(kern, dim3(nq), dim3(64), lds, s, a);
         return hipGetLastError();
     });
+}
+
+hipError_t launch_hnsw_inwalk(const HnswDeviceGraph& g, int nq, int k, int ef, const void* queries, uint32_t* bitset,
+                              size_t bitset_words, const uint32_t* allow, int n_allow, const uint32_t* tomb, const HnswOut& out,
+                              hipStream_t s) {
+    if (n_allow < 0) return hipErrorInvalidValue;
+    return inwalk_launch(g, nq, k, ef, queries, bitset, bitset_words, FilterOne{{allow, nullptr, n_allow, 0}}, tomb, out, s);
+}
+
+hipError_t launch_hnsw_inwalk_each(const HnswDeviceGraph& g, int nq, int k, int ef, const void* queries, uint32_t* bitset,
+                                   size_t bitset_words, const FilterEach& each, const uint32_t* tomb, const HnswOut& out,
+                                   hipStream_t s) {
+    if (nq > 0 && (!each.table || !each.slot)) return hipErrorInvalidValue;
+    return inwalk_launch(g, nq, k, ef, queries, bitset, bitset_words, FilterPerQuery{each}, tomb, out, s);
 }
 
 }  // namespace gfxknn

@@ -6,6 +6,7 @@
 
 #include <cmath>
 
+#include "hnsw_common_dev.hpp"
 #include "kernels.hpp"
 
 namespace gfxknn {
@@ -13,15 +14,18 @@ namespace gfxknn {
 // One wave per query.  cand / cand_d [nq][cap]: the search's results in its order, cand_n [nq] how many it wrote (nothing
 // beyond them is read).  allow, tomb: either may be null (kernel arguments: the tests are wave-uniform).  Per chunk of 64
 // entries a ballot of "keep" and the popcount of the ballot below the lane give a kept entry its place: the order of the
-// kept entries is the search's.
+// kept entries is the search's.  FILTER: FilterOne (the launch's filter) or FilterPerQuery (the query's own).
+template <class FILTER>
 __global__ __launch_bounds__(64) void hnsw_keep_topk_kernel(const int32_t* __restrict__ cand, const float* __restrict__ cand_d,
-                                                            const int32_t* __restrict__ cand_n, int cap,
-                                                            const uint32_t* __restrict__ allow, int n_allow,
+                                                            const int32_t* __restrict__ cand_n, int cap, FILTER flt,
                                                             const uint32_t* __restrict__ tomb, int n,
                                                             const int32_t* __restrict__ ext_ids, int k, int32_t* out_ids,
                                                             float* out_dists, int32_t* out_cnt) {
     using u64 = unsigned long long;
     const int q = blockIdx.x, lane = threadIdx.x;
+    const FilterSlot fs = flt.at(q);
+    const uint32_t* __restrict__ allow = fs.allow;
+    const int n_allow = fs.n_allow;
     int cnt = cand_n[q];
     cnt = cnt < 0 ? 0 : (cnt < cap ? cnt : cap);
     const int32_t* c = cand + (size_t)q * cap;
@@ -62,8 +66,18 @@ hipError_t launch_hnsw_keep_topk(const int32_t* cand, const float* cand_d, const
                                  int k, const HnswOut& out, hipStream_t s) {
     if (nq == 0) return hipSuccess;
     if (k < 1 || cap < 1 || n_allow < 0 || (!allow && !tomb) || !out.cnt) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(hnsw_keep_topk_kernel, dim3(nq), dim3(64), 0, s, cand, cand_d, cand_n, cap, allow, n_allow, tomb, n,
-                       ext_ids, k, out.ids, out.dists, out.cnt);
+    hipLaunchKernelGGL(hnsw_keep_topk_kernel<FilterOne>, dim3(nq), dim3(64), 0, s, cand, cand_d, cand_n, cap,
+                       FilterOne{{allow, nullptr, n_allow, 0}}, tomb, n, ext_ids, k, out.ids, out.dists, out.cnt);
+    return hipGetLastError();
+}
+
+hipError_t launch_hnsw_keep_topk_each(const int32_t* cand, const float* cand_d, const int32_t* cand_n, int nq, int cap,
+                                      const FilterEach& each, const uint32_t* tomb, int n, const int32_t* ext_ids, int k,
+                                      const HnswOut& out, hipStream_t s) {
+    if (nq == 0) return hipSuccess;
+    if (k < 1 || cap < 1 || !each.table || !each.slot || !out.cnt) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(hnsw_keep_topk_kernel<FilterPerQuery>, dim3(nq), dim3(64), 0, s, cand, cand_d, cand_n, cap,
+                       FilterPerQuery{each}, tomb, n, ext_ids, k, out.ids, out.dists, out.cnt);
     return hipGetLastError();
 }
 

@@ -425,6 +425,18 @@ hipError_t launch_hnsw_pack_rows16(const float* rows, int n, int ldv, int dim, f
 // position); k results with external ids, -1 / +inf padding and the count go to out.
 hipError_t launch_hnsw_rerank(const HnswDeviceGraph& g, int nq, int k, int cap, int rerank, const void* queries,
                               const int32_t* cand, const int32_t* cand_n, const HnswOut& out, hipStream_t s);
+// A batch in which every query names its own filter: the filters of the batch as a device table, and per
+// query of a launch its entry's index.  allow: the filter's bits over n_allow positions; list: its m ascending positions (the
+// subset route; null on the walk route).  A workgroup serves one query: it reads slot[q] and the entry once, into scalars.
+struct FilterSlot {
+    const uint32_t* allow;
+    const int32_t* list;
+    int n_allow, m;
+};
+struct FilterEach {
+    const FilterSlot* table;
+    const int32_t* slot;  // [nq] of the launch (a slice passes slot + q0)
+};
 // Deleted rows and filtered batches (hnsw_live_kernels.hip): cand / cand_d [nq][cap] are the results of a search launched for
 // cap results without ext_ids (internal positions, in the search's order), cand_n [nq] their counts.  One wave per query: the
 // first k entries whose position is below n_allow with its bit in allow set (allow optional) and whose bit in tomb ([ceil(n /
@@ -433,6 +445,10 @@ hipError_t launch_hnsw_rerank(const HnswDeviceGraph& g, int nq, int k, int cap, 
 hipError_t launch_hnsw_keep_topk(const int32_t* cand, const float* cand_d, const int32_t* cand_n, int nq, int cap,
                                  const uint32_t* allow, int n_allow, const uint32_t* tomb, int n, const int32_t* ext_ids,
                                  int k, const HnswOut& out, hipStream_t s);
+// ... with query q filtered by the bits of each.table[each.slot[q]] (every slot names an entry with bits)
+hipError_t launch_hnsw_keep_topk_each(const int32_t* cand, const float* cand_d, const int32_t* cand_n, int nq, int cap,
+                                      const FilterEach& each, const uint32_t* tomb, int n, const int32_t* ext_ids, int k,
+                                      const HnswOut& out, hipStream_t s);
 // The same two tests inside the walk (hnsw_inwalk_kernels.hip): disallowed and deleted nodes are stepping
 // stones, only eligible ones enter the result set of cap = max(ef, k) entries, and the walk goes on until that set is full.
 // One wave per query on the f32 rows (u8 rows: the integer distance); bitset [nq][bitset_words >= ceil(n / 32)], cleared by
@@ -442,6 +458,10 @@ hipError_t launch_hnsw_keep_topk(const int32_t* cand, const float* cand_d, const
 hipError_t launch_hnsw_inwalk(const HnswDeviceGraph& g, int nq, int k, int ef, const void* queries, uint32_t* bitset,
                               size_t bitset_words, const uint32_t* allow, int n_allow, const uint32_t* tomb, const HnswOut& out,
                               hipStream_t s);
+// ... with query q's allow bits those of each.table[each.slot[q]]
+hipError_t launch_hnsw_inwalk_each(const HnswDeviceGraph& g, int nq, int k, int ef, const void* queries, uint32_t* bitset,
+                                   size_t bitset_words, const FilterEach& each, const uint32_t* tomb, const HnswOut& out,
+                                   hipStream_t s);
 // SearchOld; ws_a / ws_r / ws_heap: the per-query HBM workspaces above (may be unused)
 hipError_t launch_hnsw_search_old(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries, uint32_t* bitset,
                                   void* ws_a, void* ws_r, void* ws_heap, const HnswOut& out, hipStream_t s);
@@ -474,6 +494,12 @@ hipError_t launch_filter_gather_ids(const int32_t* src, const int32_t* list, int
 inline size_t hnsw_subset_query_bytes(const HnswDeviceGraph& g) { return g.space == SP_L2SQR_SIFT ? 128 : (size_t)g.ldv * 4; }
 hipError_t launch_hnsw_subset_knn(const HnswDeviceGraph& g, int nq, int k, const void* queries, const int32_t* list, int m,
                                   const uint32_t* tomb, const HnswOut& out, hipStream_t s);
+// ... with query q scanning the list of each.table[each.slot[q]] (m may be 0: count 0).  One launch: the LDS is sized for
+// m_max, the largest m among the launch's queries; a workgroup sorts the filter_subset_keys of its own m.
+hipError_t launch_hnsw_subset_knn_each(const HnswDeviceGraph& g, int nq, int k, const void* queries, const FilterEach& each,
+                                       int m_max, const uint32_t* tomb, const HnswOut& out, hipStream_t s);
+// dst row i = src row list[i] for rows of any multiple of 4 bytes (results of k entries, counters): word by word
+hipError_t launch_filter_gather_words(const void* src, const int32_t* list, int m, size_t row_bytes, void* dst, hipStream_t s);
 
 // ---- HNSW construction on the GPU (hnsw_build_kernels.hip) ------------------------------------
 struct HnswBuildGraph {          // mutable twin of HnswDeviceGraph
