@@ -107,7 +107,8 @@ typedef struct {
     size_t fast_tiles_precise;
     size_t fast_tiles_fallback;
     /* HNSW with the LDS visited table, last batch (reading it waits for the stream): queries whose table filled up and
-       that the HBM-bitset kernel answered again.  0 on every BASELINE configuration. */
+       that the HBM-bitset kernel answered again.  0 on every BASELINE configuration.  SearchOld (algoType=old, hybrid from
+       ef 1000 on): queries whose table filled up, on which the whole batch ran again with bitsets. */
     size_t hnsw_redone;
     /* the last finalize: rows it inserted into the graph that was resident (index parameter gpu_append=1; 0 = it built
        the index in full), and rows it copied from the host to HBM */

@@ -334,7 +334,8 @@ class Engine {
     int fast_nqt_ = 0;
     bool fast_has_precise_ = false;
     void fast_tile_counts(size_t* tiles, size_t* precise, size_t* fallback);
-    // HNSW (LDS visited table): queries of the last batch that were re-run by the bitset kernel (waits for the batch)
+    // HNSW (LDS visited table): queries of the last batch that were re-run by the bitset kernel (waits for the batch);
+    // SearchOld: queries of the last batch whose table filled up, on which the batch ran again with bitsets
     size_t hnsw_redone();
     hipStream_t last_stream_ = nullptr;  // stream of the most recent batch (the statistics wait for THAT one)
     // Batches of one index run in the order of the calls, whatever streams they are given: they share the workspaces.
@@ -342,8 +343,11 @@ class Engine {
     // for an event recorded there.  The same stream again is a pointer compare.
     void order_after_last(hipStream_t next);
     // sw_.fix holds the last batch's count: set by hnsw_search_lds with an LDS-table plan; cleared by every other search path,
-    // reset, the consolidate and the builder
-    bool hnsw_fix_valid_ = false;
+    // reset, the consolidate and the builder (false / 0).  kRedoneOnHost: SearchOld's last batch held queries whose table
+    // filled up (status 1) and ran again with bitsets; their number is hnsw_old_redone_
+    static constexpr int kRedoneOnHost = 2;
+    int hnsw_fix_valid_ = 0;
+    size_t hnsw_old_redone_ = 0;
     size_t hbm_bytes() const;
 
     std::mutex mu;  // serialises finalize + queries on one index

@@ -29,6 +29,7 @@ static void hnsw_for_slices(size_t nq, size_t per_q, Body body) {
 size_t Engine::hnsw_redone() {
     if (!shards_.empty()) return shards_[0]->hnsw_redone();
     if ((stats_path() != 4 && stats_path() != 5) || !hnsw_fix_valid_) return 0;
+    if (hnsw_fix_valid_ == kRedoneOnHost) return hnsw_old_redone_;
     int32_t v = 0;
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hip_check(hipStreamSynchronize(last_stream_ ? last_stream_ : stream_), "stats");
@@ -112,6 +113,10 @@ void Engine::knn_hnsw_two_stage(const void* d_queries, size_t nq, size_t k, cons
 // fp16 walk rely on the same)
 void Engine::hnsw_walk(bool positions, const void* d_queries, size_t nq, size_t k, const HnswOut& out, hipStream_t stream) {
     const int ef = ef_;
+    // every search kernel stages the query row in LDS; the HBM-array kernel keeps the least next to it.  Rows that leave
+    // no workgroup room for that are refused by name (the launch functions refuse a plan beyond the limit too)
+    if (hnsw_big_lds(dg_) > HNSW_LDS_LIMIT)
+        throw EngineError(Err::QueryTooLarge, "HNSW search: rows of this dimension do not fit a workgroup's LDS");
     last_path = 4;
     hnsw_fix_valid_ = false;
     auto graph = [&] {  // (read where a path is taken: ensure_rows16 below names the fp16 copy in dg_)
@@ -125,8 +130,9 @@ void Engine::hnsw_walk(bool positions, const void* d_queries, size_t nq, size_t 
     }
     if (std::max<size_t>(ef, k) > 1024 || hnsw_nbcap(dg_) > HNSW_NBCAP_LDS) {
         const HnswDeviceGraph g = graph();
-        // beyond the LDS kernels' sorted array, or adjacency lists longer than their frontier arrays (maxM0 > 254): the
-        // same algorithm with the array in HBM and lists walked in chunks (slices of bounded workspace)
+        // beyond the LDS kernels' sorted array, or adjacency lists longer than their frontier arrays (maxM0 or maxM > 255:
+        // hnsw_nbcap sends a longest list of 255 to the 256-entry arrays): the same algorithm with the array in HBM and
+        // lists walked in chunks (slices of bounded workspace)
         const size_t cap = std::max<size_t>(ef, k), words = (d_n_ + 31) / 32;
         const size_t qbytes = dim_ * elem_bytes();
         have_counters_ = true;
@@ -155,6 +161,10 @@ void Engine::hnsw_search_lds(const HnswDeviceGraph& g, bool rows_f16, const void
     const HnswQueries queries = HnswQueries::external(d_queries);
     HnswSearchPlan p = hnsw_make_plan(g, (int)nq, (int)k, ef, false);
     p.rows_f16 = rows_f16 ? 1 : 0;
+    // (rows the HBM-array kernel still stages can leave no room for this family's sorted array)
+    if (p.lds_bytes > HNSW_LDS_LIMIT)
+        throw EngineError(Err::QueryTooLarge, "HNSW search: rows of this dimension leave a workgroup's LDS no room for the "
+                                              "sorted array; ef and k above 1024 take the kernel that keeps it in HBM");
     have_counters_ = true;
     if (p.table_size == 0) {
         uint32_t* bitset = cleared_bitset(nq, p.bitset_words, stream);
@@ -218,6 +228,11 @@ void Engine::knn_hnsw_old(const HnswDeviceGraph& g, const void* d_queries, size_
     std::vector<int32_t> status(nq);
     for (int attempt = 0; attempt < 3; ++attempt) {
         HnswSearchPlan p0 = hnsw_make_plan_old(g, 1, (int)k, ef, force_bitset, heap_cap);
+        // (the heap's first 2048 entries, the closest queue up to ef 8192 and the result queue up to k 2048 live in LDS next to
+        // the query row: long rows with large ef or k outgrow the workgroup; the slices' plans take the same LDS)
+        if (p0.lds_bytes > HNSW_LDS_LIMIT)
+            throw EngineError(Err::QueryTooLarge, "SearchOld: the query row and the queues of this ef and k do not fit a "
+                                                  "workgroup's LDS");
         const size_t per_q = hnsw_old_ws_a(p0) + hnsw_old_ws_r(p0) + hnsw_old_ws_heap(p0) + p0.bitset_words * 4;
         hnsw_for_slices(nq, per_q, [&](size_t q0, size_t m) {
             HnswSearchPlan p = hnsw_make_plan_old(g, (int)m, (int)k, ef, force_bitset, heap_cap);
@@ -235,10 +250,16 @@ void Engine::knn_hnsw_old(const HnswDeviceGraph& g, const void* d_queries, size_
         // status 1: the LDS visited table filled up -> HBM bitsets; status 2: the candidate heap outgrew its bound
         hip_check(hipMemcpyAsync(status.data(), out.status, nq * 4, hipMemcpyDeviceToHost, stream), "status");
         hip_check(hipStreamSynchronize(stream), "hnsw_search_old");
-        bool any1 = false, any2 = false;
+        bool any2 = false;
+        size_t n1 = 0;
         for (int32_t v : status) {
-            any1 |= v == 1;
+            n1 += v == 1;
             any2 |= v == 2;
+        }
+        const bool any1 = n1 > 0;
+        if (any1) {  // statistics: the queries whose table filled up (the whole batch runs again with bitsets)
+            hnsw_old_redone_ = n1;
+            hnsw_fix_valid_ = kRedoneOnHost;
         }
         if (!any1 && !any2) return;
         if (any1) force_bitset = true;

@@ -1330,15 +1330,18 @@ static hipError_t launch_space_w(const HnswArgs& a, const HnswSearchPlan& p, hip
 
 template <int SPACE, int EMAX, class ROW>
 static hipError_t launch_space_e(const HnswArgs& a, const HnswSearchPlan& p, hipStream_t s) {
-    if (a.g.maxM0 > 62 || a.g.maxM > 62) return launch_space_w<SPACE, EMAX, true, ROW>(a, p, s);
+    if (hnsw_wide(a.g)) return launch_space_w<SPACE, EMAX, true, ROW>(a, p, s);
     return launch_space_w<SPACE, EMAX, false, ROW>(a, p, s);
 }
 
 template <int SPACE, class ROW>
 static hipError_t launch_space_r(const HnswArgs& a, const HnswSearchPlan& p, hipStream_t s) {
-    if (p.cap <= 128) return launch_space_e<SPACE, 2, ROW>(a, p, s);
-    if (p.cap <= 256) return launch_space_e<SPACE, 4, ROW>(a, p, s);
-    return launch_space_e<SPACE, SA_EMAX_MAX, ROW>(a, p, s);
+    static_assert(SA_EMAX_MAX == 16, "hnsw_emax names the widest array");
+    switch (hnsw_emax(p.cap)) {
+        case 2: return launch_space_e<SPACE, 2, ROW>(a, p, s);
+        case 4: return launch_space_e<SPACE, 4, ROW>(a, p, s);
+        default: return launch_space_e<SPACE, SA_EMAX_MAX, ROW>(a, p, s);
+    }
 }
 
 // p.rows_f16: the kernels that walk the fp16 copy (float spaces, external queries; construction stays on the f32 rows)
@@ -1373,7 +1376,9 @@ static void hnsw_print_prof(hipStream_t s) {
 hipError_t launch_hnsw_search(const HnswDeviceGraph& g, const HnswSearchPlan& p, const HnswQueries& q, uint32_t* bitset,
                               const HnswOverflow& fix, const HnswOut& out, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
-    if (p.cap > 64 * SA_EMAX_MAX || hnsw_nbcap(g) > HNSW_NBCAP_LDS) return hipErrorInvalidValue;
+    // (p.lds_bytes is what the one-wave kernels ask for.  The multi-wave kernel asks for 16 bytes more, but only under a
+    // table plan, and those stay within 64 KiB: hnsw_make_plan)
+    if (p.cap > 64 * SA_EMAX_MAX || hnsw_nbcap(g) > HNSW_NBCAP_LDS || p.lds_bytes > HNSW_LDS_LIMIT) return hipErrorInvalidValue;
     HnswArgs a = hnsw_args(g, p.nq, p.k, p.ef, p.cap, q, bitset, p.bitset_words, out);
     a.capa = (p.cap + 3) & ~3;
     a.table_size = p.table_size;
@@ -1402,7 +1407,7 @@ static hipError_t launch_old_space(const HnswArgs& a, const OldWs& w, const Hnsw
         hipLaunchKernelGGL(kern, dim3(a.nq), dim3(64), p.lds_bytes, s, a, w);
         return hipGetLastError();
     };
-    const bool wide = a.g.maxM0 > 62 || a.g.maxM > 62;
+    const bool wide = hnsw_wide(a.g);
     if (p.table_size == 0) return wide ? go(hnsw_search_old_kernel<SPACE, true, true>) : go(hnsw_search_old_kernel<SPACE, true, false>);
     return wide ? go(hnsw_search_old_kernel<SPACE, false, true>) : go(hnsw_search_old_kernel<SPACE, false, false>);
 }
@@ -1410,6 +1415,7 @@ static hipError_t launch_old_space(const HnswArgs& a, const OldWs& w, const Hnsw
 hipError_t launch_hnsw_search_old(const HnswDeviceGraph& g, const HnswSearchPlan& p, const void* queries, uint32_t* bitset,
                                   void* ws_a, void* ws_r, void* ws_heap, const HnswOut& out, hipStream_t s) {
     if (p.nq == 0) return hipSuccess;
+    if (p.lds_bytes > HNSW_LDS_LIMIT) return hipErrorInvalidValue;
     HnswArgs a = hnsw_args(g, p.nq, p.k, p.ef, p.cap, HnswQueries::external(queries), bitset, p.bitset_words, out);
     a.table_size = p.table_size;
     a.table_shift = p.table_shift;
@@ -1429,9 +1435,16 @@ hipError_t launch_hnsw_search_old(const HnswDeviceGraph& g, const HnswSearchPlan
 // ---- SearchV1Merge beyond 1024 items (hnsw_search_big_kernel) ---------------------------------------------------
 template <int SPACE>
 static hipError_t launch_big_space(const HnswArgs& a, float* ws_keys, int32_t* ws_idu, size_t lds, hipStream_t s) {
-    if (a.g.maxM0 > 62 || a.g.maxM > 62) hipLaunchKernelGGL((hnsw_search_big_kernel<SPACE, true>), dim3(a.nq), dim3(64), lds, s, a, ws_keys, ws_idu);
-    else hipLaunchKernelGGL((hnsw_search_big_kernel<SPACE, false>), dim3(a.nq), dim3(64), lds, s, a, ws_keys, ws_idu);
-    return hipGetLastError();
+    // (the row of a long-row index takes more LDS than a launch gets unasked: ask, as the other launch functions do)
+    auto go = [&](auto kern) -> hipError_t {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                           (int)lds);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(kern, dim3(a.nq), dim3(64), lds, s, a, ws_keys, ws_idu);
+        return hipGetLastError();
+    };
+    if (hnsw_wide(a.g)) return go(hnsw_search_big_kernel<SPACE, true>);
+    return go(hnsw_search_big_kernel<SPACE, false>);
 }
 
 hipError_t launch_hnsw_search_big(const HnswDeviceGraph& g, int nq, int k, int ef, const void* queries, uint32_t* bitset,
@@ -1439,8 +1452,8 @@ hipError_t launch_hnsw_search_big(const HnswDeviceGraph& g, int nq, int k, int e
     if (nq == 0) return hipSuccess;
     const HnswArgs a = hnsw_args(g, nq, k, ef, ef > k ? ef : k, HnswQueries::external(queries), bitset,
                                  ((size_t)g.n + 31) / 32, out);
-    const bool u8 = g.space == SP_L2SQR_SIFT;
-    const size_t lds = (u8 ? 128 : (size_t)g.ldv * 4) + (size_t)(2 * hnsw_nbcap(g) + 2 * 64) * 4 + 16;
+    const size_t lds = hnsw_big_lds(g);
+    if (lds > HNSW_LDS_LIMIT) return hipErrorInvalidValue;
     return hnsw_dispatch_space(g.space, [&](auto sp) { return launch_big_space<sp.value>(a, ws_keys, ws_idu, lds, s); });
 }
 

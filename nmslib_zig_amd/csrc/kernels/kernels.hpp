@@ -362,10 +362,23 @@ inline int hnsw_nbcap(const HnswDeviceGraph& g) {
     const int longest = g.maxM0 > g.maxM ? g.maxM0 : g.maxM;
     return longest <= 62 ? 64 : (longest + 64) / 64 * 64;
 }
+// Narrow or wide adjacency lists: a list of up to 62 entries is one word a lane (count, ids, one lane spare); the WIDE
+// instantiations of every search kernel walk longer lists in chunks.  The launch functions choose by this alone.
+inline bool hnsw_wide(const HnswDeviceGraph& g) { return g.maxM0 > 62 || g.maxM > 62; }
+// 64-entry registers a lane of the LDS kernels' sorted array (their EMAX): 2, 4 or 16 for cap = max(ef, k) up to 128, 256, 1024
+inline int hnsw_emax(int cap) { return cap <= 128 ? 2 : cap <= 256 ? 4 : 16; }
 
-// the LDS search kernels hold frontiers of up to this many neighbours (lists up to maxM0 = 254, i.e. M <= 127); longer lists
-// go to the HBM-array kernel
+// the LDS search kernels hold frontiers of up to this many neighbours (lists up to 255 entries: hnsw_nbcap leaves one entry
+// spare); longer lists go to the HBM-array kernel
 constexpr int HNSW_NBCAP_LDS = 256;
+
+// What a workgroup may take of a gfx950 CU's LDS.  Every search kernel stages the query row there, so rows beyond some
+// 40 000 floats fit none of them: the launch functions refuse such a plan with hipErrorInvalidValue instead of launching.
+constexpr size_t HNSW_LDS_LIMIT = 160 * 1024;
+// dynamic LDS of the HBM-array kernel (hnsw_search_big_kernel): the query row, the frontier arrays, the accepted items
+inline size_t hnsw_big_lds(const HnswDeviceGraph& g) {
+    return (g.space == SP_L2SQR_SIFT ? 128 : (size_t)g.ldv * 4) + (size_t)(2 * hnsw_nbcap(g) + 2 * 64) * 4 + 16;
+}
 
 HnswSearchPlan hnsw_make_plan(const HnswDeviceGraph& g, int nq, int k, int ef, bool force_bitset);
 // Plan of the SearchOld kernel (hnsw_distfunc_opt.cc:46-150): no limit on ef or k.  heap_cap = 0 picks the default

@@ -102,9 +102,10 @@ def test_oracle_parity_same_graph_with_counters(space):
     idx.close()
 
 
-def test_visited_table_overflow_falls_back_to_bitset_not_cpu():
-    """A tiny graph degree with a huge ef fills the LDS hash: the engine re-runs on the HBM bitset
-    variant of the same kernel; results still equal the oracle."""
+def test_huge_ef_on_a_small_degree_takes_the_bitset_plan():
+    """A tiny graph degree (maxM0 = 12) with a huge ef: the planner wants a small table, 18 * ef is beyond half of it, and the
+    batch runs the HBM-bitset variant of the kernel from the start -- no LDS table, nothing re-run; results equal the
+    oracle.  (A table that really overflows: tests/test_gpu_hnsw_plan_edges.py::test_visited_table_overflow.)"""
     n, D, nq = 30000, 32, 40
     X, Q = refio.s_gauss(n, D, 61), refio.s_gauss(nq, D, 62)
     idx = make_index("l2", "hnsw", X, M=6, efConstruction=40, indexThreadQty=1)

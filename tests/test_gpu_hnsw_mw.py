@@ -88,7 +88,10 @@ def test_multiwave_oracle_parity_1024_queries_counters():
     idx.close()
 
 
-def test_multiwave_table_overflow_goes_to_the_bitset_kernel():
+def test_bitset_plan_is_the_same_under_either_mw_setting():
+    """maxM0 = 12 and ef = 250: 18 * ef is beyond half of the 8192 entries wanted, so the plan is a bitset plan, which the
+    one-wave kernel serves whatever NMSLIB_HNSW_MW says: the same bits, equal to the oracle.  (The multi-wave kernel with a
+    table that overflows: tests/test_gpu_hnsw_plan_edges.py::test_visited_table_overflow.)"""
     n, D, nq = 30000, 32, 40
     X, Q = refio.s_gauss(n, D, 61), refio.s_gauss(nq, D, 62)
     idx = make_index("l2", "hnsw", X, M=6, efConstruction=40, indexThreadQty=1)
