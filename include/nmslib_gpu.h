@@ -99,7 +99,9 @@ typedef struct {
                               were scanned exactly instead of walked (nmslib_gpu_filter_create); 8 = HNSW with the filter and
                               the tombstones tested inside the walk (query-time parameter gpu_inwalk=1); 9 = a batch with one
                               filter per query (nmslib_gpu_knn_query_batch_filtered_each: its `routes` has the paths).  A filtered
-                              batch on an exact-scan index reports the path it took over the allowed rows */
+                              batch on an exact-scan index reports the path it took over the allowed rows; 10 = a batched
+                              range query answered by the batched kernels (nmslib_gpu_range_query_batch), 11 = a batched
+                              range query answered with the single-query launches, once per query */
     /* fast paths, last slice of the last batch (reading them waits for the stream): query tiles in the slice, tiles the
        threshold kernel sent through the split-bf16-product scan instead of the one-product scan (float rows only), and
        tiles whose verification failed and were redone by the adaptive kernel */
@@ -270,6 +272,42 @@ nmslib_error_t nmslib_gpu_knn_query_batch_filtered_each_device(nmslib_index_hand
                                                                const void* d_queries, size_t query_count, size_t elem_count,
                                                                size_t k, int32_t* d_ids, float* d_dists, int32_t* d_counts,
                                                                int32_t* routes, void* stream);
+
+/* Batched range queries on the exact scan: query_count range queries,
+ * each with its own radius, in one call; the rows are read once per slice of the batch instead of once per query.
+ * Row q of the results is, bit for bit, what nmslib_range_query_fill writes for query q with radii[q] into a result of
+ * `capacity` entries: the first `capacity` rows with distance <= radius in insertion (position) order, external ids and the
+ * reference formula's distance.  The radius is converted as that entry converts it ((float)radius; l2sqr_sift:
+ * (float)(int)radius), so a negative or NaN radius matches here what it matches there.
+ *   ids / dists : [query_count][capacity]; entries beyond counts[q] are -1 / +inf, as in nmslib_gpu_knn_query_batch_device
+ *   counts      : [query_count], entries written = min(totals[q], capacity); may be NULL
+ *   totals      : [query_count], every row within the radius, no cap; may be NULL unless capacity == 0
+ *   capacity    : per query; 0 = count only, ids and dists may then be NULL
+ *   radii       : [query_count] HOST memory in both entries, read before the call returns
+ * Served: brute_force and seq_search over l2, l1, linf, cosinesimil, angulardist, negdotprod and l2sqr_sift.  Deleted rows
+ * do not appear; after nmslib_gpu_consolidate the answers are on the new positions.  The host entry also serves a sharded
+ * exact-scan index: the shards are asked in order, per query their lists are put back to back up to `capacity` and the
+ * totals are summed, which is the unsharded answer bit for bit; the device entry on a sharded index ->
+ * NMSLIB_ERROR_SPACE_INCOMPATIBLE.
+ * The device entry keeps the contract of nmslib_gpu_knn_query_batch_device (alignment of the element type only, order across
+ * streams, the stream's lifetime).  It only enqueues work; its workspaces are sized before the first kernel.  The radii
+ * cross through two pinned blocks taken in turn: a call waits on the host only if the radii copy of the call before the
+ * previous one has not run yet.
+ * last_path afterwards: 10 = the batched kernels; 11 = the single-query launches, once per query, into the batch's rows
+ * (float rows of more than 256 dimensions, or a workspace bound below one query's masks).  The bound of the mask workspace
+ * is 256 MiB; the environment switch NMSLIB_GPU_RANGE_WS_BYTES, read per call, lowers it.
+ * Checked before a device is needed, and on an error the outputs are untouched: a NULL index, queries or radii, or ids / dists
+ * NULL with capacity > 0 -> NMSLIB_ERROR_NULL_POINTER; capacity == 0 with totals == NULL -> NMSLIB_ERROR_INVALID_ARGUMENT; an
+ * index that was never built -> NMSLIB_ERROR_INDEX_BUILD_FAILED; hnsw -> NMSLIB_ERROR_SPACE_INCOMPATIBLE with the message of
+ * nmslib_range_query_fill; sparse, string and divergence indexes -> NMSLIB_ERROR_SPACE_INCOMPATIBLE, the message names what
+ * is served; a query length other than the index's -> NMSLIB_ERROR_INVALID_ARGUMENT; query_count == 0 -> NMSLIB_SUCCESS,
+ * nothing is written. */
+nmslib_error_t nmslib_gpu_range_query_batch(nmslib_index_handle_t index, const void* queries, size_t query_count,
+                                            size_t elem_count, const double* radii, size_t capacity, int32_t* ids,
+                                            float* dists, int32_t* counts, int32_t* totals);
+nmslib_error_t nmslib_gpu_range_query_batch_device(nmslib_index_handle_t index, const void* d_queries, size_t query_count,
+                                                   size_t elem_count, const double* radii, size_t capacity, int32_t* d_ids,
+                                                   float* d_dists, int32_t* d_counts, int32_t* d_totals, void* stream);
 
 #ifdef __cplusplus
 }

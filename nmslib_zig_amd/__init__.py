@@ -186,6 +186,8 @@ def lib():
         "nmslib_gpu_knn_query_batch_filtered_device": (C.c_int, [vp, vp, vp, sz, sz, sz, vp, vp, vp, vp]),
         "nmslib_gpu_knn_query_batch_filtered_each": (C.c_int, [vp, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp, vp]),
         "nmslib_gpu_knn_query_batch_filtered_each_device": (C.c_int, [vp, vp, sz, vp, vp, sz, sz, sz, vp, vp, vp, vp, vp]),
+        "nmslib_gpu_range_query_batch": (C.c_int, [vp, vp, sz, sz, vp, sz, vp, vp, vp, vp]),
+        "nmslib_gpu_range_query_batch_device": (C.c_int, [vp, vp, sz, sz, vp, sz, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sigs.items():
         fn = getattr(L, name)   # AttributeError here = a declared symbol is not exported
@@ -216,7 +218,8 @@ ABI_SYMBOLS_GPU = ["nmslib_gpu_device_count", "nmslib_gpu_finalize",
                    "nmslib_gpu_deleted_rows", "nmslib_gpu_consolidate", "nmslib_gpu_filter_create",
                    "nmslib_gpu_filter_destroy", "nmslib_gpu_filter_info", "nmslib_gpu_knn_query_batch_filtered",
                    "nmslib_gpu_knn_query_batch_filtered_device", "nmslib_gpu_knn_query_batch_filtered_each",
-                   "nmslib_gpu_knn_query_batch_filtered_each_device"]
+                   "nmslib_gpu_knn_query_batch_filtered_each_device", "nmslib_gpu_range_query_batch",
+                   "nmslib_gpu_range_query_batch_device"]
 
 
 class TrackingAllocator:
@@ -425,6 +428,34 @@ class Index:
         r = Result(ids.ctypes.data_as(C.POINTER(C.c_int32)), ds.ctypes.data_as(C.POINTER(C.c_float)), 0, capacity)
         _check(L.nmslib_range_query_fill(self.h, q.ctypes.data, qsz, float(radius), C.byref(r), ne), self.alloc)
         return ids[:r.size].copy(), ds[:r.size].copy()
+
+    def rangeQueryBatch(self, queries, radii, capacity):
+        """nmslib_gpu_range_query_batch: one range query per row of `queries`, each with its own radius (a scalar `radii`
+        broadcasts), in one pass over the rows -> ids [Q, capacity], dists [Q, capacity], counts [Q], totals [Q].  Row q
+        holds what rangeQueryFill(queries[q], radii[q], capacity) returns, bit for bit, then -1 / +inf; counts[q] =
+        min(totals[q], capacity) entries are valid and totals[q] counts every row within the radius.  capacity = 0 counts
+        only.  brute_force / seq_search over the dense float spaces and l2sqr_sift; stats()["last_path"] is 10 (the batched
+        kernels) or 11 (one single-query chain per query: rows of more than 256 dimensions)."""
+        q = np.ascontiguousarray(queries, np.uint8 if self.data_type == "DenseUInt8Vector" else np.float32)
+        nq = q.shape[0]
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, np.float64), (nq,)))
+        ids = np.empty((nq, capacity), np.int32)      # (the call writes every element: the entries, then -1 / +inf)
+        ds = np.empty((nq, capacity), np.float32)
+        cnt = np.zeros(nq, np.int32)
+        tot = np.zeros(nq, np.int32)
+        _check(lib().nmslib_gpu_range_query_batch(self.h, q.ctypes.data, nq, q.shape[1], r.ctypes.data, capacity,
+                                                  ids.ctypes.data if capacity else None,
+                                                  ds.ctypes.data if capacity else None, cnt.ctypes.data, tot.ctypes.data),
+               self.alloc)
+        return ids, ds, cnt, tot
+
+    def range_device(self, d_queries_ptr, nq, dim, radii, capacity, d_ids_ptr, d_dists_ptr, d_cnt_ptr=None,
+                     d_totals_ptr=None, stream=None):
+        """nmslib_gpu_range_query_batch_device: queries and results in device memory; radii (a scalar broadcasts) on the
+        host, read before the call returns.  The call only enqueues."""
+        r = np.ascontiguousarray(np.broadcast_to(np.asarray(radii, np.float64), (nq,)))
+        _check(lib().nmslib_gpu_range_query_batch_device(self.h, d_queries_ptr, nq, dim, r.ctypes.data, capacity, d_ids_ptr,
+                                                         d_dists_ptr, d_cnt_ptr, d_totals_ptr, stream), self.alloc)
 
     def knnQueryBatch(self, queries, k):
         """One call of nmslib_knn_query_batch: a single GPU batch.  -> ids [Q,k], dists [Q,k], counts [Q]

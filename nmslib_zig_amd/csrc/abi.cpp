@@ -1024,6 +1024,43 @@ nmslib_error_t nmslib_gpu_knn_query_batch_filtered_each_device(nmslib_index_hand
     });
 }
 
+// ---- batched range queries on the exact scan: the pointer checks here, every other refusal that needs
+// no device first thing in the engine; nothing is written on an error ----
+static nmslib_error_t range_batch_arg_check(nmslib_index_handle_t handle, const void* queries, const double* radii,
+                                            size_t capacity, const int32_t* ids, const float* dists,
+                                            const int32_t* totals) {
+    if (!handle) FAIL(NMSLIB_ERROR_NULL_POINTER, "Invalid index");
+    if (!queries || !radii) FAIL(NMSLIB_ERROR_NULL_POINTER, "queries or radii is NULL");
+    if (capacity > 0 && (!ids || !dists)) FAIL(NMSLIB_ERROR_NULL_POINTER, "ids or dists is NULL with a positive capacity");
+    if (capacity == 0 && !totals) FAIL(NMSLIB_ERROR_INVALID_ARGUMENT, "capacity 0 counts only: totals must not be NULL");
+    return NMSLIB_SUCCESS;
+}
+
+nmslib_error_t nmslib_gpu_range_query_batch(nmslib_index_handle_t handle, const void* queries, size_t query_count,
+                                            size_t elem_count, const double* radii, size_t capacity, int32_t* ids,
+                                            float* dists, int32_t* counts, int32_t* totals) {
+    const nmslib_error_t rc = range_batch_arg_check(handle, queries, radii, capacity, ids, dists, totals);
+    if (rc != NMSLIB_SUCCESS) return rc;
+    Engine* e = H(handle)->engine;
+    return guarded(NMSLIB_ERROR_QUERY_EXECUTION_FAILED, "Range query batch failed", [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        e->range_batch_host(queries, query_count, elem_count, radii, capacity, ids, dists, counts, totals);
+    });
+}
+
+nmslib_error_t nmslib_gpu_range_query_batch_device(nmslib_index_handle_t handle, const void* d_queries, size_t query_count,
+                                                   size_t elem_count, const double* radii, size_t capacity, int32_t* d_ids,
+                                                   float* d_dists, int32_t* d_counts, int32_t* d_totals, void* stream) {
+    const nmslib_error_t rc = range_batch_arg_check(handle, d_queries, radii, capacity, d_ids, d_dists, d_totals);
+    if (rc != NMSLIB_SUCCESS) return rc;
+    Engine* e = H(handle)->engine;
+    return guarded(NMSLIB_ERROR_QUERY_EXECUTION_FAILED, "Range query device batch failed", [&] {
+        std::lock_guard<std::mutex> lk(e->mu);
+        e->range_batch_device(d_queries, query_count, elem_count, radii, capacity, d_ids, d_dists, d_counts, d_totals,
+                              static_cast<hipStream_t>(stream));
+    });
+}
+
 nmslib_error_t nmslib_gpu_string_hnsw_links(nmslib_index_handle_t index, size_t node, int level, int32_t* out,
                                             size_t capacity, size_t* count, int* enterpoint, int* maxlevel) {
     if (!index || !count || !enterpoint || !maxlevel || node >= nmslib_data_qty(index) || level < 0)

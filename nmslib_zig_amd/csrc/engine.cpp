@@ -1,10 +1,12 @@
 // Engine: host logic around the gfx950 kernels (see engine.hpp).
 #include "engine.hpp"
 #include "f16_pack.hpp"
+#include "range_batch_plan.hpp"
 
 #include <algorithm>
 #include <chrono>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <set>
@@ -267,6 +269,10 @@ Engine::~Engine() {
     if (tomb_pinned_) (void)hipHostFree(tomb_pinned_);
     if (each_.event) (void)hipEventDestroy(each_.event);
     if (each_.pinned) (void)hipHostFree(each_.pinned);
+    for (int i = 0; i < 2; ++i) {
+        if (rb_.event[i]) (void)hipEventDestroy(rb_.event[i]);
+        if (rb_.pinned[i]) (void)hipHostFree(rb_.pinned[i]);
+    }
     if (stream_) (void)hipStreamDestroy(stream_);
 }
 
@@ -1307,6 +1313,217 @@ size_t Engine::range_host(const void* query, size_t elem_count, double radius, s
         hip_check(launch_range_dist(space_, d_rows_.ptr(), ld, (int)n, ws_qpad_.ptr(), (int)dim_, d, stream_),
                   "range distances");
     });
+}
+
+// ---------------------------------------------------------------------------------------------
+// Batched range queries: the rows are read once per slice of queries instead of once per query.
+// ---------------------------------------------------------------------------------------------
+void Engine::check_range_batch(size_t elem_count, bool device_entry) const {
+    if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
+    if (method_ != Method::Brute)  // the single entry's refusal (Hnsw::Search(RangeQuery*) throws, hnsw.cc:710-715)
+        throw EngineError(Err::SpaceIncompatible, "Range query not supported by method: Range search is not supported!");
+    if (sparse_ || str_space_ || diverg_)
+        throw EngineError(Err::SpaceIncompatible,
+                          "the batched range query is served over the dense float spaces (l2, l1, linf, cosinesimil, "
+                          "angulardist, negdotprod) and l2sqr_sift; sparse, string and divergence indexes answer one "
+                          "query at a time through nmslib_range_query_fill");
+    if (device_entry && (gpu_shards_ > 1 || !shards_.empty()))
+        throw EngineError(Err::SpaceIncompatible, "the device-resident batched range query is served on one device; a "
+                                                  "sharded index goes through nmslib_gpu_range_query_batch");
+    if (size() > 0 && elem_count != dim_)
+        throw EngineError(Err::InvalidArgument, "query length " + std::to_string(elem_count) +
+                                                    " does not match the rows' length " + std::to_string(dim_));
+}
+
+void Engine::range_batch_device(const void* d_queries, size_t nq, size_t elem_count, const double* radii, size_t capacity,
+                                int32_t* d_ids, float* d_dists, int32_t* d_counts, int32_t* d_totals, hipStream_t stream,
+                                bool pad) {
+    check_range_batch(elem_count, true);
+    if (nq == 0) return;
+    if (dirty_) finalize();
+    check_device();
+    if (!shards_.empty())  // (automatic sharding shows only now)
+        throw EngineError(Err::SpaceIncompatible, "the device-resident batched range query is served on one device; a "
+                                                  "sharded index goes through nmslib_gpu_range_query_batch");
+    const size_t n = d_n_;
+    // NMSLIB_GPU_RANGE_WS_BYTES (read per call) lowers the bound of the mask workspace: more, smaller slices
+    size_t budget = kRangeBatchWsBytes;
+    if (const char* env = getenv("NMSLIB_GPU_RANGE_WS_BYTES")) {
+        const long long v = atoll(env);
+        if (v > 0) budget = std::min(budget, (size_t)v);
+    }
+    const RangeBatchPlan plan = range_batch_plan(n, dim_, elem_bytes(), nq, capacity, budget);
+    // every workspace before the first launch: an allocation behind a kernel in flight waits for it
+    const size_t cnt_elems = range_count_elems((int)n);
+    // the radii cross through one of two pinned blocks, taken in turn: the wait below is for the copy of the call before
+    // the previous one, so back-to-back calls do not meet on the host
+    const int turn = rb_.turn;
+    rb_.turn ^= 1;
+    rb_.radii[turn].ensure(nq * 4);
+    if (plan.route == 10) {
+        rb_.masks.ensure(std::max<size_t>(8, plan.slice_queries * plan.mask_words * 8));
+        rb_.counts.ensure(plan.slice_queries * (plan.blocks + 1) * 4);
+    } else {
+        ws_rdist_.ensure(std::max<size_t>(4, n * 4));
+        ws_rcnt_.ensure(cnt_elems * 4);
+    }
+    if (rb_.event[turn]) hip_check(hipEventSynchronize(rb_.event[turn]), "range batch");  // the last copy has left the block
+    else hip_check(hipEventCreateWithFlags(&rb_.event[turn], hipEventDisableTiming), "hipEventCreate");
+    if (rb_.pinned_bytes[turn] < nq * 4) {
+        if (rb_.pinned[turn]) (void)hipHostFree(rb_.pinned[turn]);
+        rb_.pinned[turn] = nullptr;
+        rb_.pinned_bytes[turn] = 0;
+        const size_t bytes = nq * 4 + nq;   // a quarter more than asked for: slowly growing batches do not allocate each time
+        hip_check(hipHostMalloc(&rb_.pinned[turn], bytes, hipHostMallocDefault), "hipHostMalloc");
+        rb_.pinned_bytes[turn] = bytes;
+    }
+    // RangeQuery<dist_t>(space, obj, static_cast<dist_t>(radius)), as range_host converts it
+    float* hr = static_cast<float*>(rb_.pinned[turn]);
+    for (size_t q = 0; q < nq; ++q) hr[q] = is_u8() ? (float)(int)radii[q] : (float)radii[q];
+    order_after_last(stream);
+    hip_check(hipMemcpyAsync(rb_.radii[turn].ptr(), hr, nq * 4, hipMemcpyHostToDevice, stream), "radii H2D");
+    hip_check(hipEventRecord(rb_.event[turn], stream), "hipEventRecord");
+    const int ld = is_u8() ? 128 : ldb_;
+    const size_t qbytes = elem_count * elem_bytes();
+    const float* d_r = rb_.radii[turn].as<float>();
+    if (plan.route == 10) {
+        for (size_t s = 0; s < plan.slices; ++s) {
+            const size_t q0 = s * plan.slice_queries;
+            RangeBatchArgs a{};
+            a.space = space_;
+            a.rows = d_rows_.ptr();
+            a.ld = ld;
+            a.n = (int)n;
+            a.dim = (int)dim_;
+            a.queries = static_cast<const char*>(d_queries) + q0 * qbytes;
+            a.nq = (int)range_batch_slice_size(plan, nq, s);
+            a.radii = d_r + q0;
+            a.capacity = capacity;
+            a.out_ids = capacity ? d_ids + q0 * capacity : nullptr;
+            a.out_dists = capacity ? d_dists + q0 * capacity : nullptr;
+            a.out_counts = d_counts ? d_counts + q0 : nullptr;
+            a.out_totals = d_totals ? d_totals + q0 : nullptr;
+            a.ext_ids = d_ids_.as<int32_t>();
+            a.masks = rb_.masks.as<unsigned long long>();
+            a.mask_words = plan.mask_words;
+            a.counts = rb_.counts.as<int>();
+            a.grid_x = (unsigned)plan.grid_x;
+            a.grid_y = (unsigned)plan.grid_y;
+            a.pad = pad;
+            hip_check(launch_range_batch(a, stream), "range batch");
+        }
+    } else {
+        // the single-query launches, once per query, into the batch's rows: the old code and the old bits
+        float* dist = ws_rdist_.as<float>();
+        int* cnt = ws_rcnt_.as<int>();
+        const int cap = (int)std::min(capacity, n);
+        for (size_t q = 0; q < nq; ++q) {
+            int32_t* oi = capacity ? d_ids + q * capacity : nullptr;
+            float* od = capacity ? d_dists + q * capacity : nullptr;
+            hip_check(launch_range_dist(space_, d_rows_.ptr(), ld, (int)n, static_cast<const char*>(d_queries) + q * qbytes,
+                                        (int)dim_, dist, stream),
+                      "range distances");
+            hip_check(launch_range_select(dist, dist, (int)n, hr[q], d_ids_.as<int32_t>(), cnt, cap, oi, od, stream),
+                      "range select");
+            hip_check(launch_range_batch_finish(cnt + (cnt_elems - 1), capacity, oi, od, d_counts ? d_counts + q : nullptr,
+                                                d_totals ? d_totals + q : nullptr, pad, stream),
+                      "range batch");
+        }
+    }
+    have_counters_ = false;
+    last_path = plan.route;
+}
+
+void Engine::range_batch_host(const void* queries, size_t nq, size_t elem_count, const double* radii, size_t capacity,
+                              int32_t* ids, float* dists, int32_t* counts, int32_t* totals) {
+    check_range_batch(elem_count, false);
+    if (nq == 0) return;
+    if (dirty_) finalize();
+    check_device();
+    // what a query gets: row q = got[q] entries, then the padding
+    auto pad_rows = [&](const std::vector<size_t>& got) {
+        for (size_t q = 0; q < nq; ++q) {
+            std::fill(ids + q * capacity + got[q], ids + (q + 1) * capacity, -1);
+            std::fill(dists + q * capacity + got[q], dists + (q + 1) * capacity, INFINITY);
+        }
+    };
+    std::vector<size_t> got(nq, 0);
+    if (!shards_.empty()) {
+        // insertion order = shard order: per query the shards' lists back to back up to the capacity, the totals summed;
+        // shards report global positions.  Nothing is written before every shard has answered.
+        DeviceGuard guard(device_);
+        const size_t S = shards_.size();
+        std::vector<std::vector<int32_t>> sid(S), scnt(S), stot(S);
+        std::vector<std::vector<float>> sd(S);
+        std::vector<size_t> scap(S);
+        for (size_t s = 0; s < S; ++s) {
+            Engine& c = *shards_[s];
+            scap[s] = std::min(capacity, c.size());
+            sid[s].resize(nq * scap[s]);
+            sd[s].resize(nq * scap[s]);
+            scnt[s].resize(nq);
+            stot[s].resize(nq);
+            c.range_batch_host(queries, nq, elem_count, radii, scap[s], sid[s].data(), sd[s].data(), scnt[s].data(),
+                               stot[s].data());
+        }
+        hip_check(hipSetDevice(device_), "hipSetDevice");
+        last_path = shards_[0]->last_path;
+        for (size_t q = 0; q < nq; ++q) {
+            long long total = 0;
+            for (size_t s = 0; s < S; ++s) {
+                total += stot[s][q];
+                const size_t m = std::min<size_t>((size_t)scnt[s][q], capacity - got[q]);
+                for (size_t i = 0; i < m; ++i) {
+                    ids[q * capacity + got[q] + i] = ids_[(size_t)sid[s][q * scap[s] + i]];
+                    dists[q * capacity + got[q] + i] = sd[s][q * scap[s] + i];
+                }
+                got[q] += m;
+            }
+            if (counts) counts[q] = (int32_t)got[q];
+            if (totals) totals[q] = (int32_t)total;
+        }
+        pad_rows(got);
+        return;
+    }
+    // no more than d_n_ rows can match: the device side of a row ends there.  The device does not pad here: the counts come
+    // back first, then only the columns that hold an entry of some query (one strided copy per array), and the padding is
+    // written once, in the caller's memory.
+    const size_t cap = std::min(capacity, d_n_);
+    const size_t qbytes = nq * elem_count * elem_bytes();
+    ws_q_.ensure(qbytes);
+    rb_.res.ensure(2 * nq * cap * 4 + 2 * nq * 4);
+    char* hp = static_cast<char*>(pinned(qbytes));
+    std::memcpy(hp, queries, qbytes);
+    order_after_last(stream_);
+    hip_check(hipMemcpyAsync(ws_q_.ptr(), hp, qbytes, hipMemcpyHostToDevice, stream_), "queries H2D");
+    int32_t* d_i = rb_.res.as<int32_t>();
+    float* d_d = reinterpret_cast<float*>(d_i + nq * cap);
+    int32_t* d_c = d_i + 2 * nq * cap;
+    range_batch_device(ws_q_.ptr(), nq, elem_count, radii, cap, d_i, d_d, d_c, d_c + nq, stream_, false);
+    std::vector<int32_t> h_c(2 * nq);
+    hip_check(hipMemcpyAsync(h_c.data(), d_c, 2 * nq * 4, hipMemcpyDeviceToHost, stream_), "counts D2H");
+    hip_check(hipStreamSynchronize(stream_), "range batch");
+    size_t width = 0;
+    for (size_t q = 0; q < nq; ++q) width = std::max(width, got[q] = (size_t)h_c[q]);
+    if (width) {
+        hp = static_cast<char*>(pinned(2 * nq * width * 4));   // (the queries have left the block)
+        const int32_t* h_i = reinterpret_cast<const int32_t*>(hp);
+        const float* h_d = reinterpret_cast<const float*>(hp + nq * width * 4);
+        hip_check(hipMemcpy2DAsync(hp, width * 4, d_i, cap * 4, width * 4, nq, hipMemcpyDeviceToHost, stream_), "ids D2H");
+        hip_check(hipMemcpy2DAsync(hp + nq * width * 4, width * 4, d_d, cap * 4, width * 4, nq, hipMemcpyDeviceToHost, stream_),
+                  "dists D2H");
+        hip_check(hipStreamSynchronize(stream_), "range batch");
+        for (size_t q = 0; q < nq; ++q)
+            if (got[q]) {
+                std::memcpy(ids + q * capacity, h_i + q * width, got[q] * 4);
+                std::memcpy(dists + q * capacity, h_d + q * width, got[q] * 4);
+            }
+    }
+    for (size_t q = 0; q < nq; ++q) {
+        if (counts) counts[q] = h_c[q];
+        if (totals) totals[q] = h_c[nq + q];
+    }
+    pad_rows(got);
 }
 
 // *d_out, after the stream's work

@@ -306,6 +306,18 @@ class Engine {
     // RangeQuery on the brute-force index: matches in insertion order, the first `capacity`; returns how many were written
     size_t range_host(const void* query, size_t elem_count, double radius, size_t capacity, int32_t* ids, float* dists);
     bool is_brute() const { return method_ == Method::Brute; }
+    // ---- batched range queries on the exact scan (nmslib_gpu_range_query_batch*) ----
+    // Row q of the outputs ([nq][capacity]; -1 / +inf behind counts[q] = min(totals[q], capacity) entries) is what range_host
+    // writes for query q with radii[q]; totals[q] counts every match.  radii is host memory in both entries and is read
+    // before the call returns.  capacity == 0: count only (ids / dists unused).  counts and totals may be null.
+    // The refusals that need no device (the index kinds that are not served, the query length) come first, in both.
+    // The device entry only enqueues (range_batch_plan.hpp: last_path 10 the batched kernels, 11 the single-query
+    // launches per query); the host entry is the device entry plus copies, and asks the shards of a sharded index in order.
+    void range_batch_device(const void* d_queries, size_t nq, size_t elem_count, const double* radii, size_t capacity,
+                            int32_t* d_ids, float* d_dists, int32_t* d_counts, int32_t* d_totals, hipStream_t stream,
+                            bool pad = true);  // (pad = false: the host entry pads in host memory)
+    void range_batch_host(const void* queries, size_t nq, size_t elem_count, const double* radii, size_t capacity,
+                          int32_t* ids, float* dists, int32_t* counts, int32_t* totals);
 
     void save(const std::string& path, bool save_data);
     static std::unique_ptr<Engine> load(const std::string& path, int data_type, int dist_type, bool load_data);
@@ -392,6 +404,17 @@ class Engine {
     void scan_slices(size_t nq, size_t k, int tq, const ResultBlock& out, const ScanLaunch& launch);
     using RangeLaunch = std::function<void(float* filter, float* report)>;
     size_t range_select(bool two_dists, float r, size_t capacity, int32_t* ids, float* dists, const RangeLaunch& launch);
+    void check_range_batch(size_t elem_count, bool device_entry) const;  // the refusals that need no device
+    // a batched range query's workspaces (grow-only): the radii as floats, staged in two pinned blocks and two device
+    // buffers that calls take in turn (`event` stands behind the last copy out of a block, so a call waits for the call
+    // before the previous one at most); the match bits and block counts of a slice; the host entry's result block
+    struct RangeBatchWs {
+        DevBuf radii[2], masks, counts, res;
+        void* pinned[2] = {nullptr, nullptr};
+        size_t pinned_bytes[2] = {0, 0};
+        hipEvent_t event[2] = {nullptr, nullptr};
+        int turn = 0;
+    } rb_;
     float read_float(const float* d_out, const char* what);
     void upload_sparse();
     float pair_distance_sparse(size_t p1, size_t p2);

@@ -611,6 +611,35 @@ inline size_t range_count_elems(int n) { return (size_t)(n + 1023) / 1024 + 1; }
 hipError_t launch_range_select(const float* filter, const float* report, int n, float radius, const int32_t* ext_ids,
                                int* count_ws, int capacity, int32_t* out_ids, float* out_dists, hipStream_t s);
 
+// ---- batched range search on the brute-force index (range_batch_kernels.hip) -----
+// One slice of a batch (range_batch_plan.hpp): match bits of every (query, row), counts per 1024-row block, a scan per
+// query, then the first `capacity` matches of every query in position order, -1 / +inf behind them.  Every distance is
+// the value wave_exact_distance_f32 / _u8 returns, so row q equals launch_range_dist + launch_range_select for query q.
+struct RangeBatchArgs {
+    int space;
+    const void* rows;        // [n][ld] floats, or [n][128] bytes (l2sqr_sift)
+    int ld, n, dim;          // float rows: dim <= kRangeBatchMaxDim
+    const void* queries;     // [nq][dim] elements, unpadded, element alignment
+    int nq;                  // <= kRangeBatchMaxSliceQueries
+    const float* radii;      // [nq], device
+    size_t capacity;         // per query; 0: count only (out_ids / out_dists unused)
+    int32_t* out_ids;        // [nq][capacity]
+    float* out_dists;
+    int32_t* out_counts;     // [nq] min(total, capacity); may be null
+    int32_t* out_totals;     // [nq]; may be null
+    const int32_t* ext_ids;  // [n]
+    unsigned long long* masks;  // workspace: [nq][mask_words]
+    size_t mask_words;          // ceil(n / 64)
+    int* counts;                // workspace: [nq][ceil(n / 1024) + 1]
+    unsigned grid_x, grid_y;    // the match-bit kernel's grid (the plan's)
+    bool pad;                   // write -1 / +inf behind the entries a query gets (false: the caller pads)
+};
+hipError_t launch_range_batch(const RangeBatchArgs& a, hipStream_t s);
+// Behind launch_range_select of one query into a row of a batch's outputs (*total = its count_ws total): the query's count
+// and total (either may be null) and, with pad, the padding of its row.
+hipError_t launch_range_batch_finish(const int* total, size_t capacity, int32_t* out_ids, float* out_dists,
+                                     int32_t* out_count, int32_t* out_total, bool pad, hipStream_t s);
+
 // ---- exact scans over sparse and string rows: the plan they share ---------------------------------
 // A scan's grid is (row splits, query tiles); each workgroup keeps the best kl keys of its split per query of its tile
 // (kernels/split_topk_dev.hpp) and writes them as ascending lists that launch_merge_topk_ex merges.

@@ -144,6 +144,27 @@ class Index {
         r.distances.resize(c.size);
         return r;
     }
+    // nmslib_gpu_range_query_batch: `count` range queries, query i with radii[i], in one pass over the rows.  Result i holds
+    // what rangeQuery would return for it into a result of `capacity` entries (the first matches in insertion order);
+    // totals (optional, [count]) receives the number of rows within each radius, uncut.  brute_force / seq_search over the
+    // dense float spaces and l2sqr_sift.
+    std::vector<QueryResult> rangeQueryBatch(const void* queries, size_t count, size_t elem_count, const double* radii,
+                                             size_t capacity, std::vector<int32_t>* totals = nullptr) {
+        if (totals) totals->clear();
+        if (count == 0) return {};
+        std::vector<int32_t> ids(count * capacity), cnt(count), tot(count);
+        std::vector<float> ds(count * capacity);
+        check(nmslib_gpu_range_query_batch(h_, queries, count, elem_count, radii, capacity, capacity ? ids.data() : nullptr,
+                                           capacity ? ds.data() : nullptr, cnt.data(), tot.data()),
+              alloc_, "rangeQueryBatch");
+        std::vector<QueryResult> out(count);
+        for (size_t i = 0; i < count; ++i) {
+            out[i].ids.assign(ids.begin() + i * capacity, ids.begin() + i * capacity + cnt[i]);
+            out[i].distances.assign(ds.begin() + i * capacity, ds.begin() + i * capacity + cnt[i]);
+        }
+        if (totals) *totals = tot;
+        return out;
+    }
     // One GPU batch (the reference loops per query, lib.zig:889-931).
     std::vector<QueryResult> knnQueryBatch(const void* queries, size_t count, size_t elem_count, size_t k) {
         std::vector<QueryResult> out(count);
