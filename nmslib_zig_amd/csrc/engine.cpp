@@ -1,7 +1,6 @@
 // Engine: host logic around the gfx950 kernels (see engine.hpp).
 #include "engine.hpp"
 #include "f16_pack.hpp"
-#include "range_batch_plan.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -84,7 +83,7 @@ void ParamSet::check_unused() const {
 }
 
 // ---------------------------------------------------------------------------------------------
-// DevBuf
+// DevBuf, Event, PinnedBuf
 // ---------------------------------------------------------------------------------------------
 void* DevBuf::ensure(size_t bytes) {
     if (bytes <= n_ && p_) return p_;
@@ -123,6 +122,18 @@ void DevBuf::release() {
     if (p_) (void)hipFree(p_);
     p_ = nullptr;
     n_ = 0;
+}
+
+void Event::record(hipStream_t s) {
+    if (!e_) hip_check(hipEventCreateWithFlags(&e_, hipEventDisableTiming), "hipEventCreate");
+    hip_check(hipEventRecord(e_, s), "hipEventRecord");
+}
+void* PinnedBuf::ensure(size_t bytes, size_t slack) {
+    if (bytes <= n_ && p_) return p_;
+    if (p_) (void)hipHostFree(p_);
+    p_ = nullptr;
+    hip_check(hipHostMalloc(&p_, n_ = bytes + slack, hipHostMallocDefault), "hipHostMalloc");
+    return p_;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -261,26 +272,14 @@ Engine::~Engine() {
         (void)hipEventDestroy(pr.first);
         (void)hipEventDestroy(pr.second);
     }
-    for (hipEvent_t e : shard_events_) (void)hipEventDestroy(e);
-    if (shard_ready_) (void)hipEventDestroy(shard_ready_);
-    if (order_event_) (void)hipEventDestroy(order_event_);
-    if (pinned_) (void)hipHostFree(pinned_);
-    if (tomb_event_) (void)hipEventDestroy(tomb_event_);
-    if (tomb_pinned_) (void)hipHostFree(tomb_pinned_);
-    if (each_.event) (void)hipEventDestroy(each_.event);
-    if (each_.pinned) (void)hipHostFree(each_.pinned);
-    for (int i = 0; i < 2; ++i) {
-        if (rb_.event[i]) (void)hipEventDestroy(rb_.event[i]);
-        if (rb_.pinned[i]) (void)hipHostFree(rb_.pinned[i]);
-    }
+    // the members go after stream_: destroying an event or freeing pinned or device memory behind its stream is legal
     if (stream_) (void)hipStreamDestroy(stream_);
 }
 
 void Engine::order_after_last(hipStream_t next) {
     if (have_last_ && last_stream_ != next) {
-        if (!order_event_) hip_check(hipEventCreateWithFlags(&order_event_, hipEventDisableTiming), "hipEventCreate");
-        hip_check(hipEventRecord(order_event_, last_stream_), "hipEventRecord");
-        hip_check(hipStreamWaitEvent(next, order_event_, 0), "hipStreamWaitEvent");
+        order_event_.record(last_stream_);
+        order_event_.stream_wait(next);
     }
     last_stream_ = next;
     have_last_ = true;
@@ -393,22 +392,12 @@ void Engine::upload_tombstones() {
     const size_t words = (size() + 31) / 32;
     tomb_.resize(words, 0);
     if (words == 0) return;
-    if (tomb_event_) hip_check(hipEventSynchronize(tomb_event_), "tombstones");  // the last copy has left the pinned block
-    else hip_check(hipEventCreateWithFlags(&tomb_event_, hipEventDisableTiming), "hipEventCreate");
-    if (tomb_pinned_words_ < words) {
-        if (tomb_pinned_) (void)hipHostFree(tomb_pinned_);
-        tomb_pinned_ = nullptr;
-        tomb_pinned_words_ = 0;
-        void* p = nullptr;
-        hip_check(hipHostMalloc(&p, words * 4 + words, hipHostMallocDefault), "hipHostMalloc");  // (room to grow with appends)
-        tomb_pinned_ = static_cast<uint32_t*>(p);
-        tomb_pinned_words_ = words + words / 4;
-    }
-    std::memcpy(tomb_pinned_, tomb_.data(), words * 4);
+    void* hp = tomb_staged_.begin(words * 4, "tombstones");  // (its slack: room to grow with appends)
+    std::memcpy(hp, tomb_.data(), words * 4);
     order_after_last(stream_);  // batches in flight read the old bits (and a buffer that grows is freed)
     d_tomb_.ensure(words * 4);
-    hip_check(hipMemcpyAsync(d_tomb_.ptr(), tomb_pinned_, words * 4, hipMemcpyHostToDevice, stream_), "tombstones H2D");
-    hip_check(hipEventRecord(tomb_event_, stream_), "hipEventRecord");
+    hip_check(hipMemcpyAsync(d_tomb_.ptr(), hp, words * 4, hipMemcpyHostToDevice, stream_), "tombstones H2D");
+    tomb_staged_.sent(stream_);
 }
 
 void Engine::reset() {
@@ -937,13 +926,6 @@ void Engine::finalize_index() {
     if (method_ == Method::Hnsw && rows_f16_index_) (void)ensure_rows16();
 }
 
-// restores the calling thread's current device on every way out of a scope that visits other devices
-struct DeviceGuard {
-    int dev;
-    explicit DeviceGuard(int d) : dev(d) {}
-    ~DeviceGuard() { (void)hipSetDevice(dev); }
-};
-
 // ---------------------------------------------------------------------------------------------
 // Row shards behind one handle: shard s owns rows [s*n/S, (s+1)*n/S) on device (base + s) % count,
 // with its own workspaces, stream and (HNSW) graph.  A query batch goes to every shard; per-shard top-k lists are
@@ -1022,16 +1004,8 @@ void Engine::finalize_sharded(int nshards) {
     d_ids_.ensure(std::max<size_t>(n, 1) * 4);  // position -> external id, applied after the merge
     hip_check(hipMemcpy(d_ids_.ptr(), ids_.data(), n * 4, hipMemcpyHostToDevice), "upload ids");
     d_n_ = n;
-    for (hipEvent_t e : shard_events_) (void)hipEventDestroy(e);
-    shard_events_.clear();
-    for (int s = 0; s < nshards; ++s) {
-        hip_check(hipSetDevice(shards_[(size_t)s]->device_), "hipSetDevice");
-        hipEvent_t e;
-        hip_check(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
-        shard_events_.push_back(e);
-    }
-    hip_check(hipSetDevice(device_), "hipSetDevice");
-    if (!shard_ready_) hip_check(hipEventCreateWithFlags(&shard_ready_, hipEventDisableTiming), "hipEventCreate");
+    shard_events_.clear();  // (made again at their first record, each on its shard's device)
+    shard_events_.resize((size_t)nshards);
 }
 
 void Engine::knn_sharded(const void* d_queries, size_t nq, size_t elem_count, size_t k, int32_t* d_ids, float* d_dists,
@@ -1042,7 +1016,7 @@ void Engine::knn_sharded(const void* d_queries, size_t nq, size_t elem_count, si
     DeviceGuard guard(device_);  // an exception thrown by a shard must not leave this thread on the shard's device
     ws_sh_ids_.ensure(S * nq * k * 4);
     ws_sh_d_.ensure(S * nq * k * 4);
-    hip_check(hipEventRecord(shard_ready_, stream), "hipEventRecord");  // the queries are ready on the caller's stream
+    shard_ready_.record(stream);  // the queries are ready on the caller's stream
     for (size_t s = 0; s < S; ++s) {
         Engine& c = *shards_[s];
         hip_check(hipSetDevice(c.device_), "hipSetDevice");
@@ -1051,7 +1025,7 @@ void Engine::knn_sharded(const void* d_queries, size_t nq, size_t elem_count, si
         c.rows_f16_ = rows_f16_;
         c.rerank_ = rerank_;
         c.inwalk_ = inwalk_;
-        hip_check(hipStreamWaitEvent(c.stream_, shard_ready_, 0), "hipStreamWaitEvent");
+        shard_ready_.stream_wait(c.stream_);
         const void* q = d_queries;
         if (c.device_ != device_) {
             c.ws_q_.ensure(qbytes);
@@ -1067,14 +1041,14 @@ void Engine::knn_sharded(const void* d_queries, size_t nq, size_t elem_count, si
         hip_check(hipMemcpyPeerAsync(ws_sh_d_.as<float>() + s * nq * k, device_, c.ws_dists_.ptr(), c.device_, nq * k * 4,
                                      c.stream_),
                   "dists P2P");
-        hip_check(hipEventRecord(shard_events_[s], c.stream_), "hipEventRecord");
+        shard_events_[s].record(c.stream_);
         // NMSLIB_GPU_SHARD_SERIAL=1 (diagnostics): one shard at a time instead of all shards' kernels side by side
         static const bool serial = getenv("NMSLIB_GPU_SHARD_SERIAL") && atoi(getenv("NMSLIB_GPU_SHARD_SERIAL"));
         if (serial) hip_check(hipStreamSynchronize(c.stream_), "shard (serial)");
     }
     hip_check(hipSetDevice(device_), "hipSetDevice");
     last_path = shards_[0]->last_path;  // every shard takes the same path for the same batch shape
-    for (size_t s = 0; s < S; ++s) hip_check(hipStreamWaitEvent(stream, shard_events_[s], 0), "hipStreamWaitEvent");
+    for (size_t s = 0; s < S; ++s) shard_events_[s].stream_wait(stream);
     hip_check(launch_merge_topk_ex(ws_sh_d_.as<float>(), ws_sh_ids_.as<int32_t>(), nq * k, (int)S, (int)nq, (int)k, d_dists,
                                    d_ids, d_cnt, d_ids_.as<int32_t>(), stream),
               "merge_topk");
@@ -1152,18 +1126,6 @@ void Engine::fast_tile_counts(size_t* tiles, size_t* precise, size_t* fallback) 
     }
 }
 
-// Pinned host staging buffer (grow-only): PCIe copies from/to pageable memory are staged by the runtime in small
-// chunks and block the calling thread; one pinned block makes the batch's H2D and D2H a single DMA each.
-void* Engine::pinned(size_t bytes) {
-    if (bytes <= pinned_bytes_ && pinned_) return pinned_;
-    if (pinned_) (void)hipHostFree(pinned_);
-    pinned_ = nullptr;
-    pinned_bytes_ = 0;
-    hip_check(hipHostMalloc(&pinned_, bytes, hipHostMallocDefault), "hipHostMalloc");
-    pinned_bytes_ = bytes;
-    return pinned_;
-}
-
 // The result block of a host batch: ids | dists | counts in ONE device block (ws_ids_), so that one D2H brings it
 // into the pinned block.
 Engine::ResultBlock Engine::result_block(size_t nq, size_t k) {
@@ -1177,7 +1139,7 @@ Engine::ResultBlock Engine::result_block(size_t nq, size_t k) {
 void Engine::fetch_results(size_t nq, size_t k, const char* what, const int32_t** ids, const float** dists,
                            const int32_t** cnt) {
     const size_t rbytes = nq * k * 4;
-    char* hp = static_cast<char*>(pinned_);
+    char* hp = static_cast<char*>(pinned_.ptr());
     hip_check(hipMemcpyAsync(hp, ws_ids_.ptr(), 2 * rbytes + nq * 4, hipMemcpyDeviceToHost, stream_), "results D2H");
     hip_check(hipStreamSynchronize(stream_), what);
     *ids = reinterpret_cast<const int32_t*>(hp);
@@ -1213,7 +1175,7 @@ void Engine::scan_slices(size_t nq, size_t k, int tq, const ResultBlock& out, co
 }
 
 // the one place a divergence query's length is checked: the objects of a pair must be equally long
-static void check_diverg_query_length(size_t elem_count, size_t dim) {
+void Engine::check_diverg_query_length(size_t elem_count, size_t dim) {
     if (elem_count != dim)
         throw EngineError(Err::InvalidArgument, "query length " + std::to_string(elem_count) +
                                                     " does not match the rows' length " + std::to_string(dim));
@@ -1240,290 +1202,6 @@ void Engine::knn_host(const void* queries, size_t nq, size_t elem_count, size_t 
     hip_check(hipMemcpyAsync(ws_q_.ptr(), hp, qbytes, hipMemcpyHostToDevice, stream_), "queries H2D");
     knn_device(ws_q_.ptr(), nq, elem_count, k, out.ids, out.dists, out.cnt, stream_, f);
     fetch_results(nq, k, "knn", ids, dists, cnt);
-}
-
-// Range search over all d_n_ rows (RangeQuery::CheckAndAddToResult, src/rangequery.cc:67-76).  launch(filter, report)
-// enqueues the distances of every row: the rows with filter[position] <= r are reported in insertion order, the first
-// `capacity` of them, each with report[position] (report = filter unless the space has two distances per row).  The
-// workspaces are sized before anything is enqueued: an allocation behind a kernel in flight waits for it.
-size_t Engine::range_select(bool two_dists, float r, size_t capacity, int32_t* ids, float* dists,
-                            const RangeLaunch& launch) {
-    const int n = (int)d_n_;
-    const size_t cnt_elems = range_count_elems(n);
-    ws_rdist_.ensure((two_dists ? 2 : 1) * d_n_ * 4);
-    ws_rcnt_.ensure(cnt_elems * 4);
-    // no more than d_n_ rows can match: a caller's declared capacity beyond that asks HBM for nothing
-    capacity = std::min<size_t>(capacity, d_n_);
-    ws_ids_.ensure(capacity * 4);
-    ws_dists_.ensure(capacity * 4);
-    float* filter = ws_rdist_.as<float>();
-    float* report = two_dists ? filter + d_n_ : filter;
-    launch(filter, report);
-    hip_check(launch_range_select(filter, report, n, r, d_ids_.as<int32_t>(), ws_rcnt_.as<int>(), (int)capacity,
-                                  ws_ids_.as<int32_t>(), ws_dists_.as<float>(), stream_),
-              "range select");
-    int total = 0;
-    hip_check(hipMemcpyAsync(&total, ws_rcnt_.as<int>() + (cnt_elems - 1), 4, hipMemcpyDeviceToHost, stream_),
-              "range count");
-    hip_check(hipStreamSynchronize(stream_), "range search");
-    const size_t m = std::min<size_t>((size_t)total, capacity);
-    if (m) {
-        hip_check(hipMemcpyAsync(ids, ws_ids_.ptr(), m * 4, hipMemcpyDeviceToHost, stream_), "range ids");
-        hip_check(hipMemcpyAsync(dists, ws_dists_.ptr(), m * 4, hipMemcpyDeviceToHost, stream_), "range dists");
-        hip_check(hipStreamSynchronize(stream_), "range search");
-    }
-    return m;
-}
-
-size_t Engine::range_host(const void* query, size_t elem_count, double radius, size_t capacity, int32_t* ids,
-                          float* dists) {
-    if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
-    if (diverg_ && !ids_.empty()) check_diverg_query_length(elem_count, dim_);  // refused before any device work
-    if (dirty_) finalize();
-    check_device();
-    const size_t n = d_n_;
-    if (diverg_) {
-        order_after_last(stream_);
-        return range_diverg_host(static_cast<const float*>(query), elem_count, radius, capacity, ids, dists);
-    }
-    if (n == 0 || capacity == 0) return 0;
-    if (elem_count != dim_) throw EngineError(Err::QueryExecutionFailed, "query dimension does not match the index");
-    if (!shards_.empty()) {
-        // insertion order = shard order; shards report global positions
-        DeviceGuard guard(device_);   // (a shard that throws must not leave this thread on its device)
-        size_t got = 0;
-        for (auto& c : shards_) {
-            if (got >= capacity) break;
-            got += c->range_host(query, elem_count, radius, capacity - got, ids + got, dists + got);
-        }
-        for (size_t i = 0; i < got; ++i) ids[i] = ids_[(size_t)ids[i]];
-        hip_check(hipSetDevice(device_), "hipSetDevice");
-        return got;
-    }
-    // RangeQuery<dist_t>(space, obj, static_cast<dist_t>(radius)), nmslib_c.cpp:1092-1093
-    const float r = is_u8() ? (float)(int)radius : (float)radius;
-    const int ld = is_u8() ? 128 : ldb_;
-    const int elem = is_u8() ? 1 : 4;
-    ws_qpad_.ensure((size_t)ld * elem);
-    ws_q_.ensure(elem_count * elem);
-    order_after_last(stream_);
-    return range_select(false, r, capacity, ids, dists, [&](float* d, float*) {
-        hip_check(hipMemcpyAsync(ws_q_.ptr(), query, elem_count * elem, hipMemcpyHostToDevice, stream_), "query H2D");
-        hip_check(launch_pad_rows(ws_q_.ptr(), 1, (int)dim_, ws_qpad_.ptr(), 1, ld, elem, stream_), "pad query");
-        hip_check(launch_range_dist(space_, d_rows_.ptr(), ld, (int)n, ws_qpad_.ptr(), (int)dim_, d, stream_),
-                  "range distances");
-    });
-}
-
-// ---------------------------------------------------------------------------------------------
-// Batched range queries: the rows are read once per slice of queries instead of once per query.
-// ---------------------------------------------------------------------------------------------
-void Engine::check_range_batch(size_t elem_count, bool device_entry) const {
-    if (!created_) throw EngineError(Err::IndexBuildFailed, "Index not built");
-    if (method_ != Method::Brute)  // the single entry's refusal (Hnsw::Search(RangeQuery*) throws, hnsw.cc:710-715)
-        throw EngineError(Err::SpaceIncompatible, "Range query not supported by method: Range search is not supported!");
-    if (sparse_ || str_space_ || diverg_)
-        throw EngineError(Err::SpaceIncompatible,
-                          "the batched range query is served over the dense float spaces (l2, l1, linf, cosinesimil, "
-                          "angulardist, negdotprod) and l2sqr_sift; sparse, string and divergence indexes answer one "
-                          "query at a time through nmslib_range_query_fill");
-    if (device_entry && (gpu_shards_ > 1 || !shards_.empty()))
-        throw EngineError(Err::SpaceIncompatible, "the device-resident batched range query is served on one device; a "
-                                                  "sharded index goes through nmslib_gpu_range_query_batch");
-    if (size() > 0 && elem_count != dim_)
-        throw EngineError(Err::InvalidArgument, "query length " + std::to_string(elem_count) +
-                                                    " does not match the rows' length " + std::to_string(dim_));
-}
-
-void Engine::range_batch_device(const void* d_queries, size_t nq, size_t elem_count, const double* radii, size_t capacity,
-                                int32_t* d_ids, float* d_dists, int32_t* d_counts, int32_t* d_totals, hipStream_t stream,
-                                bool pad) {
-    check_range_batch(elem_count, true);
-    if (nq == 0) return;
-    if (dirty_) finalize();
-    check_device();
-    if (!shards_.empty())  // (automatic sharding shows only now)
-        throw EngineError(Err::SpaceIncompatible, "the device-resident batched range query is served on one device; a "
-                                                  "sharded index goes through nmslib_gpu_range_query_batch");
-    const size_t n = d_n_;
-    // NMSLIB_GPU_RANGE_WS_BYTES (read per call) lowers the bound of the mask workspace: more, smaller slices
-    size_t budget = kRangeBatchWsBytes;
-    if (const char* env = getenv("NMSLIB_GPU_RANGE_WS_BYTES")) {
-        const long long v = atoll(env);
-        if (v > 0) budget = std::min(budget, (size_t)v);
-    }
-    const RangeBatchPlan plan = range_batch_plan(n, dim_, elem_bytes(), nq, capacity, budget);
-    // every workspace before the first launch: an allocation behind a kernel in flight waits for it
-    const size_t cnt_elems = range_count_elems((int)n);
-    // the radii cross through one of two pinned blocks, taken in turn: the wait below is for the copy of the call before
-    // the previous one, so back-to-back calls do not meet on the host
-    const int turn = rb_.turn;
-    rb_.turn ^= 1;
-    rb_.radii[turn].ensure(nq * 4);
-    if (plan.route == 10) {
-        rb_.masks.ensure(std::max<size_t>(8, plan.slice_queries * plan.mask_words * 8));
-        rb_.counts.ensure(plan.slice_queries * (plan.blocks + 1) * 4);
-    } else {
-        ws_rdist_.ensure(std::max<size_t>(4, n * 4));
-        ws_rcnt_.ensure(cnt_elems * 4);
-    }
-    if (rb_.event[turn]) hip_check(hipEventSynchronize(rb_.event[turn]), "range batch");  // the last copy has left the block
-    else hip_check(hipEventCreateWithFlags(&rb_.event[turn], hipEventDisableTiming), "hipEventCreate");
-    if (rb_.pinned_bytes[turn] < nq * 4) {
-        if (rb_.pinned[turn]) (void)hipHostFree(rb_.pinned[turn]);
-        rb_.pinned[turn] = nullptr;
-        rb_.pinned_bytes[turn] = 0;
-        const size_t bytes = nq * 4 + nq;   // a quarter more than asked for: slowly growing batches do not allocate each time
-        hip_check(hipHostMalloc(&rb_.pinned[turn], bytes, hipHostMallocDefault), "hipHostMalloc");
-        rb_.pinned_bytes[turn] = bytes;
-    }
-    // RangeQuery<dist_t>(space, obj, static_cast<dist_t>(radius)), as range_host converts it
-    float* hr = static_cast<float*>(rb_.pinned[turn]);
-    for (size_t q = 0; q < nq; ++q) hr[q] = is_u8() ? (float)(int)radii[q] : (float)radii[q];
-    order_after_last(stream);
-    hip_check(hipMemcpyAsync(rb_.radii[turn].ptr(), hr, nq * 4, hipMemcpyHostToDevice, stream), "radii H2D");
-    hip_check(hipEventRecord(rb_.event[turn], stream), "hipEventRecord");
-    const int ld = is_u8() ? 128 : ldb_;
-    const size_t qbytes = elem_count * elem_bytes();
-    const float* d_r = rb_.radii[turn].as<float>();
-    if (plan.route == 10) {
-        for (size_t s = 0; s < plan.slices; ++s) {
-            const size_t q0 = s * plan.slice_queries;
-            RangeBatchArgs a{};
-            a.space = space_;
-            a.rows = d_rows_.ptr();
-            a.ld = ld;
-            a.n = (int)n;
-            a.dim = (int)dim_;
-            a.queries = static_cast<const char*>(d_queries) + q0 * qbytes;
-            a.nq = (int)range_batch_slice_size(plan, nq, s);
-            a.radii = d_r + q0;
-            a.capacity = capacity;
-            a.out_ids = capacity ? d_ids + q0 * capacity : nullptr;
-            a.out_dists = capacity ? d_dists + q0 * capacity : nullptr;
-            a.out_counts = d_counts ? d_counts + q0 : nullptr;
-            a.out_totals = d_totals ? d_totals + q0 : nullptr;
-            a.ext_ids = d_ids_.as<int32_t>();
-            a.masks = rb_.masks.as<unsigned long long>();
-            a.mask_words = plan.mask_words;
-            a.counts = rb_.counts.as<int>();
-            a.grid_x = (unsigned)plan.grid_x;
-            a.grid_y = (unsigned)plan.grid_y;
-            a.pad = pad;
-            hip_check(launch_range_batch(a, stream), "range batch");
-        }
-    } else {
-        // the single-query launches, once per query, into the batch's rows: the old code and the old bits
-        float* dist = ws_rdist_.as<float>();
-        int* cnt = ws_rcnt_.as<int>();
-        const int cap = (int)std::min(capacity, n);
-        for (size_t q = 0; q < nq; ++q) {
-            int32_t* oi = capacity ? d_ids + q * capacity : nullptr;
-            float* od = capacity ? d_dists + q * capacity : nullptr;
-            hip_check(launch_range_dist(space_, d_rows_.ptr(), ld, (int)n, static_cast<const char*>(d_queries) + q * qbytes,
-                                        (int)dim_, dist, stream),
-                      "range distances");
-            hip_check(launch_range_select(dist, dist, (int)n, hr[q], d_ids_.as<int32_t>(), cnt, cap, oi, od, stream),
-                      "range select");
-            hip_check(launch_range_batch_finish(cnt + (cnt_elems - 1), capacity, oi, od, d_counts ? d_counts + q : nullptr,
-                                                d_totals ? d_totals + q : nullptr, pad, stream),
-                      "range batch");
-        }
-    }
-    have_counters_ = false;
-    last_path = plan.route;
-}
-
-void Engine::range_batch_host(const void* queries, size_t nq, size_t elem_count, const double* radii, size_t capacity,
-                              int32_t* ids, float* dists, int32_t* counts, int32_t* totals) {
-    check_range_batch(elem_count, false);
-    if (nq == 0) return;
-    if (dirty_) finalize();
-    check_device();
-    // what a query gets: row q = got[q] entries, then the padding
-    auto pad_rows = [&](const std::vector<size_t>& got) {
-        for (size_t q = 0; q < nq; ++q) {
-            std::fill(ids + q * capacity + got[q], ids + (q + 1) * capacity, -1);
-            std::fill(dists + q * capacity + got[q], dists + (q + 1) * capacity, INFINITY);
-        }
-    };
-    std::vector<size_t> got(nq, 0);
-    if (!shards_.empty()) {
-        // insertion order = shard order: per query the shards' lists back to back up to the capacity, the totals summed;
-        // shards report global positions.  Nothing is written before every shard has answered.
-        DeviceGuard guard(device_);
-        const size_t S = shards_.size();
-        std::vector<std::vector<int32_t>> sid(S), scnt(S), stot(S);
-        std::vector<std::vector<float>> sd(S);
-        std::vector<size_t> scap(S);
-        for (size_t s = 0; s < S; ++s) {
-            Engine& c = *shards_[s];
-            scap[s] = std::min(capacity, c.size());
-            sid[s].resize(nq * scap[s]);
-            sd[s].resize(nq * scap[s]);
-            scnt[s].resize(nq);
-            stot[s].resize(nq);
-            c.range_batch_host(queries, nq, elem_count, radii, scap[s], sid[s].data(), sd[s].data(), scnt[s].data(),
-                               stot[s].data());
-        }
-        hip_check(hipSetDevice(device_), "hipSetDevice");
-        last_path = shards_[0]->last_path;
-        for (size_t q = 0; q < nq; ++q) {
-            long long total = 0;
-            for (size_t s = 0; s < S; ++s) {
-                total += stot[s][q];
-                const size_t m = std::min<size_t>((size_t)scnt[s][q], capacity - got[q]);
-                for (size_t i = 0; i < m; ++i) {
-                    ids[q * capacity + got[q] + i] = ids_[(size_t)sid[s][q * scap[s] + i]];
-                    dists[q * capacity + got[q] + i] = sd[s][q * scap[s] + i];
-                }
-                got[q] += m;
-            }
-            if (counts) counts[q] = (int32_t)got[q];
-            if (totals) totals[q] = (int32_t)total;
-        }
-        pad_rows(got);
-        return;
-    }
-    // no more than d_n_ rows can match: the device side of a row ends there.  The device does not pad here: the counts come
-    // back first, then only the columns that hold an entry of some query (one strided copy per array), and the padding is
-    // written once, in the caller's memory.
-    const size_t cap = std::min(capacity, d_n_);
-    const size_t qbytes = nq * elem_count * elem_bytes();
-    ws_q_.ensure(qbytes);
-    rb_.res.ensure(2 * nq * cap * 4 + 2 * nq * 4);
-    char* hp = static_cast<char*>(pinned(qbytes));
-    std::memcpy(hp, queries, qbytes);
-    order_after_last(stream_);
-    hip_check(hipMemcpyAsync(ws_q_.ptr(), hp, qbytes, hipMemcpyHostToDevice, stream_), "queries H2D");
-    int32_t* d_i = rb_.res.as<int32_t>();
-    float* d_d = reinterpret_cast<float*>(d_i + nq * cap);
-    int32_t* d_c = d_i + 2 * nq * cap;
-    range_batch_device(ws_q_.ptr(), nq, elem_count, radii, cap, d_i, d_d, d_c, d_c + nq, stream_, false);
-    std::vector<int32_t> h_c(2 * nq);
-    hip_check(hipMemcpyAsync(h_c.data(), d_c, 2 * nq * 4, hipMemcpyDeviceToHost, stream_), "counts D2H");
-    hip_check(hipStreamSynchronize(stream_), "range batch");
-    size_t width = 0;
-    for (size_t q = 0; q < nq; ++q) width = std::max(width, got[q] = (size_t)h_c[q]);
-    if (width) {
-        hp = static_cast<char*>(pinned(2 * nq * width * 4));   // (the queries have left the block)
-        const int32_t* h_i = reinterpret_cast<const int32_t*>(hp);
-        const float* h_d = reinterpret_cast<const float*>(hp + nq * width * 4);
-        hip_check(hipMemcpy2DAsync(hp, width * 4, d_i, cap * 4, width * 4, nq, hipMemcpyDeviceToHost, stream_), "ids D2H");
-        hip_check(hipMemcpy2DAsync(hp + nq * width * 4, width * 4, d_d, cap * 4, width * 4, nq, hipMemcpyDeviceToHost, stream_),
-                  "dists D2H");
-        hip_check(hipStreamSynchronize(stream_), "range batch");
-        for (size_t q = 0; q < nq; ++q)
-            if (got[q]) {
-                std::memcpy(ids + q * capacity, h_i + q * width, got[q] * 4);
-                std::memcpy(dists + q * capacity, h_d + q * width, got[q] * 4);
-            }
-    }
-    for (size_t q = 0; q < nq; ++q) {
-        if (counts) counts[q] = h_c[q];
-        if (totals) totals[q] = h_c[nq + q];
-    }
-    pad_rows(got);
 }
 
 // *d_out, after the stream's work

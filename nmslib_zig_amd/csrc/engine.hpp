@@ -92,6 +92,55 @@ class DevBuf {
     size_t n_ = 0;
 };
 
+// ---- an event that orders work (no timing): made at its first record, destroyed with its owner ----
+class Event {
+   public:
+    Event() = default;
+    ~Event() { if (e_) (void)hipEventDestroy(e_); }
+    Event(Event&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }  // move-only
+    void record(hipStream_t s);  // (stream_wait: after a record)
+    // the host waits for the last record (none yet: returns at once); a failure names `what`
+    void wait(const char* what) { if (e_) hip_check(hipEventSynchronize(e_), what); }
+    void stream_wait(hipStream_t s) { hip_check(hipStreamWaitEvent(s, e_, 0), "hipStreamWaitEvent"); }
+
+   private:
+    hipEvent_t e_ = nullptr;
+};
+
+// ---- pinned host block (grow-only; a growth does NOT keep the contents) ----
+class PinnedBuf {
+   public:
+    PinnedBuf() = default;
+    ~PinnedBuf() { if (p_) (void)hipHostFree(p_); }
+    PinnedBuf(PinnedBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }  // move-only
+    void* ensure(size_t bytes, size_t slack = 0);  // a growth allocates bytes + slack
+    void* ptr() const { return p_; }
+
+   private:
+    void* p_ = nullptr;
+    size_t n_ = 0;
+};
+
+// ---- staged upload: a pinned block and the event behind the last copy out of it ----
+struct StagedUpload : PinnedBuf {
+    // waits until the last copy has left the block (a failure names `what`), then the block with room for `bytes` (a growth
+    // adds a quarter: slowly growing uploads do not allocate each time)
+    void* begin(size_t bytes, const char* what) {
+        sent_.wait(what);
+        return ensure(bytes, bytes / 4);
+    }
+    void sent(hipStream_t s) { sent_.record(s); }  // the copy out of the block was enqueued on s
+   private:
+    Event sent_;
+};
+
+// restores the calling thread's current device on every way out of a scope that visits other devices
+struct DeviceGuard {
+    int dev;
+    explicit DeviceGuard(int d) : dev(d) {}
+    ~DeviceGuard() { (void)hipSetDevice(dev); }
+};
+
 // ---- HNSW graph on the host (flat arrays; same layout goes to HBM) ---------------------------
 struct HostGraph {
     int n = 0, M = 16, maxM = 16, maxM0 = 32, efConstruction = 200, delaunay = 2;
@@ -303,10 +352,10 @@ class Engine {
                        size_t elem_count, size_t k, const int32_t** ids, const float** dists, const int32_t** cnt,
                        int32_t* routes);
     float pair_distance(size_t p1, size_t p2);
-    // RangeQuery on the brute-force index: matches in insertion order, the first `capacity`; returns how many were written
+    // RangeQuery on the brute-force index (range.cpp): matches in insertion order, the first `capacity`; returns how many were written
     size_t range_host(const void* query, size_t elem_count, double radius, size_t capacity, int32_t* ids, float* dists);
     bool is_brute() const { return method_ == Method::Brute; }
-    // ---- batched range queries on the exact scan (nmslib_gpu_range_query_batch*) ----
+    // ---- batched range queries on the exact scan (nmslib_gpu_range_query_batch*; range.cpp) ----
     // Row q of the outputs ([nq][capacity]; -1 / +inf behind counts[q] = min(totals[q], capacity) entries) is what range_host
     // writes for query q with radii[q]; totals[q] counts every match.  radii is host memory in both entries and is read
     // before the call returns.  capacity == 0: count only (ids / dists unused).  counts and totals may be null.
@@ -378,19 +427,21 @@ class Engine {
     void knn_sharded(const void* d_queries, size_t nq, size_t elem_count, size_t k, int32_t* d_ids, float* d_dists,
                      int32_t* d_cnt, hipStream_t stream);
     std::vector<std::unique_ptr<Engine>> shards_;
-    std::vector<hipEvent_t> shard_events_;
-    hipEvent_t shard_ready_ = nullptr;
-    hipEvent_t order_event_ = nullptr;  // order_after_last: made at the first change of stream
+    std::vector<Event> shard_events_;
+    Event shard_ready_;
+    Event order_event_;                 // order_after_last: made at the first change of stream
     bool have_last_ = false;            // last_stream_ names a stream that work of this index went to (nullptr: the null stream)
     const Engine* parent_ = nullptr;  // shard child: rows [view_lo_, view_lo_ + view_n_) of the parent, no copy
     size_t view_lo_ = 0, view_n_ = 0;
     int forced_device_ = -1;
     int gpu_shards_ = -1;  // index parameter: -1 unset, 0 = all visible devices, N = that many
     DevBuf ws_sh_ids_, ws_sh_d_, ws_bigk_, ws_bigk_tmp_;
-    void* pinned(size_t bytes);
-    void* pinned_ = nullptr;
-    size_t pinned_bytes_ = 0;
+    // Pinned host staging buffer (grow-only): PCIe copies from/to pageable memory are staged by the runtime in small
+    // chunks and block the calling thread; one pinned block makes the batch's H2D and D2H a single DMA each.
+    void* pinned(size_t bytes) { return pinned_.ensure(bytes); }
+    PinnedBuf pinned_;
     void check_device();
+    static void check_diverg_query_length(size_t elem_count, size_t dim);
     // ---- plumbing shared by the host entries of every data type (engine.cpp) ----
     struct ResultBlock {  // device pointers into ws_ids_
         int32_t* ids;
@@ -402,19 +453,25 @@ class Engine {
                        const int32_t** cnt);
     using ScanLaunch = std::function<void(const ScanPlan& p, size_t q0, float* split_d, int32_t* split_pos)>;
     void scan_slices(size_t nq, size_t k, int tq, const ResultBlock& out, const ScanLaunch& launch);
+    // ---- dense range search (range.cpp) ----
     using RangeLaunch = std::function<void(float* filter, float* report)>;
     size_t range_select(bool two_dists, float r, size_t capacity, int32_t* ids, float* dists, const RangeLaunch& launch);
+    // RangeQuery<dist_t>(space, obj, static_cast<dist_t>(radius)), nmslib_c.cpp:1092-1093
+    float range_radius(double radius) const { return is_u8() ? (float)(int)radius : (float)radius; }
     void check_range_batch(size_t elem_count, bool device_entry) const;  // the refusals that need no device
-    // a batched range query's workspaces (grow-only): the radii as floats, staged in two pinned blocks and two device
-    // buffers that calls take in turn (`event` stands behind the last copy out of a block, so a call waits for the call
-    // before the previous one at most); the match bits and block counts of a slice; the host entry's result block
-    struct RangeBatchWs {
-        DevBuf radii[2], masks, counts, res;
-        void* pinned[2] = {nullptr, nullptr};
-        size_t pinned_bytes[2] = {0, 0};
-        hipEvent_t event[2] = {nullptr, nullptr};
+    const float* stage_radii(const double* radii, size_t nq, int turn, hipStream_t stream);  // -> the staging block's copy
+    // range_batch_host's two ways; both leave got[q] = the entries of row q and write no padding
+    void range_batch_merge_shards(const void* queries, size_t nq, size_t elem_count, const double* radii, size_t capacity,
+                                  int32_t* ids, float* dists, int32_t* counts, int32_t* totals, std::vector<size_t>& got);
+    void range_batch_fetch(const void* queries, size_t nq, size_t elem_count, const double* radii, size_t capacity,
+                           int32_t* ids, float* dists, int32_t* counts, int32_t* totals, std::vector<size_t>& got);
+    // workspaces (grow-only): range_select's block counts; a batch's radii as floats, in two staged uploads and two device
+    // buffers that calls take in turn; the match bits and block counts of a slice; the host entry's result block
+    struct RangeWs {
+        DevBuf cnt, radii[2], masks, counts, res;
+        StagedUpload staged[2];
         int turn = 0;
-    } rb_;
+    } rw_;
     float read_float(const float* d_out, const char* what);
     void upload_sparse();
     float pair_distance_sparse(size_t p1, size_t p2);
@@ -454,12 +511,10 @@ class Engine {
     // dst row i = src row list[i] (rows of a multiple of 4 bytes): the 16-byte gather where its rule holds, else word by word
     void gather_rows(const void* src, const int32_t* list, size_t m, size_t row_bytes, void* dst, hipStream_t stream);
     // what a batch with one filter per query uploads and works in (grow-only): the filter table, slots and permutations (one
-    // block, staged in `pinned`; `event` stands behind the last copy out of it), the batch in plan order and its results
+    // block, staged in `staged`), the batch in plan order and its results
     struct FilterEachWs {
         DevBuf tab, q, res;
-        void* pinned = nullptr;
-        size_t pinned_bytes = 0;
-        hipEvent_t event = nullptr;
+        StagedUpload staged;
     } each_;
     std::vector<std::unique_ptr<Filter>> filters_;
     uint64_t pos_epoch_ = 0;     // counts what moves positions: a consolidate that removed a row, a reset
@@ -535,13 +590,11 @@ class Engine {
     std::vector<float> rows_f32_;
     std::vector<uint8_t> rows_u8_;
     // deleted rows: bit = position (rows beyond the last word are live), how many bits are set; HNSW: the copy the filter
-    // kernel reads, its pinned staging block and the event behind the last copy out of it
+    // kernel reads and the block it is staged in
     std::vector<uint32_t> tomb_;
     size_t n_dead_ = 0;
     DevBuf d_tomb_;
-    uint32_t* tomb_pinned_ = nullptr;
-    size_t tomb_pinned_words_ = 0;
-    hipEvent_t tomb_event_ = nullptr;
+    StagedUpload tomb_staged_;
     bool diverg_ = false;  // a divergence space: rows_f32_ on the host, values + logarithms in d_rows_
     // sparse rows: host CSR (get_data_point / borrow) and its copy in HBM after finalize
     bool sparse_ = false;
@@ -596,7 +649,7 @@ class Engine {
 
     // workspaces
     DevBuf ws_q_, ws_qpad_, ws_qsel_, ws_qaux_, ws_cand_, ws_cnt_, ws_ids_, ws_dists_;
-    DevBuf ws_ndc_, ws_hops_, ws_hops_up_, ws_pair_, ws_rdist_, ws_rcnt_;  // (the counters: dense and string HNSW, the builder)
+    DevBuf ws_ndc_, ws_hops_, ws_hops_up_, ws_pair_, ws_rdist_;  // (the counters: dense and string HNSW, the builder)
     HnswSearchWs sw_;
     HnswBuildWs bw_;
     DevBuf ws_bq_, ws_split_;  // sparse / string batches: the packed queries; per-split lists (string HNSW: per-query state)

@@ -279,16 +279,7 @@ void Engine::knn_device_each(Filter* const* filters, size_t n_filters, const int
     const FilterSlot* d_table = nullptr;
     const int32_t *d_slot = nullptr, *d_perm = nullptr, *d_inv = nullptr;
     if (up_bytes > 0) {
-        if (each_.event) hip_check(hipEventSynchronize(each_.event), "filter batch");  // the last copy has left the block
-        else hip_check(hipEventCreateWithFlags(&each_.event, hipEventDisableTiming), "hipEventCreate");
-        if (each_.pinned_bytes < up_bytes) {
-            if (each_.pinned) (void)hipHostFree(each_.pinned);
-            each_.pinned = nullptr;
-            each_.pinned_bytes = 0;
-            hip_check(hipHostMalloc(&each_.pinned, up_bytes + up_bytes / 4, hipHostMallocDefault), "hipHostMalloc");
-            each_.pinned_bytes = up_bytes + up_bytes / 4;
-        }
-        char* hp = static_cast<char*>(each_.pinned);
+        char* hp = static_cast<char*>(each_.staged.begin(up_bytes, "filter batch"));
         each_.tab.ensure(up_bytes);
         const char* dp = static_cast<const char*>(each_.tab.ptr());
         size_t at = 0;
@@ -315,8 +306,8 @@ void Engine::knn_device_each(Filter* const* filters, size_t n_filters, const int
     }
     order_after_last(stream);
     if (up_bytes > 0) {
-        hip_check(hipMemcpyAsync(each_.tab.ptr(), each_.pinned, up_bytes, hipMemcpyHostToDevice, stream), "filter batch H2D");
-        hip_check(hipEventRecord(each_.event, stream), "hipEventRecord");
+        hip_check(hipMemcpyAsync(each_.tab.ptr(), each_.staged.ptr(), up_bytes, hipMemcpyHostToDevice, stream), "filter batch H2D");
+        each_.staged.sent(stream);
     }
 
     // ---- the batch in plan order: the caller's arrays when it is in that order already, else workspaces ----

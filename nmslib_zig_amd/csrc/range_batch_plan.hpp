@@ -1,4 +1,4 @@
-// Host arithmetic of a batched range query on the exact scan (engine.cpp: Engine::range_batch_device):
+// Host arithmetic of a batched range query on the exact scan (range.cpp: Engine::range_batch_device):
 // which route answers the batch, the grid of the match-bit kernel, the mask words per query, how the batch is cut into
 // query slices and the workspace a slice takes.  Integer arithmetic only -- no HIP, nothing of the engine -- so that
 // tests/range_batch_plan_check.cpp can check it without a GPU; tests/range_batch_plan_ref.py restates it.

@@ -304,3 +304,48 @@ def test_device_entry_on_its_own_stream(counts):
     for a, b in zip(idx.read_counters(NQ), want[1]):
         np.testing.assert_array_equal(a, b)
     close_all(filters, idx)
+
+
+def test_device_batches_back_to_back_while_the_table_block_grows():
+    """2 filters and 8 queries, then 5 filters and NQ queries under another filter_of_query, on one fresh stream with nothing
+    waited for in between, on an index whose staging block does not exist yet: the second call waits for the first one's copy
+    and replaces the block.  Results and routes equal a twin index's, batch by batch"""
+    import torch
+    n, k = 3000, 10
+    X, Q = refio.s_lowrank(n, D, 1370), refio.s_lowrank(NQ, D, 1371)
+    rng = np.random.default_rng(1372)
+    masks = [rng.random(n) < 0.5, mask_of(n, rng.permutation(n)[:30]), rng.random(n) < 0.3, rng.random(n) < 0.7,
+             mask_of(n, rng.permutation(n)[:50])]
+    batches = [(2, 8, interleaved(8, 2)), (5, NQ, interleaved(NQ, 5)[::-1].copy())]
+    twin = make_index("l2", "hnsw", X, ext_ids(n), **GPU)
+    twin.setQueryTimeParams(efSearch=EF)
+    twin_filters = [twin.makeFilter(m) for m in masks]
+    want = [each(twin, twin_filters[:nf], fq, Q[:nq], k) for nf, nq, fq in batches]
+    idx = make_index("l2", "hnsw", X, ext_ids(n), **GPU)
+    idx.setQueryTimeParams(efSearch=EF)
+    filters = [idx.makeFilter(m) for m in masks]
+    staged = torch.from_numpy(Q).cuda().reshape(-1)
+    torch.cuda.current_stream().synchronize()
+    stream = torch.cuda.Stream()
+    guard = 64
+    outs = [(torch.empty(nq * k + guard, dtype=torch.int32, device="cuda"),
+             torch.empty(nq * k + guard, dtype=torch.float32, device="cuda"),
+             torch.empty(nq + guard, dtype=torch.int32, device="cuda")) for _, nq, _ in batches]
+    routes = [np.full(nq, CNT_SENTINEL, np.int32) for _, nq, _ in batches]
+    with torch.cuda.stream(stream):
+        for (nf, nq, fq), (d_ids, d_ds, d_cnt), r in zip(batches, outs, routes):
+            d_ids.fill_(ID_SENTINEL)
+            d_ds.fill_(float("nan"))
+            d_cnt.fill_(CNT_SENTINEL)
+            mine = fq.copy()
+            idx.knn_device_each_filtered(filters[:nf], mine, staged.data_ptr(), nq, D, k, d_ids.data_ptr(), d_ds.data_ptr(),
+                                         d_cnt.data_ptr(), stream.cuda_stream, routes=r)
+            mine[:] = 99                                           # (the entry has read it)
+    stream.synchronize()
+    for (nf, nq, fq), (d_ids, d_ds, d_cnt), r, w in zip(batches, outs, routes, want):
+        h_ids, h_ds, h_cnt = d_ids.cpu().numpy(), d_ds.cpu().numpy(), d_cnt.cpu().numpy()
+        assert (h_ids[nq * k:] == ID_SENTINEL).all() and np.isnan(h_ds[nq * k:]).all() and (h_cnt[nq:] == CNT_SENTINEL).all()
+        same_bits((h_ids[:nq * k].reshape(nq, k), h_ds[:nq * k].reshape(nq, k), h_cnt[:nq]), w[0])
+        np.testing.assert_array_equal(r, w[2], err_msg="routes")
+    close_all(filters, idx)
+    close_all(twin_filters, twin)

@@ -457,3 +457,60 @@ def test_the_same_batch_twice_and_in_reverse(space):
             np.testing.assert_array_equal(x.view(np.uint32), z[::-1].view(np.uint32))
     finally:
         idx.close()
+
+
+# ---- 8. the radii's staging blocks ----------------------------------------------------------------------------------------
+@pytest.mark.parametrize("space,D,path,fractional", [("l2", 65, 10, False), ("l2", 257, 11, False),
+                                                     ("l2sqr_sift", 128, 10, True)])
+def test_device_batches_back_to_back_while_the_radii_blocks_grow(space, D, path, fractional):
+    """four device batches of 5, 7, T + 1 and 2T + 1 queries on one stream, nothing waited for in between, on an index whose
+    two staging blocks do not exist yet: the third call waits for the first one's copy and replaces its block, the fourth
+    does so with the second's (both need more than the quarter of slack).  Every call's outputs equal what a twin index
+    answers for that batch alone.  fractional (l2sqr_sift): radii k + 0.75 and -0.25, which the conversion truncates; there
+    the twin's single entry is held against its batch as well, and a query that is a row finds that row alone"""
+    import torch
+    n, cap, off = 2049, 9, 3
+    sizes = (5, 7, T + 1, 2 * T + 1)
+    cuts = np.r_[0, np.cumsum(sizes)]
+    X, Q = random_case(space, n, D, int(cuts[-1]))
+    if fractional:
+        Q[0] = X[17]                                                      # (distance 0: what a radius of -0.25 reaches as 0)
+    radii = np.array([radius_of_kind(dist64(space, X, Q[q]), q % 4) for q in range(len(Q))])
+    if fractional:
+        radii = np.floor(radii) + 0.75
+        assert (radii[0::4] == -0.25).all()
+    twin = make_index(space, "seq_search", X, ext_ids(n))
+    idx = make_index(space, "seq_search", X, ext_ids(n))
+    try:
+        want = []
+        for a, b in zip(cuts[:-1], cuts[1:]):
+            assert rbp.plan(n, D, 1 if space == "l2sqr_sift" else 4, b - a, cap).route == path
+            want.append(batch_guarded(twin, Q[a:b], radii[a:b], cap))
+            expect_path(twin, path)
+        if fractional:
+            equals_single_entry(twin, Q[:12], radii[:12], [cap], n)
+            assert want[0][3][0] == 1 and want[0][0][0, 0] == ext_ids(n)[17] and want[0][3][4] == 0
+        staged = torch.from_numpy(np.ascontiguousarray(Q)).cuda()
+        torch.cuda.current_stream().synchronize()
+        lens = [(m * cap, m * cap, m, m) for m in sizes]
+        dts = (torch.int32, torch.float32, torch.int32, torch.int32)
+        raws = [[_offset_buffer(m, dt, off)[0] for m, dt in zip(ln, dts)] for ln in lens]
+        at = lambda raw: raw.data_ptr() + off * raw.element_size()   # noqa: E731
+        stream = torch.cuda.Stream()
+        with torch.cuda.stream(stream):
+            for (a, b), out in zip(zip(cuts[:-1], cuts[1:]), raws):
+                for raw, fill in zip(out, (ID_SENTINEL, float("nan"), CNT_SENTINEL, CNT_SENTINEL)):
+                    raw.fill_(fill)
+                idx.range_device(staged[int(a)].data_ptr(), int(b - a), Q.shape[1], radii[a:b], cap, *[at(r) for r in out],
+                                 stream=stream.cuda_stream)
+        expect_path(idx, path)
+        stream.synchronize()
+        for out, ln, w in zip(raws, lens, want):
+            for raw, m, sentinel, x in zip(out, ln, (ID_SENTINEL, None, CNT_SENTINEL, CNT_SENTINEL), w):
+                h = raw.cpu().numpy()
+                guard = np.r_[h[:off], h[off + m:]]
+                assert np.isnan(guard).all() if sentinel is None else (guard == sentinel).all(), "written outside an output"
+                np.testing.assert_array_equal(h[off:off + m].view(np.uint32), x.reshape(-1).view(np.uint32))
+    finally:
+        idx.close()
+        twin.close()
