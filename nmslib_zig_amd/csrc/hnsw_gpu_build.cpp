@@ -253,9 +253,9 @@ bool Engine::can_append() const {
 }
 
 // Rows [n0, n1) added after a GPU build go into the resident graph: the buffers grow to n1 rows keeping
-// their contents, only the new rows are uploaded and prepared, the level stream goes on where the build left it, and the
-// builder's batch loop is entered at position n0.  The result is the graph a build of all n1 rows makes with a batch boundary
-// at n0 (gpu_build_cut).  false: a buffer could not grow or the insertion ran out of memory; the caller builds in full from
+// their contents, only the new rows are uploaded and prepared, the new rows take the level stream's draws [n0, n1), and the
+// builder's batch loop is entered at position n0.  On a graph that was never consolidated the result is the graph a build of
+// all n1 rows makes with a batch boundary at n0 (gpu_build_cut).  false: a buffer could not grow or the insertion ran out of memory; the caller builds in full from
 // the host rows.
 bool Engine::append_rows_gpu() {
     const auto t0 = clk::now();
@@ -264,7 +264,10 @@ bool Engine::append_rows_gpu() {
     HostGraph& g = graph_;
     hipStream_t s = stream_;
     built_n_ = 0;  // (set again at the end: an append that throws leaves no graph to append to)
-    const std::vector<int32_t> levels = hnsw_random_levels(n1, bp_);  // one stream: its first n0 draws are g.levels
+    // one stream per index, read by position: the new rows take its draws [n0, n1).  Its first n0 draws are g.levels only
+    // while the graph was never consolidated; afterwards n0 is the live count, so draws that rows in front took before
+    // are taken again
+    const std::vector<int32_t> levels = hnsw_random_levels(n1, bp_);
     size_t up_ints = graph_up_ints_;
     std::vector<int64_t> up_off;
     assign_up_offsets(levels, n0, n1, bp_.maxM, up_ints, up_off);

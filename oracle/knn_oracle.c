@@ -1140,14 +1140,13 @@ typedef struct {
     size_t cut, stop; /* stop != 0: no batch starts at or behind this position */
 } bparams;
 
-/* One insertion pass.  Every node of g is allocated (empty lists) with its level; position 0 is node 0, position i > 0 is
+/* The batch loop from position `first` (>= 1) on.  Every node of g is allocated with its level; the positions before
+ * `first` are inserted, the others have empty lists; g->maxlevel / g->enterpoint are the running state.  Position i > 0 is
  * node i, or node n - i in reverse order. */
-static void batched_pass(orc_hnsw_t* g, const bparams* P, int reverse, orc_batched_stats* st, int32_t* out_batch) {
+static void batched_insert(orc_hnsw_t* g, const bparams* P, int reverse, size_t first, orc_batched_stats* st,
+                           int32_t* out_batch) {
     const size_t n = g->n;
     const int efC = P->efC, M = P->M;
-    g->maxlevel = g->level[0];
-    g->enterpoint = 0;
-    if (out_batch) out_batch[0] = out_batch[1] = 0;
     size_t maxb = (size_t)P->max_batch < n ? (size_t)P->max_batch : n;
     int32_t* nodes = (int32_t*)malloc((maxb + 1) * sizeof(int32_t));
     int32_t* slice = (int32_t*)malloc((maxb + 1) * sizeof(int32_t)); /* batch index of the slice's q-th node */
@@ -1158,7 +1157,7 @@ static void batched_pass(orc_hnsw_t* g, const bparams* P, int reverse, orc_batch
     bcand* ranked = (bcand*)malloc(((size_t)wide + 1) * sizeof(bcand));
     breq* reqs = (breq*)malloc((maxb * (size_t)M + 1) * sizeof(breq));
     int32_t batch_no = 0;
-    for (size_t next = 1, end; next < n && (P->stop == 0 || next < P->stop); next = end, ++batch_no) {
+    for (size_t next = first, end; next < n && (P->stop == 0 || next < P->stop); next = end, ++batch_no) {
         /* ---- the batch: at most 1/div of the positions before it, at most max_batch, at least one; never across the
          * cut; closed by the first node that rises above the top level */
         size_t want = next / (size_t)P->batch_div;
@@ -1341,6 +1340,14 @@ static void batched_pass(orc_hnsw_t* g, const bparams* P, int reverse, orc_batch
     free(reqs);
 }
 
+/* One insertion pass: node 0 is the graph, the loop runs from position 1. */
+static void batched_pass(orc_hnsw_t* g, const bparams* P, int reverse, orc_batched_stats* st, int32_t* out_batch) {
+    g->maxlevel = g->level[0];
+    g->enterpoint = 0;
+    if (out_batch) out_batch[0] = out_batch[1] = 0;
+    batched_insert(g, P, reverse, 1, st, out_batch);
+}
+
 static orc_hnsw_t* batched_graph(int space, const void* base, size_t n, size_t dim, int maxM, int maxM0,
                                  const int32_t* levels) {
     orc_hnsw_t* g = graph_new(space, base, n, dim, maxM, maxM0);
@@ -1455,4 +1462,20 @@ orc_hnsw_t* orc_hnsw_build_batched(int space, const void* base, size_t n, size_t
     orc_hnsw_free(g);
     orc_hnsw_free(g2);
     return gr;
+}
+
+int orc_hnsw_insert_batched(orc_hnsw_t* g, size_t first, int M, int efConstruction, int delaunay_type, int batch_div,
+                            int max_batch, size_t cut, orc_batched_stats* st, int32_t* out_batch) {
+    if (st) memset(st, 0, sizeof(*st));
+    if (first < 1 || first > g->n) return -1;
+    for (size_t i = first; i < g->n; ++i)
+        for (int l = 0; l <= g->level[i]; ++l)
+            if (node_links(g, (int)i, l)[0] != 0) return -1;
+    const bparams P = {M, efConstruction, delaunay_type, batch_div > 0 ? batch_div : 16, max_batch > 0 ? max_batch : 4096,
+                       cut, 0};
+    g->M = M;
+    g->efC = efConstruction;
+    g->delaunay = delaunay_type;
+    batched_insert(g, &P, 0, first, st, out_batch);
+    return 0;
 }

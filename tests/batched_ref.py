@@ -92,6 +92,29 @@ def restate(space, X, **p):
         max_batch=p.get("gpu_build_batch", 0), cut=p.get("gpu_build_cut", 0))
 
 
+def resume(space, X, graph, first, levels, **p):
+    """the restatement of an append (gpu_append=1): `graph` (the keys of refio.parse_index / HnswGraph.arrays)
+    is a finished graph over X[:first], `levels` are those of the rows X[first:]; the batch loop is entered at `first`.
+    The engine's parameter names and defaults, as restate has them.  -> the orc.HnswGraph over all of X"""
+    n, M = len(X), p.get("M", 16)
+    maxM, maxM0 = int(graph["maxM"]), int(graph["maxM0"])
+    assert graph["n"] == first and len(levels) == n - first and p.get("post", 0) == 0
+    assert (maxM, maxM0) == (p.get("maxM", M), p.get("maxM0", 2 * M))
+    levels = np.asarray(levels, np.int32)
+    up_off = np.concatenate([graph["up_off"], np.full(n - first, -1, np.int64)])
+    cur = len(graph["up_links"])
+    for i in np.nonzero(levels > 0)[0]:
+        up_off[first + i] = cur
+        cur += int(levels[i]) * (maxM + 1)
+    up_links = np.concatenate([graph["up_links"], np.zeros(cur - len(graph["up_links"]), np.int32)])
+    links0 = np.concatenate([graph["links0"], np.zeros((n - first, maxM0 + 1), np.int32)])
+    g = orc.HnswGraph.from_arrays(space, X, maxM, maxM0, int(graph["maxlevel"]), int(graph["enterpoint"]),
+                                  np.concatenate([graph["levels"], levels]), links0, up_off, up_links)
+    return g.insert_batched(first, M=M, efConstruction=p.get("efConstruction", 200), delaunay_type=p.get("delaunay_type", 2),
+                            batch_div=p.get("gpu_build_div", 0), max_batch=p.get("gpu_build_batch", 0),
+                            cut=p.get("gpu_build_cut", 0))
+
+
 # name -> (space, rows, n, index parameters, witness: counter -> lower bound the restatement must reach)
 CASES = {
     "core-narrow": ("l2", "d16", 300, dict(M=6, efConstruction=100),

@@ -6,7 +6,8 @@
  *
  * Three of the small configurations of tests/batched_ref.py (core-narrow, doubling-efc100, post1-d1) and the tiny graphs,
  * over rows from a linear congruential generator that tests/test_hnsw_batched_ref_cpu.py repeats: one line per
- * configuration with a hash of every list of the graph, which the test compares with the library's graph. */
+ * configuration with a hash of every list of the graph, which the test compares with the library's graph.  Last, the
+ * builder resumed in the middle of a build (orc_hnsw_insert_batched) against the build with a cut there. */
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -66,11 +67,41 @@ static void run(const char* name, size_t n, size_t dim, int M, int efC, int dela
     free(x);
 }
 
+/* the builder resumed at `cut` on the state the build with that cut has there (orc_hnsw_insert_batched) against the build
+ * with the cut itself: the same graph */
+static void run_resume(const char* name, size_t n, size_t dim, int M, int efC, int delaunay, int div, size_t cut) {
+    float* x = dyadic_rows(n, dim, 12345u);
+    orc_batched_stats st;
+    int32_t* batch = (int32_t*)malloc((2 * n + 2) * sizeof(int32_t));
+    orc_hnsw_t* g = orc_hnsw_build_batched_state(ORC_L2, x, n, dim, M, M, 2 * M, efC, delaunay, div, 0, cut);
+    if (orc_hnsw_insert_batched(g, 0, M, efC, delaunay, div, 0, 0, NULL, NULL) != -1 ||
+        orc_hnsw_insert_batched(g, n + 1, M, efC, delaunay, div, 0, 0, NULL, NULL) != -1 ||
+        orc_hnsw_insert_batched(g, cut, M, efC, delaunay, div, 0, 0, &st, batch) != 0 ||
+        orc_hnsw_insert_batched(g, n, M, efC, delaunay, div, 0, 0, NULL, NULL) != 0 || /* nothing left: a no-op */
+        orc_hnsw_insert_batched(g, cut, M, efC, delaunay, div, 0, 0, NULL, NULL) != -1) { /* lists are filled now */
+        fprintf(stderr, "%s: orc_hnsw_insert_batched: unexpected return value\n", name);
+        exit(1);
+    }
+    orc_hnsw_t* w = orc_hnsw_build_batched(ORC_L2, x, n, dim, M, M, 2 * M, efC, delaunay, 0, div, 0, cut, NULL, NULL);
+    const uint64_t hg = graph_hash(g, n, M), hw = graph_hash(w, n, M);
+    if (hg != hw) {
+        fprintf(stderr, "%s: resumed graph %llu, cut build %llu\n", name, (unsigned long long)hg, (unsigned long long)hw);
+        exit(1);
+    }
+    printf("%s n=%zu hash=%llu shrinks=%lld mates=%lld\n", name, n, (unsigned long long)hg, (long long)st.shrinks,
+           (long long)st.mates);
+    orc_hnsw_free(g);
+    orc_hnsw_free(w);
+    free(batch);
+    free(x);
+}
+
 int main(void) {
     run("core-narrow", 300, 16, 6, 100, 2, 0, 0);
     run("doubling-efc100", 300, 16, 6, 100, 2, 0, 1);
     run("post1-d1", 300, 16, 6, 100, 1, 1, 0);
     for (size_t n = 1; n <= 3; ++n) run("tiny", n, 16, 6, 100, 2, 2, 0);
+    run_resume("resume-at-137", 300, 16, 6, 100, 2, 0, 137);
     printf("hnsw batched restatement ok\n");
     return 0;
 }

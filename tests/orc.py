@@ -79,6 +79,8 @@ def lib():
     L.orc_hnsw_build_batched_state.restype = vp
     L.orc_hnsw_build_batched_state.argtypes = [C.c_int, vp, C.c_size_t, C.c_size_t, C.c_int, C.c_int, C.c_int,
                                                C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t]
+    L.orc_hnsw_insert_batched.restype = C.c_int
+    L.orc_hnsw_insert_batched.argtypes = [vp, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_size_t, vp, vp]
     L.orc_hnsw_maxM0.restype = C.c_int
     L.orc_hnsw_maxM0.argtypes = [vp]
     L.orc_hnsw_build_distance.restype = C.c_double
@@ -177,6 +179,25 @@ class HnswGraph:
         h = lib().orc_hnsw_build_batched_state(SPACES[space], _ptr(base), base.shape[0], base.shape[1], M, maxM,
                                                maxM0, efConstruction, delaunay_type, batch_div, max_batch, cut)
         return cls(h, space, base, maxM, maxM0)
+
+    def insert_batched(self, first, M=16, efConstruction=200, delaunay_type=2, batch_div=0, max_batch=0, cut=0):
+        """Resume the batched builder on this graph at position `first` (orc_hnsw_insert_batched): the positions from
+        `first` on carry their levels and empty lists.  Sets .stats and .batch (of the nodes from `first` on; the batch
+        numbers start at 1 again) and returns the graph itself."""
+        st = BatchedStats()
+        batch = np.zeros((max(self.n, 1), 2), np.int32)
+        rc = lib().orc_hnsw_insert_batched(self.h, first, M, efConstruction, delaunay_type, batch_div, max_batch, cut,
+                                           C.byref(st), _ptr(batch))
+        if rc != 0:
+            raise ValueError(f"orc_hnsw_insert_batched refused first={first} on a graph of {self.n} rows")
+        self.stats, self.batch = st.as_dict(), batch[:self.n]
+        return self
+
+    def arrays(self):
+        """the graph in the keys of refio.parse_index (what from_arrays takes)"""
+        up_off, up_links = self.flat_upper()
+        return dict(n=self.n, maxM=self.maxM, maxM0=self.maxM0, maxlevel=self.maxlevel, enterpoint=self.enterpoint,
+                    levels=self.levels(), links0=self.links0(), up_off=up_off, up_links=up_links)
 
     def build_distance(self, a, b):
         return lib().orc_hnsw_build_distance(self.h, int(a), int(b))

@@ -119,12 +119,40 @@ def _list_of(g, i, l):
     return g["up_links"][o:o + g["maxM"] + 1]
 
 
+class _ParsedGraph:
+    """a graph in the keys of parse_index behind what assert_graph_equals_restatement reads of an orc.HnswGraph"""
+
+    def __init__(self, g):
+        self.g, self.n = g, int(g["n"])
+        self.maxlevel, self.enterpoint, self.maxM, self.maxM0 = (int(g[k]) for k in ("maxlevel", "enterpoint", "maxM", "maxM0"))
+        self.batch = g.get("batch", np.zeros((self.n, 2), np.int32))
+
+    def levels(self):
+        return self.g["levels"]
+
+    def links0(self):
+        return self.g["links0"]
+
+    def flat_upper(self):
+        return self.g["up_off"], self.g["up_links"]
+
+    def build_distance(self, a, b):
+        return float("nan")
+
+
 def assert_graph_equals_restatement(got, want):
-    """`got`: a parsed index file (parse_index); `want`: the orc.HnswGraph of orc.HnswGraph.build_batched.  Levels, top
+    """`got`: a parsed index file (parse_index); `want`: the orc.HnswGraph of orc.HnswGraph.build_batched, or a graph in
+    the keys of parse_index (then without distances and batches in the message; its ids and payload, where it has them,
+    must be the file's too).  Levels, top
     level, entry point, maxM0 and every list of every node on every level must be equal, entry by entry in list order,
     and where the file carries padding behind a count it must be zeros.  On a difference the message names the
     differing node that was inserted first, with its level, its batch and index in the batch, and both lists with the
     distances to the node."""
+    if isinstance(want, dict):
+        for key in ("ids", "payload"):
+            if key in want:
+                np.testing.assert_array_equal(got[key], want[key], err_msg=key)
+        want = _ParsedGraph(want)
     n = want.n
     assert got["n"] == n
     wl = want.levels()

@@ -13,6 +13,7 @@ import pytest
 
 import nmslib_zig_amd as nz
 from tests import refio
+from tests.consolidate_ref import adj, assert_same_graph, parse_regular_index, reachability, restate
 from tests.gpuutil import enqueue_knn, make_index, same_bits
 
 from . import consolidate_poison_child
@@ -34,34 +35,6 @@ def int_rows(n, d, seed):
 
 
 # ---- the graph of a saved index, both file formats ----
-def parse_regular_index(path):
-    """SaveRegularIndexBin (the index file of a space without an optimized form, l2sqr_sift here) -> parse_optimized_index's
-    keys, without ids and payload"""
-    raw = open(path, "rb").read()
-    flag, n, maxlevel, enterpoint, M, maxM, maxM0 = struct.unpack_from("<IIiIQQQ", raw, 0)
-    assert flag == 0
-    pos = 40
-    links0 = np.zeros((n, maxM0 + 1), np.int32)
-    levels, up_off, chunks, cur = np.zeros(n, np.int32), np.full(n, -1, np.int64), [], 0
-    for i in range(n):
-        (lv,) = struct.unpack_from("<I", raw, pos)
-        pos += 4
-        levels[i] = lv
-        blk = np.zeros((lv, maxM + 1), np.int32)
-        for l in range(lv + 1):
-            (cnt,) = struct.unpack_from("<I", raw, pos)
-            row = np.frombuffer(raw, np.int32, cnt, pos + 4)
-            pos += 4 + 4 * cnt
-            dst = links0[i] if l == 0 else blk[l - 1]
-            dst[0], dst[1:1 + cnt] = cnt, row
-        if lv:
-            up_off[i] = cur
-            chunks.append(blk.ravel())
-            cur += blk.size
-    return dict(n=n, maxlevel=maxlevel, enterpoint=enterpoint, maxM=maxM, maxM0=maxM0, links0=links0, levels=levels,
-                up_off=up_off, up_links=np.concatenate(chunks) if chunks else np.zeros(0, np.int32))
-
-
 def graph_of(idx, tmp_path, name):
     path = str(tmp_path / name)
     idx.save(path, save_data=True)
@@ -69,90 +42,6 @@ def graph_of(idx, tmp_path, name):
     g = refio.parse_optimized_index(path) if struct.unpack("<I", raw)[0] == 1 else parse_regular_index(path)
     g["path"] = path
     return g
-
-
-def adj(g, u, l):
-    if l == 0:
-        row = g["links0"][u]
-    else:
-        off = int(g["up_off"][u]) + (l - 1) * (g["maxM"] + 1)
-        row = g["up_links"][off:off + g["maxM"] + 1]
-    return row[1:1 + row[0]]
-
-
-def restate(g, rows, dead_pos, efc, delaunay):
-    """DESIGN.md 4.6c on the parsed graph `g` over `rows` (integers: the squared distance is exact) -> (graph, repaired)"""
-    n, maxM, maxM0 = g["n"], g["maxM"], g["maxM0"]
-    P = min(max(efc, maxM0), 1024)
-    R = np.asarray(rows).astype(np.int64)
-    dead = np.zeros(n, bool)
-    dead[dead_pos] = True
-    newpos = np.cumsum(~dead) - 1
-    newpos[dead] = -1
-    live = np.nonzero(~dead)[0]
-
-    def dist(u, ws):
-        return ((R[ws] - R[u]) ** 2).sum(1)
-
-    repaired = 0
-    links0 = np.zeros((len(live), maxM0 + 1), np.int32)
-    up_off, chunks, cur = np.full(len(live), -1, np.int64), [], 0
-    for u in live:
-        lv = int(g["levels"][u])
-        blk = np.zeros((lv, maxM + 1), np.int32)
-        for l in range(lv + 1):
-            lst = adj(g, u, l)
-            gone = dead[lst]
-            new = [int(v) for v in lst]
-            if gone.any():
-                repaired += 1
-                keep, target = [int(v) for v in lst[~gone]], len(lst)
-                seen, pool = set(keep) | {int(u)}, []
-                for d in lst[gone]:
-                    for w in adj(g, int(d), l):          # one hop: a deleted neighbour of a deleted neighbour is not followed
-                        if dead[w] or int(w) in seen:
-                            continue
-                        seen.add(int(w))
-                        pool.append(int(w))
-                pool = np.array(pool, np.int64)
-                dd = dist(u, pool) if len(pool) else np.zeros(0, np.int64)
-                order = np.lexsort((pool, dd))[:P]       # ascending by (distance, position), the first P
-                rejected = []
-                for c, dc in zip(pool[order], dd[order]):
-                    if len(keep) >= target:
-                        break
-                    if delaunay != 0 and keep and (dist(c, np.array(keep)) < dc).any():
-                        rejected.append(int(c))
-                        continue
-                    keep.append(int(c))
-                if delaunay == 1:
-                    keep += rejected[:target - len(keep)]
-                new = keep
-            dst = links0[newpos[u]] if l == 0 else blk[l - 1]
-            dst[0], dst[1:1 + len(new)] = len(new), newpos[new]
-        if lv:
-            up_off[newpos[u]] = cur
-            chunks.append(blk.ravel())
-            cur += blk.size
-    enter, top = int(g["enterpoint"]), int(g["maxlevel"])
-    if dead[enter]:
-        top = int(g["levels"][live].max())
-        enter = int(live[g["levels"][live] == top][0])
-    out = dict(n=len(live), maxM=maxM, maxM0=maxM0, maxlevel=top, enterpoint=int(newpos[enter]), links0=links0,
-               levels=g["levels"][live].copy(), up_off=up_off,
-               up_links=np.concatenate(chunks) if chunks else np.zeros(0, np.int32))
-    for key in ("ids", "payload"):
-        if key in g:
-            out[key] = g[key][live]
-    return out, repaired
-
-
-def assert_same_graph(got, want):
-    for key in ("n", "maxM", "maxM0", "maxlevel", "enterpoint"):
-        assert got[key] == want[key], (key, got[key], want[key])
-    for key in ("levels", "up_off", "links0", "up_links", "ids", "payload"):
-        if key in want:
-            np.testing.assert_array_equal(got[key], want[key], err_msg=key)
 
 
 def check_rule(space, X, build, dead_pos, tmp_path):
@@ -182,26 +71,6 @@ def check_rule(space, X, build, dead_pos, tmp_path):
     dat = np.fromfile(after["path"] + ".dat", np.uint8)
     assert len(dat) == 8 + len(live) * (8 + 16 + (132 if space == "l2sqr_sift" else 4 * X.shape[1]))
     return idx, before, live
-
-
-def reachability(g):
-    """reported, not asserted -> (nodes with an empty list on a level that has more than one node, nodes that a walk over
-    the level-0 lists from the entry point does not reach)"""
-    n = g["n"]
-    empty = 0
-    for l in range(int(g["maxlevel"]) + 1):
-        on = np.nonzero(g["levels"] >= l)[0]
-        if len(on) > 1:
-            empty += sum(1 for u in on if len(adj(g, u, l)) == 0)
-    seen = np.zeros(n, bool)
-    seen[g["enterpoint"]] = True
-    frontier = [int(g["enterpoint"])]
-    while frontier:
-        nxt = np.unique(np.concatenate([adj(g, u, 0) for u in frontier]))
-        nxt = nxt[~seen[nxt]]
-        seen[nxt] = True
-        frontier = nxt.tolist()
-    return empty, int(n - seen.sum())
 
 
 def check_answers(idx, space, X, ids, live):

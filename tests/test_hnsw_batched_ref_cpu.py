@@ -117,7 +117,7 @@ def test_case_shows_its_witness_at_its_row_count_and_not_below(name):
 
 def test_restatement_standalone_under_host_sanitizers(tmp_path):
     """tests/hnsw_batched_ref_check.c links oracle/knn_oracle.c and runs the restatement over three of the small
-    configurations and the tiny graphs under -fsanitize=address,undefined; the hash it prints for every graph is the one
+    configurations, the tiny graphs and one resumed build (orc_hnsw_insert_batched) under -fsanitize=address,undefined; the hash it prints for every graph is the one
     of the graph the library (no sanitizer) builds from the same rows."""
     exe = str(tmp_path / "hnsw_batched_ref_check")
     subprocess.check_call(["gcc", "-std=c11", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
@@ -148,7 +148,8 @@ def test_restatement_standalone_under_host_sanitizers(tmp_path):
     want = [("core-narrow", 300, dict(M=6, efConstruction=100)),
             ("doubling-efc100", 300, dict(M=6, efConstruction=100, gpu_build_div=1)),
             ("post1-d1", 300, dict(M=6, efConstruction=100, delaunay_type=1, post=1))] + \
-           [("tiny", n, dict(M=6, efConstruction=100, post=2)) for n in (1, 2, 3)]
+           [("tiny", n, dict(M=6, efConstruction=100, post=2)) for n in (1, 2, 3)] + \
+           [("resume-at-137", 300, dict(M=6, efConstruction=100, gpu_build_cut=137))]
     lines = run.stdout.strip().splitlines()[:-1]
     assert len(lines) == len(want)
     for line, (name, n, params) in zip(lines, want):
