@@ -1,11 +1,13 @@
 // Dense brute force on the engine (float rows and uint8 SIFT rows): what finalize prepares in HBM beside the rows
 // (BruteDense: selection copies, error bounds, the fast paths' tiles) and the k-NN batch over kernels/bf_kernels.hip.
-// A batch takes one of: the big-k scan (k > BF_MAX_K), a fast path (large index, large batch), the adaptive path.
+// A batch takes one of: a big-k scan (k > BF_MAX_K: batched, or per query), a fast path (large index, large batch), the
+// adaptive path.
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 
+#include "bigk_batch_plan.hpp"
 #include "engine.hpp"
 #include "l1_quant.hpp"
 
@@ -25,7 +27,9 @@ void BruteDense::release() {
 
 size_t BruteDense::bytes() const {
     size_t total = 0;
-    for (const DevBuf* b : {&rows_i8, &auxh, &rows_sel, &mean, &bf_hi, &bf_lo, &auxp, &f16_hi, &auxp16, &l1_u8, &l1_cols}) total += b->bytes();
+    for (const DevBuf* b : {&rows_i8, &auxh, &rows_sel, &mean, &bf_hi, &bf_lo, &auxp, &f16_hi, &auxp16, &l1_u8, &l1_cols,
+                            &ws_bigk_lists, &ws_bigk_ctl})
+        total += b->bytes();
     return total;
 }
 
@@ -259,6 +263,57 @@ void Engine::prepare_brute() {
     hip_check(hipStreamSynchronize(stream_), "finalize");
 }
 
+static size_t env_size(const char* name, size_t otherwise) {
+    const char* env = getenv(name);
+    return env && atoll(env) > 0 ? (size_t)atoll(env) : otherwise;
+}
+
+// BF_MAX_K < k <= 4096 where bigk_batch_plan.hpp takes the batch (last_path 12): slice by slice the sample
+// pass, the radii, the collect pass, the selection and the gated redo.  false: the plan declined, nothing was enqueued.
+// The gates' environment switches are read at each batch.
+bool Engine::knn_bigk_batch(const void* d_queries, size_t nq, size_t k, const BfOut& out, hipStream_t stream) {
+    const char* on = getenv("NMSLIB_GPU_BIGK_BATCH");
+    if (on && atoi(on) == 0) return false;
+    const size_t budget = std::min(kBigkBatchWsBytes, env_size("NMSLIB_GPU_BIGK_WS_BYTES", kBigkBatchWsBytes));
+    const BigkBatchPlan p = bigk_batch_plan(d_n_, dim_, elem_bytes(), nq, k, env_size("NMSLIB_GPU_BIGK_MIN_ROWS", kBigkBatchMinRows),
+                                            env_size("NMSLIB_GPU_BIGK_MIN_QUERIES", kBigkBatchMinQueries), budget);
+    if (!p.use) return false;
+    BruteDense& b = brute_;
+    // every workspace before the first launch: an allocation behind a kernel in flight waits for it
+    b.ws_bigk_lists.ensure(p.slice_queries * bigk_batch_query_bytes());
+    int* ctl = static_cast<int*>(b.ws_bigk_ctl.ensure(p.slice_queries * 12));
+    BigkBatchArgs a{};
+    a.space = space_;
+    a.rows = d_rows_.ptr();
+    a.ld = is_u8() ? 128 : ldb_;
+    a.n = (int)d_n_;
+    a.dim = (int)dim_;
+    a.k = (int)k;
+    a.lists = b.ws_bigk_lists.as<unsigned long long>();
+    a.counts = ctl;
+    a.radius = reinterpret_cast<uint32_t*>(ctl + p.slice_queries);
+    a.flags = ctl + 2 * p.slice_queries;
+    a.cap = (int)p.cap;
+    a.stride = (int)p.stride;
+    a.rank = (int)p.rank;
+    a.grid_x = (unsigned)p.grid_x;
+    a.grid_y = (unsigned)p.grid_y;
+    a.sample_grid_x = (unsigned)p.sample_grid_x;
+    a.sample_grid_y = (unsigned)p.sample_grid_y;
+    for (size_t s = 0; s < p.slices; ++s) {
+        const size_t q0 = s * p.slice_queries;
+        a.queries = static_cast<const char*>(d_queries) + q0 * row_bytes();
+        a.nq = (int)bigk_batch_slice_size(p, nq, s);
+        const BfOut o{out.ext_ids, out.ids + q0 * k, out.dists + q0 * k, out.cnt ? out.cnt + q0 : nullptr};
+        hip_check(launch_bf_bigk_batch(a, o, stream), "bf_bigk_batch");
+    }
+    last_path = 12;
+    fast_flags_ = a.flags;   // of the last slice: one flag per query
+    fast_nqt_ = a.nq;
+    fast_has_precise_ = false;
+    return true;
+}
+
 void Engine::knn_brute(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists, int32_t* d_cnt,
                        hipStream_t stream) {
     BruteDense& b = brute_;
@@ -266,7 +321,9 @@ void Engine::knn_brute(const void* d_queries, size_t nq, size_t k, int32_t* d_id
     const int dim_eff = d_n_ ? (int)dim_ : 1;
     const BfOut out{d_ids_.as<int32_t>(), d_ids, d_dists, d_cnt};
     if (k > (size_t)BF_MAX_K) {
-        // beyond the selection kernels' capacity: per query one pass with the reference formula + one stable radix sort
+        // beyond the selection kernels' capacity: the batched scan where its plan takes the batch, else per query one pass
+        // with the reference formula + one stable radix sort
+        if (knn_bigk_batch(d_queries, nq, k, out, stream)) return;
         const int ld = is_u8() ? 128 : ldb_;
         const int elem = is_u8() ? 1 : 4;
         const size_t n = d_n_;

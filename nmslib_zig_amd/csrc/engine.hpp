@@ -206,9 +206,11 @@ struct BruteDense {
     // cosine on the fast path; verified l2 path: query tiles whose proof failed (exact tail)
     DevBuf ws_top8, ws_thr, ws_list, ws_listcnt, ws_f32_q, ws_qaug, ws_flags;
     DevBuf ws_l1_qt, ws_l1_xe, ws_l1_cand, ws_l1_cnt;
+    // batched big-k scan: a slice's key lists; its counters, radii and redo flags (one block)
+    DevBuf ws_bigk_lists, ws_bigk_ctl;
 
     void release();        // drops the fast paths' resident data
-    size_t bytes() const;  // every resident buffer (no workspace)
+    size_t bytes() const;  // every resident buffer, and of the workspaces the batched big-k scan's (128 KB per query)
     // the tiles as a launch part; dp: the plan's row length; augmented: they were cut from the augmented rows
     BfF32Tiles tiles(int dp, bool augmented) const;
 };
@@ -552,6 +554,7 @@ class Engine {
     void make_l1_copy();   // the l1 fast path's resident side; leaves have_l1 = false when declined or out of memory
     void knn_brute(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
                    int32_t* d_cnt, hipStream_t stream);
+    bool knn_bigk_batch(const void* d_queries, size_t nq, size_t k, const BfOut& out, hipStream_t stream);
     // dense HNSW search (hnsw_search.cpp).  out: the results and work counters of the slice (knn_device: out.at(q0, k))
     void knn_hnsw(const void* d_queries, size_t nq, size_t k, const HnswOut& out, hipStream_t stream);
     // the search of one slice on whichever path it takes; positions: on dg_ without ext_ids, so that positions come out

@@ -604,6 +604,25 @@ struct BfBigkWs {
 hipError_t launch_bf_bigk(int space, const void* rows, int ld, int n, int dim, const void* queries_padded,
                           size_t query_stride_bytes, int nq, int k, const BfBigkWs& ws, const BfOut& out, hipStream_t s);
 
+// Exact scan for BF_MAX_K < k <= 4096 in one batched pass per slice of queries (bigk_batch_kernels.hip; DESIGN.md 4.3a;
+// the numbers are bigk_batch_plan.hpp's): a radius per query from a sample of the row blocks, one scan that lists the keys
+// of the rows inside it, a sort of each list in LDS, and an exact redo of the queries whose list fell short or overflowed.
+// Row q of the answer is what launch_bf_bigk writes for query q.  Only enqueues.
+struct BigkBatchArgs {
+    int space;
+    const void* rows;        // [n][ld] floats, or [n][128] bytes (l2sqr_sift)
+    int ld, n, dim;          // float rows: dim <= 256; n >= 2 k
+    const void* queries;     // [nq][dim] elements, unpadded, element alignment
+    int nq, k;
+    unsigned long long* lists;  // workspace: [nq][cap] keys
+    int* counts;                // workspace: [nq]
+    uint32_t* radius;           // workspace: [nq], f32_ord of each query's radius
+    int* flags;                 // [nq]: 1 = the query was redone (valid behind the launch)
+    int cap, stride, rank;      // the plan's list capacity (a power of two), sample stride and rank
+    unsigned grid_x, grid_y, sample_grid_x, sample_grid_y;
+};
+hipError_t launch_bf_bigk_batch(const BigkBatchArgs& a, const BfOut& out, hipStream_t s);
+
 // count_ws: [range_count_elems(n)] ints, the last one receives the number of matches.
 inline size_t range_count_elems(int n) { return (size_t)(n + 1023) / 1024 + 1; }
 // Range selection over a precomputed distance array: the matches of `filter` (distance <= radius), in position order,

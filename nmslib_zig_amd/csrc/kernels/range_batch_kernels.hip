@@ -1,5 +1,6 @@
 // Batched range search on the exact scan: many queries in one pass over the rows.
-//   1. range_batch_mask : a wave owns 64 consecutive rows and keeps them in registers, lane l holding each row's elements
+//   1. range_batch_mask : (the arrangement of row_tile_dev.hpp, shared with bigk_batch_kernels.hip) a wave owns 64
+//                         consecutive rows and keeps them in registers, lane l holding each row's elements
 //                         l, l + 64, ...  A tile of queries sits in LDS.  For one query every lane runs its chain for all 64
 //                         rows; the 64 x 64 partials are reduced in the order of wave_sum / wave_max as a reduce-scatter
 //                         (half the values go to the partner at xor 32, a quarter at xor 16, ...), after which lane i holds
@@ -15,70 +16,17 @@
 // _u8 returns for that pair -- the same 64 chains with the same operation per step, the same butterfly, the same finish -- so
 // a batch answers exactly as nmslib_range_query_fill does per query.  This file is built with the flags of range_kernels.hip.
 #include "../range_batch_plan.hpp"
-#include "common_dev.hpp"
 #include "kernels.hpp"
+#include "row_tile_dev.hpp"
 
 namespace gfxknn {
 
 namespace {
 
-enum { RB_L2, RB_L1, RB_LINF, RB_DOT, RB_COS };
 constexpr int kTile = (int)kRangeBatchQueryTile;
 static_assert(kRangeBatchRowsPerWg == 256 && kRangeBatchSelectRows == 1024, "the kernels' shapes");
 
-// one step of a lane's chain, as wave_exact_distance_f32 writes it
-template <int KIND>
-__device__ __forceinline__ float rb_step(float s, float a, float q) {
-    if (KIND == RB_L2) {
-        const float t = a - q;
-        return fmaf(t, t, s);
-    }
-    if (KIND == RB_L1) return s + fabsf(a - q);
-    if (KIND == RB_LINF) return fmaxf(s, fabsf(a - q));
-    return fmaf(a, q, s);
-}
-
-// v[r] = this lane's partial of row r -> the value wave_sum / wave_max returns for row `lane`.  At offset o a lane keeps the
-// o rows whose bit o equals its own and adds the partner's partials of them: the operands of every addition are those of
-// the butterfly's, so are the bits.  Every index is a compile-time constant.  Offsets 32 and 16 are one half-exchange each
-// (v_permlane32_swap: lanes 32..63 of the first operand change places with lanes 0..31 of the second; v_permlane16_swap:
-// the odd 16-lane rows of the first with the even rows of the second): afterwards one operand holds what the lane keeps
-// and the other what its partner sent, in every lane.  The smaller offsets select and shuffle.
-template <bool MAX, typename T>
-__device__ __forceinline__ T rb_combine(T a, T b) {
-    if constexpr (MAX) return fmaxf(a, b);
-    else return a + b;
-}
-template <bool MAX, typename T>
-__device__ __forceinline__ T rb_reduce_scatter(T (&v)[64], int lane) {
-    static_assert(sizeof(T) == 4, "one register per value");
-#pragma unroll
-    for (int i = 0; i < 32; ++i) {
-        const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, v[i]), __builtin_bit_cast(unsigned, v[i + 32]),
-                                                        false, false);
-        v[i] = rb_combine<MAX>(__builtin_bit_cast(T, (unsigned)r[0]), __builtin_bit_cast(T, (unsigned)r[1]));
-    }
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-        const auto r = __builtin_amdgcn_permlane16_swap(__builtin_bit_cast(unsigned, v[i]), __builtin_bit_cast(unsigned, v[i + 16]),
-                                                        false, false);
-        v[i] = rb_combine<MAX>(__builtin_bit_cast(T, (unsigned)r[0]), __builtin_bit_cast(T, (unsigned)r[1]));
-    }
-#pragma unroll
-    for (int o = 8; o > 0; o >>= 1) {
-        const bool up = (lane & o) != 0;
-#pragma unroll
-        for (int i = 0; i < o; ++i) {
-            const T lo = v[i], hi = v[i + o];
-            const T keep = up ? hi : lo, send = up ? lo : hi;
-            v[i] = rb_combine<MAX>(keep, (T)__shfl_xor(send, o, 64));
-        }
-    }
-    return v[0];
-}
-
-// C = ceil(dim / 64) elements of a row per lane; TAIL: dim is no multiple of 64, the last element's step is skipped by the
-// lanes past the row's end as the loop of wave_exact_distance_f32 skips it.
+// The arrangement and its distances: row_tile_dev.hpp.
 // grid (row blocks of 256, query splits): a workgroup takes the query tiles blockIdx.y, blockIdx.y + gridDim.y, ...
 template <int KIND, int C, bool TAIL>
 __global__ __launch_bounds__(256) void range_batch_mask_kernel(int space, const float* __restrict__ rows, int ld, int n,
@@ -94,91 +42,18 @@ __global__ __launch_bounds__(256) void range_batch_mask_kernel(int space, const 
 
     float rv[64][C];
     float rnorm = 0.f;
-    if (active) {
-#pragma unroll
-        for (int r = 0; r < 64; ++r) {
-            const size_t row = word * 64 + r < (size_t)n ? word * 64 + r : (size_t)n - 1;
-            const float* a = rows + row * (size_t)ld;
-#pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const int d = lane + 64 * c;
-                const bool ok = d < dim;
-                const float x = a[ok ? d : 0];
-                rv[r][c] = ok ? x : 0.f;
-            }
-        }
-        if (KIND == RB_COS) {   // the rows' squared norms: lane i keeps row i's
-            float v[64];
-#pragma unroll
-            for (int r = 0; r < 64; ++r) {
-                float s = 0.f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float t = fmaf(rv[r][c], rv[r][c], s);
-                    s = (TAIL && c == C - 1 && !last_ok) ? s : t;
-                }
-                v[r] = s;
-            }
-            rnorm = rb_reduce_scatter<false>(v, lane);
-        }
-    }
+    if (active) rnorm = rb_load_rows<KIND, C, TAIL>(rows, ld, n, word * 64, dim, lane, last_ok, rv);
 
     const int ntiles = (nq + kTile - 1) / kTile;
     for (int t = blockIdx.y; t < ntiles; t += gridDim.y) {
         const int q0 = t * kTile;
         const int tq = nq - q0 < kTile ? nq - q0 : kTile;
         __syncthreads();   // the last tile has been read
-        for (int i = threadIdx.x; i < kTile * C * 64; i += 256) {
-            const int qi = i / (C * 64), d = i % (C * 64);
-            const bool ok = qi < tq && d < dim;
-            const float x = queries[ok ? (size_t)(q0 + qi) * dim + d : 0];
-            qs[i] = ok ? x : 0.f;
-        }
-        __syncthreads();
-        if (KIND == RB_COS) {   // the queries' squared norms, one wave per query
-            for (int qi = wave; qi < tq; qi += 4) {
-                float s = 0.f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float y = qs[qi * C * 64 + c * 64 + lane];
-                    const float t2 = fmaf(y, y, s);
-                    s = (TAIL && c == C - 1 && !last_ok) ? s : t2;
-                }
-                s = wave_sum(s);
-                if (lane == 0) qnorm[qi] = s;
-            }
-            __syncthreads();
-        }
+        rb_stage_queries<KIND, C, TAIL, kTile>(queries, dim, q0, tq, last_ok, qs, qnorm);
         if (!active) continue;
         for (int qi = 0; qi < tq; ++qi) {
-            float qv[C];
-#pragma unroll
-            for (int c = 0; c < C; ++c) qv[c] = qs[qi * C * 64 + c * 64 + lane];
-            float v[64];
-#pragma unroll
-            for (int r = 0; r < 64; ++r) {
-                float s = 0.f;
-#pragma unroll
-                for (int c = 0; c < C; ++c) {
-                    const float t2 = rb_step<KIND>(s, rv[r][c], qv[c]);
-                    s = (TAIL && c == C - 1 && !last_ok) ? s : t2;
-                }
-                v[r] = s;
-            }
-            float d = rb_reduce_scatter<KIND == RB_LINF>(v, lane);
-            if (KIND == RB_L2) {
-                if (space == SP_L2) d = sqrtf(d);
-            } else if (KIND == RB_DOT) {
-                if (space == SP_NEGDOT) {
-                    d = -d;
-                } else {
-                    const float c = fmaxf(-1.0f, fminf(1.0f, d));
-                    d = fmaxf(0.0f, 1.0f - c);
-                }
-            } else if (KIND == RB_COS) {
-                const float sim = normdot_finish(d, rnorm, qnorm[qi]);
-                d = space == SP_ANGULAR ? acosf(sim) : fmaxf(0.0f, 1.0f - sim);
-            }
+            const float d = rb_tile_distance<KIND, C, TAIL>(space, rv, qs + qi * C * 64, lane, last_ok, rnorm,
+                                                            KIND == RB_COS ? qnorm[qi] : 0.f);
             const bool hit = word * 64 + lane < (size_t)n && d <= radii[q0 + qi];
             const u64 b = __ballot(hit);
             if (lane == 0) masks[(size_t)(q0 + qi) * mask_words + word] = b;
@@ -186,15 +61,6 @@ __global__ __launch_bounds__(256) void range_batch_mask_kernel(int space, const 
     }
 }
 
-// l2sqr_sift: 128 bytes per row, two per lane (one 16-bit load), kept as two 16-bit integers in a register; a pair is one
-// packed subtraction and one v_dot2_i32_i16.  Integer arithmetic, exact in any order.
-typedef short rb_short2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ rb_short2 rb_two_bytes(unsigned short x) {
-    rb_short2 r;
-    r.x = (short)(x & 255);
-    r.y = (short)(x >> 8);
-    return r;
-}
 __global__ __launch_bounds__(256) void range_batch_mask_u8_kernel(const uint8_t* __restrict__ rows, int n,
                                                                   const uint8_t* __restrict__ queries, int nq,
                                                                   const float* __restrict__ radii, u64* __restrict__ masks,
@@ -204,34 +70,16 @@ __global__ __launch_bounds__(256) void range_batch_mask_u8_kernel(const uint8_t*
     const size_t word = (size_t)blockIdx.x * 4 + wave;
     const bool active = word * 64 < (size_t)n;
     rb_short2 rv[64];
-    if (active) {
-#pragma unroll
-        for (int r = 0; r < 64; ++r) {
-            const size_t row = word * 64 + r < (size_t)n ? word * 64 + r : (size_t)n - 1;
-            rv[r] = rb_two_bytes(reinterpret_cast<const unsigned short*>(rows + row * 128)[lane]);   // (rows are 128-byte aligned)
-        }
-    }
+    if (active) rb_load_rows_u8(rows, n, word * 64, lane, rv);
     const int ntiles = (nq + kTile - 1) / kTile;
     for (int t = blockIdx.y; t < ntiles; t += gridDim.y) {
         const int q0 = t * kTile;
         const int tq = nq - q0 < kTile ? nq - q0 : kTile;
         __syncthreads();
-        for (int i = threadIdx.x; i < kTile * 128; i += 256) {   // (the caller's queries have no alignment: byte loads)
-            const bool ok = i / 128 < tq;
-            const uint8_t x = queries[ok ? (size_t)q0 * 128 + i : 0];
-            qs[i] = ok ? x : (uint8_t)0;
-        }
-        __syncthreads();
+        rb_stage_queries_u8<kTile>(queries, q0, tq, qs);
         if (!active) continue;
         for (int qi = 0; qi < tq; ++qi) {
-            const rb_short2 y = rb_two_bytes(reinterpret_cast<const unsigned short*>(qs + qi * 128)[lane]);
-            int v[64];
-#pragma unroll
-            for (int r = 0; r < 64; ++r) {
-                const rb_short2 d = rv[r] - y;
-                v[r] = __builtin_amdgcn_sdot2(d, d, 0, false);
-            }
-            const float d = (float)rb_reduce_scatter<false>(v, lane);
+            const float d = rb_tile_distance_u8(rv, qs + qi * 128, lane);
             const bool hit = word * 64 + lane < (size_t)n && d <= radii[q0 + qi];
             const u64 b = __ballot(hit);
             if (lane == 0) masks[(size_t)(q0 + qi) * mask_words + word] = b;
