@@ -95,6 +95,9 @@ typedef struct {
     size_t last_path;      /* selection path of the last brute-force batch: 0 adaptive f32 MFMA, 1 bf16 fast path,
                               2 adaptive int8, 3 int8 fast path; 4 = HNSW; 5 = HNSW with the walk on the fp16 copy
                               of the rows and an f32 re-rank (gpu_rows=f16), and the brute-force scan for k > 512;
+                              13 = HNSW with the walk on the 8-bit copy of the rows and the same f32 re-rank (gpu_rows=i8:
+                              index or query-time parameter of hnsw over l2, l1, cosinesimil, angulardist and negdotprod on
+                              one device; refused by name elsewhere);
                               6 = l1 fast path (8-bit SAD filter, exact f32 re-rank); 7 = HNSW under a filter whose rows
                               were scanned exactly instead of walked (nmslib_gpu_filter_create); 8 = HNSW with the filter and
                               the tombstones tested inside the walk (query-time parameter gpu_inwalk=1); 9 = a batch with one

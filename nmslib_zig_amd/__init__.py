@@ -372,7 +372,7 @@ class Index:
         self.built = True
 
     def setQueryTimeParams(self, **params):
-        """hnsw: efSearch / ef, algoType; engine extensions gpu_rows="f32"|"f16" (the walk reads an fp16 copy of the rows,
+        """hnsw: efSearch / ef, algoType; engine extensions gpu_rows="f32"|"f16"|"i8" (the walk reads an fp16 or, "i8", an 8-bit copy of the rows,
         the result is re-ranked in f32; also an index parameter of buildIndex) and gpu_rerank=R (how many entries of the
         final array are re-ranked); gpu_inwalk=0|1 (1: an index with deleted rows and a filtered batch test eligibility inside
         the walk, so that deleted and disallowed rows do not count against efSearch and selective filters return k results;

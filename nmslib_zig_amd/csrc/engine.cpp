@@ -1,6 +1,7 @@
 // Engine: host logic around the gfx950 kernels (see engine.hpp).
 #include "engine.hpp"
 #include "f16_pack.hpp"
+#include "q8_pack.hpp"
 
 #include <algorithm>
 #include <chrono>
@@ -438,7 +439,8 @@ void Engine::reset() {
     have_counters_ = false;
     d_rows16_.release();
     rows16_failed_ = false;
-    rows_f16_index_ = rows_f16_ = false;
+    drop_rows8();
+    rows_index_ = rows_ = GpuRows::F32;
     rerank_ = 0;
     inwalk_ = false;
 }
@@ -457,7 +459,7 @@ size_t Engine::memory_usage() const {
 }
 
 size_t Engine::rows16_bytes() const {
-    size_t b = d_rows16_.bytes();
+    size_t b = d_rows16_.bytes() + d_rows8_.bytes();  // (the traversal copies: fp16 and 8-bit)
     for (const auto& c : shards_) b += c->rows16_bytes();
     return b;
 }
@@ -466,7 +468,7 @@ size_t Engine::hbm_bytes() const {
     size_t sh = 0;
     for (const auto& c : shards_) sh += c->hbm_bytes();
     return sh + d_rows_.bytes() + d_aux_.bytes() + d_ids_.bytes() + d_links0_.bytes() + d_up_off_.bytes() + d_up_links_.bytes() +
-           d_rownorm_.bytes() + d_rows16_.bytes() + d_tomb_.bytes() + d_livepos_.bytes() + brute_.bytes() + d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes() + d_st_ptr_.bytes() + d_st_data_.bytes();
+           d_rownorm_.bytes() + d_rows16_.bytes() + d_rows8_.bytes() + d_tomb_.bytes() + d_livepos_.bytes() + brute_.bytes() + d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes() + d_st_ptr_.bytes() + d_st_data_.bytes();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -503,17 +505,18 @@ void Engine::create_index(const std::vector<std::string>& params) {
             ps.get("gpu_append", bp.gpu_append);        // engine extension: later rows go into the GPU-built graph (1)
         }
         ps.get("gpu_shards", gpu_shards_);  // engine extension: row shards over the visible GPUs (0 = all)
-        std::string gpu_rows = "f32";       // engine extension: f16 = the search walks an fp16 copy of the rows
+        std::string gpu_rows = "f32";       // engine extension: f16 / i8 = the search walks an fp16 / 8-bit copy of the rows
         ps.get("gpu_rows", gpu_rows);
         ps.check_unused();
-        const bool f16 = parse_gpu_rows(gpu_rows);
-        if (f16) check_rows16_served();
+        const GpuRows rows = parse_gpu_rows(gpu_rows);
+        if (rows == GpuRows::F16) check_rows16_served();
+        if (rows == GpuRows::I8) check_rows8_served();
         if (bp.gpu_append != 0 && bp.gpu_append != 1)
             throw EngineError(Err::IndexBuildFailed, "gpu_append must be 0 or 1, got " + std::to_string(bp.gpu_append));
         if (bp.gpu_build_cut < 0)
             throw EngineError(Err::IndexBuildFailed, "gpu_build_cut must be a row position (0 = off), got " +
                                                          std::to_string(bp.gpu_build_cut));
-        rows_f16_index_ = rows_f16_ = f16;
+        rows_index_ = rows_ = rows;
         rerank_ = 0;
         inwalk_ = false;
         if (defer && bp.gpu_build < 0) bp.gpu_build = 0;  // deferred upload = no device work now
@@ -529,6 +532,7 @@ void Engine::create_index(const std::vector<std::string>& params) {
         ps.get("threadQty", thread_qty);
         ps.get("gpu_defer", defer);
         ps.get("gpu_shards", gpu_shards_);
+        refuse_rows8_on_scan(params);
         ps.check_unused();
         if ((sparse_ || str_space_ || diverg_) && gpu_shards_ != -1 && gpu_shards_ != 1)
             throw EngineError(Err::IndexBuildFailed, std::string(sparse_ ? "a sparse" : str_space_ ? "a string" : "a divergence") +
@@ -585,25 +589,40 @@ void Engine::set_query_params(const std::vector<std::string>& params) {
         if (has_inwalk && inwalk != "0" && inwalk != "1")
             throw EngineError(Err::InvalidArgument, "gpu_inwalk must be 0 or 1, got '" + inwalk + "'");
         if (ef < 1) throw std::runtime_error("ef must be positive");
-        const bool f16 = has_rows && parse_gpu_rows(gpu_rows);
-        if (f16) check_rows16_served();
+        const GpuRows rows = has_rows ? parse_gpu_rows(gpu_rows) : GpuRows::F32;
+        if (rows == GpuRows::F16) check_rows16_served();
+        if (rows == GpuRows::I8) check_rows8_served();
         if (has_rerank && rerank < 1)
             throw EngineError(Err::InvalidArgument, "gpu_rerank must be at least 1 (it is clamped to [k, max(ef, k)]), got " +
                                                         std::to_string(rerank));
         ef_ = (int)ef;
         algo_ = algo;
-        if (has_rows) rows_f16_ = f16;
+        if (has_rows) rows_ = rows;
         if (has_rerank) rerank_ = (int)std::min<long long>(rerank, INT32_MAX);
         if (has_inwalk) inwalk_ = inwalk == "1";
     } else {
+        refuse_rows8_on_scan(params);
         ps.check_unused();  // SeqSearch has no query-time parameters
     }
 }
 
-bool Engine::parse_gpu_rows(const std::string& v) {
-    if (v == "f32") return false;
-    if (v == "f16") return true;
-    throw EngineError(Err::InvalidArgument, "gpu_rows must be f32 or f16, got '" + v + "'");
+// gpu_rows=i8 names a copy that only the hnsw walk reads: the exact scan refuses it by name (any other value of gpu_rows is
+// an unknown parameter there, as it always was)
+void Engine::refuse_rows8_on_scan(const std::vector<std::string>& params) const {
+    ParamSet peek(params);
+    std::string v;
+    peek.get("gpu_rows", v);
+    if (v == "i8")
+        throw EngineError(Err::InvalidArgument, "gpu_rows=i8: method '" + method_name_ + "' is the exact scan and walks no "
+                                                "graph; the 8-bit copy serves hnsw over l2, l1, cosinesimil, angulardist and "
+                                                "negdotprod on one device");
+}
+
+Engine::GpuRows Engine::parse_gpu_rows(const std::string& v) {
+    if (v == "f32") return GpuRows::F32;
+    if (v == "f16") return GpuRows::F16;
+    if (v == "i8") return GpuRows::I8;
+    throw EngineError(Err::InvalidArgument, "gpu_rows must be f32 or f16, or i8, got '" + v + "'");
 }
 
 void Engine::check_rows16_served() const {
@@ -615,6 +634,23 @@ void Engine::check_rows16_served() const {
                                                     (str_space_ ? "a string" : sparse_ ? "a sparse" : "a divergence") +
                                                     " index has no dense float rows to copy; the fp16 copy serves hnsw "
                                                     "over l2, l1, linf, cosinesimil, angulardist and negdotprod");
+}
+
+// gpu_rows=i8: hnsw over l2, l1, cosinesimil, angulardist and negdotprod, on one device
+void Engine::check_rows8_served() const {
+    static const char* served = "the 8-bit copy serves hnsw over l2, l1, cosinesimil, angulardist and negdotprod on one device";
+    if (is_u8())
+        throw EngineError(Err::InvalidArgument, std::string("gpu_rows=i8: l2sqr_sift rows are uint8 already and their walk "
+                                                            "is integer arithmetic; ") + served);
+    if (str_space_ || sparse_ || diverg_)
+        throw EngineError(Err::InvalidArgument, std::string("gpu_rows=i8: ") +
+                                                    (str_space_ ? "a string" : sparse_ ? "a sparse" : "a divergence") +
+                                                    " index has no dense float rows to copy; " + served);
+    if (space_ == SP_LINF)
+        throw EngineError(Err::InvalidArgument, std::string("gpu_rows=i8: linf has no 8-bit maximum instruction worth a "
+                                                            "kernel of its own (gpu_rows=f16 serves it); ") + served);
+    if ((gpu_shards_ != -1 && gpu_shards_ != 1) || shards_.size() > 1 || parent_)
+        throw EngineError(Err::InvalidArgument, std::string("gpu_rows=i8: gpu_shards other than 1 is not served; ") + served);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -672,6 +708,7 @@ void Engine::upload_rows(size_t first) {
     auto t0 = clk::now();
     dg_.rows16 = nullptr;  // the fp16 copy follows the rows
     rows16_failed_ = false;
+    drop_rows8();          // the 8-bit copy is packed again at the next batch that asks for it
     auto room = [&](DevBuf& b, size_t row_bytes) {
         if (first) b.grow_keep(n * row_bytes, first * row_bytes, stream_);
         else b.ensure(std::max<size_t>(n, 1) * row_bytes);
@@ -841,6 +878,36 @@ bool Engine::ensure_rows16() {
     return true;
 }
 
+// The 8-bit traversal copy of the same rows (q8_pack.hpp): always all of it, at the scale of the rows as they are now.
+bool Engine::ensure_rows8() {
+    if (dg_.rows8) return true;
+    if (rows8_failed_ || is_u8() || d_n_ == 0 || !dg_.rows) return false;
+    const size_t n = d_n_, ld8 = q8pack::row_stride(dim_);
+    int e = 0;
+    try {
+        e = q8pack::scale_exp(rows_max_abs(0, n));
+        d_rows8_.ensure(n * ld8);
+        hip_check(launch_hnsw_pack_rows8(d_rows_.as<float>(), (int)n, ldb_, (int)dim_, e, d_rows8_.ptr(), (int)ld8, stream_),
+                  "8-bit rows");
+        hip_check(hipStreamSynchronize(stream_), "8-bit rows");
+    } catch (const EngineError& x) {
+        if (x.code != Err::OutOfMemory) throw;
+        d_rows8_.release();  // (nothing partial stays behind)
+        rows8_failed_ = true;
+        return false;
+    }
+    dg_.rows8 = d_rows8_.ptr();
+    dg_.ld8 = (int)ld8;
+    dg_.scale8_exp = e;
+    return true;
+}
+
+void Engine::drop_rows8() {
+    dg_.rows8 = nullptr;
+    d_rows8_.release();
+    rows8_failed_ = false;
+}
+
 void Engine::pack_rows16(size_t first, size_t n, int e) {
     const size_t ld16 = f16pack::row_stride(dim_);
     hip_check(launch_hnsw_pack_rows16(d_rows_.as<float>() + first * (size_t)ldb_, (int)(n - first), ldb_, (int)dim_,
@@ -914,7 +981,8 @@ void Engine::finalize_index() {
         build_graph_gpu();
         graph_dirty_ = false;
         dirty_ = false;
-        if (rows_f16_index_) (void)ensure_rows16();
+        if (rows_index_ == GpuRows::F16) (void)ensure_rows16();
+        if (rows_index_ == GpuRows::I8) (void)ensure_rows8();
         return;
     }
     ensure_graph();  // host-side construction first: it needs no device
@@ -923,7 +991,8 @@ void Engine::finalize_index() {
     if (method_ == Method::Brute) prepare_brute();
     else upload_graph();
     dirty_ = false;
-    if (method_ == Method::Hnsw && rows_f16_index_) (void)ensure_rows16();
+    if (method_ == Method::Hnsw && rows_index_ == GpuRows::F16) (void)ensure_rows16();
+    if (method_ == Method::Hnsw && rows_index_ == GpuRows::I8) (void)ensure_rows8();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -960,6 +1029,9 @@ int Engine::resolve_shards() const {
 }
 
 void Engine::finalize_sharded(int nshards) {
+    if (rows_index_ == GpuRows::I8 || rows_ == GpuRows::I8)
+        throw EngineError(Err::InvalidArgument, "gpu_rows=i8: gpu_shards other than 1 is not served (" +
+                                                    std::to_string(nshards) + " shards were asked for)");
     check_device();  // primary device: queries arrive there, results are merged there
     int count = 1;
     hip_check(hipGetDeviceCount(&count), "hipGetDeviceCount");
@@ -973,7 +1045,7 @@ void Engine::finalize_sharded(int nshards) {
         c->dim_ = dim_;
         c->method_ = method_;
         c->bp_ = bp_;
-        c->rows_f16_index_ = c->rows_f16_ = rows_f16_index_;
+        c->rows_index_ = c->rows_ = rows_index_;
         c->created_ = true;
         c->forced_device_ = (device_ + s) % count;
         shards_.push_back(std::move(c));
@@ -1022,7 +1094,7 @@ void Engine::knn_sharded(const void* d_queries, size_t nq, size_t elem_count, si
         hip_check(hipSetDevice(c.device_), "hipSetDevice");
         c.ef_ = ef_;
         c.algo_ = algo_;
-        c.rows_f16_ = rows_f16_;
+        c.rows_ = rows_;
         c.rerank_ = rerank_;
         c.inwalk_ = inwalk_;
         shard_ready_.stream_wait(c.stream_);

@@ -573,16 +573,24 @@ class Engine {
                       hipStream_t stream);
     // Hnsw::Search, hnsw.cc:724: algoType=old, or hybrid with ef >= 1000, runs SearchOld
     bool search_old() const { return algo_ == "old" || (algo_ == "hybrid" && ef_ >= 1000); }
-    // SearchV1Merge on the LDS kernels: the launch, and behind it the bitset launch for queries whose visited table
+    enum class GpuRows { F32, F16, I8 };  // the rows a walk reads: gpu_rows=f32 | f16 | i8
+    // SearchV1Merge on the LDS kernels (the 8-bit walk: its own kernel, same plan): the launch, and behind it the bitset launch for queries whose visited table
     // filled up; timed: the first launch is the timed interval (else the caller closes it with prof_end)
-    void hnsw_search_lds(const HnswDeviceGraph& g, bool rows_f16, const void* d_queries, size_t nq, size_t k, int ef,
+    void hnsw_search_lds(const HnswDeviceGraph& g, GpuRows rows, const void* d_queries, size_t nq, size_t k, int ef,
                          const HnswOut& out, bool timed, hipStream_t stream);
     // gpu_rows=f16: the walk over the fp16 copy, then the f32 re-rank of its sorted array
     void knn_hnsw_f16(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, const HnswOut& fin,
                       hipStream_t stream);
     bool ensure_rows16();  // makes the copy if there is none; false: no copy (allocation failed, no rows): stay on f32
-    static bool parse_gpu_rows(const std::string& v);  // "f32" -> false, "f16" -> true, else InvalidArgument
+    // gpu_rows=i8: the walk over the 8-bit copy in its own kernel, then the same f32 re-rank; last_path 13
+    void knn_hnsw_i8(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, const HnswOut& fin,
+                     hipStream_t stream);
+    bool ensure_rows8();   // likewise for the 8-bit copy: all of it is packed here, whatever was there before
+    void drop_rows8();     // the rows change (append, consolidate, reload): the copy goes, the next i8 batch packs it again
+    static GpuRows parse_gpu_rows(const std::string& v);  // "f32" / "f16" / "i8", else InvalidArgument
     void check_rows16_served() const;                  // InvalidArgument for indexes without float rows
+    void check_rows8_served() const;                   // ... and for what the 8-bit walk does not serve (linf, shards)
+    void refuse_rows8_on_scan(const std::vector<std::string>& params) const;  // brute_force / seq_search: i8 by name
     uint32_t* cleared_bitset(size_t m, size_t words, hipStream_t stream);
 
     std::string space_name_, method_name_;
@@ -632,19 +640,21 @@ class Engine {
     int ef_ = 200;                   // the shim's default (nmslib_c.cpp:330)
     std::string algo_ = "hybrid";
     // engine extensions, index-time gpu_rows and query-time gpu_rows / gpu_rerank / gpu_inwalk: they stay as set until set again
-    bool rows_f16_index_ = false;    // make the fp16 copy at finalize
-    bool rows_f16_ = false;          // walk the fp16 copy (made at the next batch if there is none)
+    GpuRows rows_index_ = GpuRows::F32;  // F16 / I8: make that copy at finalize
+    GpuRows rows_ = GpuRows::F32;        // walk that copy (made at the next batch if there is none)
     int rerank_ = 0;                 // entries of the walk's sorted array that are re-ranked in f32; 0 = all
     bool inwalk_ = false;            // deleted rows and filters are tested inside the walk (hnsw_inwalk_kernels.hip)
     bool rows16_failed_ = false;     // the copy did not fit into HBM: f32 until the rows change
     int rows16_exp_ = 0;             // the copy's scale is 2^rows16_exp_, chosen for rows16_max_ = the largest |element|
     float rows16_max_ = 0;
+    bool rows8_failed_ = false;      // the 8-bit copy did not fit into HBM: f32 until the rows change
 
     // device state
     int device_ = -1;
     hipStream_t stream_ = nullptr;
     DevBuf d_rows_, d_aux_, d_ids_, d_links0_, d_up_off_, d_up_links_, d_rownorm_;
     DevBuf d_rows16_;  // fp16(scale * rows) [n][dg_.ld16], see dg_.rows16
+    DevBuf d_rows8_;   // the 8-bit codes and their sums [n][dg_.ld8], see dg_.rows8
     BruteDense brute_;
     size_t d_n_ = 0;
     int ldb_ = 0;

@@ -105,6 +105,7 @@ void Engine::drop_all_rows() {
     graph_ = HostGraph();
     graph_rows_.clear();
     for (DevBuf* b : {&d_tomb_, &d_rows_, &d_ids_, &d_links0_, &d_up_off_, &d_up_links_, &d_rownorm_, &d_rows16_}) b->release();
+    drop_rows8();
     brute_ = BruteDense();
     dg_ = HnswDeviceGraph{};
     d_n_ = 0;
@@ -185,6 +186,7 @@ void Engine::consolidate_resident(const std::vector<int32_t>& newpos, size_t liv
     consolidate_entry(g.levels, newpos, enter, top);
 
     // ---- compaction into buffers sized for the live rows ----
+    drop_rows8();  // (not compacted: the next i8 batch packs the live rows again)
     const bool have16 = dg_.rows16 != nullptr;
     const size_t rb = is_u8() ? 128 : (size_t)ldb_ * 4, rb16 = (size_t)dg_.ld16 * 2;
     DevBuf n_rows, n_ids, n_links0, n_up_off, n_up_links, n_norm, n_rows16;

@@ -311,9 +311,11 @@ bool Engine::append_rows_gpu() {
         rows16_exp_ = e;
         dg_.rows16 = d_rows16_.ptr();
         dg_.inv_scale16 = f16pack::scale_of(-e);
-    } else if (rows_f16_index_) {
+    } else if (rows_index_ == GpuRows::F16) {
         (void)ensure_rows16();
     }
+    // (the 8-bit copy went in upload_rows; it is packed in full, whether or not the new rows would have fitted its scale)
+    if (rows_index_ == GpuRows::I8) (void)ensure_rows8();
     built_n_ = n1;
     rows_appended = added;
     build_seconds = std::chrono::duration<double>(clk::now() - t0).count() - upload_seconds;

@@ -1,5 +1,5 @@
 // The dense HNSW search of one slice of a batch (knn_device cuts the batch and owns its HnswOut): which kernels answer it --
-// the LDS kernels, the fp16 walk with its f32 re-rank, the HBM-array kernel, SearchOld -- and, for an index with deleted rows
+// the LDS kernels, the fp16 or the 8-bit walk with its f32 re-rank, the HBM-array kernel, SearchOld -- and, for an index with deleted rows
 // or a filtered batch, the two stages around them or, under gpu_inwalk=1, the search that filters
 // inside the walk (4.6e).  The workspaces are HnswSearchWs; the resident side of the graph stays in engine.cpp.
 #include <algorithm>
@@ -28,7 +28,7 @@ static void hnsw_for_slices(size_t nq, size_t per_q, Body body) {
 
 size_t Engine::hnsw_redone() {
     if (!shards_.empty()) return shards_[0]->hnsw_redone();
-    if ((stats_path() != 4 && stats_path() != 5) || !hnsw_fix_valid_) return 0;
+    if ((stats_path() != 4 && stats_path() != 5 && stats_path() != 13) || !hnsw_fix_valid_) return 0;
     if (hnsw_fix_valid_ == kRedoneOnHost) return hnsw_old_redone_;
     int32_t v = 0;
     hip_check(hipSetDevice(device_), "hipSetDevice");
@@ -149,18 +149,30 @@ void Engine::hnsw_walk(bool positions, const void* d_queries, size_t nq, size_t 
         return;
     }
     // (SearchOld and the HBM-array kernel above stay on the f32 rows whatever gpu_rows says)
-    if (rows_f16_ && ensure_rows16()) {
-        knn_hnsw_f16(graph(), d_queries, nq, k, out, stream);
-        return;
+    switch (rows_) {
+        case GpuRows::F16:
+            if (!ensure_rows16()) break;
+            knn_hnsw_f16(graph(), d_queries, nq, k, out, stream);
+            return;
+        case GpuRows::I8:
+            if (!ensure_rows8()) break;
+            knn_hnsw_i8(graph(), d_queries, nq, k, out, stream);
+            return;
+        case GpuRows::F32: break;
     }
-    hnsw_search_lds(graph(), false, d_queries, nq, k, ef, out, true, stream);
+    hnsw_search_lds(graph(), GpuRows::F32, d_queries, nq, k, ef, out, true, stream);
 }
 
-void Engine::hnsw_search_lds(const HnswDeviceGraph& g, bool rows_f16, const void* d_queries, size_t nq, size_t k, int ef,
+void Engine::hnsw_search_lds(const HnswDeviceGraph& g, GpuRows rows, const void* d_queries, size_t nq, size_t k, int ef,
                              const HnswOut& out, bool timed, hipStream_t stream) {
     const HnswQueries queries = HnswQueries::external(d_queries);
     HnswSearchPlan p = hnsw_make_plan(g, (int)nq, (int)k, ef, false);
-    p.rows_f16 = rows_f16 ? 1 : 0;
+    p.rows_f16 = rows == GpuRows::F16 ? 1 : 0;
+    // the 8-bit walk is a kernel of its own behind the same plan and the same parts
+    auto launch = [&](const HnswSearchPlan& plan, uint32_t* bitset, const HnswOverflow& fix) {
+        return rows == GpuRows::I8 ? launch_hnsw_search_q8(g, plan, queries, bitset, fix, out, stream)
+                                   : launch_hnsw_search(g, plan, queries, bitset, fix, out, stream);
+    };
     // (rows the HBM-array kernel still stages can leave no room for this family's sorted array)
     if (p.lds_bytes > HNSW_LDS_LIMIT)
         throw EngineError(Err::QueryTooLarge, "HNSW search: rows of this dimension leave a workgroup's LDS no room for the "
@@ -169,7 +181,7 @@ void Engine::hnsw_search_lds(const HnswDeviceGraph& g, bool rows_f16, const void
     if (p.table_size == 0) {
         uint32_t* bitset = cleared_bitset(nq, p.bitset_words, stream);
         prof_begin(stream);
-        hip_check(launch_hnsw_search(g, p, queries, bitset, HnswOverflow{}, out, stream), "hnsw_search");
+        hip_check(launch(p, bitset, HnswOverflow{}), "hnsw_search");
         if (timed) prof_end(stream);
         return;
     }
@@ -187,11 +199,9 @@ void Engine::hnsw_search_lds(const HnswDeviceGraph& g, bool rows_f16, const void
     hip_check(hipMemsetAsync(fix_count, 0, 4, stream), "clear overflow count");
     hnsw_fix_valid_ = true;
     prof_begin(stream);
-    hip_check(launch_hnsw_search(g, p, queries, nullptr, HnswOverflow{0, fix_list, fix_count}, out, stream), "hnsw_search");
+    hip_check(launch(p, nullptr, HnswOverflow{0, fix_list, fix_count}), "hnsw_search");
     if (timed) prof_end(stream);
-    hip_check(launch_hnsw_search(g, pb, queries, sw_.bitset.as<uint32_t>(), HnswOverflow{fix_slots, fix_list, fix_count},
-                                 out, stream),
-              "hnsw_search(bitset)");
+    hip_check(launch(pb, sw_.bitset.as<uint32_t>(), HnswOverflow{fix_slots, fix_list, fix_count}), "hnsw_search(bitset)");
 }
 
 // The walk reads the fp16 copy; what it ends with is re-ranked against the f32 rows, so every distance returned is the f32
@@ -210,7 +220,28 @@ void Engine::knn_hnsw_f16(const HnswDeviceGraph& g, const void* d_queries, size_
     walk.ids = sw_.rr_ids.as<int32_t>();
     walk.dists = sw_.rr_d.as<float>();
     walk.cnt = sw_.rr_cnt.as<int32_t>();
-    hnsw_search_lds(g, true, d_queries, nq, cap, ef, walk, false, stream);
+    hnsw_search_lds(g, GpuRows::F16, d_queries, nq, cap, ef, walk, false, stream);
+    const size_t rerank = rerank_ > 0 ? std::min(cap, std::max<size_t>(k, (size_t)rerank_)) : cap;
+    hip_check(launch_hnsw_rerank(g, (int)nq, (int)k, (int)cap, (int)rerank, d_queries, walk.ids, walk.cnt, fin, stream),
+              "hnsw_rerank");
+    prof_end(stream);
+}
+
+// The same two steps over the 8-bit copy: hnsw_search_q8_kernel leaves its sorted array of max(ef, k)
+// entries -- array order, internal positions, integer keys -- and the f32 re-rank orders them by their f32 distances.
+void Engine::knn_hnsw_i8(const HnswDeviceGraph& g, const void* d_queries, size_t nq, size_t k, const HnswOut& fin,
+                         hipStream_t stream) {
+    const int ef = ef_;
+    const size_t cap = std::max<size_t>(ef, k);
+    last_path = 13;
+    sw_.rr_ids.ensure(nq * cap * 4);
+    sw_.rr_d.ensure(nq * cap * 4);
+    sw_.rr_cnt.ensure(nq * 4);
+    HnswOut walk = fin;
+    walk.ids = sw_.rr_ids.as<int32_t>();
+    walk.dists = sw_.rr_d.as<float>();
+    walk.cnt = sw_.rr_cnt.as<int32_t>();
+    hnsw_search_lds(g, GpuRows::I8, d_queries, nq, cap, ef, walk, false, stream);
     const size_t rerank = rerank_ > 0 ? std::min(cap, std::max<size_t>(k, (size_t)rerank_)) : cap;
     hip_check(launch_hnsw_rerank(g, (int)nq, (int)k, (int)cap, (int)rerank, d_queries, walk.ids, walk.cnt, fin, stream),
               "hnsw_rerank");

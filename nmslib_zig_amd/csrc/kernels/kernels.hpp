@@ -344,6 +344,12 @@ struct HnswDeviceGraph {
     const void* rows16;
     int ld16;
     float inv_scale16;
+    // 8-bit traversal copy of the f32 rows (gpu_rows=i8; null without one; q8_pack.hpp): codes round(row * 2^-scale8_exp) in
+    // [-127, 127], zero padded to a multiple of 16 bytes, then a 16-byte slot whose first int32 is the sum of the row's
+    // squared codes; row stride ld8 bytes
+    const void* rows8;
+    int ld8;
+    int scale8_exp;
 };
 struct HnswSearchPlan {
     int nq, k, ef, cap;        // cap = max(ef, k)
@@ -438,6 +444,16 @@ hipError_t launch_hnsw_pack_rows16(const float* rows, int n, int ldv, int dim, f
 // position); k results with external ids, -1 / +inf padding and the count go to out.
 hipError_t launch_hnsw_rerank(const HnswDeviceGraph& g, int nq, int k, int cap, int rerank, const void* queries,
                               const int32_t* cand, const int32_t* cand_n, const HnswOut& out, hipStream_t s);
+// gpu_rows=i8 (hnsw_q8_kernels.hip).  The copy: rows8 [n][ld8] bytes as HnswDeviceGraph describes it, at the
+// scale 2^scale_exp (q8_pack.hpp's rounding).
+hipError_t launch_hnsw_pack_rows8(const float* rows, int n, int ldv, int dim, int scale_exp, void* rows8, int ld8,
+                                  hipStream_t s);
+// SearchV1Merge over g.rows8 with integer distances, one wave per query: the parts and the plans of launch_hnsw_search
+// (hnsw_make_plan: table or bitset, the overflow list and its second launch).  External f32 queries only.  Like the fp16
+// kernels it writes its whole sorted array for the re-rank: p.k = p.cap entries, array order, internal positions; out.dists
+// are the walk's integer keys as floats.
+hipError_t launch_hnsw_search_q8(const HnswDeviceGraph& g, const HnswSearchPlan& p, const HnswQueries& q, uint32_t* bitset,
+                                 const HnswOverflow& fix, const HnswOut& out, hipStream_t s);
 // A batch in which every query names its own filter: the filters of the batch as a device table, and per
 // query of a launch its entry's index.  allow: the filter's bits over n_allow positions; list: its m ascending positions (the
 // subset route; null on the walk route).  A workgroup serves one query: it reads slot[q] and the entry once, into scalars.
