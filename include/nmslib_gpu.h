@@ -106,7 +106,10 @@ typedef struct {
                               range query answered by the batched kernels (nmslib_gpu_range_query_batch), 11 = a batched
                               range query answered with the single-query launches, once per query; 12 = the brute-force
                               scan for 512 < k <= 4096 on the batched kernels (one pass over the rows per slice of queries;
-                              fast_tiles then counts the slice's queries, fast_tiles_fallback those that were redone exactly) */
+                              fast_tiles then counts the slice's queries, fast_tiles_fallback those that were redone exactly);
+                              14 = the bf16 MFMA filter of the KL, generalized KL and Itakura-Saito "fast" divergences with
+                              its exact re-rank (fast_tiles then counts the batch's groups of 16 queries,
+                              fast_tiles_fallback the groups that were redone by the exact scan) */
     /* fast paths, last slice of the last batch (reading them waits for the stream): query tiles in the slice, tiles the
        threshold kernel sent through the split-bf16-product scan instead of the one-product scan (float rows only), and
        tiles whose verification failed and were redone by the adaptive kernel */

@@ -478,6 +478,20 @@ class Engine {
     void upload_sparse();
     float pair_distance_sparse(size_t p1, size_t p2);
     void upload_diverg();
+    // the MFMA filter scan of the Bregman "fast" spaces (last_path 14): its resident copy, made by
+    // upload_diverg where the plan's gates on n and D can hold (or by the first batch, if the path was off at finalize),
+    // and the workspaces of a batch (grow-only)
+    struct DivergFast {
+        DevBuf frags, rrow;
+        dvf::RowMax max{};
+        bool have = false, tried = false;
+        DevBuf ws_qsplit, ws_ce, ws_cand, ws_cnt, ws_flags, ws_sub;
+        size_t bytes() const { return frags.bytes() + rrow.bytes(); }
+    } dfast_;
+    void make_diverg_fast_copy();
+    size_t diverg_pack_bytes(size_t nq, size_t D) const;
+    DivergQueries upload_diverg_queries(const float* queries, size_t nq, size_t D);
+    void diverg_scan_batch(const float* queries, size_t nq, size_t D, size_t k, const ResultBlock& out);
     DivergRows diverg_rows() const;
     void knn_diverg_host(const float* queries, size_t nq, size_t elem_count, size_t k, const int32_t** ids,
                          const float** dists, const int32_t** cnt);

@@ -7,6 +7,8 @@
 
 #include <utility>
 
+#include "../diverg_filter.hpp"
+
 namespace gfxknn {
 
 // Space codes (host and device).  Names: include/factory/init_spaces.h:77-86,120.
@@ -822,6 +824,31 @@ hipError_t launch_diverg_dist(int space, const DivergRows& rows, const DivergQue
                               hipStream_t s);
 // *out = distance(object 0, object 1) of a pack with stride 2
 hipError_t launch_diverg_pair(int space, const DivergQueries& objs, int D, float* out, hipStream_t s);
+
+// ---- bf16 MFMA filter scan of the Bregman "fast" divergences (diverg_mfma_kernels.hip, ../diverg_filter.hpp) ----
+// the form (dvf::Form) of a space the filter serves, else -1
+int diverg_fast_form(int space);
+// The resident copy: the row operand as bf16 hi / lo fragments, [ceil(n / 32)][ksteps][2][64][8] (block, K-step, hi | lo,
+// lane, element: lane l holds row l % 32 of the block, columns 16 kc + 8 (l / 32) .. + 7 -- a wave's load of one fragment is
+// 1 KiB in a row), R_row [ceil(n / 32) * 32] and the rows' largest figures.
+struct DivergFastRows {
+    const uint16_t* frags;
+    const float* rrow;
+    dvf::RowMax max;
+};
+inline size_t diverg_fast_frag_elems(size_t n, int dim) { return (n + 31) / 32 * (size_t)((dim + 15) / 16) * 2 * 64 * 8; }
+struct DivergFastWs {
+    uint16_t* qsplit;              // [qpad][2][16 * ksteps]: hi | lo of the query operand
+    double* ce;                    // [qpad][2]: C_q, E_q
+    unsigned long long* cand;      // [qpad][nsplit][dvf::kKeep]: (ordered filter key << 32) | position, ascending
+    int* cand_cnt;                 // [qpad][nsplit]
+    int* flags;                    // [ngroups]: a query of the group has no proof
+};
+inline size_t diverg_fast_scan_lds() { return (size_t)4 * 32 * (dvf::kBuf * 8 + 4 + 8); }
+// queries [0, nq) of the pack -> ids / dists / cnt as the exact scan's merge writes them, and the groups' flags
+hipError_t launch_diverg_fast(int space, const dvf::Plan& p, int nq, int k, const DivergRows& rows,
+                              const DivergFastRows& copy, const DivergQueries& q, const DivergFastWs& ws,
+                              const int32_t* ext_ids, float* out_d, int32_t* out_ids, int32_t* out_cnt, hipStream_t s);
 
 // ---- shard merge ---------------------------------------------------------------------------
 // shard s's lists start at dists_in + s*shard_stride / ids_in + s*shard_stride (elements)
