@@ -109,7 +109,11 @@ typedef struct {
                               fast_tiles then counts the slice's queries, fast_tiles_fallback those that were redone exactly);
                               14 = the bf16 MFMA filter of the KL, generalized KL and Itakura-Saito "fast" divergences with
                               its exact re-rank (fast_tiles then counts the batch's groups of 16 queries,
-                              fast_tiles_fallback the groups that were redone by the exact scan) */
+                              fast_tiles_fallback the groups that were redone by the exact scan);
+                              15 = the inverted-file filter of the sparse inner-product spaces (cosinesimil_sparse,
+                              angulardist_sparse, negdotprod_sparse, querynorm_negdotprod_sparse) with its exact re-rank
+                              (fast_tiles then counts the batch's queries, fast_tiles_fallback the queries that were redone
+                              by the exact scan) */
     /* fast paths, last slice of the last batch (reading them waits for the stream): query tiles in the slice, tiles the
        threshold kernel sent through the split-bf16-product scan instead of the one-product scan (float rows only), and
        tiles whose verification failed and were redone by the adaptive kernel */

@@ -433,6 +433,7 @@ void Engine::reset() {
     dim_ = 0;  // a reset index accepts rows of another dimension
     brute_ = BruteDense();
     dfast_ = DivergFast();
+    sinv_ = SparseInv();
     last_path = 0;
     fast_flags_ = nullptr;
     fast_nqt_ = 0;
@@ -469,7 +470,7 @@ size_t Engine::hbm_bytes() const {
     size_t sh = 0;
     for (const auto& c : shards_) sh += c->hbm_bytes();
     return sh + d_rows_.bytes() + d_aux_.bytes() + d_ids_.bytes() + d_links0_.bytes() + d_up_off_.bytes() + d_up_links_.bytes() +
-           d_rownorm_.bytes() + d_rows16_.bytes() + d_rows8_.bytes() + d_tomb_.bytes() + d_livepos_.bytes() + brute_.bytes() + dfast_.bytes() +d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes() + d_st_ptr_.bytes() + d_st_data_.bytes();
+           d_rownorm_.bytes() + d_rows16_.bytes() + d_rows8_.bytes() + d_tomb_.bytes() + d_livepos_.bytes() + brute_.bytes() + dfast_.bytes() + sinv_.bytes() + d_sp_ptr_.bytes() + d_sp_ids_.bytes() + d_sp_vals_.bytes() + d_st_ptr_.bytes() + d_st_data_.bytes();
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1186,7 +1187,7 @@ void Engine::fast_tile_counts(size_t* tiles, size_t* precise, size_t* fallback) 
         return;
     }
     const int path = stats_path();
-    if ((path != 1 && path != 3 && path != 6 && path != 12 && path != 14) || !fast_flags_ || fast_nqt_ <= 0) return;
+    if ((path != 1 && path != 3 && path != 6 && path != 12 && path != 14 && path != 15) || !fast_flags_ || fast_nqt_ <= 0) return;
     std::vector<int> h((size_t)fast_nqt_ * 2, 0);
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hip_check(hipStreamSynchronize(last_stream_ ? last_stream_ : stream_), "stats");

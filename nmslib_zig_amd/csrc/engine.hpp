@@ -477,6 +477,35 @@ class Engine {
     float read_float(const float* d_out, const char* what);
     void upload_sparse();
     float pair_distance_sparse(size_t p1, size_t p2);
+    // the inverted-file filter of the sparse inner-product spaces (last_path 15): its resident copy, made
+    // by upload_sparse where the plan's gates on the space and n can hold (or by the first batch, if the path was off at
+    // finalize), and the workspaces of a batch (grow-only)
+    struct SparseInv {
+        DevBuf blk_term, terms, seg, blk_post, post_row, post_val;
+        float beta = 0.f;
+        int longest = 0, nblocks = 0;
+        bool have = false, tried = false;
+        DevBuf ws_cand, ws_tblock, ws_flags, ws_sub;
+        size_t bytes() const {
+            return blk_term.bytes() + terms.bytes() + seg.bytes() + blk_post.bytes() + post_row.bytes() + post_val.bytes();
+        }
+        void drop_copy() {
+            have = false;
+            for (DevBuf* b : {&blk_term, &terms, &seg, &blk_post, &post_row, &post_val}) b->release();
+        }
+    } sinv_;
+    void make_sparse_inv_copy();
+    // a batch's queries (all of them, or those listed in `pick`) packed in the pinned block and copied to ws_bq_
+    struct SparseBatch {
+        const int64_t* q_ptr;
+        const uint32_t* q_ids;
+        const float* q_vals;
+        const double* q_norm;
+    };
+    static size_t sparse_pack_bytes(size_t nq, size_t total) { return (nq + 1) * 8 + align8(total * 4) + align8(total * 4) + nq * 8; }
+    SparseBatch upload_sparse_queries(const SparseElem* const* queries, const size_t* counts, size_t nq,
+                                      const std::vector<size_t>* pick);
+    void sparse_scan_batch(const SparseBatch& q, size_t nq, size_t k, const ResultBlock& out);
     void upload_diverg();
     // the MFMA filter scan of the Bregman "fast" spaces (last_path 14): its resident copy, made by
     // upload_diverg where the plan's gates on n and D can hold (or by the first batch, if the path was off at finalize),

@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "../diverg_filter.hpp"
+#include "../sparse_filter.hpp"
 
 namespace gfxknn {
 
@@ -849,6 +850,38 @@ inline size_t diverg_fast_scan_lds() { return (size_t)4 * 32 * (dvf::kBuf * 8 + 
 hipError_t launch_diverg_fast(int space, const dvf::Plan& p, int nq, int k, const DivergRows& rows,
                               const DivergFastRows& copy, const DivergQueries& q, const DivergFastWs& ws,
                               const int32_t* ext_ids, float* out_d, int32_t* out_ids, int32_t* out_cnt, hipStream_t s);
+
+// ---- inverted-file filter of the sparse inner-product spaces (sparse_inv_kernels.hip, ../sparse_filter.hpp) ----
+// the kind (spf::Kind) of a space the filter serves, else -1
+int sparse_fast_kind(int space);
+// The resident inverted file.  Rows are cut into blocks of spf::kBlockRows consecutive positions; a
+// block's postings are grouped by term id, ascending in row inside a term.  Block b:
+//   terms     [blk_term[b], blk_term[b + 1])          the term ids present in it, ascending
+//   seg       [blk_term[b] + b ..], one more entry than terms: where each term's postings start, relative to the block's
+//             first posting; the last entry is the block's posting count
+//   post_row / post_val [blk_post[b], blk_post[b + 1])  row within the block, stored value
+struct SparseInvFile {
+    const int64_t* blk_term;
+    const uint32_t* terms;
+    const uint32_t* seg;
+    const int64_t* blk_post;
+    const uint16_t* post_row;
+    const float* post_val;
+    int n, nblocks;
+    float beta;    // >= the 2-norm of every row's stored values
+    int longest;   // elements of the longest row
+};
+struct SparseInvWs {
+    int32_t* cand;     // [queries of a slice][nblocks][keep]: positions, -1 where a block holds fewer rows
+    float* tblock;     // [queries of a slice][nblocks]: the keep-th score of the block, -inf where it listed all rows
+    int* flags;        // [nq]: the query has no proof
+};
+// queries [q0, q0 + m) of the batch (q_ptr [nq + 1], qnorm [nq]: the queries' 2-norms) -> ids / dists / cnt as the exact
+// scan's merge writes them, and the queries' flags.  m * p.nblocks < 2^31.
+hipError_t launch_sparse_inv(int space, const spf::Plan& p, const SparseInvFile& f, int q0, int m, int k,
+                             const int64_t* row_ptr, const uint32_t* ids, const float* vals, const int64_t* q_ptr,
+                             const uint32_t* q_ids, const float* q_vals, const double* qnorm, const SparseInvWs& ws,
+                             const int32_t* ext_ids, float* out_d, int32_t* out_ids, int32_t* out_cnt, hipStream_t s);
 
 // ---- shard merge ---------------------------------------------------------------------------
 // shard s's lists start at dists_in + s*shard_stride / ids_in + s*shard_stride (elements)

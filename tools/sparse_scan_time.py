@@ -10,6 +10,13 @@ Every GPU measurement runs in a fresh child process under its own time limit.  T
 to the full workload -- the extrapolated figure is labelled as such.
 
     python3 tools/sparse_scan_time.py [--rows 1000000] [--ref-rows 20000] [--ref-queries 8] [--out result.json]
+
+--compare times the inverted-file path (last_path 15) against the exact scan in the same build: for each of
+--spaces, children with NMSLIB_GPU_SPARSE_FAST=1 and =0 alternate (--rounds of each), every child builds its own index and
+times finalize, then --reps batches of each size of --batches; last_path, the fallback share and the index's HBM bytes are
+recorded with the times.  --positive replaces the workload's values, uniform in (-1, 1), by weights in [0.1, 1].
+
+    python3 tools/sparse_scan_time.py --compare [--rows 1000000] [--batches 1,16,256,1024] [--rounds 2] [--out result.json]
 """
 import argparse
 import json
@@ -81,6 +88,52 @@ def child_gpu(space, nrows, reps, nq):
             "batch_wall_s_median": float(np.median(wall)), "batch_gpu_s_mean": kms / 1e3 / max(kn, 1)}
 
 
+def child_compare(space, nrows, reps, batches, positive):
+    """one process, the path as NMSLIB_GPU_SPARSE_FAST says: finalize time, HBM bytes, and per batch size the wall times"""
+    import nmslib_zig_amd as nz
+    X = zipf_csr(1, nrows, 64)
+    Q = zipf_csr(2, max(batches), 32)
+    if positive:                                           # term weights as retrieval has them, in [0.1, 1]
+        X, Q = ((c[0], c[1], np.abs(c[2]) * 0.9 + 0.1) for c in (X, Q))
+    qrows = as_rows(Q, 0, max(batches))
+    idx = nz.Index(space, "seq_search", data_type="SparseVector")
+    idx.addSparseBatch(X)
+    t0 = time.perf_counter()
+    idx.buildIndex()
+    build = time.perf_counter() - t0
+    idx.knnQueryBatch(qrows[:8], 10)                       # warm-up: code objects
+    rec = {"space": space, "rows": nrows, "nnz": int(X[0][-1]), "fast": os.environ.get("NMSLIB_GPU_SPARSE_FAST"), "positive": positive,
+           "finalize_s": build, "hbm_bytes": int(idx.stats()["hbm_bytes"]), "k": 10, "reps": reps, "batches": {}}
+    for nq in batches:
+        wall = []
+        for _ in range(reps):
+            t0 = time.perf_counter()
+            idx.knnQueryBatch(qrows[:nq], 10)
+            wall.append(time.perf_counter() - t0)
+        st = idx.stats()
+        rec["batches"][str(nq)] = {"wall_s": wall, "wall_s_median": float(np.median(wall)), "last_path": int(st["last_path"]),
+                                   "fallback_share": st["fast_tiles_fallback"] / max(st["fast_tiles"], 1)}
+        log(f"{space} fast={rec['fast']}: batch of {nq}: {np.median(wall) * 1e3:.2f} ms, last_path {st['last_path']}")
+    idx.close()
+    return rec
+
+
+def compare(a):
+    out = []
+    for space in a.spaces.split(","):
+        for rnd in range(a.rounds):
+            for fast in ("1", "0"):
+                os.environ["NMSLIB_GPU_SPARSE_FAST"] = fast
+                rec = run_child(["--child", "compare", "--space", space, "--rows", str(a.rows), "--reps", str(a.reps),
+                                 "--batches", a.batches] + (["--positive"] if a.positive else []), a.timeout)
+                rec["round"] = rnd
+                out.append(rec)
+                print(json.dumps(rec), flush=True)
+                if a.out:
+                    with open(a.out, "w") as f:
+                        json.dump(out, f, indent=1)
+
+
 def child_ref(space, nrows, ref_rows, ref_queries):
     from tests.golden import gen_golden_sparse as gs
     X = zipf_csr(1, nrows, 64)
@@ -117,12 +170,22 @@ def main():
     ap.add_argument("--ref-queries", type=int, default=8)
     ap.add_argument("--timeout", type=int, default=600)
     ap.add_argument("--out", default=None)
-    ap.add_argument("--child", choices=["gpu", "ref"], default=None)
+    ap.add_argument("--child", choices=["gpu", "ref", "compare"], default=None)
+    ap.add_argument("--compare", action="store_true")
+    ap.add_argument("--spaces", default="cosinesimil_sparse,negdotprod_sparse")
+    ap.add_argument("--batches", default="1,16,256,1024")
+    ap.add_argument("--rounds", type=int, default=2)
+    ap.add_argument("--positive", action="store_true", help="--compare: values in [0.1, 1] instead of the workload's (-1, 1)")
     ap.add_argument("--space", default=None)
     a = ap.parse_args()
     if a.child == "gpu":
         print(json.dumps(child_gpu(a.space, a.rows, a.reps, a.batch)))
         return
+    if a.child == "compare":
+        print(json.dumps(child_compare(a.space, a.rows, a.reps, [int(b) for b in a.batches.split(",")], a.positive)))
+        return
+    if a.compare:
+        return compare(a)
     if a.child == "ref":
         print(json.dumps(child_ref(a.space, a.rows, a.ref_rows, a.ref_queries)))
         return
