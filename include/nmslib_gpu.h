@@ -113,7 +113,9 @@ typedef struct {
                               15 = the inverted-file filter of the sparse inner-product spaces (cosinesimil_sparse,
                               angulardist_sparse, negdotprod_sparse, querynorm_negdotprod_sparse) with its exact re-rank
                               (fast_tiles then counts the batch's queries, fast_tiles_fallback the queries that were redone
-                              by the exact scan) */
+                              by the exact scan);
+                              16 = the hardware-log2 filter of the Jensen-Shannon spaces (jsdivslow, jsdivfast, jsmetrslow,
+                              jsmetrfast) with its exact re-rank (fast_tiles and fast_tiles_fallback as for 14) */
     /* fast paths, last slice of the last batch (reading them waits for the stream): query tiles in the slice, tiles the
        threshold kernel sent through the split-bf16-product scan instead of the one-product scan (float rows only), and
        tiles whose verification failed and were redone by the adaptive kernel */

@@ -63,6 +63,12 @@ void Engine::upload_diverg() {
     std::vector<float> h(2 * std::max<size_t>(plane, 4), 0.f);
     float* hv = h.data();
     float* hl = h.data() + plane;
+    // the Jensen-Shannon filter's side of the pass (diverg_js_filter.hpp): R_row in f64, kept as one float
+    // per row (+inf in the padding of the last 64-row block), and the rows' maxima
+    const bool js = diverg_js_space(space_) && n >= (size_t)dvf::kMinRows;
+    std::vector<float> r32(js ? (n + 63) / 64 * 64 : 0, INFINITY);
+    djs::RowMax jm{0.f, 0.f, 0.f};
+    bool js_ok = js;
     for (size_t r = 0; r < n; ++r) {
         const float* x = &rows_f32_[r * dim_];
         const size_t base = ((r >> 6) * G) * 256 + (r & 63) * 4;
@@ -70,6 +76,10 @@ void Engine::upload_diverg() {
             const size_t at = base + (j >> 2) * 256 + (j & 3);
             hv[at] = x[j];
             hl[at] = diverg_log(space_, x[j]);
+        }
+        if (js) {
+            r32[r] = (float)djs::row(x, dim_, &jm, &js_ok);
+            js_ok = js_ok && std::isfinite(r32[r]);
         }
     }
     d_rows_.ensure(h.size() * 4);
@@ -85,6 +95,22 @@ void Engine::upload_diverg() {
     dfast_.frags.release();
     dfast_.rrow.release();
     if (diverg_fast_enabled()) make_diverg_fast_copy();
+    // a negative or non-finite element, a figure beyond f32 and a failed allocation leave the index to the exact scan
+    dfast_.js_have = false;
+    dfast_.js_r32.release();
+    if (js_ok && std::isfinite(jm.lam) && std::isfinite(jm.sum) && std::isfinite(jm.xlnx)) {
+        try {
+            dfast_.js_r32.ensure(r32.size() * 4);
+            hip_check(hipMemcpyAsync(dfast_.js_r32.ptr(), r32.data(), r32.size() * 4, hipMemcpyHostToDevice, stream_), "diverg row constants H2D");
+            hip_check(hipStreamSynchronize(stream_), "diverg row constants");
+            dfast_.js_max = jm;
+            dfast_.js_have = true;
+        } catch (const EngineError& e) {
+            if (e.code != Err::OutOfMemory) throw;
+            (void)hipGetLastError();
+            dfast_.js_r32.release();
+        }
+    }
     upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 
@@ -165,8 +191,11 @@ void Engine::knn_diverg_host(const float* queries, size_t nq, size_t elem_count,
     const int form = diverg_fast_form(space_), kk = (int)std::min<size_t>(k, INT_MAX);
     // (an index finalized with the path off: the first batch that finds it on and could take it makes the copy)
     if (opted && !dfast_.tried && dvf::plan(form, (int)d_n_, (int)D, (int)nq, kk, true).use) make_diverg_fast_copy();
-    const dvf::Plan fp = dvf::plan(form, (int)d_n_, (int)D, (int)nq, kk, dfast_.have);
-    // on by default: measured, the path beats the exact scan three times over for KL and five for Itakura-Saito
+    // (js_have: a Jensen-Shannon index; its plan takes any D and needs no copy of the rows)
+    const bool js = dfast_.js_have;
+    const dvf::Plan fp = js ? djs::plan((int)d_n_, (int)D, (int)nq, kk, true) : dvf::plan(form, (int)d_n_, (int)D, (int)nq, kk, dfast_.have);
+    // on by default: measured, the path beats the exact scan three times over for KL and Jensen-Shannon and five for
+    // Itakura-Saito
     if (!fp.use || !opted) {
         diverg_scan_batch(queries, nq, D, k, out);
         fetch_results(nq, k, "diverg knn", ids, dists, cnt);
@@ -178,21 +207,28 @@ void Engine::knn_diverg_host(const float* queries, size_t nq, size_t elem_count,
     const DivergQueries q = upload_diverg_queries(queries, nq, D);
     const size_t dpad = 16 * (size_t)fp.ksteps, lists = (size_t)fp.qpad * fp.nsplit;
     DivergFastWs ws{};
-    ws.qsplit = static_cast<uint16_t*>(f.ws_qsplit.ensure((size_t)fp.qpad * 2 * dpad * 2));
+    // (the queries' operand as the scan reads it: bf16 hi | lo, or for Jensen-Shannon the clamped value plane)
+    ws.qsplit = static_cast<uint16_t*>(f.ws_qsplit.ensure(js ? (size_t)diverg_groups((int)D) * fp.qpad * 16 : (size_t)fp.qpad * 2 * dpad * 2));
+    ws.qclamp = reinterpret_cast<float*>(ws.qsplit);
     ws.ce = static_cast<double*>(f.ws_ce.ensure((size_t)fp.qpad * 16));
     ws.cand = static_cast<unsigned long long*>(f.ws_cand.ensure(lists * dvf::kKeep * 8));
     ws.cand_cnt = static_cast<int*>(f.ws_cnt.ensure(lists * 4));
     ws.flags = static_cast<int*>(f.ws_flags.ensure((size_t)fp.ngroups * 4));
     const DivergFastRows copy{f.frags.as<uint16_t>(), f.rrow.as<float>(), f.max};
     prof_begin(stream_);
-    hip_check(launch_diverg_fast(space_, fp, (int)nq, (int)k, diverg_rows(), copy, q, ws, d_ids_.as<int32_t>(), out.dists,
-                                 out.ids, out.cnt, stream_),
-              "diverg fast scan");
+    if (js)
+        hip_check(launch_diverg_js_fast(space_, fp, (int)nq, (int)k, diverg_rows(), f.js_r32.as<float>(), f.js_max, q, ws,
+                                        d_ids_.as<int32_t>(), out.dists, out.ids, out.cnt, stream_),
+                  "diverg js fast scan");
+    else
+        hip_check(launch_diverg_fast(space_, fp, (int)nq, (int)k, diverg_rows(), copy, q, ws, d_ids_.as<int32_t>(), out.dists,
+                                     out.ids, out.cnt, stream_),
+                  "diverg fast scan");
     prof_end(stream_);
     std::vector<int> flags((size_t)fp.ngroups);
     hip_check(hipMemcpyAsync(flags.data(), ws.flags, flags.size() * 4, hipMemcpyDeviceToHost, stream_), "diverg flags D2H");
     hip_check(hipStreamSynchronize(stream_), "diverg fast scan");
-    last_path = 14;
+    last_path = js ? 16 : 14;
     fast_flags_ = ws.flags;
     fast_nqt_ = fp.ngroups;
     fast_has_precise_ = false;

@@ -1187,7 +1187,7 @@ void Engine::fast_tile_counts(size_t* tiles, size_t* precise, size_t* fallback) 
         return;
     }
     const int path = stats_path();
-    if ((path != 1 && path != 3 && path != 6 && path != 12 && path != 14 && path != 15) || !fast_flags_ || fast_nqt_ <= 0) return;
+    if ((path != 1 && path != 3 && path != 6 && path != 12 && path != 14 && path != 15 && path != 16) || !fast_flags_ || fast_nqt_ <= 0) return;
     std::vector<int> h((size_t)fast_nqt_ * 2, 0);
     hip_check(hipSetDevice(device_), "hipSetDevice");
     hip_check(hipStreamSynchronize(last_stream_ ? last_stream_ : stream_), "stats");

@@ -515,7 +515,12 @@ class Engine {
         dvf::RowMax max{};
         bool have = false, tried = false;
         DevBuf ws_qsplit, ws_ce, ws_cand, ws_cnt, ws_flags, ws_sub;
-        size_t bytes() const { return frags.bytes() + rrow.bytes(); }
+        // the hardware-log2 filter of the Jensen-Shannon spaces (last_path 16): fl32(R_row) per row and the
+        // rows' maxima, taken by upload_diverg's pass over the rows; no copy of the rows
+        DevBuf js_r32;
+        djs::RowMax js_max{};
+        bool js_have = false;
+        size_t bytes() const { return frags.bytes() + rrow.bytes() + js_r32.bytes(); }
     } dfast_;
     void make_diverg_fast_copy();
     size_t diverg_pack_bytes(size_t nq, size_t D) const;

@@ -199,8 +199,9 @@ __global__ __launch_bounds__(256) void diverg_mfma_scan_kernel(DivergScanArgs a)
 template <int F, bool REV>
 __global__ __launch_bounds__(256) void diverg_fast_rerank_kernel(const f32x4* rv, const f32x4* rl, int D, int G, const f32x4* qv,
                                                                  const f32x4* ql, int qstride, const u64* cand,
-                                                                 const int* cand_cnt, int nsplit, int k, const int32_t* ext_ids,
-                                                                 float* out_d, int32_t* out_ids, int32_t* out_cnt) {
+                                                                 const int* cand_cnt, int nsplit, int k, int metr,
+                                                                 const int32_t* ext_ids, float* out_d, int32_t* out_ids,
+                                                                 int32_t* out_cnt) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     u64* keys = reinterpret_cast<u64*>(smem);
     __shared__ int s_total;
@@ -215,8 +216,8 @@ __global__ __launch_bounds__(256) void diverg_fast_rerank_kernel(const f32x4* rv
         if (i < slots && j < cand_cnt[(size_t)q * nsplit + sp]) {
             const uint32_t pos = (uint32_t)cand[((size_t)q * nsplit + sp) * kKeep + j];
             const size_t ro = (size_t)(pos >> 6) * G * 64 + (pos & 63);
-            const float d = REV ? diverg_eval<F>(D, qv + q, ql + q, (size_t)qstride, rv + ro, rl + ro, 64, 0)
-                                : diverg_eval<F>(D, rv + ro, rl + ro, 64, qv + q, ql + q, (size_t)qstride, 0);
+            const float d = REV ? diverg_eval<F>(D, qv + q, ql + q, (size_t)qstride, rv + ro, rl + ro, 64, metr)
+                                : diverg_eval<F>(D, rv + ro, rl + ro, 64, qv + q, ql + q, (size_t)qstride, metr);
             // -0 and +0 are one distance, as in the exact scan
             key = ((u64)f32_ord(d == 0.0f ? 0.0f : d) << 32) | pos;
             ++mine;
@@ -246,8 +247,10 @@ __global__ __launch_bounds__(256) void diverg_fast_rerank_kernel(const f32x4* rv
 // a filter key of at least the list's largest, key_m, so its exact f32 distance is at least dvf::filter_floor(key_m, C_q,
 // E_q).  The answer is proven when that is strictly above d_k for every full split (a split that is not full left
 // nothing out).  Anything else -- fewer than k results, a bound that is not finite -- flags the query's group.
+// metr (jsmetr*): the floor goes through the distance's clamp and square root first (djs::proof_floor).
 __global__ __launch_bounds__(64) void diverg_fast_verify_kernel(const u64* cand, const int* cand_cnt, const double* ce,
-                                                                const float* out_d, int nq, int k, int nsplit, int* flags) {
+                                                                const float* out_d, int nq, int k, int nsplit, int metr,
+                                                                int* flags) {
     const int q = blockIdx.x * 64 + threadIdx.x;
     if (q >= nq) return;
     const float dk = out_d[(size_t)q * k + k - 1];
@@ -257,7 +260,7 @@ __global__ __launch_bounds__(64) void diverg_fast_verify_kernel(const u64* cand,
         const size_t o = (size_t)q * nsplit + sp;
         if (cand_cnt[o] < kKeep) continue;
         const float key_m = ord_f32((uint32_t)(cand[o * kKeep + kKeep - 1] >> 32));
-        ok = dvf::filter_floor(key_m, C, E) > (double)dk;
+        ok = djs::proof_floor(key_m, C, E, metr) > (double)dk;
     }
     if (!ok) atomicOr(&flags[q / dvf::kGroup], 1);
 }
@@ -270,13 +273,13 @@ __global__ void diverg_fast_clear_kernel(int* flags, int n) {
 inline const f32x4* v4(const float* p) { return reinterpret_cast<const f32x4*>(p); }
 
 template <int F, bool REV>
-hipError_t launch_rerank(const dvf::Plan& p, int nq, int k, const DivergRows& rows, const DivergQueries& q,
+hipError_t launch_rerank(const dvf::Plan& p, int nq, int k, int metr, const DivergRows& rows, const DivergQueries& q,
                          const DivergFastWs& ws, const int32_t* ext_ids, float* out_d, int32_t* out_ids, int32_t* out_cnt,
                          hipStream_t s) {
     int P = 1;
     while (P < p.nsplit * kKeep) P <<= 1;
     hipLaunchKernelGGL((diverg_fast_rerank_kernel<F, REV>), dim3(nq), dim3(256), (size_t)P * 8, s, v4(rows.vals), v4(rows.logs),
-                       rows.D, rows.G, v4(q.vals), v4(q.logs), q.stride, ws.cand, ws.cand_cnt, p.nsplit, k, ext_ids, out_d,
+                       rows.D, rows.G, v4(q.vals), v4(q.logs), q.stride, ws.cand, ws.cand_cnt, p.nsplit, k, metr, ext_ids, out_d,
                        out_ids, out_cnt);
     return hipGetLastError();
 }
@@ -324,16 +327,28 @@ hipError_t launch_diverg_fast(int space, const dvf::Plan& p, int nq, int k, cons
     else if (p.ksteps_max == 8) e = launch_with_lds(diverg_mfma_scan_kernel<8>, grid, lds, s, a);
     else e = launch_with_lds(diverg_mfma_scan_kernel<16>, grid, lds, s, a);
     if (e != hipSuccess) return e;
-    switch (form) {
-        case dvf::KL: e = launch_rerank<DV_KL, false>(p, nq, k, rows, q, ws, ext_ids, out_d, out_ids, out_cnt, s); break;
-        case dvf::KL_RQ: e = launch_rerank<DV_KL, true>(p, nq, k, rows, q, ws, ext_ids, out_d, out_ids, out_cnt, s); break;
-        case dvf::KLGEN: e = launch_rerank<DV_KLGEN, false>(p, nq, k, rows, q, ws, ext_ids, out_d, out_ids, out_cnt, s); break;
-        case dvf::KLGEN_RQ: e = launch_rerank<DV_KLGEN, true>(p, nq, k, rows, q, ws, ext_ids, out_d, out_ids, out_cnt, s); break;
-        default: e = launch_rerank<DV_IS, false>(p, nq, k, rows, q, ws, ext_ids, out_d, out_ids, out_cnt, s); break;
+    return launch_diverg_fast_rerank_verify(space, p, nq, k, rows, q, ws, ext_ids, out_d, out_ids, out_cnt, s);
+}
+
+hipError_t launch_diverg_fast_rerank_verify(int space, const dvf::Plan& p, int nq, int k, const DivergRows& rows,
+                                            const DivergQueries& q, const DivergFastWs& ws, const int32_t* ext_ids,
+                                            float* out_d, int32_t* out_ids, int32_t* out_cnt, hipStream_t s) {
+    const int metr = space == SP_JSMETR || space == SP_JSMETR_SLOW;
+    hipError_t e;
+    switch (diverg_fast_form(space)) {
+        case dvf::KL: e = launch_rerank<DV_KL, false>(p, nq, k, 0, rows, q, ws, ext_ids, out_d, out_ids, out_cnt, s); break;
+        case dvf::KL_RQ: e = launch_rerank<DV_KL, true>(p, nq, k, 0, rows, q, ws, ext_ids, out_d, out_ids, out_cnt, s); break;
+        case dvf::KLGEN: e = launch_rerank<DV_KLGEN, false>(p, nq, k, 0, rows, q, ws, ext_ids, out_d, out_ids, out_cnt, s); break;
+        case dvf::KLGEN_RQ: e = launch_rerank<DV_KLGEN, true>(p, nq, k, 0, rows, q, ws, ext_ids, out_d, out_ids, out_cnt, s); break;
+        case dvf::IS: e = launch_rerank<DV_IS, false>(p, nq, k, 0, rows, q, ws, ext_ids, out_d, out_ids, out_cnt, s); break;
+        default:
+            if (!diverg_js_space(space)) return hipErrorInvalidValue;
+            e = launch_rerank<DV_JS, false>(p, nq, k, metr, rows, q, ws, ext_ids, out_d, out_ids, out_cnt, s);
+            break;
     }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(diverg_fast_verify_kernel, dim3((nq + 63) / 64), dim3(64), 0, s, ws.cand, ws.cand_cnt, ws.ce, out_d, nq,
-                       k, p.nsplit, ws.flags);
+                       k, p.nsplit, metr, ws.flags);
     return hipGetLastError();
 }
 

@@ -8,6 +8,7 @@
 #include <utility>
 
 #include "../diverg_filter.hpp"
+#include "../diverg_js_filter.hpp"
 #include "../sparse_filter.hpp"
 
 namespace gfxknn {
@@ -844,12 +845,27 @@ struct DivergFastWs {
     unsigned long long* cand;      // [qpad][nsplit][dvf::kKeep]: (ordered filter key << 32) | position, ascending
     int* cand_cnt;                 // [qpad][nsplit]
     int* flags;                    // [ngroups]: a query of the group has no proof
+    float* qclamp;                 // Jensen-Shannon filter only: [G][qpad][4], the queries clamped to >= djs::kClamp
 };
 inline size_t diverg_fast_scan_lds() { return (size_t)4 * 32 * (dvf::kBuf * 8 + 4 + 8); }
 // queries [0, nq) of the pack -> ids / dists / cnt as the exact scan's merge writes them, and the groups' flags
 hipError_t launch_diverg_fast(int space, const dvf::Plan& p, int nq, int k, const DivergRows& rows,
                               const DivergFastRows& copy, const DivergQueries& q, const DivergFastWs& ws,
                               const int32_t* ext_ids, float* out_d, int32_t* out_ids, int32_t* out_cnt, hipStream_t s);
+// the last two steps of a filter path, over the lists in ws: exact re-rank of the listed rows, then the proof (flags); the
+// Bregman "fast" spaces and the four Jensen-Shannon spaces
+hipError_t launch_diverg_fast_rerank_verify(int space, const dvf::Plan& p, int nq, int k, const DivergRows& rows,
+                                            const DivergQueries& q, const DivergFastWs& ws, const int32_t* ext_ids,
+                                            float* out_d, int32_t* out_ids, int32_t* out_cnt, hipStream_t s);
+
+// ---- hardware-log2 filter scan of the Jensen-Shannon spaces (diverg_js_kernels.hip, ../diverg_js_filter.hpp) ----
+bool diverg_js_space(int space);
+inline size_t diverg_js_scan_lds() { return (size_t)4 * djs::kTileQ * dvf::kBuf * 8; }
+// queries [0, nq) of the pack -> ids / dists / cnt and the groups' flags, as launch_diverg_fast.  r32: fl32(R_row) per row,
+// [ceil(n / 64) * 64], +inf in the padding; m: the rows' maxima; p: djs::plan
+hipError_t launch_diverg_js_fast(int space, const dvf::Plan& p, int nq, int k, const DivergRows& rows, const float* r32,
+                                 const djs::RowMax& m, const DivergQueries& q, const DivergFastWs& ws, const int32_t* ext_ids,
+                                 float* out_d, int32_t* out_ids, int32_t* out_cnt, hipStream_t s);
 
 // ---- inverted-file filter of the sparse inner-product spaces (sparse_inv_kernels.hip, ../sparse_filter.hpp) ----
 // the kind (spf::Kind) of a space the filter serves, else -1

@@ -13,8 +13,8 @@ run over them.
 
     python3 tools/diverg_scan_time.py [--rows 1000000] [--dim 128] [--reps 20] [--out result.json]
 
---compare ROUNDS times the bf16 MFMA filter path of kldivfast and itakurasaitofast against the exact
-scan in the same call: per space ROUNDS rounds, each one fresh process with NMSLIB_GPU_DIVERG_FAST=1 and then one with 0.
+--compare ROUNDS times the bf16 MFMA filter path of kldivfast and itakurasaitofast and the hardware-log2
+filter path of jsdivfast and jsmetrfast (4.11b; --spaces picks a subset) against the exact scan in the same call: per space ROUNDS rounds, each one fresh process with NMSLIB_GPU_DIVERG_FAST=1 and then one with 0.
 Every run records the path its batches took (last_path), the 16-query groups on the filter path and the share of them
 the exact scan had to redo; the summary gives median and range per leg and says whether the filter wins by more than the
 two legs' spread.  With --trace one more filter-path process per space runs under rocprofv3 --kernel-trace --stats (a run
@@ -38,7 +38,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 SPACES = ("kldivfast", "itakurasaitofast", "jsdivfast", "l1")
-FILTER_SPACES = ("kldivfast", "itakurasaitofast")
+# the spaces --compare runs, and the last_path their filter reports: 14 = bf16 MFMA filter, 16 = hardware-log2 filter (4.11b)
+FILTER_SPACES = ("kldivfast", "itakurasaitofast", "jsdivfast", "jsmetrfast")
+FILTER_PATH = {"kldivfast": 14, "itakurasaitofast": 14, "jsdivfast": 16, "jsmetrfast": 16}
+# diverg_js_filter_kernel's inner loop, one group of 4 elements against 16 queries: 32 v_pk_add + 64 v_log + 32 v_pk_fma + 5
+JS_FILTER_VALU_PER_ELEMENT = 133 / 64
 # Vector-ALU wave instructions per (row element, query) in the inner loop of diverg_knn_kernel<.., 16>, counted in its
 # gfx950 code: the loop body serves one group of 4 elements against 16 queries, 64 pairs, and holds
 #   kldivfast        64 v_sub + 32 v_pk_mul + 32 v_pk_add + 6 moves / address adds              = 134
@@ -89,10 +93,13 @@ def child(space, nrows, dim, reps, nq):
         rec["scan_gpu_ms_mean"] = kms / kn * max(1, kn // reps)
         rec["scan_gpu_method"] = "HIP events around the scan and merge launches of a batch, mean over the same batches"
     rec["last_path"] = int(st["last_path"])
-    if st["last_path"] == 14:      # the filter path: 16-query groups it served, and those the exact scan redid
+    if st["last_path"] in (14, 16):      # a filter path: 16-query groups it served, and those the exact scan redid
         rec["hbm_mib"] = int(st["hbm_bytes"]) >> 20
         rec["fast_tiles"], rec["fast_tiles_fallback"] = int(st["fast_tiles"]), int(st["fast_tiles_fallback"])
         rec["fallback_share"] = rec["fast_tiles_fallback"] / max(1, rec["fast_tiles"])
+        if st["last_path"] == 16 and kn:      # (an upper figure: the batch's time holds the re-rank and the proof too)
+            rec["filter_valu_instr_per_element"] = JS_FILTER_VALU_PER_ELEMENT
+            rec["v_log_f32_per_s_lower_bound"] = float(nrows) * dim * nq / (rec["scan_gpu_ms_mean"] * 1e-3)
     elif space in VALU_PER_ELEMENT and kn:      # (figures of the exact scan's inner loop: for runs that ran it)
         pairs_el, sec = float(nrows) * dim * nq, rec["scan_gpu_ms_mean"] * 1e-3
         rec["valu_instr_per_element"] = VALU_PER_ELEMENT[space]
@@ -133,17 +140,18 @@ def kernel_split(a, space, outdir):
 def compare(a):
     """the filter path against the exact scan: alternating fresh processes, then the verdict"""
     runs, doc = [], {}
-    for space in FILTER_SPACES:
+    spaces = tuple(a.spaces.split(",")) if a.spaces else FILTER_SPACES
+    for space in spaces:
         for rnd in range(a.compare):
             for fast in (1, 0):
                 rec = run_child(a, space, fast=fast)
                 rec["fast"], rec["round"] = fast, rnd
-                if rec["last_path"] != (14 if fast else 0):
+                if rec["last_path"] != (FILTER_PATH[space] if fast else 0):
                     raise SystemExit(f"{space}: NMSLIB_GPU_DIVERG_FAST={fast} ran path {rec['last_path']}")
                 runs.append(rec)
                 print(json.dumps(rec), flush=True)
     summary = []
-    for space in FILTER_SPACES:
+    for space in spaces:
         leg = {}
         for fast in (1, 0):
             mine = [r for r in runs if r["space"] == space and r["fast"] == fast]
@@ -161,7 +169,7 @@ def compare(a):
            "summary": summary, "runs": runs}
     if a.trace:
         outdir = os.path.dirname(os.path.abspath(a.out)) if a.out else os.getcwd()
-        doc["kernel_split"] = [kernel_split(a, space, a.trace_dir or outdir) for space in FILTER_SPACES]
+        doc["kernel_split"] = [kernel_split(a, space, a.trace_dir or outdir) for space in spaces]
         for ks in doc["kernel_split"]:
             print(json.dumps(ks), flush=True)
     if a.out:
@@ -180,6 +188,7 @@ def main():
     ap.add_argument("--child", action="store_true")
     ap.add_argument("--space", default=None)
     ap.add_argument("--compare", type=int, default=0, metavar="ROUNDS")
+    ap.add_argument("--spaces", default=None, help="--compare: a comma-separated subset of " + ",".join(FILTER_SPACES))
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--trace-dir", default=None)
     a = ap.parse_args()
