@@ -3,6 +3,7 @@
 #include <type_traits>
 
 #include "common_dev.hpp"
+#include "hnsw_args.hpp"
 
 namespace gfxknn {
 
@@ -372,16 +373,16 @@ __device__ __forceinline__ int collect_unvisited_any(const int* list, int* nbr, 
 }
 // one greedy step on an upper level over a list of any length: the FIRST neighbour attaining the minimum, if it is closer
 // than curdist (the sequential "if (d < curdist)" scan of hnsw.cc / hnsw_distfunc_opt.cc:176-196).  Returns the list length.
-template <int SPACE, class ROW = float>
-__device__ __forceinline__ int greedy_step_any(const HnswDeviceGraph& g, const int* list, const float* qv, const uint8_t* qb,
-                                               int qnorm, int* nbr, float* nd, int lane, int& cur, float& curdist,
-                                               bool& changed) {
+// dist(ids, out, m): the distances of the query to rows ids[0..m) -> out[0..m), whatever form of the rows it gathers.
+template <class Dist>
+__device__ __forceinline__ int greedy_step_any(const int* list, int* nbr, float* nd, int lane, int& cur, float& curdist,
+                                               bool& changed, Dist&& dist) {
     const int cnt = __builtin_amdgcn_readfirstlane(list[0]);
     for (int c0 = 0; c0 < cnt; c0 += 64)
         if (c0 + lane < cnt) nbr[c0 + lane] = list[c0 + lane + 1];
     __builtin_amdgcn_wave_barrier();
     if (cnt > 0) {
-        frontier_distances<SPACE, ROW>(g, qv, qb, qnorm, nbr, nd, cnt, lane);
+        dist(nbr, nd, cnt);
         u64 key = ~0ull;
         for (int c0 = 0; c0 < cnt; c0 += 64) {
             const int i = c0 + lane;
@@ -404,6 +405,139 @@ __device__ __forceinline__ int greedy_step_any(const HnswDeviceGraph& g, const i
     }
     __builtin_amdgcn_wave_barrier();
     return cnt;
+}
+
+// ---- what the one-wave search kernels begin with --------------------------------------------------------------------
+// The query into its LDS slot qv ([ldv] floats; u8: 128 bytes), normalised where the space asks for it
+// (hnsw_distfunc_opt.cc:160-162).  query_rows (construction mode): the query is a stored row, already normalised.
+// Returns the sum of squares of a u8 query (0 otherwise).  The caller's wave barrier follows.
+template <int SPACE>
+__device__ __forceinline__ int stage_query(const HnswDeviceGraph& g, const void* queries, const int32_t* query_rows, int q,
+                                           float* qv, int lane) {
+    int qnorm = 0;
+    if constexpr (DistTraits<SPACE>::kU8) {
+        const uint8_t* src = query_rows ? reinterpret_cast<const uint8_t*>(g.rows) + (size_t)query_rows[q] * 128
+                                        : reinterpret_cast<const uint8_t*>(queries) + (size_t)q * 128;
+        const int x0 = src[2 * lane], x1 = src[2 * lane + 1];
+        reinterpret_cast<uint8_t*>(qv)[2 * lane] = (uint8_t)x0;
+        reinterpret_cast<uint8_t*>(qv)[2 * lane + 1] = (uint8_t)x1;
+        qnorm = wave_sum_i(x0 * x0 + x1 * x1);
+    } else {
+        const float* src = query_rows ? reinterpret_cast<const float*>(g.rows) + (size_t)query_rows[q] * g.ldv
+                                      : reinterpret_cast<const float*>(queries) + (size_t)q * g.dim;
+        float ss = 0.f;
+        for (int d = lane; d < g.ldv; d += 64) {
+            const float v = d < g.dim ? src[d] : 0.f;
+            qv[d] = v;
+            ss = fmaf(v, v, ss);
+        }
+        if (g.normalize_query && !query_rows) {
+            ss = wave_sum(ss);
+            if (ss != 0.0f) {
+                const float inv = 1.0f / sqrtf(ss);
+                for (int d = lane; d < g.dim; d += 64) qv[d] *= inv;
+            }
+        }
+    }
+    return qnorm;
+}
+
+// The visited set of one query, test-and-set: true when id was NOT visited before (exact).  BITSET: one bit per row in
+// HBM; otherwise an open-addressing table of table_size (a power of two) words in LDS.
+template <bool BITSET>
+struct VisitedSet {
+    uint32_t* set;
+    int table_size, table_shift;
+    __device__ __forceinline__ void clear_table(int lane) const {
+        if constexpr (!BITSET) {
+            for (int i = lane; i < table_size; i += 64) set[i] = HT_EMPTY;
+        }
+    }
+    __device__ __forceinline__ bool operator()(uint32_t id) const {
+        if constexpr (BITSET) {
+            const uint32_t bit = 1u << (id & 31);
+            const uint32_t old = atomicOr(&set[id >> 5], bit);
+            return (old & bit) == 0;
+        } else {
+            uint32_t hsh = (id * 2654435761u) >> table_shift;
+            const uint32_t mask = (uint32_t)table_size - 1u;
+            for (int probe = 0; probe < table_size; ++probe) {
+                const uint32_t old = atomicCAS(&set[hsh], HT_EMPTY, id);
+                if (old == HT_EMPTY) return true;
+                if (old == id) return false;
+                hsh = (hsh + 1) & mask;
+            }
+            return false;
+        }
+    }
+};
+
+// The result of a query over an empty index: no items, every counter 0; PAD: the k output slots filled with -1 / +inf.
+template <bool PAD>
+__device__ __forceinline__ void hnsw_empty_result(const HnswArgs& a, int q, int lane) {
+    if constexpr (PAD) {
+        for (int i = lane; i < a.k; i += 64) {
+            a.out_ids[(size_t)q * a.k + i] = -1;
+            a.out_dists[(size_t)q * a.k + i] = INFINITY;
+        }
+    }
+    if (lane == 0) {
+        a.out_cnt[q] = 0;
+        if (a.out_ndc) a.out_ndc[q] = 0;
+        if (a.out_hops) a.out_hops[q] = 0;
+        if (a.out_hops_up) a.out_hops_up[q] = 0;
+        if (a.status) a.status[q] = 0;
+    }
+}
+
+// The distance of the start node cur, then the greedy descent from level `top` down to the level above `bottom`
+// (hnsw_distfunc_opt.cc:168-198): on each level, move to the first neighbour attaining the minimum while that is closer.
+// WIDE: graphs whose upper-level lists may be longer than one word per lane (maxM > 62) walk them in chunks.
+template <bool WIDE, class Dist>
+__device__ __forceinline__ void greedy_descent(const HnswDeviceGraph& g, int top, int bottom, int* nbr, float* nd, int lane,
+                                               int& cur, float& curdist, int& ndc, int& hops_up, Dist&& dist) {
+    if (lane == 0) nbr[0] = cur;
+    __builtin_amdgcn_wave_barrier();
+    dist(nbr, nd, 1);
+    curdist = nd[0];
+    ndc += 1;
+    for (int lvl = top; lvl > bottom; --lvl) {
+        bool changed = true;
+        while (changed) {
+            changed = false;
+            const int64_t off = g.up_off[cur] + (int64_t)(lvl - 1) * (g.maxM + 1);
+            if (WIDE && g.maxM > 62) {   // upper-level lists longer than one word per lane
+                hops_up++;
+                ndc += greedy_step_any(g.up_links + off, nbr, nd, lane, cur, curdist, changed, dist);
+                continue;
+            }
+            const int v = (lane <= g.maxM) ? g.up_links[off + lane] : 0;
+            const int cntl = __builtin_amdgcn_readfirstlane(v);
+            const int nb = __shfl(v, lane + 1, 64);
+            if (lane < cntl) nbr[lane] = nb;
+            __builtin_amdgcn_wave_barrier();
+            hops_up++;
+            if (cntl > 0) {
+                dist(nbr, nd, cntl);
+                ndc += cntl;
+                // sequential "if (d < curdist)" scan == first index attaining the minimum
+                u64 key = ~0ull;
+                if (lane < cntl) key = ((u64)f32_ord(nd[lane]) << 32) | (uint32_t)lane;
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) {
+                    const u64 other = __shfl_xor(key, o, 64);
+                    key = other < key ? other : key;
+                }
+                const float dmin = ord_f32((uint32_t)(key >> 32));
+                if (dmin < curdist) {
+                    curdist = dmin;
+                    cur = nbr[(uint32_t)key];
+                    changed = true;
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+    }
 }
 
 // ---- the filter of a query ----

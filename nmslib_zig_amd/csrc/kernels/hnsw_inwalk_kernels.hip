@@ -74,36 +74,13 @@ __global__ __launch_bounds__(64) void hnsw_inwalk_kernel(InwalkArgs<FILTER> a) {
     const int n_allow = fs.n_allow;
 
     // ---- stage the query (as the other search kernels: the same operations in the same order) ----
-    int qnorm = 0;
-    if constexpr (kU8) {
-        const uint8_t* src = reinterpret_cast<const uint8_t*>(a.queries) + (size_t)q * 128;
-        const int x0 = src[2 * lane], x1 = src[2 * lane + 1];
-        reinterpret_cast<uint8_t*>(qv)[2 * lane] = (uint8_t)x0;
-        reinterpret_cast<uint8_t*>(qv)[2 * lane + 1] = (uint8_t)x1;
-        qnorm = wave_sum_i(x0 * x0 + x1 * x1);
-    } else {
-        const float* src = reinterpret_cast<const float*>(a.queries) + (size_t)q * g.dim;
-        float ss = 0.f;
-        for (int d = lane; d < g.ldv; d += 64) {
-            const float v = d < g.dim ? src[d] : 0.f;
-            qv[d] = v;
-            ss = fmaf(v, v, ss);
-        }
-        if (g.normalize_query) {
-            ss = wave_sum(ss);
-            if (ss != 0.0f) {
-                const float inv = 1.0f / sqrtf(ss);
-                for (int d = lane; d < g.dim; d += 64) qv[d] *= inv;
-            }
-        }
-    }
+    const int qnorm = stage_query<SPACE>(g, a.queries, nullptr, q, qv, lane);
     __builtin_amdgcn_wave_barrier();
     const uint8_t* qb = reinterpret_cast<const uint8_t*>(qv);
 
-    auto visit = [&](uint32_t id) -> bool {
-        const uint32_t bit = 1u << (id & 31);
-        const uint32_t old = atomicOr(&bits[id >> 5], bit);
-        return (old & bit) == 0;
+    const VisitedSet<true> visit{bits, 0, 0};
+    auto dist = [&](const int* ids, float* out, int m) __attribute__((always_inline)) {
+        frontier_distances<SPACE>(g, qv, qb, qnorm, ids, out, m, lane);
     };
     // the two tests of hnsw_keep_topk_kernel (a row added after the filter was made stands at or beyond n_allow)
     auto eligible = [&](int p) -> bool {
@@ -128,7 +105,7 @@ __global__ __launch_bounds__(64) void hnsw_inwalk_kernel(InwalkArgs<FILTER> a) {
                 changed = false;
                 const int64_t off = g.up_off[cur] + (int64_t)(lvl - 1) * (g.maxM + 1);
                 hops_up++;
-                ndc += greedy_step_any<SPACE>(g, g.up_links + off, qv, qb, qnorm, nbr, nd, lane, cur, curdist, changed);
+                ndc += greedy_step_any(g.up_links + off, nbr, nd, lane, cur, curdist, changed, dist);
             }
         }
 

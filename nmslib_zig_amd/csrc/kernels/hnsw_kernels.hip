@@ -1,14 +1,11 @@
 // HNSW search on gfx950: one wavefront (64 lanes) per query.
 //
-// Restates Hnsw::SearchV1Merge (src/method/hnsw_distfunc_opt.cc:152-283) and its generic twin
-// baseSearchAlgorithmV1Merge (src/method/hnsw.cc:1174-1300) step for step:
-//   1. greedy descent through the upper levels (:173-198);
-//   2. level-0 best-first over a bounded sorted array (SortArrBI, include/sort_arr_bi.h) of
-//      max(ef, k) items: expand the first unused item, evaluate its unvisited neighbours,
-//      keep those with d < topKey (or while fewer than ef items), insert them in ascending
-//      order with SortArrBI::push_or_replace_non_empty_exp semantics (:159-199);
-//   3. emit the first k items (:276-281) through KNNQueue ordering (knnqueue.h:55-64).
-// What changes is the execution shape: the <=32 neighbours of one expansion are a frontier
+// hnsw_search_kernel runs the SearchV1Merge body of hnsw_walk_dev.hpp (the restatement of the reference's search, shared
+// as source with the 8-bit kernel of hnsw_q8_kernels.hip) over the f32 / u8 rows or their fp16 copy; SearchOld and the
+// HBM-array SearchV1Merge below are kernels of their own.  What those two begin with -- staging the query, the visited
+// set, the empty-index result, the greedy descent -- is hnsw_common_dev.hpp's; the walk keeps those statements written out
+// where the helper changed its code (hnsw_walk_dev.hpp says where).
+// What changes against the reference is the execution shape: the <=32 neighbours of one expansion are a frontier
 // batch.  Their ids are filtered through a visited set kept in LDS (open-addressing hash,
 // exact) and the unvisited rows are gathered from HBM together - 8 lanes per row, 16 bytes
 // per lane per step, up to 32 rows in flight per wave - with the distance fused into the
@@ -19,6 +16,7 @@
 
 #include "hnsw_args.hpp"
 #include "hnsw_common_dev.hpp"
+#include "hnsw_walk_dev.hpp"
 #include "kernels.hpp"
 
 namespace gfxknn {
@@ -29,572 +27,73 @@ __device__ unsigned long long g_hnsw_prof[8];
 
 constexpr int SA_EMAX_MAX = 16;  // sorted array up to 64*16 = 1024 items
 
-// EMAX = sorted-array items per lane (cap <= 64*EMAX): 2 for ef <= 128, 4 for <= 256, 16 otherwise.
-// WIDE: level-0 lists of more than 62 neighbours (maxM0 up to 126, i.e. M >= 32): second adjacency chunk,
-// 128-entry neighbour staging, two insertion rounds.  Kept out of the common instantiation.
-// (the chunked list walk of SearchOld and the HBM-array kernel: collect_unvisited_any, greedy_step_any in hnsw_common_dev.hpp)
-template <int SPACE, bool BITSET, int SA_EMAX, bool WIDE, class ROW>
-__device__ __forceinline__ void hnsw_search_body(const HnswArgs& a, char* smem, const int q, uint32_t* const bits) {
-    const HnswDeviceGraph& g = a.g;
-    const int lane = threadIdx.x;
-    constexpr bool kU8 = DistTraits<SPACE>::kU8;
-
-    // ---- LDS carve-up (all offsets multiples of 16 bytes) ----
-    float* keys = reinterpret_cast<float*>(smem);                  // [capa]
-    int* idu = reinterpret_cast<int*>(keys + a.capa);              // [capa]  id | used<<31
-    const int qfloats = kU8 ? 32 : g.ldv;
-    float* qv = reinterpret_cast<float*>(idu + a.capa);            // [ldv] (u8: 128 bytes)
-    const int nbcap = WIDE ? a.nbcap : 64;                         // neighbours of one expansion (wide lists: a multiple of 64 >= maxM0, maxM)
-    int* nbr = reinterpret_cast<int*>(qv + qfloats);               // [nbcap]
-    float* nd = reinterpret_cast<float*>(nbr + nbcap);             // [nbcap]
-    float* sk = nd + nbcap;                                        // [64] accepted keys, sorted
-    int* si = reinterpret_cast<int*>(sk + 64);                     // [64] accepted ids
-    uint32_t* table = reinterpret_cast<uint32_t*>(si + 64);        // [table_size]
-
-    // ---- stage the query ----
-    int qnorm = 0;
-    if constexpr (kU8) {
-        const uint8_t* src = a.query_rows ? reinterpret_cast<const uint8_t*>(g.rows) + (size_t)a.query_rows[q] * 128
-                                          : reinterpret_cast<const uint8_t*>(a.queries) + (size_t)q * 128;
-        const int x0 = src[2 * lane], x1 = src[2 * lane + 1];
-        reinterpret_cast<uint8_t*>(qv)[2 * lane] = (uint8_t)x0;
-        reinterpret_cast<uint8_t*>(qv)[2 * lane + 1] = (uint8_t)x1;
-        qnorm = wave_sum_i(x0 * x0 + x1 * x1);
-    } else {
-        const float* src = a.query_rows ? reinterpret_cast<const float*>(g.rows) + (size_t)a.query_rows[q] * g.ldv
-                                        : reinterpret_cast<const float*>(a.queries) + (size_t)q * g.dim;
-        float ss = 0.f;
-        for (int d = lane; d < g.ldv; d += 64) {
-            const float v = d < g.dim ? src[d] : 0.f;
-            qv[d] = v;
-            ss = fmaf(v, v, ss);
-        }
-        if (g.normalize_query && !a.query_rows) {  // hnsw_distfunc_opt.cc:160-162 (stored rows are already normalised)
-            ss = wave_sum(ss);
-            if (ss != 0.0f) {
-                const float inv = 1.0f / sqrtf(ss);
-                for (int d = lane; d < g.dim; d += 64) qv[d] *= inv;
-            }
-        }
-    }
-    if constexpr (!BITSET) {
-        for (int i = lane; i < a.table_size; i += 64) table[i] = HT_EMPTY;
-    }
-    __builtin_amdgcn_wave_barrier();
-    const uint8_t* qb = reinterpret_cast<const uint8_t*>(qv);
-
-    int ndc = 0, hops = 0, hops_up = 0, nvisited = 0;
-    bool overflow = false;
-
-    // visited test-and-set: true when id was NOT visited before (exact)
-    auto visit = [&](uint32_t id) -> bool {
-        if constexpr (BITSET) {
-            const uint32_t bit = 1u << (id & 31);
-            const uint32_t old = atomicOr(&bits[id >> 5], bit);
-            return (old & bit) == 0;
+// The walk over the rows the graph was built on (ROW = float; u8 rows for l2sqr_sift) or over their fp16 copy (ROW =
+// half_t), as hnsw_walk_body's policy: the query as f32 (u8) in LDS and the gathers of hnsw_common_dev.hpp.  It has
+// everything: construction mode, the phase clocks, and the padded result in KNNQueue order -- except that the fp16 walk
+// hands its array to the f32 re-rank as it stands (kRaw).
+template <int SPACE, class ROW>
+struct DenseWalk {
+    static constexpr bool kBuild = true, kProf = true, kPad = true;
+    static constexpr bool kRaw = std::is_same<ROW, half_t>::value;
+    using Loads = FrontierLoads<SPACE, ROW>;
+    const float* qv;
+    const uint8_t* qb;
+    int qnorm;
+    static __device__ __forceinline__ int slot_floats(const HnswDeviceGraph& g) { return DistTraits<SPACE>::kU8 ? 32 : g.ldv; }
+    // (stage_query of hnsw_common_dev.hpp, written out: through that helper the compiler arranged the staging and the
+    //  tests around it differently in every instantiation; with these statements the walk's code is the one it had
+    //  before the body was shared, but for register names)
+    __device__ __forceinline__ void stage(const HnswArgs& a, int q, float* slot, int lane) {
+        const HnswDeviceGraph& g = a.g;
+        int qn = 0;
+        if constexpr (DistTraits<SPACE>::kU8) {
+            const uint8_t* src = a.query_rows ? reinterpret_cast<const uint8_t*>(g.rows) + (size_t)a.query_rows[q] * 128
+                                              : reinterpret_cast<const uint8_t*>(a.queries) + (size_t)q * 128;
+            const int x0 = src[2 * lane], x1 = src[2 * lane + 1];
+            reinterpret_cast<uint8_t*>(slot)[2 * lane] = (uint8_t)x0;
+            reinterpret_cast<uint8_t*>(slot)[2 * lane + 1] = (uint8_t)x1;
+            qn = wave_sum_i(x0 * x0 + x1 * x1);
         } else {
-            uint32_t hsh = (id * 2654435761u) >> a.table_shift;
-            const uint32_t mask = (uint32_t)a.table_size - 1u;
-            for (int probe = 0; probe < a.table_size; ++probe) {
-                const uint32_t old = atomicCAS(&table[hsh], HT_EMPTY, id);
-                if (old == HT_EMPTY) return true;
-                if (old == id) return false;
-                hsh = (hsh + 1) & mask;
+            const float* src = a.query_rows ? reinterpret_cast<const float*>(g.rows) + (size_t)a.query_rows[q] * g.ldv
+                                            : reinterpret_cast<const float*>(a.queries) + (size_t)q * g.dim;
+            float ss = 0.f;
+            for (int d = lane; d < g.ldv; d += 64) {
+                const float v = d < g.dim ? src[d] : 0.f;
+                slot[d] = v;
+                ss = fmaf(v, v, ss);
             }
-            return false;
+            if (g.normalize_query && !a.query_rows) {  // hnsw_distfunc_opt.cc:160-162 (stored rows are already normalised)
+                ss = wave_sum(ss);
+                if (ss != 0.0f) {
+                    const float inv = 1.0f / sqrtf(ss);
+                    for (int d = lane; d < g.dim; d += 64) slot[d] *= inv;
+                }
+            }
         }
-    };
-
-    if (g.n == 0) {
-        for (int i = lane; i < a.k; i += 64) {
-            a.out_ids[(size_t)q * a.k + i] = -1;
-            a.out_dists[(size_t)q * a.k + i] = INFINITY;
-        }
-        if (lane == 0) {
-            a.out_cnt[q] = 0;
-            if (a.out_ndc) a.out_ndc[q] = 0;
-            if (a.out_hops) a.out_hops[q] = 0;
-            if (a.out_hops_up) a.out_hops_up[q] = 0;
-            if (a.status) a.status[q] = 0;
-        }
-        return;
+        qnorm = qn;
+        qv = slot;
+        qb = reinterpret_cast<const uint8_t*>(slot);
     }
-
-    // ---- entry point + greedy descent (hnsw_distfunc_opt.cc:168-198) ----
-    const int start = a.start_nodes ? a.start_nodes[q] : -1;
-    int cur = start >= 0 ? start : g.enterpoint;
-    if (lane == 0) nbr[0] = cur;
-    __builtin_amdgcn_wave_barrier();
-    frontier_distances<SPACE, ROW>(g, qv, qb, qnorm, nbr, nd, 1, lane);
-    float curdist = nd[0];
-    ndc += 1;
-    for (int lvl = (start >= 0 ? 0 : g.maxlevel); lvl > a.level; --lvl) {
-        bool changed = true;
-        while (changed) {
-            changed = false;
-            const int64_t off = g.up_off[cur] + (int64_t)(lvl - 1) * (g.maxM + 1);
-            if (WIDE && g.maxM > 62) {   // upper-level lists longer than one word per lane
-                hops_up++;
-                ndc += greedy_step_any<SPACE, ROW>(g, g.up_links + off, qv, qb, qnorm, nbr, nd, lane, cur, curdist, changed);
-                continue;
-            }
-            const int v = (lane <= g.maxM) ? g.up_links[off + lane] : 0;
-            const int cntl = __builtin_amdgcn_readfirstlane(v);
-            const int nb = __shfl(v, lane + 1, 64);
-            if (lane < cntl) nbr[lane] = nb;
-            __builtin_amdgcn_wave_barrier();
-            hops_up++;
-            if (cntl > 0) {
-                frontier_distances<SPACE, ROW>(g, qv, qb, qnorm, nbr, nd, cntl, lane);
-                ndc += cntl;
-                // sequential "if (d < curdist)" scan == first index attaining the minimum
-                u64 key = ~0ull;
-                if (lane < cntl) key = ((u64)f32_ord(nd[lane]) << 32) | (uint32_t)lane;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const u64 other = __shfl_xor(key, o, 64);
-                    key = other < key ? other : key;
-                }
-                const float dmin = ord_f32((uint32_t)(key >> 32));
-                if (dmin < curdist) {
-                    curdist = dmin;
-                    cur = nbr[(uint32_t)key];
-                    changed = true;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
+    __device__ __forceinline__ void distances(const HnswDeviceGraph& g, const int* nbr, float* nd, int m, int lane) const {
+        frontier_distances<SPACE, ROW>(g, qv, qb, qnorm, nbr, nd, m, lane);
     }
-
-    // ---- level 0 (hnsw_distfunc_opt.cc:200-274) ----
-    int n = 1;
-    if (lane == 0) {
-        keys[0] = curdist;
-        idu[0] = cur;
+    __device__ __forceinline__ void issue(Loads& L, const HnswDeviceGraph& g, const int* nbr, int m, int lane) const {
+        frontier_issue<SPACE, ROW>(L, g, nbr, m, lane);
     }
-    {
-        bool fresh = false;
-        if (lane == 0) fresh = visit((uint32_t)cur);
-        (void)fresh;
-        nvisited = 1;
+    __device__ __forceinline__ void finish(Loads& L, const HnswDeviceGraph& g, const int* nbr, float* nd, int m, int lane) const {
+        frontier_finish<SPACE, ROW>(L, g, qv, qb, qnorm, nbr, nd, m, lane);
     }
-    __builtin_amdgcn_wave_barrier();
-
-    // cur: every item before it is used (the reference's currElem).  pre_*: adjacency of the item
-    // that will most likely be expanded next, requested one expansion early (its latency hides
-    // behind this expansion's gather); a wrong guess only costs the normal load.
-    // adjacency word `lane` of node c on the level being searched ([count][ids...])
-    auto load_adj = [&](int c) -> int {
-        if (a.level == 0) return (lane <= g.maxM0) ? g.links0[(size_t)c * (g.maxM0 + 1) + lane] : 0;
-        return (lane <= g.maxM) ? g.up_links[g.up_off[c] + (int64_t)(a.level - 1) * (g.maxM + 1) + lane] : 0;
-    };
-    int cursor = 0;
-    int pre_node = -1, pre_v = 0, pre2_node = -1, pre2_v = 0;
-    float pre_key = INFINITY;
-    bool pre_ok = false;            // pre_node is the first unused item of the array, at a position below ef
-    // Software pipeline across expansions: when the NEXT node to expand is already certain before the accepted items of
-    // this expansion are merged in (it is the array's next unused item and every accepted key is larger), its visited
-    // filter runs and its row gather is issued first, and the merge executes while those rows are in flight.
-    int pipe_node = -1, pipe_m = 0;
-    FrontierLoads<SPACE, ROW> fl;
-    long long pc[6] = {0, 0, 0, 0, 0, 0};
-    long long pt = a.prof ? (long long)__builtin_readcyclecounter() : 0;
-    auto lap = [&](int ph) __attribute__((always_inline)) {
-        if (a.prof) {
-            const long long now = (long long)__builtin_readcyclecounter();
-            pc[ph] += now - pt;
-            pt = now;
-        }
-    };
-    lap(0);
-    while (true) {
-        const int lim = n < a.ef ? n : a.ef;
-        // first unused item at or after cur
-        int fu = n;
-        for (int base = cursor; base < n && fu == n; base += 64) {
-            const int i = base + lane;
-            const u64 mk = __ballot(i < n && idu[i] >= 0);
-            if (mk) fu = base + (__ffsll((long long)mk) - 1);
-        }
-        if (fu >= lim) break;
-        const int c = idu[fu] & 0x7FFFFFFF;
-        if (lane == 0) idu[fu] |= (int)0x80000000;
-        cursor = fu + 1;
-        hops++;
-        const float topKey = keys[n - 1];
-        const int size0 = n;
-
-        int m;
-        if (c == pipe_node) {
-            // visited filter done and rows requested during the previous expansion; the guess for the expansion after
-            // this one was made there too
-            m = pipe_m;
-            pipe_node = -1;
-            lap(1);
-            lap(2);
-        } else {
-            // adjacency of c: [count][ids...]
-            int v;
-            if (c == pre_node) v = pre_v;
-            else if (c == pre2_node) v = pre2_v;
-            else v = load_adj(c);
-            // Adjacency of the NEXT expansion, requested early so that its latency (a random HBM read under
-            // load: ~2 us) hides behind this expansion's gather and inserts.  Two guesses: (A) now, the next
-            // unused item of the array -- right unless this expansion finds something closer; (B) after the
-            // distances, the best newly accepted item when it is closer than (A).
-            const int cntn = __builtin_amdgcn_readfirstlane(v);
-            lap(1);
-            const int nb = __shfl(v, lane + 1, 64);   // neighbours 0..62 (list words 1..63)
-            bool isn = false;
-            if (lane < cntn && (!WIDE || lane < 63)) isn = visit((uint32_t)nb);
-            const u64 nmask = __ballot(isn);
-            m = __popcll(nmask);
-            if (isn) nbr[__popcll(nmask & ((1ull << lane) - 1ull))] = nb;
-            if (WIDE) {
-                // wide level-0 lists (maxM0 > 62, i.e. M >= 32): neighbours 63.. are list words 64.., read on demand in chunks
-                // of 64 (round 3: any number of chunks the frontier arrays hold -- a.nbcap)
-                // (construction mode above level 0, maxM > 62: the same walk over the node's list on that level)
-                const int32_t* Lc = a.level == 0 ? g.links0 + (size_t)c * (g.maxM0 + 1)
-                                                 : g.up_links + g.up_off[c] + (int64_t)(a.level - 1) * (g.maxM + 1);
-                const int Lmax = a.level == 0 ? g.maxM0 : g.maxM;
-                for (int c0 = 63; c0 < cntn; c0 += 64) {
-                    int nb2 = 0;
-                    if (c0 + 1 + lane <= Lmax) nb2 = Lc[c0 + 1 + lane];
-                    bool isn2 = false;
-                    if (c0 + lane < cntn) isn2 = visit((uint32_t)nb2);
-                    const u64 nmask2 = __ballot(isn2);
-                    if (isn2) nbr[m + __popcll(nmask2 & ((1ull << lane) - 1ull))] = nb2;
-                    m += __popcll(nmask2);
-                }
-            }
-            nvisited += m;
-            if (!BITSET && nvisited > (a.table_size - (a.table_size >> 3))) {
-                overflow = true;  // visited table nearly full: give up, the bitset variant re-runs the query
-                break;
-            }
-            __builtin_amdgcn_wave_barrier();
-            lap(2);
-            // (issued only now: v had to be waited for first, and vmcnt retires in order -- a younger
-            //  outstanding load in front of that wait would put its whole latency into it)
-            {
-                int fu2 = n;
-                for (int base = cursor; base < n && fu2 == n; base += 64) {
-                    const int i = base + lane;
-                    const u64 mk = __ballot(i < n && idu[i] >= 0);
-                    if (mk) fu2 = base + (__ffsll((long long)mk) - 1);
-                }
-                if (fu2 < lim) {
-                    pre_node = idu[fu2] & 0x7FFFFFFF;
-                    pre_key = keys[fu2];
-                    pre_v = load_adj(pre_node);
-                    pre_ok = true;
-                } else {
-                    pre_node = -1;
-                    pre_key = INFINITY;
-                    pre_ok = false;
-                }
-                pre2_node = -1;
-            }
-            if (m > 0) frontier_issue<SPACE, ROW>(fl, g, nbr, m, lane);
-        }
-        if (m == 0) continue;
-        ndc += m;
-        frontier_finish<SPACE, ROW>(fl, g, qv, qb, qnorm, nbr, nd, m, lane);
-        lap(3);
-
-        // (more than 64 new rows only with wide lists: rounds of 64; without equal keys the final array does
-        //  not depend on the order in which accepted items are merged in)
-        for (int r0 = 0; r0 < (WIDE ? m : 1); r0 += 64) {  // one trip unless the lists are wide
-            // accept d < topKey || size < ef   (:240)
-            float dj = INFINITY;
-            int idj = -1;
-            bool acc = false;
-            if (r0 + lane < m) {
-                dj = nd[r0 + lane];
-                idj = nbr[r0 + lane];
-                acc = (dj < topKey) || (size0 < a.ef);
-            }
-            const u64 amask = __ballot(acc);
-            const int m2 = __popcll(amask);
-            if (m2 == 0) continue;
-            // ascending order of the accepted items (std::sort, :251); ties keep list order
-            int rank = 0;
-            for (u64 mm = amask; mm;) {
-                const int j = __ffsll((long long)mm) - 1;
-                mm &= mm - 1;
-                // (j comes from the ballot mask, so it is wave-uniform: v_readlane, not an LDS-routed shuffle)
-                const float dother = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(dj), j));
-                rank += (dother < dj || (dother == dj && j < lane)) ? 1 : 0;
-            }
-            __builtin_amdgcn_wave_barrier();
-            if (acc) {
-                sk[rank] = dj;
-                si[rank] = idj;
-            }
-            __builtin_amdgcn_wave_barrier();
-
-            if (sk[0] <= pre_key) {  // guess (B)
-                pre2_node = si[0];
-                pre2_v = load_adj(pre2_node);
-            } else if (!WIDE && pre_ok && !a.no_pipe) {
-                // Every accepted key is larger than the key of the array's next unused item: that item (pre_node,
-                // adjacency already here) IS the next expansion, whatever the merge below does to the positions
-                // behind it.  Run its visited filter now and request its rows; the merge overlaps the gather.
-                const int cntp = __builtin_amdgcn_readfirstlane(pre_v);
-                const int nbp = __shfl(pre_v, lane + 1, 64);
-                bool isp = false;
-                if (lane < cntp) isp = visit((uint32_t)nbp);
-                const u64 pmask = __ballot(isp);
-                const int mp = __popcll(pmask);
-                __builtin_amdgcn_wave_barrier();  // (nbr/nd of this expansion were consumed into registers above)
-                if (isp) nbr[__popcll(pmask & ((1ull << lane) - 1ull))] = nbp;
-                nvisited += mp;
-                if (!BITSET && nvisited > (a.table_size - (a.table_size >> 3))) {
-                    overflow = true;
-                    break;
-                }
-                __builtin_amdgcn_wave_barrier();
-                pipe_node = pre_node;
-                pipe_m = mp;
-                // guess for the expansion after that: the second unused item of the array, or the best accepted
-                // key if that is closer (then its position is only known after the merge: no pipelining on it)
-                int second = n;
-                {
-                    int seen = 0;
-                    for (int base = cursor; base < n && second == n; base += 64) {
-                        const int i = base + lane;
-                        u64 mk = __ballot(i < n && idu[i] >= 0);
-                        if (seen == 0 && mk) {
-                            mk &= mk - 1;
-                            seen = 1;
-                        }
-                        if (mk) second = base + (__ffsll((long long)mk) - 1);
-                    }
-                }
-                const float k2 = second < n ? keys[second] : INFINITY;
-                if (second < n && second < a.ef && k2 < sk[0]) {
-                    pre_node = idu[second] & 0x7FFFFFFF;
-                    pre_key = k2;
-                    pre_ok = true;
-                    pre_v = load_adj(pre_node);
-                } else if (sk[0] < k2) {
-                    pre_node = si[0];
-                    pre_key = sk[0];
-                    pre_ok = false;
-                    pre_v = load_adj(pre_node);
-                } else {
-                    pre_node = -1;
-                    pre_key = INFINITY;
-                    pre_ok = false;
-                }
-                pre2_node = -1;
-                if (mp > 0) frontier_issue<SPACE, ROW>(fl, g, nbr, mp, lane);
-            }
-            lap(4);
-            // All accepted items at once when no two keys involved are equal (the normal case): the result of
-            // the reference's sequential push_or_replace_non_empty_exp calls is then the merge of the two sorted
-            // sequences cut at the capacity, so every old item moves up by the number of new keys below it and
-            // new item t lands at (#old keys below it) + t; the scan cursor rewinds to the first new position
-            // (hnsw_distfunc_opt.cc:261-266).  Equal keys (rare) take the exact sequential replay below.
-            bool tie = false;
-            float kreg[SA_EMAX];
-            int cntv[SA_EMAX];
-    #pragma unroll
-            for (int e = 0; e < SA_EMAX; ++e) {
-                const int i = lane + 64 * e;
-                kreg[e] = (e * 64 < n && i < n) ? keys[i] : INFINITY;
-                cntv[e] = 0;
-            }
-            const float mykey = lane < m2 ? sk[lane] : INFINITY;
-            const int myid = lane < m2 ? si[lane] : -1;
-            int myless = 0;
-            for (int t = 0; t < m2; ++t) {
-                const float skt = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(mykey), t));
-                int less = 0;
-    #pragma unroll
-                for (int e = 0; e < SA_EMAX; ++e) {
-                    if (e * 64 < n) {
-                        less += __popcll(__ballot(kreg[e] < skt));
-                        cntv[e] += (skt < kreg[e]) ? 1 : 0;
-                        tie |= (skt == kreg[e]);
-                    }
-                }
-                if (lane == t) myless = less;
-            }
-            // (the shuffle runs in ALL lanes: under the short-circuit `&&` it sat in a divergent branch, lane m2-2 read
-            //  its inactive neighbour as 0 and a tie between the two largest accepted keys went unnoticed -- found in
-            //  round 3 by tests/test_gpu_hnsw_mw.py against the oracle)
-            const float next_key = __shfl_down(mykey, 1, 64);
-            tie |= (lane + 1 < m2) & (mykey == next_key);
-            if (!__any(tie)) {
-                int ireg[SA_EMAX];
-    #pragma unroll
-                for (int e = 0; e < SA_EMAX; ++e) {
-                    const int i = lane + 64 * e;
-                    ireg[e] = (e * 64 < n && i < n) ? idu[i] : 0;
-                }
-                const int newn = n + m2 < a.cap ? n + m2 : a.cap;
-                __builtin_amdgcn_wave_barrier();
-    #pragma unroll
-                for (int e = 0; e < SA_EMAX; ++e) {
-                    const int i = lane + 64 * e;
-                    if (e * 64 < n && i < n && cntv[e] > 0) {
-                        const int np = i + cntv[e];
-                        if (np < newn) {
-                            keys[np] = kreg[e];
-                            idu[np] = ireg[e];
-                        }
-                    }
-                }
-                if (lane < m2) {
-                    const int np = myless + lane;
-                    if (np < newn) {
-                        keys[np] = mykey;
-                        idu[np] = myid;
-                    }
-                }
-                const int first = __builtin_amdgcn_readlane(myless, 0);
-                if (first < cursor) cursor = first;
-                n = newn;
-                __builtin_amdgcn_wave_barrier();
-            } else {
-                // SortArrBI::push_or_replace_non_empty_exp for each, in order (sort_arr_bi.h:159-199)
-                for (int t = 0; t < m2; ++t) {
-                    const float key = sk[t];
-                    const int id = si[t];
-                    const float lastk = keys[n - 1];
-                    if (lastk <= key) {
-                        if (n < a.cap) {
-                            if (lane == 0) {
-                                keys[n] = key;
-                                idu[n] = id;
-                            }
-                            n++;
-                        }
-                    } else {
-                        // insertion index.  Without a key equal to the new one in the array, the reference's
-                        // exponential probe + lower_bound (sort_arr_bi.h:172-186) is simply the number of
-                        // smaller keys: one parallel count.  With equal keys present (rare) the probe is
-                        // replayed so the item lands inside the run exactly where the reference puts it.
-                        int less = 0, leq = 0;
-        #pragma unroll
-                        for (int e = 0; e < SA_EMAX; ++e) {
-                            if (e * 64 < n) {
-                                const int i = lane + 64 * e;
-                                const float kv = i < n ? keys[i] : INFINITY;
-                                less += __popcll(__ballot(kv < key));
-                                leq += __popcll(__ballot(kv <= key));
-                            }
-                        }
-                        int p = less;
-                        if (leq != less) {
-                            int curr = n - 1, prev = curr, dstep = 1;
-                            while (curr > 0 && keys[curr] > key) {
-                                prev = curr;
-                                curr -= dstep;
-                                dstep *= 2;
-                                if (dstep > curr) dstep = curr;
-                            }
-                            p = curr;
-                            for (int i = curr; i < prev && keys[i] < key; ++i) p = i + 1;
-                        }
-                        const int newn = n < a.cap ? n + 1 : a.cap;
-                        float rk[SA_EMAX];
-                        int ri[SA_EMAX];
-        #pragma unroll
-                        for (int e = 0; e < SA_EMAX; ++e) {
-                            if (e * 64 < newn) {
-                                const int i = lane + 64 * e;
-                                if (i > p && i < newn) {
-                                    rk[e] = keys[i - 1];
-                                    ri[e] = idu[i - 1];
-                                }
-                            }
-                        }
-                        __builtin_amdgcn_wave_barrier();
-        #pragma unroll
-                        for (int e = 0; e < SA_EMAX; ++e) {
-                            if (e * 64 < newn) {
-                                const int i = lane + 64 * e;
-                                if (i > p && i < newn) {
-                                    keys[i] = rk[e];
-                                    idu[i] = ri[e];
-                                }
-                            }
-                        }
-                        if (lane == 0) {
-                            keys[p] = key;
-                            idu[p] = id;
-                        }
-                        n = newn;
-                        if (p < cursor) cursor = p;  // :261-266
-                    }
-                    __builtin_amdgcn_wave_barrier();
-                }
-            }
-        }
-        if (overflow) break;  // (set inside the round loop by the pipelined visited filter)
-        lap(5);
-    }
-    if (a.prof && lane == 0) {
+    static __device__ __forceinline__ void prof_flush(const long long pc[6]) {
         for (int i = 0; i < 6; ++i) atomicAdd(&g_hnsw_prof[i], (unsigned long long)pc[i]);
         atomicAdd(&g_hnsw_prof[6], 1ull);
     }
-
-    // ---- results: first k items, ties ordered by internal id (KNNQueue holds
-    //      pair<dist, Object*> and data_rearranged_ addresses grow with the id) ----
-    //      (the fp16 walk hands its array to the f32 re-rank as it stands: array order, internal positions)
-    constexpr bool kRaw = std::is_same<ROW, half_t>::value;
-    const int kk = overflow ? 0 : (a.k < n ? a.k : n);
-    for (int i = lane; i < a.k; i += 64) {
-        if (i < kk) {
-            const float ki = keys[i];
-            const int id = idu[i] & 0x7FFFFFFF;
-            int r = i;
-            if constexpr (!kRaw) {
-                for (int j = i - 1; j >= 0 && keys[j] == ki; --j) r -= ((idu[j] & 0x7FFFFFFF) > id) ? 1 : 0;
-                for (int j = i + 1; j < kk && keys[j] == ki; ++j) r += ((idu[j] & 0x7FFFFFFF) < id) ? 1 : 0;
-            }
-            a.out_ids[(size_t)q * a.k + r] = (g.ext_ids && !kRaw) ? g.ext_ids[id] : id;
-            a.out_dists[(size_t)q * a.k + r] = ki;
-        } else {
-            a.out_ids[(size_t)q * a.k + i] = -1;
-            a.out_dists[(size_t)q * a.k + i] = INFINITY;
-        }
-    }
-    if (lane == 0) {
-        a.out_cnt[q] = kk;
-        if (a.out_ndc) a.out_ndc[q] = ndc;
-        if (a.out_hops) a.out_hops[q] = hops;
-        if (a.out_hops_up) a.out_hops_up[q] = hops_up;
-        if (a.status) a.status[q] = overflow ? 1 : 0;
-        if (!BITSET && overflow && a.fix_list) a.fix_list[atomicAdd(a.fix_count, 1)] = q;
-    }
-}
+};
 
 template <int SPACE, bool BITSET, int SA_EMAX, bool WIDE, class ROW>
 __global__ __launch_bounds__(64) void hnsw_search_kernel(HnswArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if constexpr (BITSET) {
-        if (a.fix_mode) {
-            // queries whose LDS visited table filled up in the previous launch, re-run on HBM bitsets: workgroup b
-            // owns bitset slot b and clears it before every query it takes from the list
-            const int cnt = *a.fix_count;
-            uint32_t* bits = a.bitset + (size_t)blockIdx.x * a.bitset_words;
-            for (int slot = blockIdx.x; slot < cnt; slot += gridDim.x) {
-                for (size_t i = threadIdx.x; i < a.bitset_words; i += 64) bits[i] = 0u;
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-                hnsw_search_body<SPACE, true, SA_EMAX, WIDE, ROW>(a, smem, a.fix_list[slot], bits);
-                __builtin_amdgcn_wave_barrier();
-            }
-            return;
-        }
-        hnsw_search_body<SPACE, true, SA_EMAX, WIDE, ROW>(a, smem, blockIdx.x, a.bitset + (size_t)blockIdx.x * a.bitset_words);
-    } else {
-        hnsw_search_body<SPACE, false, SA_EMAX, WIDE, ROW>(a, smem, blockIdx.x, nullptr);
-    }
+    using P = DenseWalk<SPACE, ROW>;
+    HNSW_WALK_QUERIES(P, BITSET, SA_EMAX, WIDE, a, smem);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -660,113 +159,26 @@ __global__ __launch_bounds__(64) void hnsw_search_old_kernel(HnswArgs a, OldWs w
         else heap_g[i - w.heap_lds] = v;
     };
 
-    // ---- stage the query (as the V1Merge kernel) ----
-    int qnorm = 0;
-    if constexpr (kU8) {
-        const uint8_t* src = reinterpret_cast<const uint8_t*>(a.queries) + (size_t)q * 128;
-        const int x0 = src[2 * lane], x1 = src[2 * lane + 1];
-        reinterpret_cast<uint8_t*>(qv)[2 * lane] = (uint8_t)x0;
-        reinterpret_cast<uint8_t*>(qv)[2 * lane + 1] = (uint8_t)x1;
-        qnorm = wave_sum_i(x0 * x0 + x1 * x1);
-    } else {
-        const float* src = reinterpret_cast<const float*>(a.queries) + (size_t)q * g.dim;
-        float ss = 0.f;
-        for (int d = lane; d < g.ldv; d += 64) {
-            const float v = d < g.dim ? src[d] : 0.f;
-            qv[d] = v;
-            ss = fmaf(v, v, ss);
-        }
-        if (g.normalize_query) {  // hnsw_distfunc_opt.cc:55-57
-            ss = wave_sum(ss);
-            if (ss != 0.0f) {
-                const float inv = 1.0f / sqrtf(ss);
-                for (int d = lane; d < g.dim; d += 64) qv[d] *= inv;
-            }
-        }
-    }
-    if constexpr (!BITSET) {
-        for (int i = lane; i < a.table_size; i += 64) table[i] = HT_EMPTY;
-    }
+    // ---- stage the query (as the V1Merge kernel; hnsw_distfunc_opt.cc:55-57) ----
+    const int qnorm = stage_query<SPACE>(g, a.queries, nullptr, q, qv, lane);
+    const VisitedSet<BITSET> visit{BITSET ? bits : table, a.table_size, a.table_shift};
+    visit.clear_table(lane);
     __builtin_amdgcn_wave_barrier();
     const uint8_t* qb = reinterpret_cast<const uint8_t*>(qv);
-
-    auto visit = [&](uint32_t id) -> bool {
-        if constexpr (BITSET) {
-            const uint32_t bit = 1u << (id & 31);
-            const uint32_t old = atomicOr(&bits[id >> 5], bit);
-            return (old & bit) == 0;
-        } else {
-            uint32_t hsh = (id * 2654435761u) >> a.table_shift;
-            const uint32_t mask = (uint32_t)a.table_size - 1u;
-            for (int probe = 0; probe < a.table_size; ++probe) {
-                const uint32_t old = atomicCAS(&table[hsh], HT_EMPTY, id);
-                if (old == HT_EMPTY) return true;
-                if (old == id) return false;
-                hsh = (hsh + 1) & mask;
-            }
-            return false;
-        }
+    auto dist = [&](const int* ids, float* out, int m) __attribute__((always_inline)) {
+        frontier_distances<SPACE>(g, qv, qb, qnorm, ids, out, m, lane);
     };
 
     int ndc = 0, hops = 0, hops_up = 0, nvisited = 0, status = 0;
     if (g.n == 0) {
-        for (int i = lane; i < a.k; i += 64) {
-            a.out_ids[(size_t)q * a.k + i] = -1;
-            a.out_dists[(size_t)q * a.k + i] = INFINITY;
-        }
-        if (lane == 0) {
-            a.out_cnt[q] = 0;
-            if (a.out_ndc) a.out_ndc[q] = 0;
-            if (a.out_hops) a.out_hops[q] = 0;
-            if (a.out_hops_up) a.out_hops_up[q] = 0;
-            if (a.status) a.status[q] = 0;
-        }
+        hnsw_empty_result<true>(a, q, lane);
         return;
     }
 
     // ---- entry point + greedy descent (:64-92) ----
     int cur = g.enterpoint;
-    if (lane == 0) nbr[0] = cur;
-    __builtin_amdgcn_wave_barrier();
-    frontier_distances<SPACE>(g, qv, qb, qnorm, nbr, nd, 1, lane);
-    float curdist = nd[0];
-    ndc += 1;
-    for (int lvl = g.maxlevel; lvl > 0; --lvl) {
-        bool changed = true;
-        while (changed) {
-            changed = false;
-            const int64_t off = g.up_off[cur] + (int64_t)(lvl - 1) * (g.maxM + 1);
-            if (WIDE && g.maxM > 62) {   // upper-level lists of any length
-                hops_up++;
-                ndc += greedy_step_any<SPACE>(g, g.up_links + off, qv, qb, qnorm, nbr, nd, lane, cur, curdist, changed);
-                continue;
-            }
-            const int v = (lane <= g.maxM) ? g.up_links[off + lane] : 0;
-            const int cntl = __builtin_amdgcn_readfirstlane(v);
-            const int nb = __shfl(v, lane + 1, 64);
-            if (lane < cntl) nbr[lane] = nb;
-            __builtin_amdgcn_wave_barrier();
-            hops_up++;
-            if (cntl > 0) {
-                frontier_distances<SPACE>(g, qv, qb, qnorm, nbr, nd, cntl, lane);
-                ndc += cntl;
-                u64 key = ~0ull;
-                if (lane < cntl) key = ((u64)f32_ord(nd[lane]) << 32) | (uint32_t)lane;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const u64 other = __shfl_xor(key, o, 64);
-                    key = other < key ? other : key;
-                }
-                const float dmin = ord_f32((uint32_t)(key >> 32));
-                if (dmin < curdist) {
-                    curdist = dmin;
-                    cur = nbr[(uint32_t)key];
-                    changed = true;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
+    float curdist;
+    greedy_descent<WIDE>(g, g.maxlevel, 0, nbr, nd, lane, cur, curdist, ndc, hops_up, dist);
 
     // ---- level 0 (:94-147) ----
     int nA = 1, nR = 1, hn = 1;
@@ -1021,93 +433,22 @@ __global__ __launch_bounds__(64) void hnsw_search_big_kernel(HnswArgs a, float* 
     int* idu = ws_idu + (size_t)q * a.cap;
     uint32_t* bits = a.bitset + (size_t)q * a.bitset_words;
 
-    int qnorm = 0;
-    if constexpr (kU8) {
-        const uint8_t* src = reinterpret_cast<const uint8_t*>(a.queries) + (size_t)q * 128;
-        const int x0 = src[2 * lane], x1 = src[2 * lane + 1];
-        reinterpret_cast<uint8_t*>(qv)[2 * lane] = (uint8_t)x0;
-        reinterpret_cast<uint8_t*>(qv)[2 * lane + 1] = (uint8_t)x1;
-        qnorm = wave_sum_i(x0 * x0 + x1 * x1);
-    } else {
-        const float* src = reinterpret_cast<const float*>(a.queries) + (size_t)q * g.dim;
-        float ss = 0.f;
-        for (int d = lane; d < g.ldv; d += 64) {
-            const float v = d < g.dim ? src[d] : 0.f;
-            qv[d] = v;
-            ss = fmaf(v, v, ss);
-        }
-        if (g.normalize_query) {
-            ss = wave_sum(ss);
-            if (ss != 0.0f) {
-                const float inv = 1.0f / sqrtf(ss);
-                for (int d = lane; d < g.dim; d += 64) qv[d] *= inv;
-            }
-        }
-    }
+    const int qnorm = stage_query<SPACE>(g, a.queries, nullptr, q, qv, lane);
     __builtin_amdgcn_wave_barrier();
     const uint8_t* qb = reinterpret_cast<const uint8_t*>(qv);
-    auto visit = [&](uint32_t id) -> bool {
-        const uint32_t bit = 1u << (id & 31);
-        return (atomicOr(&bits[id >> 5], bit) & bit) == 0;
+    const VisitedSet<true> visit{bits, 0, 0};
+    auto dist = [&](const int* ids, float* out, int m) __attribute__((always_inline)) {
+        frontier_distances<SPACE>(g, qv, qb, qnorm, ids, out, m, lane);
     };
     int ndc = 0, hops = 0, hops_up = 0;
     if (g.n == 0) {
-        for (int i = lane; i < a.k; i += 64) {
-            a.out_ids[(size_t)q * a.k + i] = -1;
-            a.out_dists[(size_t)q * a.k + i] = INFINITY;
-        }
-        if (lane == 0) {
-            a.out_cnt[q] = 0;
-            if (a.out_ndc) a.out_ndc[q] = 0;
-            if (a.out_hops) a.out_hops[q] = 0;
-            if (a.out_hops_up) a.out_hops_up[q] = 0;
-            if (a.status) a.status[q] = 0;
-        }
+        hnsw_empty_result<true>(a, q, lane);
         return;
     }
     // ---- entry point + greedy descent (hnsw_distfunc_opt.cc:168-198) ----
     int cur = g.enterpoint;
-    if (lane == 0) nbr[0] = cur;
-    __builtin_amdgcn_wave_barrier();
-    frontier_distances<SPACE>(g, qv, qb, qnorm, nbr, nd, 1, lane);
-    float curdist = nd[0];
-    ndc += 1;
-    for (int lvl = g.maxlevel; lvl > 0; --lvl) {
-        bool changed = true;
-        while (changed) {
-            changed = false;
-            const int64_t off = g.up_off[cur] + (int64_t)(lvl - 1) * (g.maxM + 1);
-            if (WIDE && g.maxM > 62) {   // upper-level lists of any length
-                hops_up++;
-                ndc += greedy_step_any<SPACE>(g, g.up_links + off, qv, qb, qnorm, nbr, nd, lane, cur, curdist, changed);
-                continue;
-            }
-            const int v = (lane <= g.maxM) ? g.up_links[off + lane] : 0;
-            const int cntl = __builtin_amdgcn_readfirstlane(v);
-            const int nb = __shfl(v, lane + 1, 64);
-            if (lane < cntl) nbr[lane] = nb;
-            __builtin_amdgcn_wave_barrier();
-            hops_up++;
-            if (cntl > 0) {
-                frontier_distances<SPACE>(g, qv, qb, qnorm, nbr, nd, cntl, lane);
-                ndc += cntl;
-                u64 key = ~0ull;
-                if (lane < cntl) key = ((u64)f32_ord(nd[lane]) << 32) | (uint32_t)lane;
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) {
-                    const u64 other = __shfl_xor(key, o, 64);
-                    key = other < key ? other : key;
-                }
-                const float dmin = ord_f32((uint32_t)(key >> 32));
-                if (dmin < curdist) {
-                    curdist = dmin;
-                    cur = nbr[(uint32_t)key];
-                    changed = true;
-                }
-            }
-            __builtin_amdgcn_wave_barrier();
-        }
-    }
+    float curdist;
+    greedy_descent<WIDE>(g, g.maxlevel, 0, nbr, nd, lane, cur, curdist, ndc, hops_up, dist);
     // ---- level 0 (hnsw_distfunc_opt.cc:200-274) ----
     int n = 1, cursor = 0;
     if (lane == 0) {
@@ -1266,33 +607,6 @@ __global__ __launch_bounds__(64) void hnsw_search_big_kernel(HnswArgs a, float* 
 // ---------------------------------------------------------------------------------------
 // Host side
 // ---------------------------------------------------------------------------------------
-// What every search kernel reads: the graph, the queries, the visited bitset and where the results go.  Each launch entry
-// adds what is its own (LDS carve-up, visited table, overflow list, diagnostics).
-static HnswArgs hnsw_args(const HnswDeviceGraph& g, int nq, int k, int ef, int cap, const HnswQueries& q, uint32_t* bitset,
-                          size_t bitset_words, const HnswOut& out) {
-    HnswArgs a{};
-    a.g = g;
-    a.nbcap = hnsw_nbcap(g);
-    a.queries = q.queries;
-    a.query_rows = q.query_rows;
-    a.start_nodes = q.start_nodes;
-    a.level = q.level;
-    a.bitset = bitset;
-    a.bitset_words = bitset_words;
-    a.out_ids = out.ids;
-    a.out_dists = out.dists;
-    a.out_cnt = out.cnt;
-    a.out_ndc = out.ndc;
-    a.out_hops = out.hops;
-    a.out_hops_up = out.hops_up;
-    a.status = out.status;
-    a.nq = nq;
-    a.k = k;
-    a.ef = ef;
-    a.cap = cap;
-    return a;
-}
-
 template <int SPACE, int EMAX, bool WIDE, class ROW>
 static hipError_t launch_space_w(const HnswArgs& a, const HnswSearchPlan& p, hipStream_t s) {
     hipError_t e;
@@ -1379,14 +693,7 @@ hipError_t launch_hnsw_search(const HnswDeviceGraph& g, const HnswSearchPlan& p,
     // (p.lds_bytes is what the one-wave kernels ask for.  The multi-wave kernel asks for 16 bytes more, but only under a
     // table plan, and those stay within 64 KiB: hnsw_make_plan)
     if (p.cap > 64 * SA_EMAX_MAX || hnsw_nbcap(g) > HNSW_NBCAP_LDS || p.lds_bytes > HNSW_LDS_LIMIT) return hipErrorInvalidValue;
-    HnswArgs a = hnsw_args(g, p.nq, p.k, p.ef, p.cap, q, bitset, p.bitset_words, out);
-    a.capa = (p.cap + 3) & ~3;
-    a.table_size = p.table_size;
-    a.table_shift = p.table_shift;
-    a.fix_list = fix.fix_list;
-    a.fix_count = fix.fix_count;
-    a.fix_mode = (p.table_size == 0) ? fix.fix_slots : 0;
-    a.no_pipe = getenv("NMSLIB_HNSW_PIPE") ? atoi(getenv("NMSLIB_HNSW_PIPE")) == 0 : 0;
+    HnswArgs a = hnsw_walk_args(g, p, q, bitset, fix, out);
     static const int prof = getenv("NMSLIB_HNSW_PROF") ? atoi(getenv("NMSLIB_HNSW_PROF")) : 0;
     a.prof = (prof && !q.query_rows && !p.rows_f16) ? 1 : 0;
     const bool clocked = g.space == SP_L2SQR || g.space == SP_NORMCOS;  // the spaces whose kernels carry the phase clocks

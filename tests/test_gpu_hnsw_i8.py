@@ -66,6 +66,25 @@ def test_grid_emax_edges():
     check_grid("l2", 21, 8, (128, 129, 256, 257), mults=(1.0,))  # sorted array of 2, 4 and 16 entries a lane
 
 
+def test_grid_pipeline_switch_changes_nothing(monkeypatch):
+    """NMSLIB_HNSW_PIPE=0 takes the software pipeline across expansions out of the one-wave walk: a diagnostic that may
+    change the schedule and nothing else.  On the grid ties are the rule, so both the pipelined branch and the sequential
+    replay run.  NMSLIB_HNSW_MW=0: the f32 and fp16 rows are walked by hnsw_search_kernel too (both launchers read the
+    switch per launch)."""
+    monkeypatch.setenv("NMSLIB_HNSW_MW", "0")
+    X, Q = grid(2000, 17, 117), grid(200, 17, 217)
+    idx = make_index("l2", "hnsw", X, M=8, efConstruction=40, indexThreadQty=1)
+    for ef in (16, 200):
+        for rows in ("f32", "f16", "i8"):
+            monkeypatch.delenv("NMSLIB_HNSW_PIPE", raising=False)
+            piped = search(idx, Q, K, rows, efSearch=ef)
+            monkeypatch.setenv("NMSLIB_HNSW_PIPE", "0")
+            plain = search(idx, Q, K, rows, efSearch=ef)
+            assert (piped["cnt"] == K).all() and piped["ctr"][1].min() > 0, (rows, ef)
+            same_bits(plain, piped)
+    idx.close()
+
+
 def test_grid_visited_table_overflow_route():
     """test_gpu_hnsw_f16.py's configuration, whose docstring shows why it overflows the LDS visited table: both the table
     launch and the bitset launch that re-runs the overflowed queries are launches of the 8-bit kernel."""
