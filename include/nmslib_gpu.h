@@ -115,7 +115,9 @@ typedef struct {
                               (fast_tiles then counts the batch's queries, fast_tiles_fallback the queries that were redone
                               by the exact scan);
                               16 = the hardware-log2 filter of the Jensen-Shannon spaces (jsdivslow, jsdivfast, jsmetrslow,
-                              jsmetrfast) with its exact re-rank (fast_tiles and fast_tiles_fallback as for 14) */
+                              jsmetrfast) with its exact re-rank (fast_tiles and fast_tiles_fallback as for 14);
+                              17 = the exact bit_hamming scan on the int8 matrix cores (65 536 rows and 256 queries or more,
+                              k <= 128, codes of at most 1024 bits; NMSLIB_GPU_HAM_FAST=0 turns it off) */
     /* fast paths, last slice of the last batch (reading them waits for the stream): query tiles in the slice, tiles the
        threshold kernel sent through the split-bf16-product scan instead of the one-product scan (float rows only), and
        tiles whose verification failed and were redone by the adaptive kernel */

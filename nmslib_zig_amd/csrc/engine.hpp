@@ -455,6 +455,7 @@ class Engine {
                        const int32_t** cnt);
     using ScanLaunch = std::function<void(const ScanPlan& p, size_t q0, float* split_d, int32_t* split_pos)>;
     void scan_slices(size_t nq, size_t k, int tq, const ResultBlock& out, const ScanLaunch& launch);
+    void knn_ham_fast(const hamfast::Plan& f, const uint32_t* d_qw, size_t nq, size_t k, const ResultBlock& out);
     // ---- dense range search (range.cpp) ----
     using RangeLaunch = std::function<void(float* filter, float* report)>;
     size_t range_select(bool two_dists, float r, size_t capacity, int32_t* ids, float* dists, const RangeLaunch& launch);

@@ -9,6 +9,7 @@
 
 #include "../diverg_filter.hpp"
 #include "../diverg_js_filter.hpp"
+#include "../ham_fast_plan.hpp"
 #include "../sparse_filter.hpp"
 
 namespace gfxknn {
@@ -757,6 +758,12 @@ hipError_t launch_leven_knn(const ScanPlan& p, const int64_t* row_ptr, const uin
                             float* split_d, int32_t* split_pos, hipStream_t s);
 hipError_t launch_ham_knn(const ScanPlan& p, const uint32_t* rows, int W, const uint32_t* q, float* split_d,
                           int32_t* split_pos, hipStream_t s);
+// bit_hamming on the int8 matrix cores (ham_mfma_kernels.hip; the plan: ham_fast_plan.hpp): the same per-split lists for
+// the nq queries at q, p made for a batch of at least nq queries.  sample: over the plan's first sample_rows rows in
+// sample_nsplit splits, else over all n rows in nsplit splits; bound (may be null): [nq][k] ascending distances of k
+// rows per query, whose last one no row of the result exceeds
+hipError_t launch_ham_mfma_knn(const hamfast::Plan& p, bool sample, const uint32_t* rows, int n, const uint32_t* q, int nq,
+                               int k, const float* bound, float* split_d, int32_t* split_pos, hipStream_t s);
 // d_out[r] = distance(row r, query); leven: mw_ws holds 2 * nw * 256 * leven_dist_grid(n) words when nw > 1
 int leven_dist_grid(int n);
 hipError_t launch_leven_dist(const int64_t* row_ptr, const uint8_t* data, int n, const uint64_t* peq, int m, int nw,

@@ -325,6 +325,16 @@ void Engine::knn_string_host(const char* const* queries, const size_t* lens, siz
         return;
     }
     have_counters_ = false;
+    if (!lev) {
+        const char* env = getenv("NMSLIB_GPU_HAM_FAST");
+        const hamfast::Plan f = hamfast::plan(method_ == Method::Brute, (long long)d_n_, (long long)nq, (long long)k, st_bits_);
+        if (f.use && !(env && atoi(env) == 0)) {
+            knn_ham_fast(f, d_qw, nq, k, out);
+            fetch_results(nq, k, "string knn", ids, dists, cnt);
+            last_path = 17;
+            return;
+        }
+    }
     const int tq = (lev && nw_max > 1) ? 1 : kStrTileQ;
     scan_slices(nq, k, tq, out, [&](const ScanPlan& p, size_t q0, float* split_d, int32_t* split_pos) {
         if (lev) {
@@ -341,6 +351,40 @@ void Engine::knn_string_host(const char* const* queries, const size_t* lens, siz
     });
     fetch_results(nq, k, "string knn", ids, dists, cnt);
     last_path = 0;
+}
+
+// bit_hamming on the int8 matrix cores (kernels/ham_mfma_kernels.hip; last_path 17): the batch in slices of whole query
+// tiles whose per-split lists stay within 256 MiB, each merged into `out` like a slice of scan_slices
+void Engine::knn_ham_fast(const hamfast::Plan& f, const uint32_t* d_qw, size_t nq, size_t k, const ResultBlock& out) {
+    const size_t max_split_keys = (size_t)1 << 25;
+    size_t m = std::min<size_t>(nq, 32768);
+    const size_t fit = max_split_keys / ((size_t)f.nsplit * k) / f.tile * f.tile;
+    m = std::min(m, std::max<size_t>(fit, f.tile));
+    // per-split lists | the sample's merged result (distances, ids, counts); sized before the first kernel: the first
+    // slice is the largest
+    const size_t lists = (size_t)f.nsplit * m * k * 8;
+    ws_split_.ensure(lists + 2 * m * k * 4 + m * 4);
+    for (size_t q0 = 0; q0 < nq; q0 += m) {
+        const size_t mm = std::min(m, nq - q0);
+        float* split_d = ws_split_.as<float>();
+        float* bound = reinterpret_cast<float*>(ws_split_.as<char>() + lists);
+        int32_t* bound_ids = reinterpret_cast<int32_t*>(bound + mm * k);
+        const uint32_t* rows = d_st_data_.as<uint32_t>();
+        prof_begin(stream_);
+        for (int pass = 0; pass < 2; ++pass) {   // the sample's rows, then all rows under the sample's bounds
+            const bool sample = pass == 0;
+            const int ns = sample ? f.sample_nsplit : f.nsplit;
+            int32_t* split_pos = reinterpret_cast<int32_t*>(split_d + (size_t)ns * mm * k);
+            hip_check(launch_ham_mfma_knn(f, sample, rows, (int)d_n_, d_qw + q0 * f.W, (int)mm, (int)k, sample ? nullptr : bound,
+                                          split_d, split_pos, stream_),
+                      "bit_hamming matrix-core scan");
+            hip_check(launch_merge_topk_ex(split_d, split_pos, mm * k, ns, (int)mm, (int)k, sample ? bound : out.dists + q0 * k,
+                                           sample ? bound_ids : out.ids + q0 * k, sample ? bound_ids + mm * k : out.cnt + q0,
+                                           d_ids_.as<int32_t>(), stream_),
+                      "scan merge");
+        }
+        prof_end(stream_);
+    }
 }
 
 size_t Engine::range_string_host(const char* query, size_t len, double radius, size_t capacity, int32_t* ids,
