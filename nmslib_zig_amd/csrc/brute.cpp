@@ -5,11 +5,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
+#include <cstdio>
 #include <cstring>
 
 #include "bigk_batch_plan.hpp"
 #include "engine.hpp"
 #include "l1_quant.hpp"
+#include "short_scan_plan.hpp"
 
 namespace gfxknn {
 
@@ -23,11 +25,17 @@ void BruteDense::release() {
     f16_hi.release();
     auxp.release();
     auxp16.release();
+    have_short = false;
+    short_tiles = BfShortTiles{};
+    short_h16.release();
+    short_aux16.release();
+    short_vh.release();
 }
 
 size_t BruteDense::bytes() const {
     size_t total = 0;
-    for (const DevBuf* b : {&rows_i8, &auxh, &rows_sel, &mean, &bf_hi, &bf_lo, &auxp, &f16_hi, &auxp16, &l1_u8, &l1_cols,
+    for (const DevBuf* b : {&rows_i8, &auxh, &rows_sel, &mean, &bf_hi, &bf_lo, &auxp, &f16_hi, &auxp16, &short_h16, &short_aux16, &short_vh,
+                            &l1_u8, &l1_cols,
                             &ws_bigk_lists, &ws_bigk_ctl})
         total += b->bytes();
     return total;
@@ -45,6 +53,7 @@ BfF32Tiles BruteDense::tiles(int dp, bool augmented) const {
     t.dp = dp;
     t.bmax = augmented ? bmax_c : bmax;
     t.bres = augmented ? bres_c : bres;
+    if (have_short && !augmented) t.sh = short_tiles;
     return t;
 }
 
@@ -86,6 +95,70 @@ void Engine::make_fast_tiles(const BfSplitSrc& src, int dp, const float* aux, fl
     b.auxp16.ensure(n_pad * 4);
     hip_check(launch_split_bf16(src, aux, aux_pad, aux16_mul, b.tiles(dp, false), stream_), "split rows");
     b.have_bf16 = true;
+}
+
+// The resident side of the short scan (short_scan_plan.hpp) for the n selection rows: the rotation from
+// the second moment of a fixed-stride sample, the rows' heads and tails, the index gate (NMSLIB_GPU_F32_SHORT=1 skips it,
+// =0 skips everything), the head tiles.  A failed allocation leaves the index without the tier.
+void Engine::make_short_tiles(const float* rows, size_t n, const float* aux, float aux_pad) {
+    using namespace shortscan;
+    BruteDense& b = brute_;
+    const char* env = getenv("NMSLIB_GPU_F32_SHORT");
+    const int forced = env ? (atoi(env) != 0 ? 1 : 0) : -1;
+    if (forced == 0 || dim_ <= (size_t)kHead || dim_ > (size_t)kMaxDim) return;
+    const int dim = (int)dim_;
+    try {
+        DevBuf d_m, d_out;
+        d_m.ensure((size_t)dim * dim * 8);
+        d_out.ensure(16);
+        const int stride = (int)((n + kMaxSample - 1) / kMaxSample);
+        hip_check(launch_short_moment(rows, (int)n, ldb_, dim, stride, d_m.as<double>(), stream_), "second moment");
+        std::vector<double> m((size_t)dim * dim);
+        hip_check(hipMemcpyAsync(m.data(), d_m.ptr(), m.size() * 8, hipMemcpyDeviceToHost, stream_), "second moment");
+        hip_check(hipStreamSynchronize(stream_), "second moment");
+        for (double v : m)
+            if (!std::isfinite(v)) return;
+        const Rotation rot = make_rotation(m, dim);
+        b.short_vh.ensure(rot.vh.size() * 4);
+        hip_check(hipMemcpyAsync(b.short_vh.ptr(), rot.vh.data(), rot.vh.size() * 4, hipMemcpyHostToDevice, stream_), "rotation");
+        BfShortTiles t{};
+        t.vh = b.short_vh.as<float>();
+        float mx[4] = {0.f, 0.f, 0.f, 0.f};
+        hip_check(launch_short_rows(rows, (int)n, ldb_, dim, nullptr, 0.f, 0.f, t, d_out.as<float>(), stream_), "row heads");
+        hip_check(hipMemcpyAsync(mx, d_out.ptr(), 16, hipMemcpyDeviceToHost, stream_), "row heads");
+        hip_check(hipStreamSynchronize(stream_), "row heads");   // (`rot` is read by the copy above)
+        const float b_tail = tail_allowance(mx[1], b.bmax, rot.tail_abs);
+        const bool gate = index_gate(b_tail, b.bmax);
+        if (getenv("NMSLIB_GPU_DEBUG") && (atoi(getenv("NMSLIB_GPU_DEBUG")) & 4096))
+            fprintf(stderr, "[short scan] finalize: b_tailmax %.6g bmax %.6g ratio %.4g gate %d forced %d delta %.3g coeff %.3g\n",
+                    (double)b_tail, (double)b.bmax, b.bmax > 0 ? (double)(b_tail / b.bmax) : 0.0, gate ? 1 : 0, forced, rot.delta,
+                    (double)rot.coeff);
+        if (!(gate || forced == 1) || !(mx[0] > 0.f) || !std::isfinite(mx[0]) || !std::isfinite(mx[1])) return;
+        t.scale = std::ldexp(1.f, std::max(-40, std::min(40, 13 - (int)std::floor(std::log2(mx[0])))));
+        const size_t n_pad = (size_t)bf_short_rows_padded((int)n);
+        t.h16 = b.short_h16.ensure(n_pad * kHead * 2);
+        t.aux16 = static_cast<float*>(b.short_aux16.ensure(n_pad * 4));
+        hip_check(launch_short_rows(rows, (int)n, ldb_, dim, aux, aux_pad, aux ? t.scale * t.scale : 0.f, t, d_out.as<float>(), stream_),
+                  "short tiles");
+        hip_check(hipMemcpyAsync(mx, d_out.ptr(), 16, hipMemcpyDeviceToHost, stream_), "short tiles");
+        hip_check(hipStreamSynchronize(stream_), "short tiles");
+        t.bscale_h = t.scale * mx[2];
+        t.bres_h = mx[3];
+        t.b_tail = b_tail;
+        t.bmax = b.bmax;
+        t.coeff = rot.coeff;
+        t.tail_abs = rot.tail_abs;
+        t.miss = static_cast<int*>(b.short_miss.ensure(64));
+        *t.miss = 0;
+        b.short_tiles = t;
+        b.have_short = true;
+    } catch (const EngineError& e) {
+        if (e.code != Err::OutOfMemory) throw;
+        (void)hipGetLastError();
+        b.short_h16.release();
+        b.short_aux16.release();
+        b.short_vh.release();
+    }
 }
 
 // The resident side of the l1 fast path (l1_quant.hpp): column ranges -> common step -> byte copy in the scan's layout and
@@ -258,6 +331,8 @@ void Engine::prepare_brute() {
         make_fast_tiles({sel_rows, (int)n, n_pad, ldb_, (int)dim_}, f0.use ? f0.dp : 128,
                         space_ == SP_NEGDOT ? nullptr : d_aux_.as<float>(), space_ == SP_L2 ? -INFINITY : 0.f,
                         space_ == SP_L2 ? b.f16_scale * b.f16_scale : 1.f);
+        if (f0.use && !b.centred && (space_ == SP_L2 || space_ == SP_NEGDOT))
+            make_short_tiles(sel_rows, n, space_ == SP_NEGDOT ? nullptr : d_aux_.as<float>(), space_ == SP_L2 ? -INFINITY : 0.f);
     }
     if (space_ == SP_L1 && n >= 65536 && dim_ <= (size_t)BF_L1_MAX_DIM) make_l1_copy();
     hip_check(hipStreamSynchronize(stream_), "finalize");
@@ -407,6 +482,9 @@ void Engine::knn_brute(const void* d_queries, size_t nq, size_t k, int32_t* d_id
                 q.sel_ld = f.dp;
             }
             const BfFastWs ws = fast_ws(bf_fast_ws_bytes(f));
+            // (the short scan: a query of an earlier batch found no room for its bound -- the word is read as it stands, without
+            //  a synchronisation -- and the index stays on the 128-column scan until the next finalize)
+            if (b.have_short && *static_cast<volatile int*>(b.short_tiles.miss) != 0) b.have_short = false;
             hip_check(launch_bf_f32_fast(f, space_, (int)nq, (int)k, rows, b.tiles(f.dp, f.cosc), q, ws, out, prof_pair(), stream),
                       "bf_f32_fast");
             last_path = 1;

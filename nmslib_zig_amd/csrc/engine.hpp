@@ -113,6 +113,14 @@ class PinnedBuf {
     PinnedBuf() = default;
     ~PinnedBuf() { if (p_) (void)hipHostFree(p_); }
     PinnedBuf(PinnedBuf&& o) noexcept : p_(o.p_), n_(o.n_) { o.p_ = nullptr, o.n_ = 0; }  // move-only
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept {
+        if (this != &o) {
+            if (p_) (void)hipHostFree(p_);
+            p_ = o.p_, n_ = o.n_;
+            o.p_ = nullptr, o.n_ = 0;
+        }
+        return *this;
+    }
     void* ensure(size_t bytes, size_t slack = 0);  // a growth allocates bytes + slack
     void* ptr() const { return p_; }
 
@@ -197,6 +205,13 @@ struct BruteDense {
     float f16_scale_q = 1.f;             // scale of a batch's fp16 queries (the rows' scale, except centred cosine)
     float cosc_lambda = 1.f;             // centred cosine on the fast path: scale of the two constant columns (row_aug_cosc_kernel)
     float bmax_c = 0, bres_c = 0;        // largest norm / bf16 rounding residual of the augmented rows
+    // short scan: fp16 head tiles of the rotated rows, their start values, the rotation's first 64 columns;
+    // the constants of its bound (short.h16 etc. point into the three buffers); short_miss: one pinned word the threshold
+    // kernel sets when a query finds no room -- read at the next batch, which then leaves the tier until the next finalize
+    DevBuf short_h16, short_aux16, short_vh;
+    PinnedBuf short_miss;
+    bool have_short = false;
+    BfShortTiles short_tiles{};
     // l1 fast path: the 8-bit copy of the rows in the scan's layout, per column lo / hi / rmax ([3][dim]
     // floats) and the common step; have_l1 = false: declined (l1_quant.hpp) or no room in HBM, the index stays adaptive
     DevBuf l1_u8, l1_cols;
@@ -600,6 +615,8 @@ class Engine {
     void prepare_brute();
     void measure_rows_f16(const float* rows, size_t n, int ld, int dim, bool relative, float* bm);
     void make_fast_tiles(const BfSplitSrc& src, int dp, const float* aux, float aux_pad, float aux16_mul);
+    // the short scan's resident side; leaves have_short = false when the gate declines or HBM has no room
+    void make_short_tiles(const float* rows, size_t n, const float* aux, float aux_pad);
     void make_l1_copy();   // the l1 fast path's resident side; leaves have_l1 = false when declined or out of memory
     void knn_brute(const void* d_queries, size_t nq, size_t k, int32_t* d_ids, float* d_dists,
                    int32_t* d_cnt, hipStream_t stream);

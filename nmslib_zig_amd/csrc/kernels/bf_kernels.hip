@@ -1827,8 +1827,15 @@ __global__ __launch_bounds__(256) void bf_scan_f32_kernel(BfScanF32Args a) {
 // KCH > 1 (round 3): rows longer than 128 -- KCH chunks of 128 dimensions, one stage per (64-row tile, chunk); the two
 // blocks of a tile keep accumulating through the tile's KCH stages and are checked after its last one; the query
 // fragments of all chunks live in AGPRs (32 * KCH per group: QG = 1, NW = 4 -- 128 queries per workgroup).
-template <int MODE, bool SAMPLE, int QG, int NW, int KCH = 1>
+// SHORT = the short scan: the tiles hold fp16 HEADS of 64 columns, rows r and r + 32 of a 64-row group in one
+// 256-byte tile row, so a stage is 128 rows and DMA, swizzle, ring and fragment addresses stay as they are.  K-steps 0..3
+// of a 32-tile-row block score rows 0..31 of its group into one accumulator set, K-steps 4..7 rows 32..63 into the other
+// (each from its own start values, with the same four query fragments); the set that just finished is checked under the
+// other's four K-steps -- one group every 4 / QG steps.  a.tps counts 128-row stages.
+template <int MODE, bool SAMPLE, int QG, int NW, int KCH = 1, bool SHORT = false>
 __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) {
+    static_assert(!SHORT || (KCH == 1 && MODE != SC_COS), "the short scan serves one chunk of l2 / inner-product rows");
+    constexpr int kRows = SHORT ? 2 * BF_BN : BF_BN;   // rows of a stage
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, l31 = lane & 31;
@@ -1844,15 +1851,17 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
     // kSync in flight
     constexpr int kSync = 4, kRing = 2 * kSync + 1, kAuxRing = 16, kStageBytes = BF_BN * 256;
     char* ring = smem;
-    float* auxr = reinterpret_cast<float*>(ring + kRing * kStageBytes);  // [kAuxRing][BN]
+    float* auxr = reinterpret_cast<float*>(ring + kRing * kStageBytes);  // [kAuxRing][kRows]
     const int tstr = SAMPLE ? a.tile_stride : 1;
-    const int tiles_all = (a.n + BF_BN - 1) / BF_BN;
+    const int tiles_all = (a.n + kRows - 1) / kRows;
     const int stiles_all = (tiles_all + tstr - 1) / tstr;
     const int ntiles = max(0, min(a.tps, stiles_all - split * a.tps));
     const int nstages = ntiles * KCH;   // one stage per (tile, chunk of 128 dimensions)
     constexpr int kDp = 128 * KCH;       // row length of the bf16 tiles
-    const int r_begin = split * a.tps * tstr * BF_BN;
-    const int stage_rows = tstr * BF_BN;
+    constexpr int kRowBytes = SHORT ? 128 : kDp * 2;   // tile bytes of one base row
+    constexpr int kQd = SHORT ? 64 : kDp;              // columns of a query's fragments
+    const int r_begin = split * a.tps * tstr * kRows;
+    const int stage_rows = tstr * kRows;
 
     // one stage = 16 DMA pieces of 1 KiB (4 rows x 256 B): wave w issues pieces (16/NW) w .. and the stage's 64 aux values.
     // Written out in the scalar-base form (round 3): `global_load_lds_dwordx4 voff, s[base]` with the lane's constant byte
@@ -1874,7 +1883,7 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
     auto issue_tile = [&](int stage) __attribute__((always_inline)) {
         const int slot = stage % kRing;
         const int row0 = r_begin + (stage / KCH) * stage_rows;
-        const unsigned long long sbase = (unsigned long long)(uintptr_t)a.base_h16 + ((unsigned long long)row0 * kDp + (stage % KCH) * 128) * 2ull;
+        const unsigned long long sbase = (unsigned long long)(uintptr_t)a.base_h16 + (unsigned long long)row0 * kRowBytes + (unsigned long long)((stage % KCH) * 256);
         const uint32_t m0v = dma_lds0 + (uint32_t)slot * kStageBytes;
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
@@ -1884,11 +1893,15 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
                          :: "v"(dma_voff[jj]), "s"(sbase), "s"(m0v + (uint32_t)jj * 1024u) : "memory", "m0");
         const unsigned long long abase = (unsigned long long)(uintptr_t)a.auxp16 + (unsigned long long)row0 * 4ull;
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1"
-                     :: "v"(aux_voff), "s"(abase), "s"(aux_lds0 + (uint32_t)((stage % kAuxRing) * BF_BN * 4)) : "memory", "m0");
+                     :: "v"(aux_voff), "s"(abase), "s"(aux_lds0 + (uint32_t)((stage % kAuxRing) * kRows * 4)) : "memory", "m0");
+        if constexpr (SHORT)   // (the stage's second 64 start values)
+            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1"
+                         :: "v"(aux_voff), "s"(abase + 256ull), "s"(aux_lds0 + (uint32_t)((stage % kAuxRing) * kRows * 4 + 256)) : "memory", "m0");
 #pragma clang diagnostic pop
     };
 
-    f16x8 qh[QG][8 * KCH];
+    constexpr int kQf = SHORT ? 4 : 8 * KCH;   // query fragments of a group
+    f16x8 qh[QG][kQf];
     float thr[QG];
     int cnt[QG], ecnt[QG];
     uint32_t* lp[QG];
@@ -1897,8 +1910,8 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
     for (int g = 0; g < QG; ++g) {
         const int qidx = (qt * NW + wave) * (32 * QG) + g * 32 + l31;
 #pragma unroll
-        for (int kc = 0; kc < 8 * KCH; ++kc)
-            asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(qh[g][kc]) : "v"(static_cast<const _Float16*>(a.q_h16) + (size_t)qidx * kDp + 16 * kc + 8 * h) : "memory");
+        for (int kc = 0; kc < kQf; ++kc)
+            asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(qh[g][kc]) : "v"(static_cast<const _Float16*>(a.q_h16) + (size_t)qidx * kQd + 16 * kc + 8 * h) : "memory");
         cnt[g] = 0;
         ecnt[g] = 0;
         if constexpr (SAMPLE) {
@@ -2125,7 +2138,8 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
     // (Each copy of the loop carries its own prologue reads and its own final wait: a pinned fragment register alive across
     //  the branch between the copies is merged with COPIES of registers whose reads are in flight -- tests/test_isa_audit.py.)
     auto main_loop = [&](auto stag_tag) __attribute__((always_inline)) {
-    constexpr int kStag = decltype(stag_tag)::value;
+    // (the short scan checks a group every two K-steps when a wave serves two: no room for the stagger there)
+    constexpr int kStag = SHORT && QG == 2 ? 0 : decltype(stag_tag)::value;
     // (static priority for the second-dispatched half, the arbitration loser of every SIMD pair: same guide, item 4;
     //  NMSLIB_GPU_BF16_PRIO=0 in the launcher's environment switches it off for experiments)
     if (kStag != 0 && a.prio_half) __builtin_amdgcn_s_setprio(1);
@@ -2138,7 +2152,7 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
         const int t = tt * KCH + ch;
         constexpr bool kOne = KCH == 1;
         const bool first_ch = kOne || ch == 0, last_ch = kOne || ch == KCH - 1;
-        const float* axs = auxr + (t % kAuxRing) * BF_BN + 4 * h;
+        const float* axs = auxr + (t % kAuxRing) * kRows + 4 * h;
         const int row0 = r_begin + tt * stage_rows;
 #pragma unroll
         for (int blk = 0; blk < 2; ++blk) {
@@ -2148,15 +2162,24 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
             const bool init_next = blk == 0 ? first_ch : last_ch;
             // (block 1's last two K-steps prefetch from the NEXT stage's slot: the addresses move there one by one)
             const int dslot = ((t + 1) % kRing == 0) ? -(kRing - 1) * kStageBytes : kStageBytes;
-            const uint32_t nax = blk == 0 ? aux_a + ((t % kAuxRing) * BF_BN + 32) * 4 : aux_a + (((t + 1) % kAuxRing) * BF_BN) * 4;
+            // (the short scan: the start values of the rows that K-steps 4..7 score are read at K-step 2, those of the next
+            //  block's first rows at K-step 6 -- 32 values each, four sets to a stage)
+            const uint32_t nax = SHORT ? (blk == 0 ? aux_a + ((t % kAuxRing) * kRows + 64) * 4 : aux_a + (((t + 1) % kAuxRing) * kRows) * 4)
+                                       : (blk == 0 ? aux_a + ((t % kAuxRing) * BF_BN + 32) * 4 : aux_a + (((t + 1) % kAuxRing) * BF_BN) * 4);
+            const uint32_t max_ = aux_a + ((t % kAuxRing) * kRows + 64 * blk + 32) * 4;   // SHORT: this block's second set
 #pragma unroll
             for (int kc = 0; kc < 8; ++kc) {
+                // K-step inside the accumulating set and the set itself (the short scan starts a new one at K-step 4)
+                const int kq = SHORT ? (kc & 3) : kc;
+                const int cur = SHORT ? (kc >> 2) : blk;
                 // the read of step kc+kPre, then the wait for step kc's fragment: at most the reads of steps kc+1 .. kc+kPre
                 // (and the next block's start values) stay in flight
                 if (kc + kPre < 8) {
+                    if (SHORT && kc == 2) load_init(max_);
                     if (blk == 0) load_frag(Off0{}, kc + kPre);
                     else load_frag(Off1{}, kc + kPre);
-                    wait_frag(std::integral_constant<int, kPre>{}, kc, kc == 0 && MODE == SC_L2 && first_ch);
+                    if (SHORT && kInitReads && (kc == 2 || kc == 3)) wait_frag(std::integral_constant<int, kPre + 4>{}, kc, false);
+                    else wait_frag(std::integral_constant<int, kPre>{}, kc, kq == 0 && MODE == SC_L2 && first_ch);
                 } else {
                     // (also in the very last block: see bf_scan_f32_kernel)
                     if (kc == 6 && init_next) load_init(nax);
@@ -2177,29 +2200,30 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
                 // branch at the end of the step that computes it costs ~125 clocks (the wave issues in order: the branch
                 // waits for the VALU chain that waited for the step's last MFMA to issue; measured 252 vs 129 clocks
                 // per K-step).
-                constexpr int kEvery = 8 / QG;
-                const int gc = kc >= kStag ? (kc - kStag) / kEvery : 0;
-                const bool chk = prev_final && kc >= kStag && ((kc - kStag) % kEvery) == 0;
-                const bool br = prev_final && kc >= kStag && ((kc - kStag) % kEvery) == 1;
+                constexpr int kEvery = (SHORT ? 4 : 8) / QG;
+                const int gc = kq >= kStag ? (kq - kStag) / kEvery : 0;
+                const bool chk = prev_final && kq >= kStag && ((kq - kStag) % kEvery) == 0;
+                const bool br = prev_final && kq >= kStag && ((kq - kStag) % kEvery) == 1;
                 float m = 0.f;
                 // (the written-out MFMAs of a block's first K-step are invisible to sched_group_barrier: there the check's
                 //  VALU work is placed by hand -- leaves under the first MFMA, root under the second)
-                const bool by_hand = MODE == SC_L2 && kc == 0 && first_ch && chk && QG == 2;
+                const bool by_hand = MODE == SC_L2 && kq == 0 && first_ch && chk && QG == 2;
+                const int qf = SHORT ? kq : 8 * ch + kc;   // (the short scan: the same four fragments for either set)
                 float m5[5];
-                if (chk && !by_hand) m = block_max(acc[blk ^ 1][gc], pv_ax);   // (also before the first block: no branch between the MFMAs)
-                mfma_step(acc[blk][0], qh[0][8 * ch + kc], kc, first_ch);
+                if (chk && !by_hand) m = block_max(acc[cur ^ 1][gc], pv_ax);   // (also before the first block: no branch between the MFMAs)
+                mfma_step(acc[cur][0], qh[0][qf], kq, first_ch);
                 if (by_hand) {
                     if constexpr (QG == 2) {
                         __builtin_amdgcn_sched_barrier(0);
-                        block_max_leaves(acc[blk ^ 1][gc], pv_ax, m5);
+                        block_max_leaves(acc[cur ^ 1][gc], pv_ax, m5);
                         __builtin_amdgcn_sched_barrier(0);
-                        mfma_step(acc[blk][1], qh[1][8 * ch + kc], kc, first_ch);
+                        mfma_step(acc[cur][1], qh[1][qf], kq, first_ch);
                         __builtin_amdgcn_sched_barrier(0);
-                        m = block_max_root(acc[blk ^ 1][gc], pv_ax, m5);
+                        m = block_max_root(acc[cur ^ 1][gc], pv_ax, m5);
                     }
                 } else if (br) {
                     __builtin_amdgcn_sched_barrier(0);
-                    finish_check(trig_pend, m_pend, acc[blk ^ 1][gc], gc, pv_ax, pv_row0);
+                    finish_check(trig_pend, m_pend, acc[cur ^ 1][gc], gc, pv_ax, pv_row0);
                     __builtin_amdgcn_sched_barrier(0);
                 } else {
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -2208,7 +2232,7 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
 #pragma unroll
                 for (int g = 1; g < QG; ++g) {
                     if (by_hand) break;
-                    mfma_step(acc[blk][g], qh[g][8 * ch + kc], kc, first_ch);
+                    mfma_step(acc[cur][g], qh[g][qf], kq, first_ch);
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x002, 12 / QG, 0);
                 }
@@ -2222,11 +2246,15 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
                     m_pend = m;
                     trig_pend = trig;
                 }
+                if (SHORT && kc == 3) {   // the set of K-steps 0..3 is the one the next four steps check
+                    pv_ax = axs + blk * 64;
+                    pv_row0 = row0 + blk * 64;
+                }
                 __builtin_amdgcn_sched_barrier(0);
             }
             if (last_ch) {
-                pv_ax = axs + blk * 32;
-                pv_row0 = row0 + blk * 32;
+                pv_ax = axs + (SHORT ? blk * 64 + 32 : blk * 32);
+                pv_row0 = row0 + (SHORT ? blk * 64 + 32 : blk * 32);
                 have_pv = true;
             }
             if (blk == 1) {
@@ -2323,6 +2351,127 @@ __global__ void bf_f32_prep_kernel(const float* raw, int nq, int dim, const floa
     for (size_t i = gtid; i < n2; i += gsz) clr2[i] = 0u;
 }
 
+// ---- the short scan's operands (DESIGN 4.1b "short scan"; bounds: short_scan_plan.hpp) ----------------------------------
+// Vh [128][64] (the rotation's first 64 columns, rows >= dim zero) in LDS, row stride 65: lane j walks a column without
+// bank conflicts, lane i a row likewise.
+constexpr int kShortVld = shortscan::kHead + 1;
+__device__ __forceinline__ void short_load_v(const float* vh, float* vs) {
+    for (int i = threadIdx.x; i < shortscan::kMaxDim * shortscan::kHead; i += blockDim.x) vs[(i >> 6) * kShortVld + (i & 63)] = vh[i];
+    __syncthreads();
+}
+// One wave, one vector x of up to 128 values (lane l holds x[l] and x[l + 64], zeros beyond the dimension): lane j gets
+// head_j = sum_i x_i Vh[i][j] (one fma chain in the order of i), tail2 the squared norm of x - Vh head (per element one
+// fma chain in the order of j) in every lane.
+__device__ __forceinline__ float short_head_tail(float x0, float x1, int lane, const float* vs, float& tail2) {
+    float hd = 0.f;
+    for (int i = 0; i < 64; ++i) hd = fmaf(__shfl(x0, i, 64), vs[i * kShortVld + lane], hd);
+    for (int i = 0; i < 64; ++i) hd = fmaf(__shfl(x1, i, 64), vs[(64 + i) * kShortVld + lane], hd);
+    float r0 = x0, r1 = x1;
+    for (int j = 0; j < 64; ++j) {
+        const float hj = __shfl(hd, j, 64);
+        r0 = fmaf(-hj, vs[lane * kShortVld + j], r0);
+        r1 = fmaf(-hj, vs[(64 + lane) * kShortVld + j], r1);
+    }
+    tail2 = wave_sum(fmaf(r0, r0, r1 * r1));
+    return hd;
+}
+
+// Heads and tails of the rows.  tiles == null: the maxima only -- out_bits[0] largest |head element| (the fp16 scale is
+// chosen from it), [1] largest tail, [2] largest |head|.  Else also the short tiles, n_pad rows (a multiple of 128): fp16(scale
+// * head), rows r and r + 32 of a 64-row group in one 256-byte tile row; their start values auxp = aux * aux_mul (null: 0;
+// aux_pad behind the n rows); out_bits[3] = largest fp16 residual |scale head - fp16(scale head)|.
+__global__ __launch_bounds__(256) void short_rows_kernel(const float* rows, int n, int n_pad, int ld, int dim, const float* vh,
+                                                         float scale, _Float16* tiles, const float* aux, float aux_pad,
+                                                         float aux_mul, float* auxp, unsigned* out_bits) {
+    __shared__ float vs[shortscan::kMaxDim * kShortVld];
+    short_load_v(vh, vs);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    float m_el = 0.f, m_tail = 0.f, m_head = 0.f, m_res = 0.f;
+    const int rows_all = tiles ? n_pad : n;
+    for (int row = blockIdx.x * 4 + wave; row < rows_all; row += gridDim.x * 4) {
+        const bool real = row < n;
+        const float* p = rows + (size_t)row * ld;
+        const float x0 = real && lane < dim ? p[lane] : 0.f, x1 = real && lane + 64 < dim ? p[lane + 64] : 0.f;
+        float t2;
+        const float hd = short_head_tail(x0, x1, lane, vs, t2);
+        m_el = fmaxf(m_el, fabsf(hd));
+        m_tail = fmaxf(m_tail, sqrtf(t2));
+        m_head = fmaxf(m_head, sqrtf(wave_sum(hd * hd)));
+        if (tiles) {
+            const float v = scale * hd;
+            const _Float16 hh = (_Float16)v;
+            const float w = v - (float)hh;
+            m_res = fmaxf(m_res, sqrtf(wave_sum(w * w)));
+            const int rr = row & 63;
+            tiles[((size_t)(row >> 6) * 32 + (rr & 31)) * 128 + (rr >> 5) * 64 + lane] = hh;
+            if (lane == 0) auxp[row] = real ? (aux ? aux[row] * aux_mul : 0.f) : aux_pad;
+        }
+    }
+    m_el = wave_max(m_el);
+    if (lane == 0) {
+        atomicMax(out_bits + 0, __float_as_uint(m_el));
+        atomicMax(out_bits + 1, __float_as_uint(m_tail));
+        atomicMax(out_bits + 2, __float_as_uint(m_head));
+        atomicMax(out_bits + 3, __float_as_uint(m_res));
+    }
+}
+
+// Second moment of every stride-th row, f64: block i, thread j sums x_i x_j in the order of the rows -> m [dim][dim]
+__global__ void short_moment_kernel(const float* rows, int n, int ld, int dim, int stride, double* m) {
+    const int i = blockIdx.x, j = threadIdx.x;
+    if (j >= dim) return;
+    double acc = 0.0;
+    for (size_t r = 0; r < (size_t)n; r += (size_t)stride) acc += (double)rows[r * ld + i] * (double)rows[r * ld + j];
+    m[(size_t)i * dim + j] = acc;
+}
+
+// The short scan's query preparation, launched in bf_f32_prep_kernel's place: the padded f32 copy, fp16(scale * head) of
+// every query [qpad][64], its bound E_s (shortscan::short_error; 0 for padding queries) and the batch's clears.
+struct ShortPrepArgs {
+    const float* raw;   // [nq][dim]
+    int nq, dim, qpad, ld;
+    float* pad_out;     // [qpad][ld]
+    const float* vh;
+    _Float16* qh16;     // [qpad][64]
+    float* es;          // [qpad]
+    int *clr0, *clr1;
+    uint32_t* clr2;
+    int n0, n1;
+    size_t n2;
+    float scale_q, unit;        // scale of the query heads; scale_rows * scale_queries
+    float bscale_h, bres_h;     // scale * largest |row head|; largest fp16 residual of the scaled row heads
+    float b_tail, bmax, coeff, tail_abs;   // largest row tail (with its allowance), largest row norm, Rotation's constants
+};
+__global__ __launch_bounds__(256) void bf_f32_prep_short_kernel(ShortPrepArgs a) {
+    __shared__ float vs[shortscan::kMaxDim * kShortVld];
+    const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = gtid; i < (size_t)a.n0; i += gsz) a.clr0[i] = 0;
+    for (size_t i = gtid; i < (size_t)a.n1; i += gsz) a.clr1[i] = 0;
+    for (size_t i = gtid; i < a.n2; i += gsz) a.clr2[i] = 0u;
+    short_load_v(a.vh, vs);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int q = blockIdx.x * 4 + wave; q < a.qpad; q += gridDim.x * 4) {
+        const bool real = q < a.nq;
+        const float* p = a.raw + (size_t)q * a.dim;
+        const float x0 = real && lane < a.dim ? p[lane] : 0.f, x1 = real && lane + 64 < a.dim ? p[lane + 64] : 0.f;
+        for (int c = lane; c < a.ld; c += 64) a.pad_out[(size_t)q * a.ld + c] = c < 64 ? x0 : (c < 128 ? x1 : 0.f);
+        float t2;
+        const float hd = short_head_tail(x0, x1, lane, vs, t2);
+        const float qn = sqrtf(wave_sum(fmaf(x0, x0, x1 * x1)));
+        const float v = a.scale_q * hd;
+        const _Float16 hh = (_Float16)v;
+        const float w = v - (float)hh;
+        const bool over = !(fabsf(v) <= 65504.f);
+        const float qnh = sqrtf(wave_sum(v * v)), qr = sqrtf(wave_sum(w * w));
+        // (one_product_error over the head parts)
+        const float e_head = __any(over) ? INFINITY : 1.01f * (qr * a.bscale_h + 1.004f * qnh * a.bres_h) + 2e-5f * qnh * a.bscale_h;
+        const float q_tail = shortscan::tail_allowance(sqrtf(t2), qn, a.tail_abs);
+        const float es = shortscan::short_error(e_head, a.unit, q_tail, a.b_tail, qn, a.bmax, a.coeff);
+        a.qh16[(size_t)q * 64 + lane] = hh;
+        if (lane == 0) a.es[q] = real ? es : 0.f;
+    }
+}
+
 // Error bound of the one-product score q_hi . b_hi of one query against any row (first wave of the workgroup; result
 // in every lane):  |q.b - q^.b^| <= |q - q^||b| + |q^||b - b^|  with the ACTUAL rounding residual of this query and the
 // largest residual of the rows (bres; relative to |b| for the cosine score, where bscale = 1), plus the f32 accumulation
@@ -2364,7 +2513,8 @@ template <int NPER>
 __global__ __launch_bounds__(256) void bf_f32_threshold_kernel(const float* top8, int nlists, int depth, int r, int rcap, int nq,
                                                                int qpad, const float* queries_sel, int ldb, int dim, float bscale,
                                                                float bres, int group_q, int force_precise, float* thr3,
-                                                               float* thr1, int* precise, float scale_q, float unit) {
+                                                               float* thr1, int* precise, float scale_q, float unit,
+                                                               const float* e_short, int* short_miss) {
     const int lane = threadIdx.x & 63, q = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (q >= qpad) return;
     if (q >= nq) {  // padding queries: nothing passes
@@ -2382,7 +2532,8 @@ __global__ __launch_bounds__(256) void bf_f32_threshold_kernel(const float* top8
         const int l = depth == 4 ? idx >> 2 : idx >> 3, j = idx - l * depth;   // (depth is 4 or 8)
         key[i] = idx < total ? f32_ord(top8[((size_t)q * nlists + l) * 8 + j]) : 0u;
     }
-    const float e1 = one_product_error(queries_sel + (size_t)q * ldb, dim, lane, bscale, bres, scale_q);   // (the scan's units)
+    // (the short scan: its bound E_s, which the preparation kernel left per query, stands where E1 stands)
+    const float e1 = e_short ? e_short[q] : one_product_error(queries_sel + (size_t)q * ldb, dim, lane, bscale, bres, scale_q);   // (the scan's units)
     const uint32_t T = total >= r ? wave_rth_largest_u32<NPER>(key, r) : 0u;
     const float t3 = total >= r ? ord_f32(T) : -INFINITY;   // s^_r
     float t1 = t3;
@@ -2418,6 +2569,7 @@ __global__ __launch_bounds__(256) void bf_f32_threshold_kernel(const float* top8
         thr3[q] = (t3 - 1.02f * e1) / unit;   // (the split-product scan runs on the unscaled bf16 tiles)
         thr1[q] = force_precise == 2 ? INFINITY : t1;   // (2: NMSLIB_GPU_DEBUG & 8192 -- a scan without hits, timing experiments)
         if (!ok) atomicOr(&precise[q / group_q], 1);
+        if (!ok && short_miss) *short_miss = 1;   // (host memory: the engine leaves the short scan before its next batch)
     }
 }
 
@@ -2447,6 +2599,7 @@ struct RerankListF32Args {
     const float* qaux;         // centred cosine / angular: [qpad][4] = |q'|^2, |q| - |mu|, |q|, flag (0: zero-norm query); else null
     size_t list_m_off;         // one-product tiles: words from an entry to its second word (BfScanF32Args::list_m_off)
     unsigned long long* prof;  // NMSLIB_GPU_DEBUG & 4096: phase clocks (100 MHz), summed over the workgroups
+    const float* e_short;      // the short scan served the batch: [qpad] its bound E_s per query, in E1's place (else null)
 };
 
 // kappa of the cut in bf_rerank_f32_list_kernel: the r-th largest second word over the ENTRIES among the `total` gathered
@@ -2574,7 +2727,7 @@ __global__ __launch_bounds__(256) void bf_rerank_f32_list_kernel(RerankListF32Ar
         float ss = 0.f;
         for (int d = lane; d < a.sel_dim; d += 64) ss = fmaf(qs[d], qs[d], ss);
         ss = wave_sum(ss);
-        const float e1 = split_product ? 0.f : one_product_error(qs, a.sel_dim, lane, a.scale * (SPACE == SP_L2 || SPACE == SP_NEGDOT || COSC ? a.bmax : 1.0f), a.bres16, a.scale_q);
+        const float e1 = split_product ? 0.f : a.e_short ? a.e_short[q] : one_product_error(qs, a.sel_dim, lane, a.scale * (SPACE == SP_L2 || SPACE == SP_NEGDOT || COSC ? a.bmax : 1.0f), a.bres16, a.scale_q);
         if (lane == 0) {
             s_qn2 = ss;
             s_e1 = e1;
@@ -3865,6 +4018,14 @@ BfF32Fast bf_f32_fast_plan(int n, int dim, int nq, int k, int space, bool cosine
     f.lds_thr = (size_t)host_next_pow2(nss * 2 * 8) * 8 + 16;
     f.fallback = bf_make_plan(n, dim_rows, nq, k, false, tq);
     if (f.kch > 1) f.force_precise = false;   // (no split-product scan at these lengths: such tiles go to the adaptive kernel)
+    // the short scan: the same splits over 128-row stages (a split's first row stays where it is: tps = 2 * short_tps)
+    f.short_ok = (space == SP_L2 || space == SP_NEGDOT) && !cosine_centred && dim > shortscan::kHead && dim <= shortscan::kMaxDim &&
+                 !f.force_precise;
+    if (const char* e = getenv("NMSLIB_GPU_F32_SHORT")) f.short_ok = f.short_ok && atoi(e) != 0;
+    const int stages_all = (n + 2 * BF_BN - 1) / (2 * BF_BN);
+    f.short_tps = (stages_all + ns - 1) / ns;
+    f.short_s_tps = ((stages_all + f.stride - 1) / f.stride + nss - 1) / nss;
+    f.lds_short = 9 * BF_BN * 256 + 16 * 2 * BF_BN * 4 + 64;
     return f;
 }
 
@@ -3891,6 +4052,23 @@ hipError_t launch_split_bf16(const BfSplitSrc& src, const float* aux, float aux_
     return hipGetLastError();
 }
 
+hipError_t launch_short_moment(const float* rows, int n, int ld, int dim, int stride, double* m, hipStream_t s) {
+    if (n == 0 || dim > 128) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(short_moment_kernel, dim3(dim), dim3(128), 0, s, rows, n, ld, dim, stride, m);
+    return hipGetLastError();
+}
+hipError_t launch_short_rows(const float* rows, int n, int ld, int dim, const float* aux, float aux_pad, float aux_mul,
+                             const BfShortTiles& dst, float* out, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(out, 0, 16, s);
+    if (e != hipSuccess || n == 0) return e;
+    const int n_pad = bf_short_rows_padded(n);
+    int grid = (n_pad + 3) / 4;
+    if (grid > 2048) grid = 2048;
+    hipLaunchKernelGGL(short_rows_kernel, dim3(grid), dim3(256), 0, s, rows, n, n_pad, ld, dim, dst.vh, dst.scale,
+                       static_cast<_Float16*>(dst.h16), aux, aux_pad, aux_mul, dst.aux16, reinterpret_cast<unsigned*>(out));
+    return hipGetLastError();
+}
+
 template <int MODE, bool SAMPLE, int QG>
 static hipError_t launch_scan_f32_one(const BfScanF32Args& a, int grid, size_t lds, hipStream_t s) {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(bf_scan_f32_kernel<MODE, SAMPLE, QG>),
@@ -3908,6 +4086,22 @@ static hipError_t launch_scan_bf16_one(const BfScanF32Args& a, int grid, size_t 
     return hipGetLastError();
 }
 // terms: 3 = the split product, 1 = one bf16 product (the sample pass: always, 256 queries per workgroup)
+// the short scan's instantiations: eight waves, like the served shapes of the 128-column scan
+template <int MODE>
+static hipError_t launch_scan_short_mode(const BfScanF32Args& a, bool sample, int qg, int grid, size_t lds, hipStream_t s) {
+    if constexpr (MODE == SC_COS) {
+        return hipErrorInvalidValue;
+    } else {
+        auto go = [&](auto kern) -> hipError_t {
+            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a);
+            return hipGetLastError();
+        };
+        if (sample) return go(bf_scan_bf16_kernel<MODE, true, 1, 8, 1, true>);
+        return qg == 2 ? go(bf_scan_bf16_kernel<MODE, false, 2, 8, 1, true>) : go(bf_scan_bf16_kernel<MODE, false, 1, 8, 1, true>);
+    }
+}
 template <int MODE>
 static hipError_t launch_scan_f32_mode(const BfScanF32Args& a, bool sample, int terms, int qg, int grid, size_t lds, hipStream_t s, int kch = 1) {
     // The one-product kernel runs with EIGHT waves per workgroup, two per SIMD, each serving half the query groups of the
@@ -4047,7 +4241,42 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
     void* q_lo = ws.q_tile(f, BfFastWs::Q_LO);
     void* q_h16 = ws.q_tile(f, BfFastWs::Q_H16);
     hipError_t e;
-    {   // pad (when the caller passes the raw queries) + bf16 split + every clear of the batch
+    // the short scan serves the batch: head tiles of 64 columns through the sample pass and the scan, the
+    // bound E_s per query in E1's place, no split-product scan (a tile without room goes to the adaptive kernel)
+    const BfShortTiles& sh = tiles.sh;
+    const bool shortscan_on = f.short_ok && sh.h16 != nullptr && q.raw != nullptr;
+    float* e_short = shortscan_on ? static_cast<float*>(q_hi) : nullptr;   // (the bf16 query tiles are not made)
+    static const int dbg = getenv("NMSLIB_GPU_DEBUG") ? atoi(getenv("NMSLIB_GPU_DEBUG")) : 0;
+    if (shortscan_on) {
+        const BfPlan& fb = f.fallback;
+        ShortPrepArgs pa{};
+        pa.raw = q.raw;
+        pa.nq = nq;
+        pa.dim = sdim;
+        pa.qpad = f.qpad;
+        pa.ld = sld;
+        pa.pad_out = q.padded;
+        pa.vh = sh.vh;
+        pa.qh16 = static_cast<_Float16*>(q_h16);
+        pa.es = e_short;
+        pa.clr0 = tile_fail;
+        pa.n0 = 2 * f.nqt;
+        pa.clr1 = ws.flags_fb;
+        pa.n1 = fb.nqt;
+        pa.clr2 = reinterpret_cast<uint32_t*>(ws.fb.cnt + (size_t)fb.qpad * fb.nsplit);
+        pa.n2 = 2 * ((size_t)fb.qpad + (size_t)fb.qpad * fb.nsplit);
+        pa.scale_q = sh.scale;
+        pa.unit = sh.scale * sh.scale;
+        pa.bscale_h = sh.bscale_h;
+        pa.bres_h = sh.bres_h;
+        pa.b_tail = sh.b_tail;
+        pa.bmax = sh.bmax;
+        pa.coeff = sh.coeff;
+        pa.tail_abs = sh.tail_abs;
+        hipLaunchKernelGGL(bf_f32_prep_short_kernel, dim3((unsigned)(f.qpad / 4)), dim3(256), 0, s, pa);
+        e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    } else {   // pad (when the caller passes the raw queries) + bf16 split + every clear of the batch
         const BfPlan& fb = f.fallback;
         uint32_t* gthr = reinterpret_cast<uint32_t*>(ws.fb.cnt + (size_t)fb.qpad * fb.nsplit);
         const size_t gwords = 2 * ((size_t)fb.qpad + (size_t)fb.qpad * fb.nsplit);
@@ -4062,6 +4291,11 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
         if (e != hipSuccess) return e;
     }
     auto scan = [&](const BfScanF32Args& sa, bool sample, int terms, int grid) -> hipError_t {
+        if (shortscan_on) {
+            if (terms != 1) return hipSuccess;   // (no split-product scan beside the short scan)
+            if (f.mode == 0) return launch_scan_short_mode<SC_L2>(sa, sample, f.qg, grid, f.lds_short, s);
+            return launch_scan_short_mode<SC_DOT>(sa, sample, f.qg, grid, f.lds_short, s);
+        }
         const size_t lds = terms == 1 ? f.lds_scan1 : f.lds_scan;
         if (f.mode == 0) return launch_scan_f32_mode<SC_L2>(sa, sample, terms, f.qg, grid, lds, s, f.kch);
         if (f.mode == 1) return launch_scan_f32_mode<SC_DOT>(sa, sample, terms, f.qg, grid, lds, s, f.kch);
@@ -4080,13 +4314,17 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
     }
     a.q_h16 = q_h16;
     a.auxp16 = tiles.auxp16;
+    if (shortscan_on) {
+        a.base_h16 = sh.h16;
+        a.auxp16 = sh.aux16;
+    }
     a.n = rows.n;
     a.nqt = f.nqt;
     // 1. sample pass (one product: the scores carry the error E1) + thresholds + the choice of the scan per query tile
     BfScanF32Args sa = a;
     sa.nqt = f.qpad / (f.kch > 1 ? 128 : 256);
     sa.nsplit = f.s_nsplit;
-    sa.tps = f.s_tps;
+    sa.tps = shortscan_on ? f.short_s_tps : f.s_tps;
     sa.tile_stride = f.stride;
     sa.top8 = top8;
     e = scan(sa, true, 1, 8 * sa.nqt * (f.s_nsplit / 8));
@@ -4098,7 +4336,8 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
         const dim3 tgrid((f.qpad + 3) / 4);
 #define BF_THR_ARGS                                                                                                               \
     top8, 2 * f.s_nsplit, depth, f.r, f.rcap, nq, f.qpad, q.sel, sld, sdim, tiles.scale * (f.mode == 2 ? 1.0f : tiles.bmax), tiles.bres16, f.tq, \
-        f.force_precise ? 1 : (dbg_nohit ? 2 : 0), thr, thr1, precise, q.scale_q, tiles.scale * q.scale_q
+        f.force_precise ? 1 : (dbg_nohit ? 2 : 0), thr, thr1, precise, q.scale_q, tiles.scale * q.scale_q, e_short,                    \
+        shortscan_on ? sh.miss : nullptr
         if (2 * f.s_nsplit * depth <= 512) hipLaunchKernelGGL(bf_f32_threshold_kernel<8>, tgrid, dim3(256), 0, s, BF_THR_ARGS);
         else hipLaunchKernelGGL(bf_f32_threshold_kernel<16>, tgrid, dim3(256), 0, s, BF_THR_ARGS);   // (s_nsplit <= 64)
 #undef BF_THR_ARGS
@@ -4109,7 +4348,7 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
     a.list = ws.list;
     a.list_cnt = ws.list_cnt;
     a.nsplit = f.nsplit;
-    a.tps = f.tps;
+    a.tps = shortscan_on ? f.short_tps : f.tps;
     a.caph = f.caph;
     a.tile_stride = 1;
     a.group_flag = precise;
@@ -4142,18 +4381,19 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
     r.k = k;
     r.nsplit = f.nsplit;
     r.caph = f.caph;
-    r.tps = f.tps;
+    r.tps = shortscan_on ? 2 * f.short_tps : f.tps;   // (64-row tiles: a split's first row)
     r.p2max = f.p2max;
     r.fail_queries = f.tq;
-    r.no_split = f.kch > 1 ? 1 : 0;
+    r.no_split = f.kch > 1 || shortscan_on ? 1 : 0;
+    r.e_short = e_short;
     r.space = space;
     r.dim = rows.dim;
     r.ldb = rows.ldb;
     r.queries_sel = q.sel;
     r.sel_dim = sdim;
     r.sel_ld = sld;
-    r.scale = tiles.scale;
-    r.scale_q = q.scale_q;
+    r.scale = shortscan_on ? sh.scale : tiles.scale;
+    r.scale_q = shortscan_on ? sh.scale : q.scale_q;
     r.bres16 = tiles.bres16;
     r.qaux = f.cosc ? q.qaux_cosc : nullptr;
     r.thr = thr;
@@ -4162,7 +4402,6 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
     r.list_m_off = ws.list_m_off(f);
     r.bmax = tiles.bmax;
     r.bres = tiles.bres;
-    static const int dbg = getenv("NMSLIB_GPU_DEBUG") ? atoi(getenv("NMSLIB_GPU_DEBUG")) : 0;
     static unsigned long long* d_prof = nullptr;
     if (dbg & 4096) {
         if (!d_prof) (void)hipMalloc(&d_prof, 16 * 8);
@@ -4178,6 +4417,25 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
     if (dbg & 4096) {
         dump_rerank_list_clocks(d_prof, s);
         dump_rerank_list_residency(rerank, f.lds_rerank, nq);
+    }
+    // (the short scan's line follows the switch as it stands at this batch, not as the process first saw it: a caller can
+    //  ask one batch which tier served it)
+    const char* dbg_now = getenv("NMSLIB_GPU_DEBUG");
+    if (dbg_now && (atoi(dbg_now) & 4096)) {
+        if (shortscan_on) {
+            (void)hipStreamSynchronize(s);
+            std::vector<float> es((size_t)nq);
+            (void)hipMemcpy(es.data(), e_short, es.size() * 4, hipMemcpyDeviceToHost);
+            double sum = 0, mx = 0;
+            for (float v : es) {
+                sum += v;
+                mx = v > mx ? v : mx;
+            }
+            fprintf(stderr, "[short scan] served 1 E_s mean %.6g max %.6g (units of scale^2 = %.6g) b_tailmax %.6g bmax %.6g\n",
+                    nq ? sum / nq : 0.0, mx, (double)sh.scale * sh.scale, (double)sh.b_tail, (double)sh.bmax);
+        } else {
+            fprintf(stderr, "[short scan] served 0\n");
+        }
     }
     if (dbg & 2048) dump_f32_fast_checksums(f, ws, s);
     // 4. fallback: the adaptive f32 kernel + its re-rank (verified for l2, with its exact tail) for flagged query tiles

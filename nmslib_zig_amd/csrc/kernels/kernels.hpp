@@ -10,6 +10,7 @@
 #include "../diverg_filter.hpp"
 #include "../diverg_js_filter.hpp"
 #include "../ham_fast_plan.hpp"
+#include "../short_scan_plan.hpp"
 #include "../sparse_filter.hpp"
 
 namespace gfxknn {
@@ -208,6 +209,11 @@ struct BfF32Fast {
     int s_nsplit, s_tps;
     size_t lds_scan, lds_scan1, lds_thr, lds_rerank;
     BfPlan fallback;
+    // the short scan: the batch may run on an index's short tiles (l2 / negdotprod, 64 < dim <= 128, not
+    // centred; NMSLIB_GPU_F32_SHORT=0 forbids it) -- with these 128-row stages per split of the scan / of the sample pass
+    bool short_ok;
+    int short_tps, short_s_tps;
+    size_t lds_short;
 };
 BfF32Fast bf_f32_fast_plan(int n, int dim, int nq, int k, int space, bool cosine_centred);
 
@@ -260,6 +266,27 @@ hipError_t launch_row_maxnorm(const float* rows, int n, int ld, int dim, bool re
 // [n_pad][128] and start values auxp [n_pad] of the split-product scan (hi / lo: null when dp > 128); fp16(scale * row)
 // tiles [n_pad][dp] and start values auxp16 of the one-product scan, with the rows' largest fp16 residual (scaled units);
 // largest norm and bf16 residual of the rows the tiles were cut from (centred cosine / angular: the augmented rows).
+// The short scan's resident side (h16 null: the index has none, or the batch may not use it): fp16(scale * head) tiles
+// [n_pad / 2][128] (rows r and r + 32 of a 64-row group share a tile row), their start values, the rotation's first 64
+// columns [128][64] and the constants of the bound E_s (short_scan_plan.hpp); miss: a word the threshold kernel sets when a
+// query finds no room for its bound (pinned host memory)
+struct BfShortTiles {
+    void* h16;
+    float* aux16;
+    const float* vh;
+    float scale;               // of the row heads and the query heads
+    float bscale_h, bres_h;    // scale * largest |row head|; largest fp16 residual of the scaled row heads
+    float b_tail, bmax;        // largest row tail with its allowance; largest row norm
+    float coeff, tail_abs;     // shortscan::Rotation's
+    int* miss;
+};
+inline int bf_short_rows_padded(int n) { return (n + 2 * BF_BN - 1) / (2 * BF_BN) * (2 * BF_BN); }
+// m [dim][dim] (f64) = sum over every stride-th row of x x^T
+hipError_t launch_short_moment(const float* rows, int n, int ld, int dim, int stride, double* m, hipStream_t s);
+// out (16 bytes, cleared here): largest |head element|, largest tail, largest |head|, largest fp16 residual of scale * head;
+// dst.h16 null: those maxima only (the first two say which scale to take), else the tiles and start values too
+hipError_t launch_short_rows(const float* rows, int n, int ld, int dim, const float* aux, float aux_pad, float aux_mul,
+                             const BfShortTiles& dst, float* out, hipStream_t s);
 struct BfF32Tiles {
     void *hi, *lo;
     float* auxp;
@@ -268,6 +295,7 @@ struct BfF32Tiles {
     float scale, bres16;
     int dp;
     float bmax, bres;
+    BfShortTiles sh;
 };
 // src rows [n][ld] of `cols` columns -> the tiles of dst, n_pad rows of dst.dp columns each; auxp = aux (null: 0),
 // auxp16 = aux * aux16_mul, both aux_pad behind the n rows
