@@ -117,7 +117,10 @@ typedef struct {
                               16 = the hardware-log2 filter of the Jensen-Shannon spaces (jsdivslow, jsdivfast, jsmetrslow,
                               jsmetrfast) with its exact re-rank (fast_tiles and fast_tiles_fallback as for 14);
                               17 = the exact bit_hamming scan on the int8 matrix cores (65 536 rows and 256 queries or more,
-                              k <= 128, codes of at most 1024 bits; NMSLIB_GPU_HAM_FAST=0 turns it off) */
+                              k <= 128, codes of at most 1024 bits; NMSLIB_GPU_HAM_FAST=0 turns it off);
+                              18 = the exact bit_jaccard scan on the int8 matrix cores (65 536 rows and 256 queries or more,
+                              k <= 16, or k <= 32 on codes of 1024 bits or more, codes of at most 2048 bits;
+                              NMSLIB_GPU_JAC_FAST=0 turns it off) */
     /* fast paths, last slice of the last batch (reading them waits for the stream): query tiles in the slice, tiles the
        threshold kernel sent through the split-bf16-product scan instead of the one-product scan (float rows only), and
        tiles whose verification failed and were redone by the adaptive kernel */

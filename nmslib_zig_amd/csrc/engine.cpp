@@ -232,13 +232,26 @@ Engine::Engine(const std::string& space, const std::string& method, int data_typ
         return;
     }
     if (data_type == 3) {
-        // the int-registry string spaces (include/factory/init_spaces.h:47-53) with the int distance; normleven and
-        // bit_jaccard are float spaces that the reference's data type 3 dispatch would treat as int indexes
+        // the int-registry string spaces (include/factory/init_spaces.h:47-53) with the int distance, and bit_jaccard
+        // (SpaceBitJaccard<float, uint32_t>, the float registry) with the float distance over bit_hamming's objects: an
+        // exact scan only.  The reference's data type 3 dispatch would treat it, and normleven, as an int index
         // (nmslib_c.cpp:205-208)
+        if (space == "bit_jaccard") {
+            if (dist_type != 0)
+                throw EngineError(Err::SpaceIncompatible, "string space 'bit_jaccard' is served with the float distance type");
+            if (method != "brute_force" && method != "seq_search")
+                throw EngineError(Err::SpaceIncompatible,
+                                  "method '" + method + "' over bit_jaccard is not served: no graph is built over it "
+                                  "(bit_jaccard: brute_force, seq_search)");
+            space_ = SP_BIT_JACCARD;
+            str_space_ = true;
+            thread_pool_size = std::thread::hardware_concurrency();
+            return;
+        }
         if (space != "leven" && space != "bit_hamming")
             throw EngineError(Err::SpaceIncompatible,
                               "string space '" + space + "' is not served by the GPU engine (string spaces: leven, "
-                              "bit_hamming)");
+                              "bit_hamming, bit_jaccard)");
         if (dist_type != 1)
             throw EngineError(Err::SpaceIncompatible, "string space '" + space + "' is served with the int distance type");
         if (method != "brute_force" && method != "seq_search" && method != "hnsw")

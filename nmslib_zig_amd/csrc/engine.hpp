@@ -470,7 +470,13 @@ class Engine {
                        const int32_t** cnt);
     using ScanLaunch = std::function<void(const ScanPlan& p, size_t q0, float* split_d, int32_t* split_pos)>;
     void scan_slices(size_t nq, size_t k, int tq, const ResultBlock& out, const ScanLaunch& launch);
+    // the two matrix-core scans over bit rows: one slicing and merging body, the scan kernel given by its launcher
+    using BitFastLaunch = hipError_t (*)(const hamfast::Plan& p, bool sample, const uint32_t* rows, int n, const uint32_t* q,
+                                         int nq, int k, const float* bound, float* split_d, int32_t* split_pos, hipStream_t s);
+    void knn_bit_fast(BitFastLaunch launch, const char* what, const hamfast::Plan& f, const uint32_t* d_qw, size_t nq,
+                      size_t k, const ResultBlock& out);
     void knn_ham_fast(const hamfast::Plan& f, const uint32_t* d_qw, size_t nq, size_t k, const ResultBlock& out);
+    void knn_jac_fast(const jacfast::Plan& f, const uint32_t* d_qw, size_t nq, size_t k, const ResultBlock& out);
     // ---- dense range search (range.cpp) ----
     using RangeLaunch = std::function<void(float* filter, float* report)>;
     size_t range_select(bool two_dists, float r, size_t capacity, int32_t* ids, float* dists, const RangeLaunch& launch);
@@ -556,6 +562,8 @@ class Engine {
     static bool parse_bits(const char* s, size_t len, std::vector<uint32_t>& words, size_t& bits);
     void string_query(const char* s, size_t len, Err parse_err, std::vector<uint32_t>& words) const;
     size_t ham_words() const { return st_bits_ > 0 ? (size_t)(st_bits_ + 31) / 32 : 0; }
+    // the bit rows' space as error messages name it (bit_hamming and bit_jaccard share parser, store and objects)
+    std::string bit_name() const { return space_ == SP_BIT_JACCARD ? "bit_jaccard" : "bit_hamming"; }
     void ensure_graph();
     void finalize_index();                        // finalize() without the tombstones' upload
     bool is_dead(size_t pos) const { return (pos >> 5) < tomb_.size() && ((tomb_[pos >> 5] >> (pos & 31)) & 1u); }

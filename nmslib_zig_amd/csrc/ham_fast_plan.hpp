@@ -38,14 +38,11 @@ struct Plan {
     size_t lds = 0;            // dynamic LDS of a workgroup: query words [W][tile], lists [cap][tile], counters [tile]
 };
 
-inline Plan plan(bool exact_scan, long long n, long long nq, long long k, long long bits) {
-    Plan p;
-    if (!exact_scan || n < kMinRows || n > 0x7FFFFFFFll || nq < kMinQueries || k < 1 || k > kMaxK || bits < kMinBits ||
-        bits > kMaxBits)
-        return p;
+// The split of n >= kMinRows rows and nq queries at 1 <= k <= kMaxK, the sample pass and the list capacity (everything but
+// W and lds); false when no split keeps within both limits.  Shared with the bit_jaccard scan (jac_fast_plan.hpp).
+inline bool split_rows(Plan& p, long long n, long long nq, long long k) {
     const long long min_split = (n + kSplitMaxRows - 1) / kSplitMaxRows, max_split = kMergeKeys / k;
-    if (min_split > max_split) return p;
-    p.W = (int)((bits + 31) / 32);
+    if (min_split > max_split) return false;
     p.cap = 2 * (int)k + 32;
     p.qb = kQueryGroups;
     p.tile = 32 * p.qb;
@@ -61,6 +58,16 @@ inline Plan plan(bool exact_scan, long long n, long long nq, long long k, long l
     p.sample_rows = kSampleRows;   // (< kMinRows <= n; >= kMaxK rows: every query has a k-th distance there)
     p.sample_nsplit = p.nsplit < kSampleSplits ? p.nsplit : kSampleSplits;
     while (p.sample_rows % (p.sample_nsplit * kRowBlock)) --p.sample_nsplit;
+    return true;
+}
+
+inline Plan plan(bool exact_scan, long long n, long long nq, long long k, long long bits) {
+    Plan p;
+    if (!exact_scan || n < kMinRows || n > 0x7FFFFFFFll || nq < kMinQueries || k < 1 || k > kMaxK || bits < kMinBits ||
+        bits > kMaxBits)
+        return p;
+    if (!split_rows(p, n, nq, k)) return p;
+    p.W = (int)((bits + 31) / 32);
     p.lds = ((size_t)p.W + p.cap + 1) * p.tile * 4;
     p.use = true;
     return p;

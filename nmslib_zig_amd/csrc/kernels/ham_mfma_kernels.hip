@@ -28,7 +28,7 @@
 //   then takes about rows * k / kSampleRows keys and is rarely cut before the end.
 //   Output.  The per-split format of the other scans: split_d / split_pos [nsplit][nq][k], ascending, padded with
 //   (+inf, -1); launch_merge_topk_ex merges the splits.
-#include "common_dev.hpp"
+#include "bit_list_dev.hpp"
 
 namespace gfxknn {
 
@@ -91,39 +91,9 @@ __global__ __launch_bounds__(64) void ham_mfma_knn_kernel(const uint32_t* __rest
         thr[g] = bound ? ((uint32_t)bound[(size_t)min(q_first + g * 32 + l31, nq - 1) * k + (k - 1)] + 1u) << 16 : kNoKey;
     }
 
-    // Every list cut to its k smallest keys, ascending: lane t sorts the list of query t of the tile (the same network
-    // for all lanes).  The network is the bitonic sorter with every comparator ascending (a merge's first step pairs
-    // i with its mirror), over the power of two P >= cap: the places at and beyond cap stand for keys above every real
-    // one, which an ascending comparator never moves, so comparators that reach them are skipped.
+    // every list cut to its k smallest keys (bit_list_dev.hpp); a full list's k-th key is its query's new threshold
     auto cut = [&]() __attribute__((always_inline)) {
-        __syncthreads();   // (one wave: the appends before, the reads below)
-        uint32_t* s = s_keys + lane;
-        const int c = s_cnt[lane];
-        for (int e = 0; e < cap; ++e)
-            if (e >= c) s[(size_t)e * QT] = kNoKey;
-        auto order = [&](int i, int l) __attribute__((always_inline)) {
-            if (l < cap) {
-                const uint32_t a = s[(size_t)i * QT], b = s[(size_t)l * QT];
-                s[(size_t)i * QT] = min(a, b);
-                s[(size_t)l * QT] = max(a, b);
-            }
-        };
-        int P = 2;
-        while (P < cap) P <<= 1;
-        for (int k2 = 2; k2 <= P; k2 <<= 1) {
-            const int hk = k2 >> 1;
-            for (int t = 0; t < (P >> 1); ++t) {
-                const int i = (t / hk) * k2 + (t & (hk - 1));
-                order(i, i ^ (k2 - 1));
-            }
-            for (int j = k2 >> 2; j > 0; j >>= 1)
-                for (int t = 0; t < (P >> 1); ++t) {
-                    const int i = 2 * t - (t & (j - 1));
-                    order(i, i + j);
-                }
-        }
-        if (c >= k) s_cnt[lane] = k;
-        __syncthreads();
+        bit_list_cut<uint32_t, QT>(s_keys, s_cnt, lane, cap, k, kNoKey);
 #pragma unroll
         for (int g = 0; g < QB; ++g)
             if (s_cnt[g * 32 + l31] >= k) thr[g] = s_keys[(size_t)(k - 1) * QT + g * 32 + l31];
@@ -146,25 +116,11 @@ __global__ __launch_bounds__(64) void ham_mfma_knn_kernel(const uint32_t* __rest
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[rb][g][i] = pq[g];
 
-        auto load = [&](int w0, uint32_t (&x)[4][4]) __attribute__((always_inline)) {
-#pragma unroll
-            for (int rb = 0; rb < 4; ++rb) {
-                if constexpr (VEC) {
-                    const uint4 v = *reinterpret_cast<const uint4*>(rp[rb] + w0);
-                    x[rb][0] = v.x;
-                    x[rb][1] = v.y;
-                    x[rb][2] = v.z;
-                    x[rb][3] = v.w;
-                } else {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) x[rb][j] = w0 + j < W ? rp[rb][w0 + j] : 0u;
-                }
-            }
-        };
         uint32_t cur[4][4], nxt[4][4] = {};
-        load(0, cur);
+        bit_rows_load<VEC>(rp, 0, W, cur);
         for (int w0 = 0; w0 < W; w0 += 4) {
-            if (w0 + 4 < W) load(w0 + 4, nxt);   // the next four words are in flight under this chunk's MFMAs
+            // the next four words are in flight under this chunk's MFMAs
+            if (w0 + 4 < W) bit_rows_load<VEC>(rp, w0 + 4, W, nxt);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 if (w0 + j < W) {

@@ -10,6 +10,7 @@
 #include "../diverg_filter.hpp"
 #include "../diverg_js_filter.hpp"
 #include "../ham_fast_plan.hpp"
+#include "../jac_fast_plan.hpp"
 #include "../short_scan_plan.hpp"
 #include "../sparse_filter.hpp"
 
@@ -45,6 +46,8 @@ enum SpaceCode : int {
     SP_JSDIV_SLOW = 19,
     SP_JSMETR = 20,
     SP_JSMETR_SLOW = 21,
+    // strings again: Tanimoto distance over the packed bit rows of SP_BIT_HAMMING, a float distance
+    SP_BIT_JACCARD = 22,
 };
 
 // ---- geometry shared by host and device ------------------------------------------------
@@ -791,6 +794,16 @@ hipError_t launch_ham_knn(const ScanPlan& p, const uint32_t* rows, int W, const 
 // sample_nsplit splits, else over all n rows in nsplit splits; bound (may be null): [nq][k] ascending distances of k
 // rows per query, whose last one no row of the result exceeds
 hipError_t launch_ham_mfma_knn(const hamfast::Plan& p, bool sample, const uint32_t* rows, int n, const uint32_t* q, int nq,
+                               int k, const float* bound, float* split_d, int32_t* split_pos, hipStream_t s);
+// bit_jaccard over the same rows and queries (jaccard_kernels.hip; the distance: jaccard_dev.hpp): the scan in the shape of
+// launch_ham_knn, one distance per row, one pair
+hipError_t launch_jac_knn(const ScanPlan& p, const uint32_t* rows, int W, const uint32_t* q, float* split_d,
+                          int32_t* split_pos, hipStream_t s);
+hipError_t launch_jac_dist(const uint32_t* rows, int W, int n, const uint32_t* q, float* d_out, hipStream_t s);
+hipError_t launch_jac_pair(const uint32_t* rows, int W, int p1, int p2, float* out, hipStream_t s);
+// bit_jaccard on the int8 matrix cores (jaccard_mfma_kernels.hip; the plan: jac_fast_plan.hpp): launch_ham_mfma_knn's
+// interface, the bound's distances being the f32 Jaccard distances of the sample
+hipError_t launch_jac_mfma_knn(const jacfast::Plan& p, bool sample, const uint32_t* rows, int n, const uint32_t* q, int nq,
                                int k, const float* bound, float* split_d, int32_t* split_pos, hipStream_t s);
 // d_out[r] = distance(row r, query); leven: mw_ws holds 2 * nw * 256 * leven_dist_grid(n) words when nw > 1
 int leven_dist_grid(int n);

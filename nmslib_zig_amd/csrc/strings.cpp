@@ -4,6 +4,8 @@
 //   leven      : CSR of the strings' bytes (StringSpace::CreateObjFromStr keeps the bytes as they are).
 //   bit_hamming: the text is parsed as the reference's ReadBitMaskVect does (include/space/space_bit_vector.h:
 //                156-200) and packed into W uint32 words per row; the bit count is fixed by the first row.
+//   bit_jaccard: bit_hamming's rows, through the same functions; the float distance of kernels/jaccard_kernels.hip, exact
+//                scan only.
 #include <algorithm>
 #include <cctype>
 #include <cerrno>
@@ -95,14 +97,17 @@ void Engine::add_strings(const char* const* strs, const size_t* lens, size_t cou
     } else {
         std::vector<uint32_t> packed, w;
         int64_t bits = st_bits_;
+        const std::string name = bit_name();
+        // bit_jaccard: both counts of a pair are exact in f32 below 2^24
+        const size_t max_bits = space_ == SP_BIT_JACCARD ? ((size_t)1 << 24) - 1 : (size_t)INT32_MAX;
         for (size_t i = 0; i < count; ++i) {
             size_t b = 0;
             if (!parse_bits(strs[i], lens[i], w, b))
-                throw EngineError(Err::Runtime, "bit_hamming: failed to parse the row (only 0 and 1 values are allowed)");
-            if (b == 0) throw EngineError(Err::InvalidArgument, "bit_hamming: a row holds at least one bit");
-            if (b > (size_t)INT32_MAX) throw EngineError(Err::InvalidArgument, "bit_hamming: row too long");
+                throw EngineError(Err::Runtime, name + ": failed to parse the row (only 0 and 1 values are allowed)");
+            if (b == 0) throw EngineError(Err::InvalidArgument, name + ": a row holds at least one bit");
+            if (b > max_bits) throw EngineError(Err::InvalidArgument, name + ": row too long");
             if (bits >= 0 && (int64_t)b != bits)
-                throw EngineError(Err::InvalidArgument, "bit_hamming: the row has " + std::to_string(b) +
+                throw EngineError(Err::InvalidArgument, name + ": the row has " + std::to_string(b) +
                                                             " bits, the index " + std::to_string(bits));
             bits = (int64_t)b;
             packed.insert(packed.end(), w.begin(), w.end());
@@ -261,9 +266,9 @@ void Engine::string_query(const char* s, size_t len, Err parse_err, std::vector<
     }
     size_t b = 0;
     if (!parse_bits(s, len, words, b))
-        throw EngineError(parse_err, "bit_hamming: failed to parse the query (only 0 and 1 values are allowed)");
+        throw EngineError(parse_err, bit_name() + ": failed to parse the query (only 0 and 1 values are allowed)");
     if ((int64_t)b != st_bits_)
-        throw EngineError(Err::InvalidArgument, "bit_hamming: the query has " + std::to_string(b) + " bits, the index " +
+        throw EngineError(Err::InvalidArgument, bit_name() + ": the query has " + std::to_string(b) + " bits, the index " +
                                                     std::to_string(st_bits_));
 }
 
@@ -287,7 +292,7 @@ void Engine::knn_string_host(const char* const* queries, const size_t* lens, siz
             qwords.insert(qwords.end(), w.begin(), w.end());
         }
     }
-    if (!lev && st_bits_ < 0) throw EngineError(Err::QueryExecutionFailed, "bit_hamming: the index holds no rows");
+    if (!lev && st_bits_ < 0) throw EngineError(Err::QueryExecutionFailed, bit_name() + ": the index holds no rows");
     if (dirty_) finalize();
     check_device();
     order_after_last(stream_);
@@ -325,7 +330,19 @@ void Engine::knn_string_host(const char* const* queries, const size_t* lens, siz
         return;
     }
     have_counters_ = false;
-    if (!lev) {
+    const bool jac = space_ == SP_BIT_JACCARD;
+    if (jac) {
+        const char* env = getenv("NMSLIB_GPU_JAC_FAST");
+        // 0: the path off; 2: its k gate lifted to what the kernel holds, for tools/jac_fast_time.py to time a cell outside it
+        const jacfast::Plan f = jacfast::plan(method_ == Method::Brute, (long long)d_n_, (long long)nq, (long long)k, st_bits_,
+                                              env && atoi(env) == 2);
+        if (f.use && !(env && atoi(env) == 0)) {
+            knn_jac_fast(f, d_qw, nq, k, out);
+            fetch_results(nq, k, "string knn", ids, dists, cnt);
+            last_path = 18;
+            return;
+        }
+    } else if (!lev) {
         const char* env = getenv("NMSLIB_GPU_HAM_FAST");
         const hamfast::Plan f = hamfast::plan(method_ == Method::Brute, (long long)d_n_, (long long)nq, (long long)k, st_bits_);
         if (f.use && !(env && atoi(env) == 0)) {
@@ -344,6 +361,9 @@ void Engine::knn_string_host(const char* const* queries, const size_t* lens, siz
                                        d_peq, nw_max, mw ? ws_st_mw_.as<uint64_t>() : nullptr, split_d, split_pos,
                                        stream_),
                       "leven scan");
+        } else if (jac) {
+            hip_check(launch_jac_knn(p, d_st_data_.as<uint32_t>(), (int)W, d_qw + q0 * W, split_d, split_pos, stream_),
+                      "bit_jaccard scan");
         } else {
             hip_check(launch_ham_knn(p, d_st_data_.as<uint32_t>(), (int)W, d_qw + q0 * W, split_d, split_pos, stream_),
                       "bit_hamming scan");
@@ -356,6 +376,17 @@ void Engine::knn_string_host(const char* const* queries, const size_t* lens, siz
 // bit_hamming on the int8 matrix cores (kernels/ham_mfma_kernels.hip; last_path 17): the batch in slices of whole query
 // tiles whose per-split lists stay within 256 MiB, each merged into `out` like a slice of scan_slices
 void Engine::knn_ham_fast(const hamfast::Plan& f, const uint32_t* d_qw, size_t nq, size_t k, const ResultBlock& out) {
+    knn_bit_fast(launch_ham_mfma_knn, "bit_hamming matrix-core scan", f, d_qw, nq, k, out);
+}
+
+// bit_jaccard likewise (kernels/jaccard_mfma_kernels.hip; last_path 18): the same lists, float distances in them
+void Engine::knn_jac_fast(const jacfast::Plan& f, const uint32_t* d_qw, size_t nq, size_t k, const ResultBlock& out) {
+    knn_bit_fast(launch_jac_mfma_knn, "bit_jaccard matrix-core scan", f, d_qw, nq, k, out);
+}
+
+// the slices of both: whole query tiles whose per-split lists stay within 256 MiB
+void Engine::knn_bit_fast(BitFastLaunch launch, const char* what, const hamfast::Plan& f, const uint32_t* d_qw, size_t nq,
+                          size_t k, const ResultBlock& out) {
     const size_t max_split_keys = (size_t)1 << 25;
     size_t m = std::min<size_t>(nq, 32768);
     const size_t fit = max_split_keys / ((size_t)f.nsplit * k) / f.tile * f.tile;
@@ -375,9 +406,9 @@ void Engine::knn_ham_fast(const hamfast::Plan& f, const uint32_t* d_qw, size_t n
             const bool sample = pass == 0;
             const int ns = sample ? f.sample_nsplit : f.nsplit;
             int32_t* split_pos = reinterpret_cast<int32_t*>(split_d + (size_t)ns * mm * k);
-            hip_check(launch_ham_mfma_knn(f, sample, rows, (int)d_n_, d_qw + q0 * f.W, (int)mm, (int)k, sample ? nullptr : bound,
-                                          split_d, split_pos, stream_),
-                      "bit_hamming matrix-core scan");
+            hip_check(launch(f, sample, rows, (int)d_n_, d_qw + q0 * f.W, (int)mm, (int)k, sample ? nullptr : bound, split_d,
+                             split_pos, stream_),
+                      what);
             hip_check(launch_merge_topk_ex(split_d, split_pos, mm * k, ns, (int)mm, (int)k, sample ? bound : out.dists + q0 * k,
                                            sample ? bound_ids : out.ids + q0 * k, sample ? bound_ids + mm * k : out.cnt + q0,
                                            d_ids_.as<int32_t>(), stream_),
@@ -398,10 +429,11 @@ size_t Engine::range_string_host(const char* query, size_t len, double radius, s
     order_after_last(stream_);
     const size_t n = d_n_;
     if (n == 0 || capacity == 0) return 0;
-    // RangeQuery<int>(space, obj, static_cast<int>(radius)), nmslib_c.cpp:1092-1093: the radius truncates to int
+    // RangeQuery<int>(space, obj, static_cast<int>(radius)), nmslib_c.cpp:1092-1093: the radius truncates to int.
+    // bit_jaccard is a float space: the radius is a float, and a row is returned when d <= (float)radius
     const double rc = std::max(-1.0, std::min(radius, 2147483647.0));
-    const float r = (float)(int)rc;
-    // both distances are symmetric: the filter d(row, query) is also the reported d(query, row)
+    const float r = space_ == SP_BIT_JACCARD ? (float)radius : (float)(int)rc;
+    // the distances are symmetric: the filter d(row, query) is also the reported d(query, row)
     return range_select(false, r, capacity, ids, dists, [&](float* d, float*) {
         if (lev) {
             const size_t nw = (len + 63) / 64;
@@ -417,8 +449,9 @@ size_t Engine::range_string_host(const char* query, size_t len, double radius, s
         } else {
             ws_q_.ensure(std::max<size_t>(qw.size(), 1) * 4);
             hip_check(hipMemcpyAsync(ws_q_.ptr(), qw.data(), qw.size() * 4, hipMemcpyHostToDevice, stream_), "query H2D");
-            hip_check(launch_ham_dist(d_st_data_.as<uint32_t>(), (int)ham_words(), (int)n, ws_q_.as<uint32_t>(), d, stream_),
-                      "bit_hamming range distances");
+            const auto dist = space_ == SP_BIT_JACCARD ? launch_jac_dist : launch_ham_dist;
+            hip_check(dist(d_st_data_.as<uint32_t>(), (int)ham_words(), (int)n, ws_q_.as<uint32_t>(), d, stream_),
+                      (bit_name() + " range distances").c_str());
         }
     });
 }
@@ -441,8 +474,9 @@ float Engine::pair_distance_string(size_t p1, size_t p2) {
                                     d_peq + peq.size(), out, stream_),
                   "leven pair distance");
     } else {
-        hip_check(launch_ham_pair(d_st_data_.as<uint32_t>(), (int)ham_words(), (int)p1, (int)p2, out, stream_),
-                  "bit_hamming pair distance");
+        const auto pair = space_ == SP_BIT_JACCARD ? launch_jac_pair : launch_ham_pair;
+        hip_check(pair(d_st_data_.as<uint32_t>(), (int)ham_words(), (int)p1, (int)p2, out, stream_),
+                  (bit_name() + " pair distance").c_str());
     }
     return read_float(out, "string pair distance");
 }
