@@ -104,7 +104,8 @@ void Engine::make_short_tiles(const float* rows, size_t n, const float* aux, flo
     using namespace shortscan;
     BruteDense& b = brute_;
     const char* env = getenv("NMSLIB_GPU_F32_SHORT");
-    const int forced = env ? (atoi(env) != 0 ? 1 : 0) : -1;
+    // (unset: the gates decide; 0: off; 32 / 64: that width without its gate; any other value: 64 without its gate)
+    const int forced = env ? (atoi(env) == 0 ? 0 : (atoi(env) == kHeadNarrow ? kHeadNarrow : kHead)) : -1;
     if (forced == 0 || dim_ <= (size_t)kHead || dim_ > (size_t)kMaxDim) return;
     const int dim = (int)dim_;
     try {
@@ -124,19 +125,32 @@ void Engine::make_short_tiles(const float* rows, size_t n, const float* aux, flo
         BfShortTiles t{};
         t.vh = b.short_vh.as<float>();
         float mx[4] = {0.f, 0.f, 0.f, 0.f};
-        hip_check(launch_short_rows(rows, (int)n, ldb_, dim, nullptr, 0.f, 0.f, t, d_out.as<float>(), stream_), "row heads");
-        hip_check(hipMemcpyAsync(mx, d_out.ptr(), 16, hipMemcpyDeviceToHost, stream_), "row heads");
-        hip_check(hipStreamSynchronize(stream_), "row heads");   // (`rot` is read by the copy above)
-        const float b_tail = tail_allowance(mx[1], b.bmax, rot.tail_abs);
-        const bool gate = index_gate(b_tail, b.bmax);
-        if (getenv("NMSLIB_GPU_DEBUG") && (atoi(getenv("NMSLIB_GPU_DEBUG")) & 4096))
-            fprintf(stderr, "[short scan] finalize: b_tailmax %.6g bmax %.6g ratio %.4g gate %d forced %d delta %.3g coeff %.3g\n",
-                    (double)b_tail, (double)b.bmax, b.bmax > 0 ? (double)(b_tail / b.bmax) : 0.0, gate ? 1 : 0, forced, rot.delta,
-                    (double)rot.coeff);
-        if (!(gate || forced == 1) || !(mx[0] > 0.f) || !std::isfinite(mx[0]) || !std::isfinite(mx[1])) return;
+        // the tier: the narrow head if its tails pass the gate, else the 64 columns if theirs do, else none (a forced width
+        // is the only one tried)
+        HeadConstants hc;
+        float b_tail = 0.f;
+        bool chosen = false;
+        for (const int width : {kHeadNarrow, kHead}) {
+            if (forced > 0 && forced != width) continue;
+            hc = head_constants(rot, dim, width);
+            t.width = width;
+            hip_check(launch_short_rows(rows, (int)n, ldb_, dim, nullptr, 0.f, 0.f, t, d_out.as<float>(), stream_), "row heads");
+            hip_check(hipMemcpyAsync(mx, d_out.ptr(), 16, hipMemcpyDeviceToHost, stream_), "row heads");
+            hip_check(hipStreamSynchronize(stream_), "row heads");   // (`rot` is read by the copy above)
+            b_tail = tail_allowance(mx[1], b.bmax, hc.tail_abs);
+            const bool gate = index_gate(b_tail, b.bmax);
+            if (getenv("NMSLIB_GPU_DEBUG") && (atoi(getenv("NMSLIB_GPU_DEBUG")) & 4096))
+                fprintf(stderr, "[short scan] finalize: b_tailmax %.6g bmax %.6g ratio %.4g gate %d forced %d delta %.3g coeff %.3g P %d\n",
+                        (double)b_tail, (double)b.bmax, b.bmax > 0 ? (double)(b_tail / b.bmax) : 0.0, gate ? 1 : 0,
+                        forced > 0 ? 1 : forced, hc.delta, (double)hc.coeff, width);
+            if (!(mx[0] > 0.f) || !std::isfinite(mx[0]) || !std::isfinite(mx[1])) return;
+            chosen = gate || forced == width;
+            if (chosen) break;
+        }
+        if (!chosen) return;
         t.scale = std::ldexp(1.f, std::max(-40, std::min(40, 13 - (int)std::floor(std::log2(mx[0])))));
-        const size_t n_pad = (size_t)bf_short_rows_padded((int)n);
-        t.h16 = b.short_h16.ensure(n_pad * kHead * 2);
+        const size_t n_pad = (size_t)bf_short_rows_padded((int)n, t.width);
+        t.h16 = b.short_h16.ensure(n_pad * t.width * 2);
         t.aux16 = static_cast<float*>(b.short_aux16.ensure(n_pad * 4));
         hip_check(launch_short_rows(rows, (int)n, ldb_, dim, aux, aux_pad, aux ? t.scale * t.scale : 0.f, t, d_out.as<float>(), stream_),
                   "short tiles");
@@ -146,8 +160,8 @@ void Engine::make_short_tiles(const float* rows, size_t n, const float* aux, flo
         t.bres_h = mx[3];
         t.b_tail = b_tail;
         t.bmax = b.bmax;
-        t.coeff = rot.coeff;
-        t.tail_abs = rot.tail_abs;
+        t.coeff = hc.coeff;
+        t.tail_abs = hc.tail_abs;
         t.miss = static_cast<int*>(b.short_miss.ensure(64));
         *t.miss = 0;
         b.short_tiles = t;

@@ -1832,10 +1832,17 @@ __global__ __launch_bounds__(256) void bf_scan_f32_kernel(BfScanF32Args a) {
 // of a 32-tile-row block score rows 0..31 of its group into one accumulator set, K-steps 4..7 rows 32..63 into the other
 // (each from its own start values, with the same four query fragments); the set that just finished is checked under the
 // other's four K-steps -- one group every 4 / QG steps.  a.tps counts 128-row stages.
-template <int MODE, bool SAMPLE, int QG, int NW, int KCH = 1, bool SHORT = false>
+// SHORT is the head's width: 0 (no short scan), 64, or 32 -- the narrow tier: rows r, r + 32, r + 64 and r + 96 of a 128-row
+// group in one tile row, 64 bytes each, so a stage is 256 rows; K-steps (0,1), (2,3), (4,5), (6,7) of a block score four sets
+// of 32 rows with the same two query fragments, alternating between the accumulator sets (narrow_loop below).  a.tps counts
+// 256-row stages.
+template <int MODE, bool SAMPLE, int QG, int NW, int KCH = 1, int SHORT = 0>
 __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) {
+    static_assert(SHORT == 0 || SHORT == 64 || SHORT == 32, "head widths of the short scan");
     static_assert(!SHORT || (KCH == 1 && MODE != SC_COS), "the short scan serves one chunk of l2 / inner-product rows");
-    constexpr int kRows = SHORT ? 2 * BF_BN : BF_BN;   // rows of a stage
+    constexpr bool kNarrow = SHORT == 32;
+    static_assert(!kNarrow || NW == 8, "the narrow tier runs with eight waves");
+    constexpr int kRows = kNarrow ? 4 * BF_BN : (SHORT ? 2 * BF_BN : BF_BN);   // rows of a stage
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int h = lane >> 5, l31 = lane & 31;
@@ -1849,7 +1856,10 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
     // hi tile only: 16 KB stages.  The waves meet every kSync stages (a wave that met a hit runs ~200 clocks late; the
     // fewer meetings, the less of that lateness everyone waits for): ring = the stage being read + kSync landed +
     // kSync in flight
-    constexpr int kSync = 4, kRing = 2 * kSync + 1, kAuxRing = 16, kStageBytes = BF_BN * 256;
+    // (the narrow tier's 256 start values per stage: 12 stages of them -- the stage whose last set is still being checked, the
+    //  one being read, 2 kSync behind it -- keep the workgroup inside 160 KB)
+    constexpr int kSync = 4, kRing = 2 * kSync + 1, kAuxRing = kNarrow ? 12 : 16, kStageBytes = BF_BN * 256;
+    static_assert(kAuxRing >= 2 * kSync + 2, "start values of every stage in flight and of the one before");
     char* ring = smem;
     float* auxr = reinterpret_cast<float*>(ring + kRing * kStageBytes);  // [kAuxRing][kRows]
     const int tstr = SAMPLE ? a.tile_stride : 1;
@@ -1858,8 +1868,8 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
     const int ntiles = max(0, min(a.tps, stiles_all - split * a.tps));
     const int nstages = ntiles * KCH;   // one stage per (tile, chunk of 128 dimensions)
     constexpr int kDp = 128 * KCH;       // row length of the bf16 tiles
-    constexpr int kRowBytes = SHORT ? 128 : kDp * 2;   // tile bytes of one base row
-    constexpr int kQd = SHORT ? 64 : kDp;              // columns of a query's fragments
+    constexpr int kRowBytes = SHORT ? 2 * SHORT : kDp * 2;   // tile bytes of one base row
+    constexpr int kQd = SHORT ? SHORT : kDp;                 // columns of a query's fragments
     const int r_begin = split * a.tps * tstr * kRows;
     const int stage_rows = tstr * kRows;
 
@@ -1894,13 +1904,19 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
         const unsigned long long abase = (unsigned long long)(uintptr_t)a.auxp16 + (unsigned long long)row0 * 4ull;
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1"
                      :: "v"(aux_voff), "s"(abase), "s"(aux_lds0 + (uint32_t)((stage % kAuxRing) * kRows * 4)) : "memory", "m0");
-        if constexpr (SHORT)   // (the stage's second 64 start values)
+        if constexpr (SHORT != 0)   // (the stage's second 64 start values)
             asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1"
                          :: "v"(aux_voff), "s"(abase + 256ull), "s"(aux_lds0 + (uint32_t)((stage % kAuxRing) * kRows * 4 + 256)) : "memory", "m0");
+        if constexpr (kNarrow) {   // (its third and fourth)
+            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1"
+                         :: "v"(aux_voff), "s"(abase + 512ull), "s"(aux_lds0 + (uint32_t)((stage % kAuxRing) * kRows * 4 + 512)) : "memory", "m0");
+            asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %0, %1"
+                         :: "v"(aux_voff), "s"(abase + 768ull), "s"(aux_lds0 + (uint32_t)((stage % kAuxRing) * kRows * 4 + 768)) : "memory", "m0");
+        }
 #pragma clang diagnostic pop
     };
 
-    constexpr int kQf = SHORT ? 4 : 8 * KCH;   // query fragments of a group
+    constexpr int kQf = SHORT ? SHORT / 16 : 8 * KCH;   // query fragments of a group
     f16x8 qh[QG][kQf];
     float thr[QG];
     int cnt[QG], ecnt[QG];
@@ -2077,7 +2093,10 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
                     else asm volatile(STR : "+{v[224:227]}"(fh[0]));                                            \
                     break;                                                                                      \
                 case 1: asm volatile(STR : "+{v[228:231]}"(fh[1])); break;                                      \
-                case 2: asm volatile(STR : "+{v[232:235]}"(fh[2])); break;                                      \
+                case 2:                                                                                         \
+                    if (with_init) asm volatile(STR : "+{v[232:235]}"(fh[2]), "+{v[240:255]}"(iv));             \
+                    else asm volatile(STR : "+{v[232:235]}"(fh[2]));                                            \
+                    break;                                                                                      \
                 default: asm volatile(STR : "+{v[236:239]}"(fh[3])); break;                                     \
             }                                                                                                   \
         } else {                                                                                                \
@@ -2087,7 +2106,10 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
                     else asm volatile(STR : "+{v[96:99]}"(fh[0]));                                              \
                     break;                                                                                      \
                 case 1: asm volatile(STR : "+{v[100:103]}"(fh[1])); break;                                      \
-                case 2: asm volatile(STR : "+{v[104:107]}"(fh[2])); break;                                      \
+                case 2:                                                                                         \
+                    if (with_init) asm volatile(STR : "+{v[104:107]}"(fh[2]), "+{v[112:127]}"(iv));             \
+                    else asm volatile(STR : "+{v[104:107]}"(fh[2]));                                            \
+                    break;                                                                                      \
                 default: asm volatile(STR : "+{v[108:111]}"(fh[3])); break;                                     \
             }                                                                                                   \
         }
@@ -2275,13 +2297,116 @@ __global__ __launch_bounds__(NW * 64) void bf_scan_bf16_kernel(BfScanF32Args a) 
     // (the prefetches the last block issued for a block that does not exist: their registers are free only now)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     };
-    if constexpr (NW == 8) {
+    // The narrow tier's loop.  A set of 32 rows takes two K-steps: the first starts every group's accumulators from the set's
+    // start values and takes the maxima (and the compares) of the set before, the second holds the branches -- a compare never
+    // feeds a branch of its own K-step.  The start values of the next set are requested at the top of the second step, when the
+    // MFMAs that read the current ones have issued.  LDS reads in the order of their issue, odd step o: 4 start-value reads,
+    // fragment o + 3; even step e: fragment e + 3.  An even step needs its fragment and the start values requested one step
+    // before: behind them only fragments e + 2 and e + 3 are in flight -- lgkmcnt(2), which retires fragment e + 1 as well; the
+    // odd step's wait (7: fragments o + 1, o + 2, the four reads, fragment o + 3) therefore retires nothing and only hands the
+    // fragment's registers to the compiler.  Inner-product rows have no start values: three fragments in flight, as ever.
+    // No stagger between a SIMD's two waves: there is no free K-step.
+    auto narrow_loop = [&](auto w_tag) __attribute__((always_inline)) {
+    static_assert(decltype(w_tag)::value == 32 && KCH == 1, "the narrow tier");
+    auto mfma_narrow = [&](f32x16& c, const f16x8& q, int kc) __attribute__((always_inline)) {
+        const bool first = (kc & 1) == 0;
+        if constexpr (MODE == SC_L2) {
+            if (first) {   // (fragment slot 0 or 2)
+                if (kc % 4 == 0) asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(c) : "{v[96:99]}"(fh[0]), "a"(q), "{v[112:127]}"(iv));
+                else asm("v_mfma_f32_32x32x16_f16 %0, %1, %2, %3" : "=&v"(c) : "{v[104:107]}"(fh[2]), "a"(q), "{v[112:127]}"(iv));
+                return;
+            }
+        }
+        c = __builtin_amdgcn_mfma_f32_32x32x16_f16(fh[kc % 4], q, first ? iv : c, 0, 0, 0);
+    };
+    float m_pd[QG];
+    unsigned long long trig_pd[QG];
+#pragma unroll
+    for (int g = 0; g < QG; ++g) {
+        m_pd[g] = 0.f;
+        trig_pd[g] = 0ull;
+    }
+    load_init(aux_a);
+#pragma unroll
+    for (int kc = 0; kc < kPre; ++kc) load_frag(Off0{}, kc);
+    for (int t = 0; t < ntiles; ++t) {
+        const float* axs = auxr + (t % kAuxRing) * kRows + 4 * h;
+        const int row0 = r_begin + t * stage_rows;
+        const uint32_t aux_t = aux_a + (uint32_t)((t % kAuxRing) * kRows * 4), aux_n = aux_a + (uint32_t)(((t + 1) % kAuxRing) * kRows * 4);
+#pragma unroll
+        for (int blk = 0; blk < 2; ++blk) {
+            const int dslot = ((t + 1) % kRing == 0) ? -(kRing - 1) * kStageBytes : kStageBytes;
+#pragma unroll
+            for (int kc = 0; kc < 8; ++kc) {
+                const int set = kc >> 1, kq = kc & 1, cur = set & 1;
+                // (also in the very last block: the reads stay inside the rings -- see bf_scan_f32_kernel)
+                if (kq == 1) load_init(kc < 7 ? aux_t + (uint32_t)((128 * blk + 32 * (set + 1)) * 4) : (blk == 0 ? aux_t + 128u * 4u : aux_n));
+                if (kc + kPre < 8) {
+                    if (blk == 0) load_frag(Off0{}, kc + kPre);
+                    else load_frag(Off1{}, kc + kPre);
+                } else if (blk == 0) {
+                    load_frag(Off1{}, kc + kPre - 8);
+                } else {
+                    vad[kc + kPre - 8] += (uint32_t)dslot;
+                    load_frag(Off0{}, kc + kPre - 8);
+                }
+                if (kInitReads == 0) wait_frag(std::integral_constant<int, kPre>{}, kc, false);
+                else if (kq == 0) wait_frag(std::integral_constant<int, 2>{}, kc, true);
+                else wait_frag(std::integral_constant<int, kPre + 4>{}, kc, false);
+                __builtin_amdgcn_sched_barrier(0);
+                if (kq == 0) {
+                    float m[QG];
+#pragma unroll
+                    for (int g = 0; g < QG; ++g) {   // (also before the first set: no branch between the MFMAs)
+                        mfma_narrow(acc[cur][g], qh[g][0], kc);
+                        __builtin_amdgcn_sched_barrier(0);
+                        m[g] = block_max(acc[cur ^ 1][g], pv_ax);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+#pragma unroll
+                    for (int g = 0; g < QG; ++g) {
+                        asm volatile("" : "+v"(m[g]));
+                        unsigned long long trig = trigger_of(m[g], g);
+                        asm volatile("" : "+s"(trig));
+                        m_pd[g] = m[g];
+                        trig_pd[g] = trig;
+                    }
+                } else {
+#pragma unroll
+                    for (int g = 0; g < QG; ++g) {
+                        mfma_narrow(acc[cur][g], qh[g][1], kc);
+                        __builtin_amdgcn_sched_barrier(0);
+                        finish_check(trig_pd[g], m_pd[g], acc[cur ^ 1][g], g, pv_ax, pv_row0);
+                        __builtin_amdgcn_sched_barrier(0);
+                    }
+                    // this set is the one the next two K-steps check
+                    pv_ax = axs + 128 * blk + 32 * set;
+                    pv_row0 = row0 + 128 * blk + 32 * set;
+                    have_pv = true;
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            if (blk == 1) {
+#pragma unroll
+                for (int kc = kPre; kc < 8; ++kc) vad[kc] += (uint32_t)dslot;
+            }
+            if (blk == 0 && t % kSync == 0) {   // (the meeting of main_loop)
+                asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
+                for (int u = t + kSync + 1; u <= t + 2 * kSync && u < nstages; ++u) issue_tile(u);
+            }
+        }
+    }
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    };
+    if constexpr (kNarrow) {
+        narrow_loop(std::integral_constant<int, SHORT>{});
+    } else if constexpr (NW == 8) {
         if (__builtin_amdgcn_readfirstlane(wave) >= 4) main_loop(std::integral_constant<int, 2>{});
         else main_loop(std::integral_constant<int, 0>{});
     } else {
         main_loop(std::integral_constant<int, 0>{});
     }
-    if (have_pv) {   // the last block (nstages > 0: it was block 1 of its stage)
+    if (have_pv) {   // the last block (nstages > 0: it was block 1 of its stage; the narrow tier: its last set)
 #pragma unroll
         for (int g = 0; g < QG; ++g) {
             const float m = block_max(acc[1][g], pv_ax);
@@ -2361,13 +2486,16 @@ __device__ __forceinline__ void short_load_v(const float* vh, float* vs) {
 }
 // One wave, one vector x of up to 128 values (lane l holds x[l] and x[l + 64], zeros beyond the dimension): lane j gets
 // head_j = sum_i x_i Vh[i][j] (one fma chain in the order of i), tail2 the squared norm of x - Vh head (per element one
-// fma chain in the order of j) in every lane.
+// fma chain in the order of j) in every lane.  W = the head's width: lanes >= W hold a head of 0 and the reconstruction
+// stops at column W (W = 64: the chains of the 64-column tier, bit for bit).
+template <int W>
 __device__ __forceinline__ float short_head_tail(float x0, float x1, int lane, const float* vs, float& tail2) {
     float hd = 0.f;
     for (int i = 0; i < 64; ++i) hd = fmaf(__shfl(x0, i, 64), vs[i * kShortVld + lane], hd);
     for (int i = 0; i < 64; ++i) hd = fmaf(__shfl(x1, i, 64), vs[(64 + i) * kShortVld + lane], hd);
+    if (W < 64 && lane >= W) hd = 0.f;
     float r0 = x0, r1 = x1;
-    for (int j = 0; j < 64; ++j) {
+    for (int j = 0; j < W; ++j) {
         const float hj = __shfl(hd, j, 64);
         r0 = fmaf(-hj, vs[lane * kShortVld + j], r0);
         r1 = fmaf(-hj, vs[(64 + lane) * kShortVld + j], r1);
@@ -2380,6 +2508,8 @@ __device__ __forceinline__ float short_head_tail(float x0, float x1, int lane, c
 // chosen from it), [1] largest tail, [2] largest |head|.  Else also the short tiles, n_pad rows (a multiple of 128): fp16(scale
 // * head), rows r and r + 32 of a 64-row group in one 256-byte tile row; their start values auxp = aux * aux_mul (null: 0;
 // aux_pad behind the n rows); out_bits[3] = largest fp16 residual |scale head - fp16(scale head)|.
+// W = 32: n_pad a multiple of 256; rows r, r + 32, r + 64, r + 96 of a 128-row group in one tile row, 64 bytes each.
+template <int W>
 __global__ __launch_bounds__(256) void short_rows_kernel(const float* rows, int n, int n_pad, int ld, int dim, const float* vh,
                                                          float scale, _Float16* tiles, const float* aux, float aux_pad,
                                                          float aux_mul, float* auxp, unsigned* out_bits) {
@@ -2393,7 +2523,7 @@ __global__ __launch_bounds__(256) void short_rows_kernel(const float* rows, int 
         const float* p = rows + (size_t)row * ld;
         const float x0 = real && lane < dim ? p[lane] : 0.f, x1 = real && lane + 64 < dim ? p[lane + 64] : 0.f;
         float t2;
-        const float hd = short_head_tail(x0, x1, lane, vs, t2);
+        const float hd = short_head_tail<W>(x0, x1, lane, vs, t2);
         m_el = fmaxf(m_el, fabsf(hd));
         m_tail = fmaxf(m_tail, sqrtf(t2));
         m_head = fmaxf(m_head, sqrtf(wave_sum(hd * hd)));
@@ -2402,8 +2532,13 @@ __global__ __launch_bounds__(256) void short_rows_kernel(const float* rows, int 
             const _Float16 hh = (_Float16)v;
             const float w = v - (float)hh;
             m_res = fmaxf(m_res, sqrtf(wave_sum(w * w)));
-            const int rr = row & 63;
-            tiles[((size_t)(row >> 6) * 32 + (rr & 31)) * 128 + (rr >> 5) * 64 + lane] = hh;
+            if constexpr (W == 64) {
+                const int rr = row & 63;
+                tiles[((size_t)(row >> 6) * 32 + (rr & 31)) * 128 + (rr >> 5) * 64 + lane] = hh;
+            } else {
+                const int rr = row & 127;
+                if (lane < W) tiles[((size_t)(row >> 7) * 32 + (rr & 31)) * 128 + (rr >> 5) * W + lane] = hh;
+            }
             if (lane == 0) auxp[row] = real ? (aux ? aux[row] * aux_mul : 0.f) : aux_pad;
         }
     }
@@ -2432,7 +2567,7 @@ struct ShortPrepArgs {
     int nq, dim, qpad, ld;
     float* pad_out;     // [qpad][ld]
     const float* vh;
-    _Float16* qh16;     // [qpad][64]
+    _Float16* qh16;     // [qpad][W]
     float* es;          // [qpad]
     int *clr0, *clr1;
     uint32_t* clr2;
@@ -2442,6 +2577,7 @@ struct ShortPrepArgs {
     float bscale_h, bres_h;     // scale * largest |row head|; largest fp16 residual of the scaled row heads
     float b_tail, bmax, coeff, tail_abs;   // largest row tail (with its allowance), largest row norm, Rotation's constants
 };
+template <int W>
 __global__ __launch_bounds__(256) void bf_f32_prep_short_kernel(ShortPrepArgs a) {
     __shared__ float vs[shortscan::kMaxDim * kShortVld];
     const size_t gtid = (size_t)blockIdx.x * blockDim.x + threadIdx.x, gsz = (size_t)gridDim.x * blockDim.x;
@@ -2456,7 +2592,7 @@ __global__ __launch_bounds__(256) void bf_f32_prep_short_kernel(ShortPrepArgs a)
         const float x0 = real && lane < a.dim ? p[lane] : 0.f, x1 = real && lane + 64 < a.dim ? p[lane + 64] : 0.f;
         for (int c = lane; c < a.ld; c += 64) a.pad_out[(size_t)q * a.ld + c] = c < 64 ? x0 : (c < 128 ? x1 : 0.f);
         float t2;
-        const float hd = short_head_tail(x0, x1, lane, vs, t2);
+        const float hd = short_head_tail<W>(x0, x1, lane, vs, t2);
         const float qn = sqrtf(wave_sum(fmaf(x0, x0, x1 * x1)));
         const float v = a.scale_q * hd;
         const _Float16 hh = (_Float16)v;
@@ -2467,7 +2603,7 @@ __global__ __launch_bounds__(256) void bf_f32_prep_short_kernel(ShortPrepArgs a)
         const float e_head = __any(over) ? INFINITY : 1.01f * (qr * a.bscale_h + 1.004f * qnh * a.bres_h) + 2e-5f * qnh * a.bscale_h;
         const float q_tail = shortscan::tail_allowance(sqrtf(t2), qn, a.tail_abs);
         const float es = shortscan::short_error(e_head, a.unit, q_tail, a.b_tail, qn, a.bmax, a.coeff);
-        a.qh16[(size_t)q * 64 + lane] = hh;
+        if (W == 64 || lane < W) a.qh16[(size_t)q * W + lane] = hh;
         if (lane == 0) a.es[q] = real ? es : 0.f;
     }
 }
@@ -4026,6 +4162,11 @@ BfF32Fast bf_f32_fast_plan(int n, int dim, int nq, int k, int space, bool cosine
     f.short_tps = (stages_all + ns - 1) / ns;
     f.short_s_tps = ((stages_all + f.stride - 1) / f.stride + nss - 1) / nss;
     f.lds_short = 9 * BF_BN * 256 + 16 * 2 * BF_BN * 4 + 64;
+    // the narrow tier: 256-row stages (tps = 4 * narrow_tps), twelve stages of start values beside the ring of nine
+    const int nstages_all = (n + 4 * BF_BN - 1) / (4 * BF_BN);
+    f.narrow_tps = (nstages_all + ns - 1) / ns;
+    f.narrow_s_tps = ((nstages_all + f.stride - 1) / f.stride + nss - 1) / nss;
+    f.lds_narrow = 9 * BF_BN * 256 + 12 * 4 * BF_BN * 4 + 64;
     return f;
 }
 
@@ -4061,11 +4202,13 @@ hipError_t launch_short_rows(const float* rows, int n, int ld, int dim, const fl
                              const BfShortTiles& dst, float* out, hipStream_t s) {
     hipError_t e = hipMemsetAsync(out, 0, 16, s);
     if (e != hipSuccess || n == 0) return e;
-    const int n_pad = bf_short_rows_padded(n);
+    const bool narrow = dst.width == shortscan::kHeadNarrow;
+    const int n_pad = bf_short_rows_padded(n, dst.width);
     int grid = (n_pad + 3) / 4;
     if (grid > 2048) grid = 2048;
-    hipLaunchKernelGGL(short_rows_kernel, dim3(grid), dim3(256), 0, s, rows, n, n_pad, ld, dim, dst.vh, dst.scale,
-                       static_cast<_Float16*>(dst.h16), aux, aux_pad, aux_mul, dst.aux16, reinterpret_cast<unsigned*>(out));
+    hipLaunchKernelGGL(narrow ? short_rows_kernel<shortscan::kHeadNarrow> : short_rows_kernel<shortscan::kHead>, dim3(grid), dim3(256),
+                       0, s, rows, n, n_pad, ld, dim, dst.vh, dst.scale, static_cast<_Float16*>(dst.h16), aux, aux_pad, aux_mul,
+                       dst.aux16, reinterpret_cast<unsigned*>(out));
     return hipGetLastError();
 }
 
@@ -4088,7 +4231,7 @@ static hipError_t launch_scan_bf16_one(const BfScanF32Args& a, int grid, size_t 
 // terms: 3 = the split product, 1 = one bf16 product (the sample pass: always, 256 queries per workgroup)
 // the short scan's instantiations: eight waves, like the served shapes of the 128-column scan
 template <int MODE>
-static hipError_t launch_scan_short_mode(const BfScanF32Args& a, bool sample, int qg, int grid, size_t lds, hipStream_t s) {
+static hipError_t launch_scan_short_mode(const BfScanF32Args& a, bool sample, int qg, bool narrow, int grid, size_t lds, hipStream_t s) {
     if constexpr (MODE == SC_COS) {
         return hipErrorInvalidValue;
     } else {
@@ -4098,8 +4241,12 @@ static hipError_t launch_scan_short_mode(const BfScanF32Args& a, bool sample, in
             hipLaunchKernelGGL(kern, dim3(grid), dim3(512), lds, s, a);
             return hipGetLastError();
         };
-        if (sample) return go(bf_scan_bf16_kernel<MODE, true, 1, 8, 1, true>);
-        return qg == 2 ? go(bf_scan_bf16_kernel<MODE, false, 2, 8, 1, true>) : go(bf_scan_bf16_kernel<MODE, false, 1, 8, 1, true>);
+        if (narrow) {
+            if (sample) return go(bf_scan_bf16_kernel<MODE, true, 1, 8, 1, 32>);
+            return qg == 2 ? go(bf_scan_bf16_kernel<MODE, false, 2, 8, 1, 32>) : go(bf_scan_bf16_kernel<MODE, false, 1, 8, 1, 32>);
+        }
+        if (sample) return go(bf_scan_bf16_kernel<MODE, true, 1, 8, 1, 64>);
+        return qg == 2 ? go(bf_scan_bf16_kernel<MODE, false, 2, 8, 1, 64>) : go(bf_scan_bf16_kernel<MODE, false, 1, 8, 1, 64>);
     }
 }
 template <int MODE>
@@ -4245,6 +4392,7 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
     // bound E_s per query in E1's place, no split-product scan (a tile without room goes to the adaptive kernel)
     const BfShortTiles& sh = tiles.sh;
     const bool shortscan_on = f.short_ok && sh.h16 != nullptr && q.raw != nullptr;
+    const bool narrow = shortscan_on && sh.width == shortscan::kHeadNarrow;
     float* e_short = shortscan_on ? static_cast<float*>(q_hi) : nullptr;   // (the bf16 query tiles are not made)
     static const int dbg = getenv("NMSLIB_GPU_DEBUG") ? atoi(getenv("NMSLIB_GPU_DEBUG")) : 0;
     if (shortscan_on) {
@@ -4273,7 +4421,8 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
         pa.bmax = sh.bmax;
         pa.coeff = sh.coeff;
         pa.tail_abs = sh.tail_abs;
-        hipLaunchKernelGGL(bf_f32_prep_short_kernel, dim3((unsigned)(f.qpad / 4)), dim3(256), 0, s, pa);
+        hipLaunchKernelGGL(narrow ? bf_f32_prep_short_kernel<shortscan::kHeadNarrow> : bf_f32_prep_short_kernel<shortscan::kHead>,
+                           dim3((unsigned)(f.qpad / 4)), dim3(256), 0, s, pa);
         e = hipGetLastError();
         if (e != hipSuccess) return e;
     } else {   // pad (when the caller passes the raw queries) + bf16 split + every clear of the batch
@@ -4293,8 +4442,9 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
     auto scan = [&](const BfScanF32Args& sa, bool sample, int terms, int grid) -> hipError_t {
         if (shortscan_on) {
             if (terms != 1) return hipSuccess;   // (no split-product scan beside the short scan)
-            if (f.mode == 0) return launch_scan_short_mode<SC_L2>(sa, sample, f.qg, grid, f.lds_short, s);
-            return launch_scan_short_mode<SC_DOT>(sa, sample, f.qg, grid, f.lds_short, s);
+            const size_t lds = narrow ? f.lds_narrow : f.lds_short;
+            if (f.mode == 0) return launch_scan_short_mode<SC_L2>(sa, sample, f.qg, narrow, grid, lds, s);
+            return launch_scan_short_mode<SC_DOT>(sa, sample, f.qg, narrow, grid, lds, s);
         }
         const size_t lds = terms == 1 ? f.lds_scan1 : f.lds_scan;
         if (f.mode == 0) return launch_scan_f32_mode<SC_L2>(sa, sample, terms, f.qg, grid, lds, s, f.kch);
@@ -4324,7 +4474,7 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
     BfScanF32Args sa = a;
     sa.nqt = f.qpad / (f.kch > 1 ? 128 : 256);
     sa.nsplit = f.s_nsplit;
-    sa.tps = shortscan_on ? f.short_s_tps : f.s_tps;
+    sa.tps = narrow ? f.narrow_s_tps : (shortscan_on ? f.short_s_tps : f.s_tps);
     sa.tile_stride = f.stride;
     sa.top8 = top8;
     e = scan(sa, true, 1, 8 * sa.nqt * (f.s_nsplit / 8));
@@ -4348,7 +4498,7 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
     a.list = ws.list;
     a.list_cnt = ws.list_cnt;
     a.nsplit = f.nsplit;
-    a.tps = shortscan_on ? f.short_tps : f.tps;
+    a.tps = narrow ? f.narrow_tps : (shortscan_on ? f.short_tps : f.tps);
     a.caph = f.caph;
     a.tile_stride = 1;
     a.group_flag = precise;
@@ -4381,7 +4531,7 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
     r.k = k;
     r.nsplit = f.nsplit;
     r.caph = f.caph;
-    r.tps = shortscan_on ? 2 * f.short_tps : f.tps;   // (64-row tiles: a split's first row)
+    r.tps = narrow ? 4 * f.narrow_tps : (shortscan_on ? 2 * f.short_tps : f.tps);   // (64-row tiles: a split's first row)
     r.p2max = f.p2max;
     r.fail_queries = f.tq;
     r.no_split = f.kch > 1 || shortscan_on ? 1 : 0;
@@ -4431,8 +4581,8 @@ hipError_t launch_bf_f32_fast(const BfF32Fast& f, int space, int nq, int k, cons
                 sum += v;
                 mx = v > mx ? v : mx;
             }
-            fprintf(stderr, "[short scan] served 1 E_s mean %.6g max %.6g (units of scale^2 = %.6g) b_tailmax %.6g bmax %.6g\n",
-                    nq ? sum / nq : 0.0, mx, (double)sh.scale * sh.scale, (double)sh.b_tail, (double)sh.bmax);
+            fprintf(stderr, "[short scan] served 1 E_s mean %.6g max %.6g (units of scale^2 = %.6g) b_tailmax %.6g bmax %.6g P %d\n",
+                    nq ? sum / nq : 0.0, mx, (double)sh.scale * sh.scale, (double)sh.b_tail, (double)sh.bmax, sh.width);
         } else {
             fprintf(stderr, "[short scan] served 0\n");
         }

@@ -217,6 +217,9 @@ struct BfF32Fast {
     bool short_ok;
     int short_tps, short_s_tps;
     size_t lds_short;
+    // the same for an index whose tier is the narrow one (32 columns): 256-row stages, a shorter ring of start values
+    int narrow_tps, narrow_s_tps;
+    size_t lds_narrow;
 };
 BfF32Fast bf_f32_fast_plan(int n, int dim, int nq, int k, int space, bool cosine_centred);
 
@@ -272,8 +275,10 @@ hipError_t launch_row_maxnorm(const float* rows, int n, int ld, int dim, bool re
 // The short scan's resident side (h16 null: the index has none, or the batch may not use it): fp16(scale * head) tiles
 // [n_pad / 2][128] (rows r and r + 32 of a 64-row group share a tile row), their start values, the rotation's first 64
 // columns [128][64] and the constants of the bound E_s (short_scan_plan.hpp); miss: a word the threshold kernel sets when a
-// query finds no room for its bound (pinned host memory)
+// query finds no room for its bound (pinned host memory).  width = 32 (the narrow tier): tiles [n_pad / 4][128], rows r,
+// r + 32, r + 64 and r + 96 of a 128-row group share a tile row; the constants are those of the 32-column prefix of vh.
 struct BfShortTiles {
+    int width;                 // columns of a head: shortscan::kHead or kHeadNarrow
     void* h16;
     float* aux16;
     const float* vh;
@@ -283,7 +288,11 @@ struct BfShortTiles {
     float coeff, tail_abs;     // shortscan::Rotation's
     int* miss;
 };
-inline int bf_short_rows_padded(int n) { return (n + 2 * BF_BN - 1) / (2 * BF_BN) * (2 * BF_BN); }
+inline int bf_short_stage_rows(int width) { return width == shortscan::kHeadNarrow ? 4 * BF_BN : 2 * BF_BN; }
+inline int bf_short_rows_padded(int n, int width = shortscan::kHead) {
+    const int st = bf_short_stage_rows(width);
+    return (n + st - 1) / st * st;
+}
 // m [dim][dim] (f64) = sum over every stride-th row of x x^T
 hipError_t launch_short_moment(const float* rows, int n, int ld, int dim, int stride, double* m, hipStream_t s);
 // out (16 bytes, cleared here): largest |head element|, largest tail, largest |head|, largest fp16 residual of scale * head;

@@ -123,6 +123,34 @@ inline Rotation make_rotation(std::vector<double>& m, int dim) {
     return r;
 }
 
+// The narrow tier: a head of the first kHeadNarrow columns.  The columns are sorted by falling eigenvalue, so the narrow Vh is
+// the PREFIX of the stored one (row stride kHead) and no second matrix exists.  The derivation above holds with 32 in place
+// of 64 throughout: delta and F measured on the stored prefix, 32 fma per element of the reconstruction (gamma(33)).
+constexpr int kHeadNarrow = 32;
+struct HeadConstants {
+    double delta = 0, frob = 0;
+    float coeff = 0, tail_abs = 0;
+};
+// the constants of the bound for a head of the first `width` columns of r.vh (width = kHead: Rotation's own, bit for bit)
+inline HeadConstants head_constants(const Rotation& r, int dim, int width) {
+    HeadConstants c;
+    double d2 = 0, f2 = 0;
+    for (int a = 0; a < width; ++a)
+        for (int b = 0; b < width; ++b) {
+            double s = 0;
+            for (int i = 0; i < dim; ++i) s += (double)r.vh[(size_t)i * kHead + a] * (double)r.vh[(size_t)i * kHead + b];
+            const double e = s - (a == b ? 1.0 : 0.0);
+            d2 += e * e;
+            if (a == b) f2 += s;
+        }
+    c.delta = std::sqrt(d2);
+    c.frob = std::sqrt(f2);
+    const double g = gamma_of(dim), F = c.frob, nu = std::sqrt(1 + c.delta);
+    c.coeff = (float)(1.01 * nu * (1 + g * F) * (g * F + c.delta * nu + (1 + c.delta) * g * F));
+    c.tail_abs = (float)(1.01 * gamma_of(width + 1) * (1 + nu * F * (1 + g * F)));
+    return c;
+}
+
 // a measured tail and the norm of its vector -> an upper bound of the true tail
 SHORT_SCAN_HD inline float tail_allowance(float tail, float norm, float tail_abs) {
     return tail * (1.0f + 9.6e-7f) + tail_abs * norm;
